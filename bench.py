@@ -6,7 +6,12 @@ GPUPhotons.propagate to completion (max_steps) + per-channel hit reduction (coun
 flat-hit count and compaction (get_flat_hits' two kernels) + -- with more than one GPU -- the RCCL
 all-reduce of the per-channel arrays inside the library, + the read-back of those two small arrays.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|detector|lite|tiny|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|detector|lite|tiny|c5] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds what takes runs of its own: the counting
+pass and the roofline figures, the other input order and the direction sort, the exact walk and the CPU baseline.
+--dump-outputs DIR writes what the last timed step computed (per-channel arrays, a fixed sample of the final photon records
+and of the flat hits) as DIR/<name>.npy, for comparing two builds output for output.
 
 N > 1: one rank per GPU (the driver starts them through torch.distributed.run; started by hand with
 --gpus N and no WORLD_SIZE, this script starts that launcher itself as a child process).  Local rank 0
@@ -119,7 +124,13 @@ def main():
     ap.add_argument('--wavelength-hi', type=float, default=0.0, help='> 400: wavelengths uniform in [400, hi] nm')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--cpu-sample', type=int, default=0)
+    ap.add_argument('--full', action='store_true', help='also the counting pass and roofline, the other input order, the '
+                    'direction sort, the exact walk and the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write what the last timed step computed as DIR/<name>.npy '
+                    '(rank 0\'s shard with more than one GPU)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # started by hand: become the launcher's parent BEFORE anything touches a GPU (a child process, never an exec)
@@ -244,7 +255,7 @@ def main():
         _lib.check(ctx._lib.chroma_comm_init(ctx.handle, 1, 0, ident))
     t_upload = time.time() - t0
     log('device: %s; geometry upload %.1f s; traversal stack need %d' % (ctx.device_name(), t_upload, gg.stack_need()))
-    run_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline
+    run_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
     if not run_cpu:
         packed = None                 # (the host arrays are only needed again by the CPU baseline)
 
@@ -351,7 +362,58 @@ def main():
         stats['hits'] = stats.get('hits', 0) + int(nhits.value)
         stats['copied'] = stats.get('copied', 0) + int(ncopied.value)
         stats['channel_sum'] = stats.get('channel_sum', 0) + int(np.asarray(c, dtype=np.uint64).sum())
-        return c, e
+        return c, e, int(ncopied.value)
+
+    def dump_outputs(path, batch, c, e, ncopied, rows=1 << 18, block=4096):
+        """What the last timed step handed its caller, as `path`/<name>.npy: float data in float32, integer data in float64
+        (exact).  The per-channel hit counts and earliest times whole; the batch's final photon records as `rows` // `block`
+        runs of `block` consecutive photons at seeded places (photon_index names them); the flat hits with their channels as
+        about `rows` of them chosen by a hash of each hit's own bits -- the order the compaction appends hits in is not
+        fixed -- put in one canonical order.  Under 40 MB in all at C3; the same arguments give the same inputs, so two
+        builds compare file for file."""
+        from chroma_amd.gpu.photon import _vec3_to_rows
+        out = {'channel_hit_count': np.asarray(c).astype(np.float64),
+               'channel_earliest_time': np.ascontiguousarray(e, dtype=np.uint32).view(np.float32)}
+        if nphotons <= rows:
+            spans = [(0, nphotons)]
+        else:
+            starts = np.sort(np.random.default_rng(ENGINE_SEED).choice(nphotons // block, rows // block, replace=False)) * block
+            spans = [(int(s), int(s) + block) for s in starts]
+        ph = batch.ph
+        out['photon_index'] = np.concatenate([np.arange(a, b) for a, b in spans]).astype(np.float64)
+        for name in ('pos', 'dir', 'pol', 'wavelengths', 't', 'weights', 'flags', 'last_hit_triangles', 'rng_counters'):
+            out['photon_' + name] = np.concatenate([getattr(ph, name)[a:b].get() for a, b in spans])
+
+        hit = {name: getattr(hits[0], name)[:ncopied].get() for name in ('pos', 'dir', 'pol', 'wavelengths', 't', 'weights', 'flags', 'last_hit_triangles')}
+        hit['channels'] = hits[2][:ncopied].get()
+        bits = {name: (_vec3_to_rows(a) if a.dtype.fields else a.reshape(-1, 1)).view(np.uint32) for name, a in hit.items()}
+        if ncopied > rows:
+            key = np.zeros(ncopied, np.uint64)
+            for col in (bits['t'][:, 0], bits['pos'][:, 0], bits['pos'][:, 1], bits['pos'][:, 2], bits['channels'][:, 0]):
+                key = (key ^ col.astype(np.uint64)) * np.uint64(0x9E3779B97F4A7C15)
+                key ^= key >> np.uint64(29)
+            chosen = np.flatnonzero(key < np.uint64(int(rows / ncopied * 2.0 ** 64)))
+        else:
+            chosen = np.arange(ncopied)
+        order_keys = [bits[name][chosen, j] for name in ('weights', 'wavelengths', 'flags', 'last_hit_triangles', 'pol', 'dir', 'pos', 't', 'channels')
+                      for j in range(bits[name].shape[1])]
+        chosen = chosen[np.lexsort(order_keys)]           # (the last key first: channel, time, position, ...)
+        out['hit_total'] = np.array([ncopied], dtype=np.float64)
+        for name, a in hit.items():
+            out['hit_' + name] = a[chosen]
+
+        os.makedirs(path, exist_ok=True)
+        total = 0
+        for name, a in out.items():
+            if a.dtype.fields:
+                a = _vec3_to_rows(a)
+            elif a.dtype.kind != 'f':
+                a = a.astype(np.float64)
+            assert a.dtype in (np.float32, np.float64), name
+            np.save(os.path.join(path, name + '.npy'), np.ascontiguousarray(a))
+            total += a.nbytes
+        assert total <= 64 << 20, 'dump of %d bytes' % total
+        log('outputs of the last timed step: %d arrays, %.1f MB under %s' % (len(out), total / 2.0 ** 20, path))
 
     def sync_all():
         if world > 1:
@@ -360,28 +422,32 @@ def main():
             torch.cuda.synchronize()
         ctx.synchronize()
 
-    # ---- algorithmic work per photon: one counting pass on a batch of its own (untimed) -------
+    # ---- algorithmic work per photon (--full): one counting pass on a batch of its own (untimed) -------
+    # (a plain run propagates the same untimed batch without the counters: the library sizes its working sets on it, before
+    #  the warm-up, in either case)
     t0 = time.time()
     count_n_stats = {}
-    ctx.set_counting(True)
+    ctx.set_counting(args.full)
     probe = Batch().fill(10_000)
     ensure_hit_buffers(int(0.12 * nphotons) + 65536)
     run_step(probe, False, count_n_stats)
     ctx.set_counting(False)
-    steps_pp = count_n_stats['photon_steps'] / nphotons
-    nodes_ps = count_n_stats['nodes_visited'] / max(1, count_n_stats['photon_steps'])
-    tris_ps = count_n_stats['triangles_tested'] / max(1, count_n_stats['photon_steps'])
-    bytes_per_step = 16.0 * nodes_ps + 48.0 * tris_ps + 40 + 120 + 8
-    bytes_per_photon = bytes_per_step * steps_pp
-    log('counting pass %.1f s: %.3f steps/photon, %.1f nodes/step, %.2f triangle tests/step -> %.0f B/step, %.0f B/photon; '
-        'hit fraction %.4f; %d stack entries spilled' % (time.time() - t0, steps_pp, nodes_ps, tris_ps, bytes_per_step, bytes_per_photon,
-                                                         count_n_stats['hits'] / nphotons, count_n_stats.get('stack_spills', 0)))
-    if count_n_stats.get('packet_nodes_visited'):
-        log('  diagnostic counters: %r' % {k: v for k, v in count_n_stats.items() if k.startswith('packet_')})
-    if world > 1:
-        assert count_n_stats['channel_sum'] >= count_n_stats['hits'], 'reduced channel counts smaller than this rank\'s own'
-    else:
-        assert count_n_stats['channel_sum'] == count_n_stats['hits'] == count_n_stats['copied']
+    steps_pp = nodes_ps = tris_ps = None
+    if args.full:
+        steps_pp = count_n_stats['photon_steps'] / nphotons
+        nodes_ps = count_n_stats['nodes_visited'] / max(1, count_n_stats['photon_steps'])
+        tris_ps = count_n_stats['triangles_tested'] / max(1, count_n_stats['photon_steps'])
+        bytes_per_step = 16.0 * nodes_ps + 48.0 * tris_ps + 40 + 120 + 8
+        bytes_per_photon = bytes_per_step * steps_pp
+        log('counting pass %.1f s: %.3f steps/photon, %.1f nodes/step, %.2f triangle tests/step -> %.0f B/step, %.0f B/photon; '
+            'hit fraction %.4f; %d stack entries spilled' % (time.time() - t0, steps_pp, nodes_ps, tris_ps, bytes_per_step, bytes_per_photon,
+                                                             count_n_stats['hits'] / nphotons, count_n_stats.get('stack_spills', 0)))
+        if count_n_stats.get('packet_nodes_visited'):
+            log('  diagnostic counters: %r' % {k: v for k, v in count_n_stats.items() if k.startswith('packet_')})
+        if world > 1:
+            assert count_n_stats['channel_sum'] >= count_n_stats['hits'], 'reduced channel counts smaller than this rank\'s own'
+        else:
+            assert count_n_stats['channel_sum'] == count_n_stats['hits'] == count_n_stats['copied']
 
     if resident:
         buffers = [probe.fill(0)] + [Batch().fill(i) for i in range(1, nbatches)]
@@ -411,7 +477,8 @@ def main():
     for i in range(args.warmup, nbatches):
         t_step = time.perf_counter()
         k0 = stats.get('kernel_ms', 0.0)
-        run_step(batch_for(i), True, stats)
+        last_batch = batch_for(i)
+        last_outputs = run_step(last_batch, True, stats)
         step_walls.append(time.perf_counter() - t_step)
         log('  step %d: %.1f ms wall, %.1f ms in propagate kernels' % (i - args.warmup, 1e3 * step_walls[-1], stats['kernel_ms'] - k0))
     sync_all()
@@ -422,49 +489,53 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_batch, *last_outputs)
+
     total_photons = nphotons * args.steps * world
     value = total_photons / elapsed
     kernel_s = stats['kernel_ms'] / 1e3
     launches = max(1, stats['launches'])
-    path_achieved = (bytes_per_photon * nphotons * args.steps) / kernel_s / 1e9 if kernel_s > 0 else 0.0
-    # dominant kernel: the ray cast (k_raycast_quad; the retry pass after it is normally empty).
-    # Algorithmic bytes per photon step: 16 B per child entry fetched (a 128-B wide node = 8 entries)
-    # + 48 B per triangle tested + 64 B ray record read + 8 B hit written
     ray_s = stats['raycast_ms'] / 1e3
     ray_launches = max(1, stats['raycast_launches'])
-    ray_bytes_per_step = 16.0 * nodes_ps + 48.0 * tris_ps + 64 + 8
-    ray_bytes_total = ray_bytes_per_step * steps_pp * nphotons * args.steps
-    achieved = ray_bytes_total / ray_s / 1e9 if ray_s > 0 else 0.0
     avg_launch_ms = 1e3 * ray_s / ray_launches
     log('timed: %.3f s for %d steps; propagate kernels %.3f s in %d launches, of which ray cast %.3f s in %d launches '
         '(avg %.3f ms); hits/photon %.4f' % (elapsed, args.steps, kernel_s, launches, ray_s, ray_launches,
                                              avg_launch_ms, stats['hits'] / (nphotons * args.steps)))
-    # HBM traffic of the same command from rocprofv3 PMC passes (tools/pmc_traffic.py -> profiles/pmc_traffic.json):
-    # quoted only when that profile was taken with the kernels this run was built from
-    traffic, traffic_source, measured = None, 'none: no PMC profile of this command under profiles/', None
-    src_hash = kernel_source_hash()
-    sq, physics_traffic, physics_sq = None, None, None
-    try:
-        pmc = json.load(open(os.path.join(ROOT, 'profiles', 'pmc_traffic.json')))
-        key = '%s:%d:%d' % (args.config, nphotons, args.max_steps)
-        # issue-side counters and the second kernel's traffic: quoted under the same rule (this build's hash only)
-        if pmc.get(key + ':sq', {}).get('source_hash') == src_hash:
-            sq = pmc[key + ':sq']
-        if pmc.get(key + ':physics', {}).get('source_hash') == src_hash:
-            physics_traffic = pmc[key + ':physics']
-        if pmc.get(key + ':physics:sq', {}).get('source_hash') == src_hash:
-            physics_sq = pmc[key + ':physics:sq']
-        if key in pmc:
-            rec = pmc[key]
-            if rec.get('source_hash') == src_hash:
-                traffic = rec['hbm_bytes_per_launch']
-                traffic_source = 'profiles/pmc_traffic.json[%s]: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command, %s, %d launches, kernels %s (= this build); %s' % (
-                    key, rec.get('date', '?'), rec.get('launches', 0), src_hash, rec.get('correction', ''))
-                measured = traffic / (avg_launch_ms * 1e-3) / 1e9
-            else:
-                traffic_source = 'stale: profiles/pmc_traffic.json[%s] was taken with kernels %s, this build is %s' % (key, rec.get('source_hash', '?'), src_hash)
-    except Exception:
-        pass
+    if args.full:
+        path_achieved = (bytes_per_photon * nphotons * args.steps) / kernel_s / 1e9 if kernel_s > 0 else 0.0
+        # dominant kernel: the ray cast (k_raycast_quad; the retry pass after it is normally empty).
+        # Algorithmic bytes per photon step: 16 B per child entry fetched (a 128-B wide node = 8 entries)
+        # + 48 B per triangle tested + 64 B ray record read + 8 B hit written
+        ray_bytes_per_step = 16.0 * nodes_ps + 48.0 * tris_ps + 64 + 8
+        ray_bytes_total = ray_bytes_per_step * steps_pp * nphotons * args.steps
+        achieved = ray_bytes_total / ray_s / 1e9 if ray_s > 0 else 0.0
+        # HBM traffic of the same command from rocprofv3 PMC passes (tools/pmc_traffic.py -> profiles/pmc_traffic.json):
+        # quoted only when that profile was taken with the kernels this run was built from
+        traffic, traffic_source, measured = None, 'none: no PMC profile of this command under profiles/', None
+        src_hash = kernel_source_hash()
+        sq, physics_traffic, physics_sq = None, None, None
+        try:
+            pmc = json.load(open(os.path.join(ROOT, 'profiles', 'pmc_traffic.json')))
+            key = '%s:%d:%d' % (args.config, nphotons, args.max_steps)
+            # issue-side counters and the second kernel's traffic: quoted under the same rule (this build's hash only)
+            if pmc.get(key + ':sq', {}).get('source_hash') == src_hash:
+                sq = pmc[key + ':sq']
+            if pmc.get(key + ':physics', {}).get('source_hash') == src_hash:
+                physics_traffic = pmc[key + ':physics']
+            if pmc.get(key + ':physics:sq', {}).get('source_hash') == src_hash:
+                physics_sq = pmc[key + ':physics:sq']
+            if key in pmc:
+                rec = pmc[key]
+                if rec.get('source_hash') == src_hash:
+                    traffic = rec['hbm_bytes_per_launch']
+                    traffic_source = 'profiles/pmc_traffic.json[%s]: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command, %s, %d launches, kernels %s (= this build); %s' % (
+                        key, rec.get('date', '?'), rec.get('launches', 0), src_hash, rec.get('correction', ''))
+                    measured = traffic / (avg_launch_ms * 1e-3) / 1e9
+                else:
+                    traffic_source = 'stale: profiles/pmc_traffic.json[%s] was taken with kernels %s, this build is %s' % (key, rec.get('source_hash', '?'), src_hash)
+        except Exception:
+            pass
 
     def rate_stats(walls):
         """mean and standard deviation of the per-batch rates, and of the per-batch times, over one leg's batches"""
@@ -507,7 +578,7 @@ def main():
     headline_order = rate_stats(step_walls)
     # (the extra legs below run on one GPU only: run_step holds the all-reduce of the per-channel arrays, a collective EVERY
     #  rank would have to enter)
-    extra_legs = world == 1 and not os.environ.get('CHROMA_BENCH_NO_EXACT') and os.environ.get('CHROMA_WALK', 'quad') == 'quad'
+    extra_legs = args.full and world == 1 and not os.environ.get('CHROMA_BENCH_NO_EXACT') and os.environ.get('CHROMA_WALK', 'quad') == 'quad'
     nleg = int(os.environ.get('CHROMA_BENCH_LEG_BATCHES', args.steps))
 
     def leg_batch(i, index_base, sort):
@@ -563,26 +634,28 @@ def main():
         log('exact (literal reference) walk: %.4g +- %.2g photons/s over %d batches (%.1fx slower than the default walk)' % (
             exact_walk['value'], exact_walk['std'], nleg, exact_walk['slower_than_default']))
 
-    # the second kernel of a step, k_physics (main pass): per photon step it reads the hit entry (8 B), the photon's
-    # record (64 B) and the winning triangle's record (48 B), writes a survivor's record, next ray and queue slot
-    # (64 + 64 + 4 B) or a finished photon's ten array entries (64 B); every photon ends exactly once
-    phys_s = stats.get('physics_ms', 0.0) / 1e3
-    phys_bytes_per_step = 120.0 + 132.0 * (1.0 - 1.0 / steps_pp) + 64.0 / steps_pp
-    phys_bytes_total = phys_bytes_per_step * steps_pp * nphotons * args.steps
-    phys_launches = max(1, stats.get('physics_launches', 0))
-    physics = {'kernel': 'k_physics<%s>' % ('false' if gg_plain(gg) else 'true'), 'kernel_s': phys_s, 'launches': int(stats.get('physics_launches', 0)),
-               'ms_per_batch': 1e3 * phys_s / args.steps,
-               'algorithmic_bytes_per_photon_step': phys_bytes_per_step,
-               'algorithmic_GBps': phys_bytes_total / phys_s / 1e9 if phys_s > 0 else None,
-               'algorithmic_frac': phys_bytes_total / phys_s / 1e9 / HBM_PEAK_GBS if phys_s > 0 else None,
-               'hbm_measured_GBps': None, 'traffic_over_algorithmic': None,
-               'valu_lane_utilisation': physics_sq['valu_lane_utilisation'] if physics_sq else None,
-               'wait_frac': physics_sq['wait_frac'] if physics_sq else None}
-    if physics_traffic and phys_s > 0:
-        # (the PMC figure is per launch over main AND fix-up launches, which come in pairs: two launches per step)
-        per_step = 2.0 * physics_traffic['hbm_bytes_per_launch']
-        physics['hbm_measured_GBps'] = per_step * stats.get('physics_launches', 0) / phys_s / 1e9
-        physics['traffic_over_algorithmic'] = per_step * stats.get('physics_launches', 0) / phys_bytes_total
+    physics = None
+    if args.full:
+        # the second kernel of a step, k_physics (main pass): per photon step it reads the hit entry (8 B), the photon's
+        # record (64 B) and the winning triangle's record (48 B), writes a survivor's record, next ray and queue slot
+        # (64 + 64 + 4 B) or a finished photon's ten array entries (64 B); every photon ends exactly once
+        phys_s = stats.get('physics_ms', 0.0) / 1e3
+        phys_bytes_per_step = 120.0 + 132.0 * (1.0 - 1.0 / steps_pp) + 64.0 / steps_pp
+        phys_bytes_total = phys_bytes_per_step * steps_pp * nphotons * args.steps
+        phys_launches = max(1, stats.get('physics_launches', 0))
+        physics = {'kernel': 'k_physics<%s>' % ('false' if gg_plain(gg) else 'true'), 'kernel_s': phys_s, 'launches': int(stats.get('physics_launches', 0)),
+                   'ms_per_batch': 1e3 * phys_s / args.steps,
+                   'algorithmic_bytes_per_photon_step': phys_bytes_per_step,
+                   'algorithmic_GBps': phys_bytes_total / phys_s / 1e9 if phys_s > 0 else None,
+                   'algorithmic_frac': phys_bytes_total / phys_s / 1e9 / HBM_PEAK_GBS if phys_s > 0 else None,
+                   'hbm_measured_GBps': None, 'traffic_over_algorithmic': None,
+                   'valu_lane_utilisation': physics_sq['valu_lane_utilisation'] if physics_sq else None,
+                   'wait_frac': physics_sq['wait_frac'] if physics_sq else None}
+        if physics_traffic and phys_s > 0:
+            # (the PMC figure is per launch over main AND fix-up launches, which come in pairs: two launches per step)
+            per_step = 2.0 * physics_traffic['hbm_bytes_per_launch']
+            physics['hbm_measured_GBps'] = per_step * stats.get('physics_launches', 0) / phys_s / 1e9
+            physics['traffic_over_algorithmic'] = per_step * stats.get('physics_launches', 0) / phys_bytes_total
 
     cpu_baseline = None
     if run_cpu:
@@ -654,6 +727,7 @@ def main():
                        'generation_order': generation, 'presorted': presorted, 'sort': sort_cost, 'exact_walk': exact_walk,
                        'exact_walk_photons_per_s': exact_walk['value'] if exact_walk else None,
                        'value_is': 'presorted' if SORT_DIRECTIONS else 'generation_order',
+                       'full': args.full,
                        'geometry_build_s': t_build, 'geometry_cached': geometry_cached, 'geometry_upload_s': t_upload,
                        'reduction': ('none: one GPU' if world == 1 and not os.environ.get('CHROMA_BENCH_COMM') else
                                      'library RCCL (chroma_allreduce_hits, in place on the device arrays)' if lib_comm else
@@ -661,6 +735,7 @@ def main():
             # achieved/frac: ALGORITHMIC bytes over the HIP-event time of the ray-cast launches (cache hits included, so
             # this is effective bandwidth); traffic: fabric-side bytes per launch from PMC counters of this very build,
             # hbm_measured_*: that traffic over the same launch time.  The kernel is latency-bound.
+            # (--full only: the figures rest on the counting pass; null in a plain run)
             'roofline': {'bound': 'hbm', 'kernel': RAYCAST_KERNEL, 'achieved': achieved, 'peak': HBM_PEAK_GBS,
                          'unit': 'GB/s', 'frac': achieved / HBM_PEAK_GBS, 'traffic': traffic, 'traffic_source': traffic_source,
                          'hbm_measured_GBps': measured, 'hbm_measured_frac': (measured / HBM_PEAK_GBS) if measured else None,
@@ -677,7 +752,7 @@ def main():
                          'kernel_s': ray_s, 'kernel_source_hash': src_hash,
                          'path': {'achieved': path_achieved, 'frac': path_achieved / HBM_PEAK_GBS,
                                   'algorithmic_bytes_per_photon': bytes_per_photon, 'launches': int(stats['launches']),
-                                  'kernel_s': kernel_s}},
+                                  'kernel_s': kernel_s}} if args.full else None,
             'cpu_baseline': cpu_baseline,
         }
         print(json.dumps(result), flush=True)

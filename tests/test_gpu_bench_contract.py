@@ -1,11 +1,12 @@
 """The one JSON line `bench.py` prints is a contract with the driver (metric, value, unit, n_gpus, steps, warmup,
-ms_per_step, higher_is_better, scaling, vs_baseline, dtype, data, config.workload + the `roofline` and `cpu_baseline`
-objects): run it as the driver does -- a child process -- on the smallest configuration and check the line."""
+ms_per_step, higher_is_better, scaling, vs_baseline, dtype, data, config.workload + with --full the `roofline` and
+`cpu_baseline` objects): run it as the driver does -- a child process -- on the smallest configuration and check the line."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -26,7 +27,7 @@ def _run(*extra):
 
 @pytest.mark.timeout(900)
 def test_bench_line_carries_the_contract():
-    j = _run()
+    j = _run('--full')
     assert j['metric'].startswith('photons/sec') and j['unit'] == 'photons/s' and j['higher_is_better'] is True
     assert j['n_gpus'] == 1 and j['steps'] == 2 and j['warmup'] == 1 and j['scaling'] == 'weak'
     assert j['vs_baseline'] is None and j['dtype'] == 'f32' and j['data'] == 'synthetic'
@@ -54,6 +55,30 @@ def test_bench_line_carries_the_contract():
 
 
 @pytest.mark.timeout(900)
+def test_plain_bench_line_and_its_dumped_outputs(tmp_path):
+    """A plain run (no --full) times the headline steps only and prints the same headline keys; --dump-outputs writes what
+    the last timed step computed, float32 / float64, at most 64 MB, and two runs with the same arguments write the same."""
+    runs = []
+    for name in ('a', 'b'):
+        j = _run('--dump-outputs', str(tmp_path / name))
+        assert j['metric'].startswith('photons/sec') and j['unit'] == 'photons/s' and j['higher_is_better'] is True and j['dtype'] == 'f32'
+        assert j['steps'] == 2 and j['warmup'] == 1 and j['config']['full'] is False
+        assert j['value'] > 1e7 and abs(j['value'] * j['ms_per_step'] * 1e-3 / j['config']['photons_per_gpu_per_step'] - 1.0) < 1e-6
+        assert j['config']['generation_order']['batches'] == 2          # (the headline loop's own per-step times)
+        assert j['roofline'] is None and j['cpu_baseline'] is None
+        assert j['config']['presorted'] is None and j['config']['exact_walk'] is None and j['config']['sort'] is None
+        runs.append({f.name: np.load(f) for f in sorted((tmp_path / name).iterdir())})
+    a, b = runs
+    assert sorted(a) == sorted(b) and {'channel_hit_count.npy', 'channel_earliest_time.npy', 'photon_pos.npy', 'hit_pos.npy'} <= set(a)
+    assert all(x.dtype in (np.float32, np.float64) for x in a.values()) and sum(x.nbytes for x in a.values()) <= 64 << 20
+    for name in a:
+        assert a[name].shape == b[name].shape and a[name].tobytes() == b[name].tobytes(), name
+    hits = int(a['hit_total.npy'][0])
+    assert hits > 0 and a['channel_hit_count.npy'].sum() == hits == len(a['hit_pos.npy'])       # (tiny: every hit is dumped)
+    assert len(a['photon_pos.npy']) == len(a['photon_index.npy']) == 1 << 18
+
+
+@pytest.mark.timeout(900)
 def test_bench_refuses_a_world_size_that_is_not_gpus():
     env = dict(os.environ, WORLD_SIZE='2', RANK='0', LOCAL_RANK='0')
     p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--config', 'tiny', '--gpus', '1', '--steps', '1', '--warmup', '0'],
@@ -75,7 +100,7 @@ def test_two_rank_flow_of_bench_rehearsed_over_gloo():
     env = dict(os.environ, CHROMA_BENCH_BACKEND='gloo', HSA_ENABLE_IPC_MODE_LEGACY='0')
     env.pop('CHROMA_BENCH_GEOMETRY_CACHE', None)
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
-           '--master-port', str(port), os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--config', 'tiny', '--steps', '2', '--warmup', '1']
+           '--master-port', str(port), os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--config', 'tiny', '--steps', '2', '--warmup', '1', '--full']
     p = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     lines = [l for l in p.stdout.decode().splitlines() if l.strip().startswith('{')]

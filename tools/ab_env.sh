@@ -6,5 +6,5 @@ for v in "$@"; do
   name=${parts[0]}
   ( if [ $name != base ]; then export CHROMA_HIP_LIBRARY=$PWD/build_variants/lib_$name.so; fi
     for kv in "${parts[@]:1}"; do export "$kv"; done
-    echo "== $v: $(python bench.py $args --no-cpu-baseline 2>&1 >/dev/null | grep 'timed' )" )
+    echo "== $v: $(python bench.py --full $args --no-cpu-baseline 2>&1 >/dev/null | grep 'timed' )" )
 done

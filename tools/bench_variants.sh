@@ -8,7 +8,7 @@ export CHROMA_BENCH_GEOMETRY_CACHE=/dev/shm/chroma_geo_cache CHROMA_BENCH_NO_EXA
 for cfg in c3 detector; do
   for v in "400nm_steps100:" "u400_800_steps100:--wavelength-hi 800" "400nm_steps10:--max-steps 10" "u400_800_steps10:--wavelength-hi 800 --max-steps 10"; do
     name=${v%%:*}; args=${v#*:}
-    python bench.py --config $cfg --steps 5 --warmup 1 --no-cpu-baseline $args > $out/bench_${cfg}_$name.json 2> $out/bench_${cfg}_$name.log || exit 1
+    python bench.py --full --config $cfg --steps 5 --warmup 1 --no-cpu-baseline $args > $out/bench_${cfg}_$name.json 2> $out/bench_${cfg}_$name.log || exit 1
     echo "$cfg $name: $(grep timed $out/bench_${cfg}_$name.log)"
   done
 done

@@ -1,6 +1,6 @@
 #!/bin/bash
 # PMC passes (one counter group per run, --pmc alone: no trace flags) for the bench command given as arguments.
-# usage: tools/pmc.sh OUTDIR python bench.py --config lite --steps 1 --warmup 0 --no-cpu-baseline
+# usage: tools/pmc.sh OUTDIR python bench.py --full --config lite --steps 1 --warmup 0 --no-cpu-baseline
 set -u
 out=$1; shift
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT

@@ -3,7 +3,7 @@
 # s_memtime around the phases of k_raycast_quad; a few waves of every large launch print their totals.
 # usage (GPU box): tools/quad_timing.sh OUT.txt
 export CHROMA_BENCH_GEOMETRY_CACHE=${CHROMA_BENCH_GEOMETRY_CACHE:-/dev/shm/chroma_geo_cache}
-CHROMA_HIP_LIBRARY=$PWD/build_variants/lib_timing.so python bench.py --no-cpu-baseline --steps 1 --warmup 0 2>&1 | grep -E "^QT|timed" > $1
+CHROMA_HIP_LIBRARY=$PWD/build_variants/lib_timing.so python bench.py --full --no-cpu-baseline --steps 1 --warmup 0 2>&1 | grep -E "^QT|timed" > $1
 python - "$1" <<'PY'
 import sys, collections
 rows = collections.defaultdict(list)
