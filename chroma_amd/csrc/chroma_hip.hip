@@ -586,6 +586,21 @@ __global__ void k_triangle_records(const float *vertices, const uint32_t *triang
         tri[(size_t)TRI_STRIDE * k + c] = make_float4(vv[0], vv[1], vv[2], __uint_as_float(extra[c]));
     }
 }
+// the 32-byte physics records (TriPhys, device_common.h), one per 48-byte record and in the same order: the normal by
+// fill_state's expression and the leaf box by the reference's rule, from the record's vertices, in k_physics's arithmetic
+__global__ void k_triangle_phys(GeoView g, uint32_t nrecords, uint4 *out)
+{
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= nrecords) return;
+    const float4 *t = g.tri + (size_t)TRI_STRIDE * k;
+    const float4 a = t[0], b = t[1], c = t[2];
+    const v3 v0 = mk3(a.x, a.y, a.z), v1 = mk3(b.x, b.y, b.z), v2 = mk3(c.x, c.y, c.z);
+    const v3 n = triangle_normal(v0, v1, v2);
+    uint32_t bx, by, bz;
+    leaf_words(g, v0, v1, v2, bx, by, bz);
+    out[2 * (size_t)k] = make_uint4(__float_as_uint(n.x), __float_as_uint(n.y), __float_as_uint(n.z), __float_as_uint(a.w));
+    out[2 * (size_t)k + 1] = make_uint4(__float_as_uint(b.w), bx, by, bz);
+}
 // Worst-case number of simultaneously live stack entries of the depth-first walk in
 // intersect_mesh for this tree (every box test succeeding).  Children always have larger
 // indices than their parent (layers are stored root first), so one backward sweep suffices.
@@ -1296,6 +1311,8 @@ int chroma_geometry_create(chroma_ctx *ctx, const chroma_geometry_desc *d, chrom
     { const float *p; if ((rc = upload(g, d->vertices, (size_t)d->nvertices * 3, &p)) != CHROMA_OK) { chroma_geometry_destroy(g); return rc; } g->d_vertices = (void *)p; }
     { const uint32_t *p; if ((rc = upload(g, d->triangles, (size_t)d->ntriangles * 3, &p)) != CHROMA_OK) { chroma_geometry_destroy(g); return rc; } g->d_triangles = (void *)p; }
     { const uint32_t *p; if ((rc = upload(g, d->material_codes, d->ntriangles, &p)) != CHROMA_OK) { chroma_geometry_destroy(g); return rc; } g->d_material_codes = (void *)p; }
+    memcpy(v.world_origin, d->world_origin, sizeof v.world_origin);   // (the leaf boxes of the physics records need them)
+    v.world_scale = d->world_scale;
     // 48-byte triangle records in device order: gathered on the device from those arrays (+ the ranks, uploaded for this only)
     {
         void *dtri = nullptr;
@@ -1317,6 +1334,20 @@ int chroma_geometry_create(chroma_ctx *ctx, const chroma_geometry_desc *d, chrom
         hipFree(d_rank);
         if (rc != CHROMA_OK) { chroma_geometry_destroy(g); return rc; }
         v.tri = (const float4 *)dtri;
+    }
+    // 32-byte physics records, in the same order: derived from the 48-byte ones (k_physics reads only these)
+    {
+        void *dphys = nullptr;
+        size_t bytes = std::max<size_t>(nrecords, 1) * 32;
+        hipError_t e = ctx_malloc(ctx, &dphys, bytes);
+        if (e != hipSuccess) { chroma_geometry_destroy(g); return set_error((int)e, "hipMalloc(%zu) for physics records: %s", bytes, hipGetErrorString(e)); }
+        g->allocations.push_back(dphys);
+        g->device_bytes += bytes;
+        if (nrecords) hipLaunchKernelGGL(k_triangle_phys, dim3((unsigned)((nrecords + 255) / 256)), dim3(256), 0, ctx->stream, v, (uint32_t)nrecords, (uint4 *)dphys);
+        e = hipStreamSynchronize(ctx->stream);
+        if (e == hipSuccess) e = hipGetLastError();
+        if (e != hipSuccess) { chroma_geometry_destroy(g); return set_error((int)e, "physics records: %s", hipGetErrorString(e)); }
+        v.tri_phys = (const uint4 *)dphys;
     }
     phase("triangle records");
     { const uint32_t *p; if ((rc = upload(g, d->colors, d->colors ? d->ntriangles : 0, &p)) != CHROMA_OK) { chroma_geometry_destroy(g); return rc; } g->d_colors = (void *)p; }
@@ -1353,8 +1384,6 @@ int chroma_geometry_create(chroma_ctx *ctx, const chroma_geometry_desc *d, chrom
     UP(dichroic_transmit, d->dichroic_transmit, d->ndichroic_angles_total * wn);
     UP(solid_id_to_channel_index, d->solid_id_to_channel_index, d->nsolids);
 #undef UP
-    memcpy(v.world_origin, d->world_origin, sizeof v.world_origin);
-    v.world_scale = d->world_scale;
     {   // ~16 ulp of the largest world coordinate (record_hit_is_regular)
         float maxabs = 0.0f;
         for (int a = 0; a < 3; a++)
@@ -1421,6 +1450,7 @@ int chroma_geometry_device_ptr(chroma_geometry *g, const char *name, void **d_pt
     else if (n == "solid_id_map") { p = (void *)g->view.solid_id_map; bytes = g->ntriangles * 4; }
     else if (n == "solid_id_to_channel_index") { p = (void *)g->view.solid_id_to_channel_index; bytes = (size_t)g->view.nsolids * 4; }
     else if (n == "triangle_records") { p = (void *)g->view.tri; bytes = g->nrecords * (16 * TRI_STRIDE); }
+    else if (n == "triangle_phys") { p = (void *)g->view.tri_phys; bytes = g->nrecords * 32; }
     else if (n == "wide_nodes") { p = (void *)g->view.wnodes; bytes = g->nwide * 128; }
     else if (n == "tri_to_dev") { p = (void *)g->view.tri_to_dev; bytes = g->ntriangles * 4; }
     else if (n == "dev_to_tri") { p = (void *)g->view.dev_to_tri; bytes = g->nrecords * 4; }

@@ -49,6 +49,10 @@ __device__ inline void store3(float *p, size_t i, v3 v) { p[3 * i] = v.x; p[3 * 
 //                                    one wide node -- tested together -- sit in adjacent 128-B lines.
 //                                    Both trees hold that "device" index in their leaves;
 //                                    tri_to_dev / dev_to_tri translate at ray start and end.
+//   tri_phys uint4[nrecords][2]      32 B physics record, in record order: {unit normal.xyz, material code}
+//                                    {triangle id, leaf words x, y, z}.  What k_physics needs of the winning
+//                                    triangle -- one aligned 32-B sector instead of the 48-B record, and the
+//                                    normal and leaf box computed once instead of on every step (TriPhys)
 //   tables  float[...]               optics tables, row-major [row][wavelength_n]
 struct SurfaceInfo { uint32_t model; uint32_t transmissive; float thickness; int32_t dichroic_index; };
 
@@ -61,6 +65,7 @@ struct GeoView {
     const uint4  *nodes;             // traversal copy: leaf child = device triangle index
     const uint4  *wnodes;            // derived 8-wide tree, 8 entries (128 B) per node
     const float4 *tri;               // [device triangle index][3]
+    const uint4  *tri_phys;          // [device triangle index][2]: the physics record (TriPhys)
     const uint32_t *tri_to_dev, *dev_to_tri;
     // materials
     const float *mat_refractive_index, *mat_absorption_length, *mat_scattering_length;
@@ -84,6 +89,17 @@ struct GeoView {
     uint32_t nnodes, ntriangles, nsolids, nchannels, nwide;
     uint32_t plain_optics;           // no re-emitting material component, every surface of the default model
 };
+
+// the physics record of a triangle, as k_physics reads it: normalize(cross(v1 - v0, v2 - v1)) (fill_state's
+// expression), the material code, the triangle id, and the leaf box by the reference's rule (leaf_words,
+// propagate_device.h); written by k_triangle_phys at geometry creation
+struct TriPhys { v3 normal; uint32_t code, id, bx, by, bz; };
+__device__ inline TriPhys load_tri_phys(const GeoView &g, size_t record)
+{
+    const uint4 *r = g.tri_phys + 2 * record;
+    const uint4 a = r[0], b = r[1];
+    return TriPhys{mk3(__uint_as_float(a.x), __uint_as_float(a.y), __uint_as_float(a.z)), a.w, b.x, b.y, b.z, b.w};
+}
 
 struct PhotonView {   // device pointers of chroma_photon_arrays
     float *pos, *dir, *pol, *wavelengths, *t;

@@ -63,7 +63,7 @@ k_physics(GeoView g, PhotonView pv, StepState *st, const float4 *work_in, uint32
         if (id < nthreads) {
             const int tri0 = hit_triangle[id];
             if (tri0 >= 0) {
-                const uint32_t code = __float_as_uint(g.tri[TRI_STRIDE * (size_t)tri0].w);
+                const uint32_t code = g.tri_phys[2 * (size_t)tri0].w;                    // (TriPhys::code)
                 const int surface = convert(0xFF & (code >> 8));                       // -1: no surface (a material boundary)
                 cls = 1u + (uint32_t)min(surface + 1, PHYS_CLASSES - 2);
             }
@@ -100,6 +100,10 @@ k_physics(GeoView g, PhotonView pv, StepState *st, const float4 *work_in, uint32
         const float4 w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3];
         int tri = hit_triangle[slot];
         const float hit_dist = hit_distance[slot];
+        // the winner's 32-byte physics record (normal, code, id, leaf box): all this pass reads of the triangle -- one
+        // aligned sector, where the 48-byte record (the ray cast's: it needs the vertices) straddles two 128-byte lines
+        // in a quarter of the gathers and leaves the normal and the box to be recomputed on every step
+        TriPhys rec = {};
         if (tri != HIT_RETRY) {
             photon_id = __float_as_uint(w3.w);
             p.position = mk3(w0.x, w0.y, w0.z);
@@ -109,15 +113,16 @@ k_physics(GeoView g, PhotonView pv, StepState *st, const float4 *work_in, uint32
                 p.direction = p.direction / norm(p.direction);           // (the same arithmetic as k_ray_setup: the ray's)
                 p.polarization = p.polarization / norm(p.polarization);
             }
+            if (tri >= 0) rec = load_tri_phys(g, (size_t)tri);
             if (!fixup && tri >= 0) {
-                // is the fast walk's winner one the reference is sure to find too?
-                const float4 *t = g.tri + TRI_STRIDE * (size_t)tri;
+                // is the fast walk's winner one the reference is sure to find too?  (asked of the stored leaf box: see
+                // phys_hit_is_plainly_regular, propagate_device.h, for why the cheap part is sufficient and sends no more
+                // hits round than the vertex form did)
                 // (the plain build leaves the exact question to k_raycast_retry: it is rare there -- hits within ulps of
                 //  a leaf box's upper face -- and its divisions cost registers; the all-models build asks it here, because
                 //  the geometries it serves (faces ON the world box: every hit "near a face") would send everything round)
-                const float4 ta = t[0], tb = t[1], tc = t[2];
-                const bool regular = FULL ? record_hit_is_regular(g, ta, tb, tc, p.position, p.direction, hit_dist)
-                                          : record_hit_is_plainly_regular(g, ta, tb, tc, p.position, p.direction, hit_dist);
+                const bool regular = FULL ? phys_hit_is_regular(g, rec, p.position, p.direction, hit_dist)
+                                          : phys_hit_is_plainly_regular(g, rec, p.position, p.direction, hit_dist);
                 if (!regular) {
                     retry_list[atomicAdd(&st->retry, 1u)] = (uint32_t)slot;
                     tri = HIT_RETRY;
@@ -130,7 +135,7 @@ k_physics(GeoView g, PhotonView pv, StepState *st, const float4 *work_in, uint32
             p.time = w1.w;
             p.weight = w2.w;
             p.history = __float_as_uint(w3.x);
-            p.last_hit_triangle = -1;                // (set by apply_hit_dev)
+            p.last_hit_triangle = -1;                // (set by apply_hit_phys / apply_hit_dev)
             p.evidx = 0;
             last_hit_record = __float_as_int(w3.z);
             cm_rng rng;
@@ -141,7 +146,8 @@ k_physics(GeoView g, PhotonView pv, StepState *st, const float4 *work_in, uint32
                 p.history |= CHROMA_NO_HIT | CHROMA_NAN_ABORT;
             } else {
                 State s;
-                apply_hit_dev(s, p, g, tri, hit_dist);
+                if (tri >= 0) apply_hit_phys(s, p, g, rec, hit_dist);
+                else apply_hit_dev(s, p, g, tri, hit_dist);      // (-1: no hit)
                 if (tri != -1) step_after_hit<FULL>(p, s, rng, g, use_weights != 0, scatter_first);
                 // (a photon scattered or absorbed in the bulk forgets the triangle, photon.h:232,262,283)
                 last_hit_record = (p.last_hit_triangle < 0) ? -1 : tri;

@@ -195,6 +195,32 @@ __device__ inline bool record_hit_is_regular(const GeoView &g, float4 a, float4 
 {
     return record_hit_is_plainly_regular(g, a, b, c, origin, direction, t) || record_hit_is_exactly_regular(g, a, b, c, origin, direction, t);
 }
+// The same two questions asked with the physics record (k_physics), which holds the leaf box itself.  Cheap part: the
+// hit point lies at least a margin (g.suspect_margin, ~16 ulp of the largest world coordinate) inside the float box
+// the reference evaluates, world_origin + q * world_scale, on every axis.  That is sufficient: the slab test's entry
+// and exit distances (lower or upper * 1/d + -o/d) and the hit point o + t d each round by a few ulp of the largest
+// coordinate (origins and boxes lie in the world box), far less than the margin, so tmin <= t <= tmax survives the
+// rounding -- the argument of the vertex form above, with the box the reference really tests instead of the vertices'.
+// It passes wherever the vertex form does, so it sends no more hits to k_raycast_retry: that form asks for
+// p >= min - ws/2 with the min at least a quantum above the box's lower face (p >= lower + ws/2 > lower + margin for a
+// world box within a few widths of the origin; a lower word of 0 is lower = world_origin exactly, and fine here), and
+// for p <= max - 2 margin with the upper face at most a few ulp below the max (p <= upper - margin).
+__device__ inline bool leaf_slab_plainly_contains(float p, uint32_t w, float org, float ws, float m)
+{
+    return p >= (org + (float)(w & 0xFFFFu) * ws) + m && p <= (org + (float)(w >> 16) * ws) - m;
+}
+__device__ inline bool phys_hit_is_plainly_regular(const GeoView &g, const TriPhys &r, v3 origin, v3 direction, float t)
+{
+    const float m = g.suspect_margin, ws = g.world_scale;
+    float px = origin.x + t * direction.x, py = origin.y + t * direction.y, pz = origin.z + t * direction.z;
+    return leaf_slab_plainly_contains(px, r.bx, g.world_origin[0], ws, m) && leaf_slab_plainly_contains(py, r.by, g.world_origin[1], ws, m) &&
+           leaf_slab_plainly_contains(pz, r.bz, g.world_origin[2], ws, m);
+}
+// the exact route is the reference's slab test on the stored box itself
+__device__ inline bool phys_hit_is_regular(const GeoView &g, const TriPhys &r, v3 origin, v3 direction, float t)
+{
+    return phys_hit_is_plainly_regular(g, r, origin, direction, t) || reference_tests_leaf(g, r.bx, r.by, r.bz, origin, direction, t);
+}
 
 // the leaf box of a triangle by the reference's rule (cuda/bvh.cu:149-203: truncate, one quantum down,
 // one up), for the lane-per-ray kernels, which do not carry the box of a postponed triangle
@@ -437,23 +463,17 @@ __device__ inline int convert(int c) { return (c & 0x80) ? (int)(0xFFFFFF00u | (
 __device__ inline float get_theta(v3 a, v3 b)                                                         // photon.h:77-81
 { return cm_acosf(cm_fmaxf(-1.0f, cm_fminf(1.0f, dot(a, b)))); }
 
-// fill_state (photon.h:83-135), the part after the ray cast.  The triangle record already holds
-// the three vertices and the material code, so the second triangle fetch of the reference is one
-// 48-B read (an L2 hit right after the cast).  `record` is the index of the triangle's record.
-__device__ inline void apply_hit_record(State &s, Photon &p, const GeoView &g, size_t record, float distance,
-                                        float4 a, float4 b, float4 c)
+// fill_state (photon.h:83-135), the part after the ray cast, given the triangle's unit normal (before the flip towards the
+// photon) and its material code: from the physics record (apply_hit_dev) or from the vertices (apply_hit_record).
+__device__ inline void apply_hit_normal(State &s, Photon &p, const GeoView &g, float distance, v3 normal, uint32_t material_code)
 {
     s.distance_to_boundary = distance;
-    v3 v0 = mk3(a.x, a.y, a.z), v1 = mk3(b.x, b.y, b.z), v2 = mk3(c.x, c.y, c.z);
-    uint32_t material_code = __float_as_uint(a.w);
 
     int inner_material_index = convert(0xFF & (material_code >> 24));
     int outer_material_index = convert(0xFF & (material_code >> 16));
     s.surface_index = convert(0xFF & (material_code >> 8));
 
-    v3 v01 = v1 - v0;
-    v3 v12 = v2 - v1;
-    s.surface_normal = normalize(cross(v01, v12));
+    s.surface_normal = normal;
 
     int material1, material2;
     if (dot(s.surface_normal, -p.direction) > 0.0f) {
@@ -470,6 +490,18 @@ __device__ inline void apply_hit_record(State &s, Photon &p, const GeoView &g, s
     s.scattering_length = interp_property(g, p.wavelength, row(g.mat_scattering_length, g, material1));
     s.material1 = material1;
 }
+// the triangle's unit normal as fill_state computes it (k_triangle_phys stores exactly this value)
+__device__ inline v3 triangle_normal(v3 v0, v3 v1, v3 v2)
+{
+    v3 v01 = v1 - v0;
+    v3 v12 = v2 - v1;
+    return normalize(cross(v01, v12));
+}
+// The 48-B triangle record form, for the callers that have the vertices in hand (the fused kernel).
+__device__ inline void apply_hit_record(State &s, Photon &p, const GeoView &g, float distance, float4 a, float4 b, float4 c)
+{
+    apply_hit_normal(s, p, g, distance, triangle_normal(mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), mk3(c.x, c.y, c.z)), __float_as_uint(a.w));
+}
 // by triangle id (fused kernel)
 __device__ inline void apply_hit(State &s, Photon &p, const GeoView &g, int triangle, float distance)
 {
@@ -481,7 +513,13 @@ __device__ inline void apply_hit(State &s, Photon &p, const GeoView &g, int tria
     }
     size_t record = g.tri_to_dev[triangle];
     const float4 *t = g.tri + TRI_STRIDE * record;
-    apply_hit_record(s, p, g, record, distance, t[0], t[1], t[2]);
+    apply_hit_record(s, p, g, distance, t[0], t[1], t[2]);
+}
+// by the physics record (its normal, code and triangle id) of the winning triangle
+__device__ inline void apply_hit_phys(State &s, Photon &p, const GeoView &g, const TriPhys &r, float distance)
+{
+    p.last_hit_triangle = (int)r.id;
+    apply_hit_normal(s, p, g, distance, r.normal, r.code);
 }
 // by record index (what the per-step ray cast hands over); the record names its triangle
 __device__ inline void apply_hit_dev(State &s, Photon &p, const GeoView &g, int record, float distance)
@@ -492,10 +530,7 @@ __device__ inline void apply_hit_dev(State &s, Photon &p, const GeoView &g, int 
         p.history |= CHROMA_NO_HIT;
         return;
     }
-    const float4 *t = g.tri + TRI_STRIDE * (size_t)record;
-    float4 a = t[0], b = t[1], c = t[2];
-    p.last_hit_triangle = (int)__float_as_uint(b.w);
-    apply_hit_record(s, p, g, (size_t)record, distance, a, b, c);
+    apply_hit_phys(s, p, g, load_tri_phys(g, (size_t)record), distance);
 }
 
 
