@@ -1,8 +1,10 @@
 """The reference's own timing harness for this path (chroma/benchmark.py:22-96): ``intersect``
 (ray intersections per second through distance_to_mesh), ``load_photons`` (host -> device photon
-upload rate) and ``propagate`` (photons per second, default max_steps=10, Morton-sorted isotropic
-bomb of U(400, 800) nm photons).  Returns (mean, std) of the rate instead of an ``uncertainties.ufloat``
-(that package is not a dependency here).  ``pdf`` / ``pdf_eval`` belong to the likelihood layer (out of scope).
+upload rate), ``propagate`` (photons per second, default max_steps=10, Morton-sorted isotropic
+bomb of U(400, 800) nm photons), ``pdf`` (events histogrammed per second) and ``pdf_eval`` (events
+accumulated into a PDF evaluation per second).  Returns (mean, std) of the rate instead of an
+``uncertainties.ufloat`` (that package is not a dependency here).  ``pdf`` and ``pdf_eval`` take a photon
+bomb of ``nphotons`` at the centre as their event, in place of the reference's GEANT4 100 MeV electron.
 """
 import ctypes
 import time
@@ -75,3 +77,68 @@ def propagate(gpu_detector, number=10, nphotons=500000, nthreads_per_block=64, m
             run_times.append(time.time() - t0)
         del gp
     return _rate(nphotons, run_times)
+
+
+def pdf(gpu_detector, npdfs=10, nevents=100, nreps=16, ndaq=1, nphotons=20000, nthreads_per_block=64, max_blocks=1024):
+    """Events histogrammed per second (mean, std) (chroma/benchmark.py:98-150): ``nevents`` bombs, each propagated
+    ``nreps`` times, each copy through ``ndaq`` DAQ acquisitions (one GPUDaq(ndaq) call) binned into (100 x 10)-bin
+    time and charge histograms per channel."""
+    ctx = gpu_detector.ctx
+    rng_states = gpu.get_rng_states(nthreads_per_block * max_blocks)
+    gpu_daq = gpu.GPUDaq(gpu_detector, ndaq=ndaq)
+    gpu_pdf = gpu.GPUPDF(ctx)
+    gpu_pdf.setup_pdf(gpu_detector.nchannels, 100, (-0.5, 999.5), 10, (-0.5, 9.5))
+    photons = _bomb(nphotons)
+    run_times = []
+    for i in range(npdfs):
+        t0 = time.time()
+        gpu_pdf.clear_pdf()
+        for _ in range(nevents):
+            gpu_photons = gpu.GPUPhotons(photons, ncopies=nreps)
+            gpu_photons.propagate(gpu_detector, rng_states, nthreads_per_block, max_blocks)
+            for gpu_photon_slice in gpu_photons.iterate_copies():
+                gpu_daq.begin_acquire()
+                gpu_daq.acquire(gpu_photon_slice, rng_states, nthreads_per_block, max_blocks)
+                gpu_pdf.add_hits_to_pdf(gpu_daq.end_acquire(), nthreads_per_block)
+        gpu_pdf.get_pdfs()
+        if i > 0:       # the first pass pays one-off costs
+            run_times.append(time.time() - t0)
+    return _rate(nevents * nreps * ndaq, run_times)
+
+
+def pdf_eval(gpu_detector, npdfs=10, nevents=25, nreps=16, ndaq=128, nphotons=20000, nthreads_per_block=64,
+             max_blocks=1024):
+    """Events accumulated into a PDF evaluation per second (mean, std) (chroma/benchmark.py:152-232): one bomb
+    through the DAQ is the data event; ``nevents`` bombs, each propagated ``nreps`` times, each copy's detected
+    photons through ``ndaq`` DAQ acquisitions (GPUDaq chunks of at most 64 copies, one accumulate call each)."""
+    ctx = gpu_detector.ctx
+    rng_states = gpu.get_rng_states(nthreads_per_block * max_blocks)
+    photons = _bomb(nphotons)
+    data_photons = gpu.GPUPhotons(photons)
+    data_photons.propagate(gpu_detector, rng_states, nthreads_per_block, max_blocks)
+    data_daq = gpu.GPUDaq(gpu_detector)
+    data_daq.begin_acquire()
+    data_daq.acquire(data_photons, rng_states, nthreads_per_block, max_blocks)
+    data_channels = data_daq.end_acquire().get()
+
+    daqs = [gpu.GPUDaq(gpu_detector, ndaq=min(64, ndaq - first)) for first in range(0, ndaq, 64)]
+    gpu_pdf = gpu.GPUPDF(ctx)
+    gpu_pdf.setup_pdf_eval(data_channels.hit, data_channels.t, data_channels.q, 0.05, (-0.5, 999.5), 1.0, (-0.5, 20),
+                           min_bin_content=20, time_only=True)
+    run_times = []
+    for i in range(npdfs):
+        t0 = time.time()
+        gpu_pdf.clear_pdf_eval()
+        for _ in range(nevents):
+            gpu_photons = gpu.GPUPhotons(photons, ncopies=nreps)
+            gpu_photons.propagate(gpu_detector, rng_states, nthreads_per_block, max_blocks)
+            for gpu_photon_slice in gpu_photons.iterate_copies():
+                detected = gpu_photon_slice.select(event.SURFACE_DETECT)
+                for gpu_daq in daqs:
+                    gpu_daq.begin_acquire()
+                    gpu_daq.acquire(detected, rng_states, nthreads_per_block, max_blocks)
+                    gpu_pdf.accumulate_pdf_eval(gpu_daq.end_acquire(), nthreads_per_block)
+        gpu_pdf.get_pdf_eval()
+        if i > 0:
+            run_times.append(time.time() - t0)
+    return _rate(nevents * nreps * ndaq, run_times)

@@ -15,6 +15,7 @@
 //   kernels_working_set.h         k_load_working, k_store_working
 //   kernels_photons_hits.h        photon-array kernels, hit extraction, k_finalize_hits
 //   kernels_daq_render.h          DAQ, distance_to_mesh, render, transforms, bomb generator, probe
+//   kernels_pdf.h                 per-channel PDFs over DAQ output: binning, PDF evaluation, moments, kernel estimate
 //   experimental/*.h              measured-and-not-faster kernels: ONLY in build_variants/libchroma_hip_experimental.so
 // See DESIGN.md for the data layout and what bounds each kernel.
 #include <hip/hip_runtime.h>
@@ -233,6 +234,8 @@ extern "C" hipError_t chroma_internal_malloc(chroma_ctx *ctx, void **ptr, size_t
 #include "kernels_photons_hits.h"
 
 #include "kernels_daq_render.h"
+
+#include "kernels_pdf.h"
 
 // ---------------------------------------------------------------------------------------------------
 // host helpers
@@ -2128,6 +2131,91 @@ int chroma_daq_convert(chroma_ctx *ctx, uint32_t nchannels, float charge_unit, c
     if (nchannels == 0) return CHROMA_OK;
     hipLaunchKernelGGL(k_daq_convert, dim3((nchannels + 255) / 256), dim3(256), 0, ctx->stream, nchannels, charge_unit,
                        d_earliest_time_int, d_channel_q_int, d_earliest_time, d_channel_q);
+    HIP_TRY(hipGetLastError());
+    return CHROMA_OK;
+}
+
+// ---- PDFs over DAQ output (kernels_pdf.h) ----
+static int check_pdf_layout(uint32_t nchannels, int32_t ndaq, uint32_t stride)
+{
+    if (ndaq < 1 || stride < nchannels)
+        return set_error(CHROMA_ERR_INVALID, "ndaq must be positive and the channel stride at least the number of channels");
+    return CHROMA_OK;
+}
+
+int chroma_pdf_bin_hits(chroma_ctx *ctx, uint32_t nchannels, int32_t ndaq, uint32_t stride, const float *d_channel_q,
+                        const float *d_channel_t, int32_t tbins, float tmin, float tmax, int32_t qbins, float qmin, float qmax,
+                        uint32_t *d_hitcount, uint32_t *d_pdf)
+{
+    if (!ctx || !d_channel_q || !d_channel_t || !d_hitcount || !d_pdf) return set_error(CHROMA_ERR_INVALID, "bad argument");
+    int rc = check_pdf_layout(nchannels, ndaq, stride); if (rc) return rc;
+    if (tbins < 1 || qbins < 1 || (int64_t)tbins * qbins > INT32_MAX)
+        return set_error(CHROMA_ERR_INVALID, "need at least one time and one charge bin (and fewer than 2^31 per channel)");
+    if (!(tmin < tmax) || !(qmin < qmax)) return set_error(CHROMA_ERR_INVALID, "empty or inverted time or charge range");
+    if (nchannels == 0) return CHROMA_OK;
+    std::lock_guard<std::mutex> call_lock(ctx->call_mu);
+    hipLaunchKernelGGL(k_pdf_bin_hits, dim3((nchannels + 255) / 256), dim3(256), 0, ctx->stream, nchannels, (int)ndaq, stride,
+                       d_channel_q, d_channel_t, d_hitcount, (int)tbins, tmin, tmax, (int)qbins, qmin, qmax, d_pdf);
+    HIP_TRY(hipGetLastError());
+    return CHROMA_OK;
+}
+
+int chroma_pdf_eval_accumulate(chroma_ctx *ctx, uint32_t nchannels, int32_t ndaq, uint32_t stride, const uint32_t *d_event_hit,
+                               const float *d_event_time, const float *d_mc_time, uint32_t nhit, const uint32_t *d_hit_channels,
+                               float min_twidth, float tmin, float tmax, int32_t min_bin_content, uint32_t *d_hitcount,
+                               uint32_t *d_bincount, float *d_nearest)
+{
+    if (!ctx || !d_event_hit || !d_event_time || !d_mc_time || !d_hitcount || !d_bincount || (nhit && (!d_hit_channels || !d_nearest)))
+        return set_error(CHROMA_ERR_INVALID, "bad argument");
+    int rc = check_pdf_layout(nchannels, ndaq, stride); if (rc) return rc;
+    if (min_bin_content < 1 || min_bin_content > 1024) return set_error(CHROMA_ERR_INVALID, "min_bin_content must be in 1 .. 1024");
+    if (!(tmin < tmax)) return set_error(CHROMA_ERR_INVALID, "empty or inverted time range");
+    if (nhit > nchannels) return set_error(CHROMA_ERR_INVALID, "more hit channels than channels");
+    if (nchannels == 0) return CHROMA_OK;
+    std::lock_guard<std::mutex> call_lock(ctx->call_mu);
+    hipLaunchKernelGGL(k_pdf_eval_hitcount, dim3((nchannels + 255) / 256), dim3(256), 0, ctx->stream, nchannels, (int)ndaq, stride,
+                       d_event_hit, d_mc_time, tmin, tmax, d_hitcount);
+    HIP_TRY(hipGetLastError());
+    if (nhit == 0) return CHROMA_OK;          // an event with no hit channel: nothing to sort
+    hipLaunchKernelGGL(k_pdf_eval_accumulate, dim3((nhit + PDF_EVAL_WAVES - 1) / PDF_EVAL_WAVES), dim3(64 * PDF_EVAL_WAVES), 0,
+                       ctx->stream, nchannels, (int)ndaq, stride, nhit, d_hit_channels, d_event_hit, d_event_time, d_mc_time,
+                       0.5f * min_twidth, tmin, tmax, (int)min_bin_content, d_hitcount, d_bincount, d_nearest);
+    HIP_TRY(hipGetLastError());
+    return CHROMA_OK;
+}
+
+int chroma_pdf_moments(chroma_ctx *ctx, int32_t time_only, uint32_t nchannels, int32_t ndaq, uint32_t stride, const float *d_mc_time,
+                       const float *d_mc_charge, float tmin, float tmax, float qmin, float qmax, uint32_t *d_mom0, float *d_t_mom1,
+                       float *d_t_mom2, float *d_q_mom1, float *d_q_mom2)
+{
+    if (!ctx || !d_mc_time || !d_mom0 || !d_t_mom1 || !d_t_mom2 || (!time_only && (!d_mc_charge || !d_q_mom1 || !d_q_mom2)))
+        return set_error(CHROMA_ERR_INVALID, "bad argument");
+    int rc = check_pdf_layout(nchannels, ndaq, stride); if (rc) return rc;
+    if (!(tmin < tmax) || (!time_only && !(qmin < qmax))) return set_error(CHROMA_ERR_INVALID, "empty or inverted time or charge range");
+    if (nchannels == 0) return CHROMA_OK;
+    std::lock_guard<std::mutex> call_lock(ctx->call_mu);
+    hipLaunchKernelGGL(k_pdf_moments, dim3((nchannels + 255) / 256), dim3(256), 0, ctx->stream, (int)(time_only != 0), nchannels,
+                       (int)ndaq, stride, d_mc_time, d_mc_charge, tmin, tmax, qmin, qmax, d_mom0, d_t_mom1, d_t_mom2, d_q_mom1, d_q_mom2);
+    HIP_TRY(hipGetLastError());
+    return CHROMA_OK;
+}
+
+int chroma_pdf_kernel_eval(chroma_ctx *ctx, int32_t time_only, uint32_t nchannels, int32_t ndaq, uint32_t stride,
+                           const uint32_t *d_event_hit, const float *d_event_time, const float *d_event_charge, const float *d_mc_time,
+                           const float *d_mc_charge, float tmin, float tmax, float qmin, float qmax, const float *d_inv_time_bandwidths,
+                           const float *d_inv_charge_bandwidths, uint32_t *d_hitcount, float *d_time_pdf_values,
+                           float *d_charge_pdf_values)
+{
+    if (!ctx || !d_event_hit || !d_event_time || !d_mc_time || !d_inv_time_bandwidths || !d_hitcount || !d_time_pdf_values ||
+        (!time_only && (!d_event_charge || !d_mc_charge || !d_inv_charge_bandwidths || !d_charge_pdf_values)))
+        return set_error(CHROMA_ERR_INVALID, "bad argument");
+    int rc = check_pdf_layout(nchannels, ndaq, stride); if (rc) return rc;
+    if (!(tmin < tmax) || (!time_only && !(qmin < qmax))) return set_error(CHROMA_ERR_INVALID, "empty or inverted time or charge range");
+    if (nchannels == 0) return CHROMA_OK;
+    std::lock_guard<std::mutex> call_lock(ctx->call_mu);
+    hipLaunchKernelGGL(k_pdf_kernel_eval, dim3((nchannels + 255) / 256), dim3(256), 0, ctx->stream, (int)(time_only != 0), nchannels,
+                       (int)ndaq, stride, d_event_hit, d_event_time, d_event_charge, d_mc_time, d_mc_charge, tmin, tmax, qmin, qmax,
+                       d_inv_time_bandwidths, d_inv_charge_bandwidths, d_hitcount, d_time_pdf_values, d_charge_pdf_values);
     HIP_TRY(hipGetLastError());
     return CHROMA_OK;
 }

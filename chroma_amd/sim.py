@@ -1,9 +1,10 @@
 """Simulation driver: batches events, propagates them on the GPU and extracts hits.
 
-Reference: chroma/sim.py:21-186 (``Simulation.__init__``, ``_simulate_batch``, ``simulate``).
+Reference: chroma/sim.py:21-343 (``Simulation.__init__``, ``_simulate_batch``, ``simulate``, and the PDF entry
+points ``create_pdf``, ``eval_pdf``, ``setup_kernel``, ``eval_kernel``).
 Out of scope here, as in SURVEY.md section 8: GEANT4 photon generation (``geant4_processes``
-is accepted; Event/Vertex inputs need a generator that this package does not provide), the
-PDF / likelihood entry points.
+is accepted; Event/Vertex inputs need a generator that this package does not provide).  The PDF entry points take
+Photons (or Events that carry ``photons_beg``) and run their DAQ acquisitions as GPUDaq(ndaq=K) chunks of at most 64.
 """
 import os
 import time
@@ -70,6 +71,10 @@ class Simulation(object):
         packed = None
         self.rng_states = gpu.get_rng_states(self.nthreads_per_block * self.max_blocks, seed=self.seed)
         self.pdf_config = None
+        # the PDF entry points' device state, made on first use: GPUPDF, GPUKernelPDF and GPUDaq(ndaq=K) per K
+        self._gpu_pdf = self._gpu_pdf_kernel = None
+        self._pdf_daqs = {}
+        self._pdf_acquisition = 0
 
     def _upload_batch(self, batch_events, upload=True):
         """The photons of all ``batch_events`` as one GPUPhotons (chroma/sim.py:66-72) + the events' bounds in it.
@@ -255,6 +260,123 @@ class Simulation(object):
             while pending:
                 lane, fut = pending.popleft()
                 yield from fut.result()
+
+    # ---- PDFs and likelihood terms (chroma/sim.py:188-343) ----------------------------------------------------------
+    @property
+    def gpu_pdf(self):
+        if self._gpu_pdf is None:
+            self._gpu_pdf = gpu.GPUPDF(self.context)
+        return self._gpu_pdf
+
+    @property
+    def gpu_pdf_kernel(self):
+        if self._gpu_pdf_kernel is None:
+            self._gpu_pdf_kernel = gpu.GPUKernelPDF(self.context)
+        return self._gpu_pdf_kernel
+
+    @staticmethod
+    def _photon_sets(iterable):
+        """The Photons of each item of ``iterable`` (Photons, or Events that carry photons_beg), as ``simulate`` takes them."""
+        if isinstance(iterable, event.Photons):
+            iterable = [iterable]
+        first, iterable = itertoolset.peek(iterable)
+        if isinstance(first, event.Photons):
+            return iterable
+        if isinstance(first, event.Event):
+            if first.photons_beg is None:
+                raise NotImplementedError('events without photons need the GEANT4 generator, which is out of scope')
+            return (ev.photons_beg for ev in iterable)
+        raise NotImplementedError('Vertex input needs the GEANT4 generator, which is out of scope')
+
+    def _daq_chunks(self, ndaq):
+        """GPUDaq objects for ``ndaq`` acquisitions of one photon set, at most 64 copies each."""
+        if ndaq < 1:
+            raise ValueError('ndaq must be at least 1')
+        for first in range(0, ndaq, 64):
+            k = min(64, ndaq - first)
+            if k not in self._pdf_daqs:
+                self._pdf_daqs[k] = gpu.GPUDaq(self.gpu_geometry, ndaq=k)
+            yield self._pdf_daqs[k]
+
+    def _acquire(self, daq, sources):
+        """One acquisition (``daq.ndaq`` copies) of the (photons, weight) ``sources``.  The PDF entry points' GPUDaq
+        objects share one acquisition counter, so two of them never draw the same random numbers for one photon."""
+        daq.acquisition = self._pdf_acquisition
+        daq.begin_acquire()
+        for photons, weight in sources:
+            daq.acquire(photons, self.rng_states, nthreads_per_block=self.nthreads_per_block, max_blocks=self.max_blocks,
+                        weight=weight)
+        self._pdf_acquisition = daq.acquisition
+        return daq.end_acquire()
+
+    def create_pdf(self, iterable, tbins, trange, qbins, qrange, nreps=1):
+        """Returns tuple: 1D array of channel hit counts, 3D array of (channel, time, charge) pdfs."""
+        photon_sets = self._photon_sets(iterable)
+        pdf_config = (tbins, trange, qbins, qrange)
+        if pdf_config != self.pdf_config:
+            self.pdf_config = pdf_config
+            self.gpu_pdf.setup_pdf(self.detector.num_channels(), tbins, trange, qbins, qrange)
+        else:
+            self.gpu_pdf.clear_pdf()
+        if nreps > 1:
+            photon_sets = (p for p in photon_sets for _ in range(nreps))
+        daq = next(self._daq_chunks(1))
+        for photons in photon_sets:
+            gpu_photons = gpu.GPUPhotons(photons)
+            gpu_photons.propagate(self.gpu_geometry, self.rng_states, nthreads_per_block=self.nthreads_per_block,
+                                  max_blocks=self.max_blocks)
+            self.gpu_pdf.add_hits_to_pdf(self._acquire(daq, [(gpu_photons, 1.0)]))
+        return self.gpu_pdf.get_pdfs()
+
+    def eval_pdf(self, event_channels, iterable, min_twidth, trange, min_qwidth, qrange, min_bin_content=100, nreps=1,
+                 ndaq=1, nscatter=1, time_only=True):
+        """Returns tuple: 1D array of channel hit counts, 1D array of PDF probability densities, 1D array of their
+        uncertainties.  Each photon set is propagated ``nreps`` times without scattering and ``nreps * nscatter`` times
+        scattering at the first step (weighted photons, chroma/sim.py:236-294); each of those runs through exactly
+        ``ndaq`` DAQ acquisitions, in chunks of at most 64 copies and one accumulate call per chunk."""
+        self.gpu_pdf.setup_pdf_eval(event_channels.hit, event_channels.t, event_channels.q, min_twidth, trange,
+                                    min_qwidth, qrange, min_bin_content=min_bin_content, time_only=True)
+        for photons in self._photon_sets(iterable):
+            gpu_photons_no_scatter = gpu.GPUPhotons(photons, ncopies=nreps)
+            gpu_photons_scatter = gpu.GPUPhotons(photons, ncopies=nreps * nscatter)
+            gpu_photons_no_scatter.propagate(self.gpu_geometry, self.rng_states, nthreads_per_block=self.nthreads_per_block,
+                                             max_blocks=self.max_blocks, use_weights=True, scatter_first=-1, max_steps=10)
+            gpu_photons_scatter.propagate(self.gpu_geometry, self.rng_states, nthreads_per_block=self.nthreads_per_block,
+                                          max_blocks=self.max_blocks, use_weights=True, scatter_first=1, max_steps=5)
+            nphotons = gpu_photons_no_scatter.true_nphotons
+            for i in range(nreps):
+                no_scatter = gpu_photons_no_scatter.select(event.SURFACE_DETECT, start_photon=i * nphotons, nphotons=nphotons)
+                if len(no_scatter) == 0:
+                    continue
+                sources = [(no_scatter, 1.0)]
+                sources += [(gpu_photons_scatter.select(event.SURFACE_DETECT, start_photon=(nscatter * i + j) * nphotons,
+                                                        nphotons=nphotons), 1.0 / nscatter) for j in range(nscatter)]
+                for daq in self._daq_chunks(ndaq):
+                    self.gpu_pdf.accumulate_pdf_eval(self._acquire(daq, sources))
+        return self.gpu_pdf.get_pdf_eval()
+
+    def _accumulate_copies(self, iterable, nreps, ndaq, accumulate):
+        for photons in self._photon_sets(iterable):
+            gpu_photons = gpu.GPUPhotons(photons, ncopies=nreps)
+            gpu_photons.propagate(self.gpu_geometry, self.rng_states, nthreads_per_block=self.nthreads_per_block,
+                                  max_blocks=self.max_blocks)
+            for gpu_photon_slice in gpu_photons.iterate_copies():
+                for daq in self._daq_chunks(ndaq):
+                    accumulate(self._acquire(daq, [(gpu_photon_slice, 1.0)]))
+
+    def setup_kernel(self, event_channels, bandwidth_iterable, trange, qrange, nreps=1, ndaq=1, time_only=True,
+                     scale_factor=1.0):
+        """Call this before eval_kernel(): sets up the event information and computes the kernel bandwidths."""
+        self.gpu_pdf_kernel.setup_moments(len(event_channels.hit), trange, qrange, time_only=time_only)
+        self._accumulate_copies(bandwidth_iterable, nreps, ndaq, self.gpu_pdf_kernel.accumulate_moments)
+        self.gpu_pdf_kernel.compute_bandwidth(event_channels.hit, event_channels.t, event_channels.q,
+                                              scale_factor=scale_factor)
+
+    def eval_kernel(self, event_channels, kernel_iterable, trange, qrange, nreps=1, ndaq=1, naverage=1, time_only=True):
+        """Returns tuple: 1D array of channel hit counts, 1D array of PDF probability densities, zeros."""
+        self.gpu_pdf_kernel.setup_kernel(event_channels.hit, event_channels.t, event_channels.q)
+        self._accumulate_copies(kernel_iterable, nreps, ndaq, self.gpu_pdf_kernel.accumulate_kernel)
+        return self.gpu_pdf_kernel.get_kernel_eval()
 
     def __del__(self):
         try:

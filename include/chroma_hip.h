@@ -369,6 +369,46 @@ int chroma_daq_acquire_many(chroma_ctx *ctx, chroma_geometry *geom, const chroma
 int chroma_daq_convert(chroma_ctx *ctx, uint32_t nchannels, float charge_unit, const uint32_t *d_earliest_time_int,
                        const uint32_t *d_channel_q_int, float *d_earliest_time, float *d_channel_q);
 
+/* ---- PDFs and likelihood terms over DAQ output (chroma/cuda/pdf.cu) ------------------------
+ * Every call reads the GPUChannels layout: `ndaq` copies of `nchannels` entries, copy i at
+ * [i * stride, i * stride + nchannels) (stride >= nchannels).  An MC time >= 1e8 means "not hit".
+ * The copies of a channel are taken in copy order, so one call over K copies gives the same bits as
+ * K calls of one copy each.  All arrays are device arrays, accumulated into; launches go on the
+ * context's stream.  CHROMA_ERR_INVALID for a bad layout, zero bins, an empty or inverted range. */
+/* `bin_hits` (pdf.cu:9-32): per channel, copies with t < 1e8, tmin <= t < tmax, qmin <= q < qmax
+ * (q truncated to an unsigned integer, negative -> 0) add 1 to hitcount and to the bin
+ * (channel, tbin, qbin) of the row-major uint32 histogram; bin indices clamped to the histogram. */
+int chroma_pdf_bin_hits(chroma_ctx *ctx, uint32_t nchannels, int32_t ndaq, uint32_t stride,
+                        const float *d_channel_q, const float *d_channel_t, int32_t tbins, float tmin,
+                        float tmax, int32_t qbins, float qmin, float qmax, uint32_t *d_hitcount,
+                        uint32_t *d_pdf);
+/* `accumulate_bincount` + `accumulate_nearest_neighbor` (pdf.cu:34-219): per channel, copies with
+ * an MC time < 1e8 inside [tmin, tmax] add 1 to hitcount; for the `nhit` channels the event hit,
+ * listed in d_hit_channels (each at most once; d_event_hit non-zero there), d = |mc - event_time|
+ * adds 1 to bincount when d < min_twidth / 2 and, while the running bincount is below
+ * min_bin_content (1 .. 1024), is a candidate for d_nearest[h * min_bin_content ...]: the
+ * min_bin_content smallest candidate distances of hit channel h so far, ascending, padded with 1e9
+ * (initialise it so). */
+int chroma_pdf_eval_accumulate(chroma_ctx *ctx, uint32_t nchannels, int32_t ndaq, uint32_t stride,
+                               const uint32_t *d_event_hit, const float *d_event_time, const float *d_mc_time,
+                               uint32_t nhit, const uint32_t *d_hit_channels, float min_twidth, float tmin,
+                               float tmax, int32_t min_bin_content, uint32_t *d_hitcount,
+                               uint32_t *d_bincount, float *d_nearest);
+/* `accumulate_moments` (pdf.cu:223-265): count, sum and sum of squares of the MC times (and charges
+ * unless time_only; the charge arrays may be NULL when time_only) inside the closed ranges. */
+int chroma_pdf_moments(chroma_ctx *ctx, int32_t time_only, uint32_t nchannels, int32_t ndaq, uint32_t stride,
+                       const float *d_mc_time, const float *d_mc_charge, float tmin, float tmax, float qmin,
+                       float qmax, uint32_t *d_mom0, float *d_t_mom1, float *d_t_mom2, float *d_q_mom1,
+                       float *d_q_mom2);
+/* `accumulate_kernel_eval` (pdf.cu:267-368): per channel, copies inside the closed ranges add 1 to
+ * hitcount and, on channels the event hit, a Gaussian kernel term (inverse bandwidths given per
+ * channel) normalised inside the window to the PDF values.  Charge arrays may be NULL when time_only. */
+int chroma_pdf_kernel_eval(chroma_ctx *ctx, int32_t time_only, uint32_t nchannels, int32_t ndaq, uint32_t stride,
+                           const uint32_t *d_event_hit, const float *d_event_time, const float *d_event_charge,
+                           const float *d_mc_time, const float *d_mc_charge, float tmin, float tmax, float qmin,
+                           float qmax, const float *d_inv_time_bandwidths, const float *d_inv_charge_bandwidths,
+                           uint32_t *d_hitcount, float *d_time_pdf_values, float *d_charge_pdf_values);
+
 /* Isotropic photon bomb generated on the device (the benchmark source of
  * chroma/benchmark.py:77-83, formulas chroma/sample.py:16-30), photon i drawn from
  * Philox stream (seed, 0xB0B0000000000000 + id_base + i).  wavelength_hi <= wavelength_lo
