@@ -604,6 +604,19 @@ __global__ void k_triangle_phys(GeoView g, uint32_t nrecords, uint4 *out)
     out[2 * (size_t)k] = make_uint4(__float_as_uint(n.x), __float_as_uint(n.y), __float_as_uint(n.z), __float_as_uint(a.w));
     out[2 * (size_t)k + 1] = make_uint4(__float_as_uint(b.w), bx, by, bz);
 }
+// the 48-byte intersection records (GeoView::tri_isect, device_common.h), one per triangle record and in the same order:
+// the edges by intersect_triangle's expressions (v1 - v0, v2 - v0 in float), laid out for intersect_triangle_edges
+__global__ void k_triangle_isect(GeoView g, uint32_t nrecords, float4 *out)
+{
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= nrecords) return;
+    const float4 *t = g.tri + (size_t)TRI_STRIDE * k;
+    const float4 a = t[0], b = t[1], c = t[2];
+    const v3 v0 = mk3(a.x, a.y, a.z), e1 = mk3(b.x, b.y, b.z) - v0, e2 = mk3(c.x, c.y, c.z) - v0;
+    out[3 * (size_t)k] = make_float4(e1.x, e2.x, e1.y, e2.y);
+    out[3 * (size_t)k + 1] = make_float4(e1.z, e2.z, v0.x, v0.y);
+    out[3 * (size_t)k + 2] = make_float4(v0.z, c.w, 0.0f, 0.0f);
+}
 // Worst-case number of simultaneously live stack entries of the depth-first walk in
 // intersect_mesh for this tree (every box test succeeding).  Children always have larger
 // indices than their parent (layers are stored root first), so one backward sweep suffices.
@@ -1352,6 +1365,20 @@ int chroma_geometry_create(chroma_ctx *ctx, const chroma_geometry_desc *d, chrom
         if (e != hipSuccess) { chroma_geometry_destroy(g); return set_error((int)e, "physics records: %s", hipGetErrorString(e)); }
         v.tri_phys = (const uint4 *)dphys;
     }
+    // 48-byte intersection records, in the same order: the edge form of the fast walks' triangle test
+    {
+        void *disect = nullptr;
+        size_t bytes = std::max<size_t>(nrecords, 1) * 48;
+        hipError_t e = ctx_malloc(ctx, &disect, bytes);
+        if (e != hipSuccess) { chroma_geometry_destroy(g); return set_error((int)e, "hipMalloc(%zu) for intersection records: %s", bytes, hipGetErrorString(e)); }
+        g->allocations.push_back(disect);
+        g->device_bytes += bytes;
+        if (nrecords) hipLaunchKernelGGL(k_triangle_isect, dim3((unsigned)((nrecords + 255) / 256)), dim3(256), 0, ctx->stream, v, (uint32_t)nrecords, (float4 *)disect);
+        e = hipStreamSynchronize(ctx->stream);
+        if (e == hipSuccess) e = hipGetLastError();
+        if (e != hipSuccess) { chroma_geometry_destroy(g); return set_error((int)e, "intersection records: %s", hipGetErrorString(e)); }
+        v.tri_isect = (const float4 *)disect;
+    }
     phase("triangle records");
     { const uint32_t *p; if ((rc = upload(g, d->colors, d->colors ? d->ntriangles : 0, &p)) != CHROMA_OK) { chroma_geometry_destroy(g); return rc; } g->d_colors = (void *)p; }
     UP(solid_id_map, d->solid_id_map, d->solid_id_map ? d->ntriangles : 0);
@@ -1454,6 +1481,7 @@ int chroma_geometry_device_ptr(chroma_geometry *g, const char *name, void **d_pt
     else if (n == "solid_id_to_channel_index") { p = (void *)g->view.solid_id_to_channel_index; bytes = (size_t)g->view.nsolids * 4; }
     else if (n == "triangle_records") { p = (void *)g->view.tri; bytes = g->nrecords * (16 * TRI_STRIDE); }
     else if (n == "triangle_phys") { p = (void *)g->view.tri_phys; bytes = g->nrecords * 32; }
+    else if (n == "triangle_isect") { p = (void *)g->view.tri_isect; bytes = g->nrecords * 48; }
     else if (n == "wide_nodes") { p = (void *)g->view.wnodes; bytes = g->nwide * 128; }
     else if (n == "tri_to_dev") { p = (void *)g->view.tri_to_dev; bytes = g->ntriangles * 4; }
     else if (n == "dev_to_tri") { p = (void *)g->view.dev_to_tri; bytes = g->nrecords * 4; }

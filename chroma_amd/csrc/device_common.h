@@ -14,6 +14,9 @@
 
 #define WAVE 64
 
+// two floats in one register pair: v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32 do the same IEEE operation on each half
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
 // ---- float3 algebra (operation order as chroma/cuda/linalg.h) -------------------------
 struct v3 { float x, y, z; };
 __device__ inline v3 mk3(float x, float y, float z) { return v3{x, y, z}; }
@@ -49,6 +52,11 @@ __device__ inline void store3(float *p, size_t i, v3 v) { p[3 * i] = v.x; p[3 * 
 //                                    one wide node -- tested together -- sit in adjacent 128-B lines.
 //                                    Both trees hold that "device" index in their leaves;
 //                                    tri_to_dev / dev_to_tri translate at ray start and end.
+//   tri_isect float4[nrecords][3]    48 B intersection record, in record order: {e1.x, e2.x, e1.y, e2.y}
+//                                    {e1.z, e2.z, v0.x, v0.y} {v0.z, rank, 0, 0} with e1 = v1 - v0, e2 = v2 - v0.
+//                                    What the fast walks' Moeller-Trumbore reads (intersect_triangle_edges): the
+//                                    edges computed once instead of in every test, and every packed operand of
+//                                    the test an aligned register pair straight from the three 16-B loads
 //   tri_phys uint4[nrecords][2]      32 B physics record, in record order: {unit normal.xyz, material code}
 //                                    {triangle id, leaf words x, y, z}.  What k_physics needs of the winning
 //                                    triangle -- one aligned 32-B sector instead of the 48-B record, and the
@@ -65,6 +73,7 @@ struct GeoView {
     const uint4  *nodes;             // traversal copy: leaf child = device triangle index
     const uint4  *wnodes;            // derived 8-wide tree, 8 entries (128 B) per node
     const float4 *tri;               // [device triangle index][3]
+    const float4 *tri_isect;         // [device triangle index][3]: the intersection record (intersect_triangle_edges)
     const uint4  *tri_phys;          // [device triangle index][2]: the physics record (TriPhys)
     const uint32_t *tri_to_dev, *dev_to_tri;
     // materials

@@ -245,9 +245,7 @@ k_raycast_literal(GeoView g, const float4 *rays, StepState *st, int32_t *hit_tri
             bool hit = false;
             float distance = 0.0f;
             if (waiting && (w_qm & jbit)) {
-                const float4 *tp = g.tri + TRI_STRIDE * (size_t)(w_node & ~CHROMA_NCHILD_MASK);
-                const float4 a = tp[0], b = tp[1], c = tp[2];
-                hit = intersect_triangle(origin, direction, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), mk3(c.x, c.y, c.z), distance);
+                hit = intersect_triangle_edges(origin, direction, g.tri_isect + 3 * (size_t)(w_node & ~CHROMA_NCHILD_MASK), distance);
             }
             const uint32_t hm = quad_or_u32(hit ? jbit : 0u);
             // Replay of mesh.h:74-108 over the chunk's four children in order.  Every lane of the quad fetches the four box
@@ -371,9 +369,7 @@ __device__ inline int literal_cast_group8(const GeoView &g, v3 origin, v3 direct
                 bool hit = false;
                 float distance = 0.0f;
                 if (is_tri) {
-                    const float4 *tp = g.tri + TRI_STRIDE * (size_t)(nd.w & ~CHROMA_NCHILD_MASK);
-                    const float4 a = tp[0], b = tp[1], c = tp[2];
-                    hit = intersect_triangle(origin, direction, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), mk3(c.x, c.y, c.z), distance);
+                    hit = intersect_triangle_edges(origin, direction, g.tri_isect + 3 * (size_t)(nd.w & ~CHROMA_NCHILD_MASK), distance);
                 }
                 const uint32_t hm = quad_or_u32(hit ? jbit : 0u);
                 const float t0 = quad_bcast_f32<0>(tmin), t1 = quad_bcast_f32<1>(tmin), t2 = quad_bcast_f32<2>(tmin), t3 = quad_bcast_f32<3>(tmin);

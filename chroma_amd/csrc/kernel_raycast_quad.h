@@ -21,8 +21,8 @@
 #define QUAD_REFILL_MIN 4    // refill once this many of the 16 rays are done
 #endif
 #ifndef QUAD_WAVES_PER_EU
-#define QUAD_WAVES_PER_EU 8  // 63 VGPRs; the one value that does not fit (the base of the global spill area) is reloaded from
-#endif                       // scratch in the rare deep-stack push only.  -4 % against 7 (68 VGPRs), profiles/r02/ab_quad_8waves.txt
+#define QUAD_WAVES_PER_EU 8  // 64 VGPRs, no scratch (the edge-form triangle test freed the registers of the vertex form's operand
+#endif                       // copies).  -4 % against 7 (68 VGPRs), profiles/r02/ab_quad_8waves.txt
 #ifndef QUAD_TIMING
 #define QUAD_TIMING 0        // diagnostic build: s_memtime stamps around the phases of a wave, printed by a few waves
 #endif
@@ -48,7 +48,6 @@ __device__ inline uint32_t quad_max_u32(uint32_t v)
 
 // box_interval_fast with the two faces of an axis as one packed operation (v_pk_fma_f32: same fused
 // multiply-add per half, half the issue slots)
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ inline void box_interval_pk(float ax, float ay, float az, f32x2 bx, f32x2 by, f32x2 bz, uint4 nd, float &tmin, float &tmax)
 {
     f32x2 qx = {(float)(nd.x & 0xFFFFu), (float)(nd.x >> 16)};
@@ -121,7 +120,8 @@ k_raycast_quad(GeoView g, const float4 *rays, int first_photon, StepState *st,
     // per-ray state, identical in the 4 lanes of a quad
     bool has_ray = false, active = false;
     int slot = 0;
-    float *ray_od = (float *)(stack_n + 2 * QUAD_STACK + QUAD_PENDING);      // origin, direction of this quad's ray
+    float *ray_od = (float *)(stack_n + 2 * QUAD_STACK + QUAD_PENDING);      // origin and direction of this quad's ray, by axis:
+                                                                             // o.x d.x o.y d.y o.z d.z (intersect_triangle_edges)
     float rax = 0.f, ray_ = 0.f, raz = 0.f; // RayFast::a (three scalars: as a struct it ended up in LDS), and {blo, bhi} per axis
     f32x2 rbx = {0.f, 0.f}, rby = {0.f, 0.f}, rbz = {0.f, 0.f};
     uint32_t rsx = 0, rsy = 0, rsz = 0;     // 16 for an axis the ray runs down (box_interval_signed)
@@ -164,7 +164,7 @@ k_raycast_quad(GeoView g, const float4 *rays, int first_photon, StepState *st,
                 const float4 r0 = r[0], r1 = r[1];
                 if (__float_as_int(r1.w) == 0) {                 // (other slots were settled by k_ray_setup)
                     const float4 r2 = r[2], r3 = r[3];
-                    if (j == 0) { ray_od[0] = r0.x; ray_od[1] = r0.y; ray_od[2] = r0.z; ray_od[3] = r1.x; ray_od[4] = r1.y; ray_od[5] = r1.z; }
+                    if (j == 0) { ray_od[0] = r0.x; ray_od[1] = r1.x; ray_od[2] = r0.y; ray_od[3] = r1.y; ray_od[4] = r0.z; ray_od[5] = r1.z; }
                     { const int lh = __float_as_int(r0.w); last_hit_w = lh >= 0 ? (0x80000000u | (uint32_t)lh) : WIDE_NONE; }
                     rax = r2.x; ray_ = r2.y; raz = r2.z;
                     { const float mx = r2.w * cm_fabsf(rax), my = r2.w * cm_fabsf(ray_), mz = r2.w * cm_fabsf(raz);       // (growth of the boxes: ray_growth)
@@ -316,11 +316,8 @@ k_raycast_quad(GeoView g, const float4 *rays, int first_photon, StepState *st,
                 if ((int)j < take) tri = pending[(phead + j) & (QUAD_PENDING - 1u)];
                 if ((int)j < take && (0x80000000u | tri) != last_hit_w) {
                     if (COUNT) cnt.tris++;
-                    const float4 *tp = g.tri + TRI_STRIDE * (size_t)tri;
-                    float4 a = tp[0], b = tp[1], c = tp[2];
-                    const v3 origin = mk3(ray_od[0], ray_od[1], ray_od[2]), direction = mk3(ray_od[3], ray_od[4], ray_od[5]);
-                    hit = intersect_triangle(origin, direction, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), mk3(c.x, c.y, c.z), distance);
-                    rank = __float_as_uint(c.w);
+                    hit = intersect_triangle_edges((f32x2){ray_od[0], ray_od[1]}, (f32x2){ray_od[2], ray_od[3]}, (f32x2){ray_od[4], ray_od[5]},
+                                                   g.tri_isect + 3 * (size_t)tri, distance, rank);
                 }
                 const uint32_t dkey = hit ? __float_as_uint(distance) : 0x7F800000u;
                 const uint32_t dmin = quad_min_u32(dkey);

@@ -96,10 +96,8 @@ __device__ inline int coop_cast(const GeoView &g, v3 origin, v3 direction, int l
                 if ((int)j < take) {
                     tri = pending[j];
                     if (COUNT) cnt.tris++;
-                    const float4 *tp = g.tri + TRI_STRIDE * (size_t)tri;
-                    float4 a = tp[0], b = tp[1], c = tp[2];
-                    hit = intersect_triangle(origin, direction, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), mk3(c.x, c.y, c.z), distance);
-                    rank = __float_as_uint(c.w);
+                    hit = intersect_triangle_edges((f32x2){origin.x, direction.x}, (f32x2){origin.y, direction.y}, (f32x2){origin.z, direction.z},
+                                                   g.tri_isect + 3 * (size_t)tri, distance, rank);
                 }
                 const float dm = group8_min(hit ? distance : inf);
                 if (dm < inf) {

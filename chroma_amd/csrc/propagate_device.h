@@ -85,6 +85,49 @@ __device__ inline bool intersect_triangle(v3 origin, v3 direction, v3 v0, v3 v1,
     return false;
 }
 
+// The same test over the intersection record (GeoView::tri_isect, written by k_triangle_isect): the edges e1 = v1 - v0 and
+// e2 = v2 - v0 come stored (the same float subtractions, done once), and the two cross products and the four dot products
+// run as packed pairs.  The ray comes as one pair per axis, r_c = (origin.c, direction.c); with s = origin - v0,
+//     S_c = (s.c, direction.c),  E_c = (e1.c, e2.c)                         [record words 0-5]
+//     (q.x, h.x) = S_y * E_z - S_z * E_y  (and cyclically)                   q = cross(s, e1), h = cross(direction, e2)
+//     (a, t')    = E_x * (h.x, q.x) + E_y * (h.y, q.y) + E_z * (h.z, q.z)    a = dot(e1, h),  t' = dot(e2, q)
+//     (u', v')   = S_x * (h.x, q.x) + S_y * (h.y, q.y) + S_z * (h.z, q.z)    u' = dot(s, h),  v' = dot(direction, q)
+// Every half is the scalar operation intersect_triangle does, on the same operands in the same order (a product's two
+// factors may trade places, which IEEE multiplication does not notice; sums keep their grouping), and a packed add or
+// multiply rounds each half like its scalar form: the result is the vertex form's bit for bit.
+// (rank: the record's tie-break rank; distance: written always, the hit distance where the result is true)
+__device__ inline bool intersect_triangle_edges(f32x2 rx, f32x2 ry, f32x2 rz, const float4 *rec, float &distance, uint32_t &rank)
+{
+    const float4 w0 = rec[0], w1 = rec[1], w2 = rec[2];
+    const f32x2 ex = {w0.x, w0.y}, ey = {w0.z, w0.w}, ez = {w1.x, w1.y};
+    const f32x2 sx = {rx.x - w1.z, rx.y}, sy = {ry.x - w1.w, ry.y}, sz = {rz.x - w2.x, rz.y};
+    rank = __float_as_uint(w2.y);
+    const f32x2 qx = sy * ez - sz * ey, qy = sz * ex - sx * ez, qz = sx * ey - sy * ex;
+    const f32x2 at = (ex * qx.yx + ey * qy.yx) + ez * qz.yx;
+    const f32x2 uv = (sx * qx.yx + sy * qy.yx) + sz * qz.yx;
+    // the tests of intersect_triangle, as one predicate: where an early return would have left, the values computed past
+    // it (a quotient by a tiny a, say) only feed a result that is discarded.  A wave whose lanes all leave at the same test
+    // is rare, so the branches saved nothing and cost their exec-mask bookkeeping
+    const float a = at.x;
+    const float f = 1.0f / a;
+    const f32x2 w = (f32x2){f, f} * uv;
+    const float u = w.x, v = w.y, t = f * at.y;
+    const bool hit = !(a > -FLT_EPSILON && a < FLT_EPSILON) & !(u < MT_NEG_EPS || u > MT_ONE_EPS) &
+                     !(v < MT_NEG_EPS || (u + v) > MT_ONE_EPS) & (t > MT_POS_EPS && t < cm_inff());
+    distance = t;                   // (meaningful where the test passes)
+    return hit;
+}
+// the ray held as two v3 (the lane-per-ray walks); like intersect_triangle, `distance` is written on a hit only
+__device__ inline bool intersect_triangle_edges(v3 origin, v3 direction, const float4 *rec, float &distance)
+{
+    uint32_t rank;
+    float t;
+    const bool hit = intersect_triangle_edges((f32x2){origin.x, direction.x}, (f32x2){origin.y, direction.y},
+                                              (f32x2){origin.z, direction.z}, rec, t, rank);
+    if (hit) distance = t;
+    return hit;
+}
+
 // Slab test of intersect_box (intersect.h:107-147) for one child, in the reference's arithmetic.
 // Returns tmin (the distance to the box) or -1 when the ray misses it.  For an axis the ray is exactly
 // parallel to (1/d = +-inf) the reference skips the slab altogether (intersect.h:115,124,133), which
@@ -370,10 +413,8 @@ __device__ inline int intersect_mesh_strict(const GeoView &g, v3 origin, v3 dire
                 if ((nd.w >> CHROMA_CHILD_BITS) == 0) {
                     if ((int)child == last_hit_record) continue;
                     if (COUNT) cnt.tris++;
-                    const float4 *t = g.tri + TRI_STRIDE * (size_t)child;
-                    float4 a = t[0], b = t[1], c = t[2];
                     float distance;
-                    if (intersect_triangle(origin, direction, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), mk3(c.x, c.y, c.z), distance)) {
+                    if (intersect_triangle_edges(origin, direction, g.tri_isect + 3 * (size_t)child, distance)) {
                         if (triangle_index == -1 || distance < min_distance) {
                             triangle_index = (int)child;
                             min_distance = distance;
