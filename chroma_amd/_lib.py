@@ -164,6 +164,13 @@ SIGNATURES = {
     'chroma_generate_bomb': (c_int32, [c_void_p, POINTER(PhotonArrays), c_uint64, c_uint64, c_uint64,
                                        POINTER(c_float), c_float, c_float]),
     'chroma_render': (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32]),
+    'chroma_hybrid_lookup': (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, POINTER(c_float), Rng, c_void_p, c_uint32,
+                                       c_float, POINTER(c_float), c_void_p, c_void_p, c_uint32, c_int32, c_void_p, c_void_p,
+                                       c_void_p, c_void_p]),
+    'chroma_hybrid_image': (c_int32, [c_void_p, c_void_p, c_int32, Rng, c_void_p, c_uint32, c_void_p, c_void_p, c_float,
+                                      POINTER(c_float), c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_int32, c_int32,
+                                      c_void_p, c_void_p, c_void_p]),
+    'chroma_hybrid_pixels': (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_int32]),
     'chroma_points_translate': (c_int32, [c_void_p, c_int32, c_void_p, POINTER(c_float)]),
     'chroma_points_rotate': (c_int32, [c_void_p, c_int32, c_void_p, c_float, POINTER(c_float)]),
     'chroma_color_solids': (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_uint32]),

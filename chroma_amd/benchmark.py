@@ -1,8 +1,9 @@
 """The reference's own timing harness for this path (chroma/benchmark.py:22-96): ``intersect``
 (ray intersections per second through distance_to_mesh), ``load_photons`` (host -> device photon
 upload rate), ``propagate`` (photons per second, default max_steps=10, Morton-sorted isotropic
-bomb of U(400, 800) nm photons), ``pdf`` (events histogrammed per second) and ``pdf_eval`` (events
-accumulated into a PDF evaluation per second).  Returns (mean, std) of the rate instead of an
+bomb of U(400, 800) nm photons), ``pdf`` (events histogrammed per second), ``pdf_eval`` (events
+accumulated into a PDF evaluation per second) and ``hybrid_render`` (the camera's hybrid mode: triangle samples
+and image rays per second).  Returns (mean, std) of the rate instead of an
 ``uncertainties.ufloat`` (that package is not a dependency here).  ``pdf`` and ``pdf_eval`` take a photon
 bomb of ``nphotons`` at the centre as their event, in place of the reference's GEANT4 100 MeV electron.
 """
@@ -142,3 +143,33 @@ def pdf_eval(gpu_detector, npdfs=10, nevents=25, nreps=16, ndaq=128, nphotons=20
         if i > 0:
             run_times.append(time.time() - t0)
     return _rate(nevents * nreps * ndaq, run_times)
+
+
+def hybrid_render(gpu_geometry, number=5, size=(800, 600), source_position=None, max_steps=10, seed=1):
+    """The camera's hybrid mode (GPUHybridRender; chroma/camera.py:188-249) from the camera's initial view: ((triangle
+    samples per second of one update_xyz_lookup: 3 wavelengths x every triangle), (image rays per second of one
+    update_image: 3 wavelengths x every pixel)), each (mean, std) over ``number`` timed passes after one untimed one.
+    The source sits at the camera unless ``source_position`` is given.  ``gpu_geometry`` must keep its Geometry."""
+    from chroma_amd.render_cli import camera_rays
+    ctx = gpu_geometry.ctx
+    point, pos, dirs = camera_rays(gpu_geometry.geometry, size)
+    rays = gpu.GPURays(pos, dirs, max_alpha_depth=1)
+    renderer = gpu.GPUHybridRender(gpu_geometry, rays, seed=seed, max_steps=max_steps)
+    source = point if source_position is None else source_position
+    lookup_times, image_times = [], []
+    for i in range(number + 1):
+        ctx.synchronize()
+        t0 = time.time()
+        renderer.clear_xyz_lookup()
+        renderer.update_xyz_lookup(source)
+        ctx.synchronize()
+        t1 = time.time()
+        renderer.clear_image()
+        renderer.update_image()
+        renderer.process_image()
+        ctx.synchronize()
+        t2 = time.time()
+        if i > 0:
+            lookup_times.append(t1 - t0)
+            image_times.append(t2 - t1)
+    return (_rate(3 * renderer.ntriangles, lookup_times), _rate(3 * renderer.npixels, image_times))

@@ -544,3 +544,23 @@ extern "C" int chroma_internal_direction_order(chroma_ctx *ctx, const float *d_d
     if (e != hipSuccess) return chroma_internal_set_error((int)e, "direction order: %s", hipGetErrorString(e));
     return CHROMA_OK;
 }
+
+// ---- a plain stable sort of (key, value) pairs for the other translation units (chroma_hybrid_lookup's records) ----------
+// Scratch from the context's pool, freed behind the stream's work.
+extern "C" int chroma_internal_sort_pairs(chroma_ctx *ctx, const uint32_t *d_keys, uint32_t *d_keys_out, const uint32_t *d_values,
+                                          uint32_t *d_values_out, uint32_t n, int end_bit)
+{
+    if (n == 0) return CHROMA_OK;
+    if (n >= 0x7fffffffu || end_bit < 1 || end_bit > 32) return chroma_internal_set_error(CHROMA_ERR_INVALID, "sort_pairs: bad argument");
+    hipStream_t stream = chroma_internal_stream(ctx);
+    size_t tmp_bytes = 0;
+    hipError_t e = hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, d_keys, d_keys_out, d_values, d_values_out, (int)n, 0, end_bit, stream);
+    if (e != hipSuccess) return chroma_internal_set_error((int)e, "sort_pairs: %s", hipGetErrorString(e));
+    void *tmp = nullptr;
+    int rc = chroma_malloc(ctx, std::max<size_t>(tmp_bytes, 4), &tmp);
+    if (rc != CHROMA_OK) return rc;
+    e = hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, d_keys, d_keys_out, d_values, d_values_out, (int)n, 0, end_bit, stream);
+    chroma_free(ctx, tmp);                 // (parked behind the sort)
+    if (e != hipSuccess) return chroma_internal_set_error((int)e, "sort_pairs: %s", hipGetErrorString(e));
+    return CHROMA_OK;
+}

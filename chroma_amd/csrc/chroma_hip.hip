@@ -39,6 +39,9 @@
 #ifndef CHROMA_EXPERIMENTAL
 #define CHROMA_EXPERIMENTAL 0      // 1: build_variants/libchroma_hip_experimental.so (csrc/experimental/: packet ray cast, dealt physics, autosort)
 #endif
+#ifndef CHROMA_HYBRID_RENDER
+#define CHROMA_HYBRID_RENDER 1     // 0 only for tests/test_hybrid_isa.py: the other kernels compiled without the hybrid render's
+#endif
 #include "propagate_device.h"
 #include "wide_build.h"
 #include "host_utils.h"
@@ -236,6 +239,10 @@ extern "C" hipError_t chroma_internal_malloc(chroma_ctx *ctx, void **ptr, size_t
 #include "kernels_daq_render.h"
 
 #include "kernels_pdf.h"
+
+#if CHROMA_HYBRID_RENDER
+#include "kernels_hybrid_render.h"
+#endif
 
 // ---------------------------------------------------------------------------------------------------
 // host helpers
@@ -2263,6 +2270,103 @@ int chroma_render(chroma_ctx *ctx, chroma_geometry *geom, int32_t nthreads, cons
     HIP_TRY(hipGetLastError());
     return CHROMA_OK;
 }
+
+#if CHROMA_HYBRID_RENDER
+// ---- the hybrid render (chroma/cuda/hybrid_render.cu as chroma/camera.py:188-249 drives it; kernels_hybrid_render.h) ----
+// Everything is checked before the first launch.  The two sample passes take the context's call lock: they run the step
+// functions and count stack overflows into the context's counters, as the propagate calls do.
+static int hybrid_check(chroma_ctx *ctx, chroma_geometry *geom, int32_t nthreads, const uint32_t *d_rng_counters, uint32_t ncounters,
+                        uint32_t nlookup, int32_t max_steps, const void *s_tri, const void *s_side, const void *s_history)
+{
+    if (!ctx || !geom || !d_rng_counters) return set_error(CHROMA_ERR_INVALID, "bad argument");
+    if (nthreads < 0) return set_error(CHROMA_ERR_INVALID, "negative thread count");
+    if ((uint32_t)nthreads > ncounters) return set_error(CHROMA_ERR_INVALID, "%d threads but %u rng counters", nthreads, ncounters);
+    if ((size_t)nlookup != geom->ntriangles)
+        return set_error(CHROMA_ERR_INVALID, "lookup tables of %u entries for %zu triangles", nlookup, geom->ntriangles);
+    if (geom->ntriangles >= 0x7fffffffu) return set_error(CHROMA_ERR_INVALID, "at most 2^31-2 triangles");
+    if (max_steps < 0) return set_error(CHROMA_ERR_INVALID, "max_steps %d is negative", max_steps);
+    if ((s_tri != nullptr) != (s_side != nullptr) || (s_tri != nullptr) != (s_history != nullptr))
+        return set_error(CHROMA_ERR_INVALID, "sample outputs: give all or none");
+    if (geom->stack_need > STACK_LDS + STACK_SCRATCH)
+        return set_error(CHROMA_ERR_STACK, "BVH needs %u traversal stack entries, more than the %d supported", geom->stack_need, STACK_LDS + STACK_SCRATCH);
+    return CHROMA_OK;
+}
+
+int chroma_hybrid_lookup(chroma_ctx *ctx, chroma_geometry *geom, int32_t nthreads, int32_t total_threads, int32_t offset,
+                         const float position[3], chroma_rng rng, uint32_t *d_rng_counters, uint32_t ncounters, float wavelength,
+                         const float xyz[3], float *d_lookup1, float *d_lookup2, uint32_t nlookup, int32_t max_steps,
+                         int32_t *d_sample_triangle, uint32_t *d_sample_side, uint32_t *d_sample_history, float *d_sample_cos)
+{
+    int rc = hybrid_check(ctx, geom, nthreads, d_rng_counters, ncounters, nlookup, max_steps, d_sample_triangle, d_sample_side,
+                          d_sample_history);
+    if (rc) return rc;
+    if (!position || !xyz || !d_lookup1 || !d_lookup2) return set_error(CHROMA_ERR_INVALID, "bad argument");
+    if ((d_sample_triangle != nullptr) != (d_sample_cos != nullptr)) return set_error(CHROMA_ERR_INVALID, "sample outputs: give all or none");
+    if (total_threads < 0 || offset < 0) return set_error(CHROMA_ERR_INVALID, "negative triangle range");
+    const int64_t end = std::min<int64_t>(std::min<int64_t>((int64_t)offset + nthreads, total_threads), (int64_t)geom->ntriangles);
+    const int64_t n = end - offset;                    // threads whose triangle exists; the rest return at once (draw nothing)
+    if (n <= 0) return CHROMA_OK;
+    const uint32_t key_none = 2u * (uint32_t)geom->ntriangles;            // past every (2 * triangle + side)
+    const int end_bit = 32 - __builtin_clz(key_none);
+    std::lock_guard<std::mutex> call_lock(ctx->call_mu);
+    void *buf[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};          // keys, ids, sorted keys, order, values
+    const size_t bytes[5] = {(size_t)n * 4, (size_t)n * 4, (size_t)n * 4, (size_t)n * 4, (size_t)n * 12};
+    for (int i = 0; i < 5 && rc == CHROMA_OK; i++) rc = chroma_malloc(ctx, bytes[i], &buf[i]);
+    uint32_t *keys = (uint32_t *)buf[0], *ids = (uint32_t *)buf[1], *sorted = (uint32_t *)buf[2], *order = (uint32_t *)buf[3];
+    float *values = (float *)buf[4];
+    if (rc == CHROMA_OK) {
+        hipLaunchKernelGGL((k_hybrid_lookup<STACK_LDS>), dim3((unsigned)((n + PROP_BLOCK - 1) / PROP_BLOCK)), dim3(PROP_BLOCK), 0,
+                           ctx->stream, geom->view, (int)n, (int)offset, position[0], position[1], position[2], rng.seed,
+                           rng.photon_id_base, d_rng_counters, wavelength, xyz[0], xyz[1], xyz[2], max_steps, key_none, keys, ids,
+                           values, d_sample_triangle, d_sample_side, d_sample_history, d_sample_cos, ctx->d_counters);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) rc = set_error((int)e, "k_hybrid_lookup: %s", hipGetErrorString(e));
+    }
+    if (rc == CHROMA_OK) rc = chroma_internal_sort_pairs(ctx, keys, sorted, ids, order, (uint32_t)n, end_bit);
+    if (rc == CHROMA_OK) {
+        hipLaunchKernelGGL(k_hybrid_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (int)n, sorted, order,
+                           values, key_none, d_lookup1, d_lookup2);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) rc = set_error((int)e, "k_hybrid_reduce: %s", hipGetErrorString(e));
+    }
+    for (void *p : buf) if (p) chroma_free(ctx, p);       // (parked behind the stream's work)
+    return rc;
+}
+
+int chroma_hybrid_image(chroma_ctx *ctx, chroma_geometry *geom, int32_t nthreads, chroma_rng rng, uint32_t *d_rng_counters,
+                        uint32_t ncounters, const float *d_positions, const float *d_directions, float wavelength, const float xyz[3],
+                        const float *d_lookup1, const float *d_lookup2, uint32_t nlookup, float *d_image, uint32_t nimage,
+                        int32_t nlookup_calls, int32_t max_steps, int32_t *d_sample_triangle, uint32_t *d_sample_side,
+                        uint32_t *d_sample_history)
+{
+    int rc = hybrid_check(ctx, geom, nthreads, d_rng_counters, ncounters, nlookup, max_steps, d_sample_triangle, d_sample_side,
+                          d_sample_history);
+    if (rc) return rc;
+    if (!d_positions || !d_directions || !xyz || !d_lookup1 || !d_lookup2 || !d_image) return set_error(CHROMA_ERR_INVALID, "bad argument");
+    if ((uint32_t)nthreads > nimage) return set_error(CHROMA_ERR_INVALID, "%d rays but an image of %u pixels", nthreads, nimage);
+    if (nlookup_calls < 1) return set_error(CHROMA_ERR_INVALID, "nlookup_calls must be at least 1");
+    if (nthreads == 0) return CHROMA_OK;
+    std::lock_guard<std::mutex> call_lock(ctx->call_mu);
+    hipLaunchKernelGGL((k_hybrid_image<STACK_LDS>), dim3((unsigned)((nthreads + PROP_BLOCK - 1) / PROP_BLOCK)), dim3(PROP_BLOCK), 0,
+                       ctx->stream, geom->view, (int)nthreads, rng.seed, rng.photon_id_base, d_rng_counters, d_positions, d_directions,
+                       wavelength, xyz[0], xyz[1], xyz[2], d_lookup1, d_lookup2, d_image, (int)nlookup_calls, max_steps,
+                       d_sample_triangle, d_sample_side, d_sample_history, ctx->d_counters);
+    HIP_TRY(hipGetLastError());
+    return CHROMA_OK;
+}
+
+int chroma_hybrid_pixels(chroma_ctx *ctx, int32_t nthreads, const float *d_image, uint32_t *d_pixels, int32_t nimages)
+{
+    if (!ctx || !d_image || !d_pixels) return set_error(CHROMA_ERR_INVALID, "bad argument");
+    if (nthreads < 0) return set_error(CHROMA_ERR_INVALID, "negative pixel count");
+    if (nimages < 1) return set_error(CHROMA_ERR_INVALID, "nimages must be at least 1");
+    if (nthreads == 0) return CHROMA_OK;
+    hipLaunchKernelGGL(k_hybrid_pixels, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, ctx->stream, (int)nthreads, d_image,
+                       d_pixels, (int)nimages);
+    HIP_TRY(hipGetLastError());
+    return CHROMA_OK;
+}
+#endif  // CHROMA_HYBRID_RENDER
 
 int chroma_color_solids(chroma_ctx *ctx, chroma_geometry *geom, int32_t first_triangle, int32_t ntriangles, const uint8_t *d_solid_hit,
                         const uint32_t *d_solid_colors, uint32_t nsolids)

@@ -137,11 +137,65 @@ def _color_solids(first_triangle, nthreads, solid_id_map, solid_hit, solid_color
                                             solid_colors.ptr, min(len(solid_hit), len(solid_colors))))
 
 
+# ---- chroma/cuda/hybrid_render.cu ---------------------------------------------------------------------------------
+# Both kernels of a camera share one rng_states (camera.py:189): thread k's draw counter is kept per rng_states object, so a
+# call continues the streams of the last one.  Thread k of every call draws from (seed, id base + k).
+_hybrid_counters = {}      # id(rng_states) -> (rng_counters GPUArray, chroma_rng)
+
+
+def _hybrid_stream(rng_states, nthreads, ctx):
+    key = id(rng_states)
+    if key not in _hybrid_counters:
+        size = max(int(getattr(rng_states, 'size', 0)), int(nthreads))
+        base = rng_states.reserve(size) if isinstance(rng_states, RNGStates) else 0
+        seed = rng_states.seed if isinstance(rng_states, RNGStates) else int(getattr(rng_states, 'seed', 0))
+        _hybrid_counters[key] = (zeros(size, np.uint32, ctx), _lib.Rng(seed & 0xFFFFFFFFFFFFFFFF, base))
+        weakref.finalize(rng_states, _hybrid_counters.pop, key, None)
+    return _hybrid_counters[key]
+
+
+def _float3_arg(v):
+    a = np.asarray(v)
+    vals = [a['x'], a['y'], a['z']] if a.dtype.fields else list(a.reshape(-1)[:3])
+    return (ctypes.c_float * 3)(*[float(np.asarray(x).reshape(-1)[0]) for x in vals])
+
+
+def _update_xyz_lookup(nthreads, total_threads, offset, position, rng_states, wavelength, xyz, xyz_lookup1, xyz_lookup2,
+                       max_steps, geometry, block=None, grid=None):
+    ctx = xyz_lookup1.ctx
+    counters, rng = _hybrid_stream(rng_states, _scalar(nthreads), ctx)
+    _lib.check(ctx._lib.chroma_hybrid_lookup(ctx.handle, geometry, _scalar(nthreads), _scalar(total_threads), _scalar(offset),
+                                             _float3_arg(position), rng, counters.ptr, counters.size, float(_scalar(wavelength)),
+                                             _float3_arg(xyz), xyz_lookup1.ptr, xyz_lookup2.ptr,
+                                             min(xyz_lookup1.size, xyz_lookup2.size), _scalar(max_steps), None, None, None, None))
+
+
+def _update_xyz_image(nthreads, rng_states, positions, directions, wavelength, xyz, xyz_lookup1, xyz_lookup2, image,
+                      nlookup_calls, max_steps, geometry, block=None, grid=None):
+    ctx = image.ctx
+    counters, rng = _hybrid_stream(rng_states, _scalar(nthreads), ctx)
+    if min(positions.size, directions.size) < _scalar(nthreads):
+        raise ValueError('%d threads but %d rays' % (_scalar(nthreads), min(positions.size, directions.size)))
+    _lib.check(ctx._lib.chroma_hybrid_image(ctx.handle, geometry, _scalar(nthreads), rng, counters.ptr, counters.size, positions.ptr,
+                                            directions.ptr, float(_scalar(wavelength)), _float3_arg(xyz), xyz_lookup1.ptr,
+                                            xyz_lookup2.ptr, min(xyz_lookup1.size, xyz_lookup2.size), image.ptr, image.size,
+                                            _scalar(nlookup_calls), _scalar(max_steps), None, None, None))
+
+
+def _process_image(nthreads, image, pixels, nimages, block=None, grid=None):
+    ctx = image.ctx
+    if _scalar(nthreads) > min(image.size, pixels.size):
+        raise ValueError('%d threads but %d pixels' % (_scalar(nthreads), min(image.size, pixels.size)))
+    _lib.check(ctx._lib.chroma_hybrid_pixels(ctx.handle, _scalar(nthreads), image.ptr, pixels.ptr, _scalar(nimages)))
+
+
 _MODULES = {
     'propagate.cu': {'photon_duplicate': _photon_duplicate, 'count_photons': _count_photons, 'copy_photons': _copy_photons,
                      'copy_photon_queue': _copy_photon_queue, 'count_photon_hits': _count_photon_hits,
                      'copy_photon_hits': _copy_photon_hits, 'propagate': _propagate},
     'mesh.h': {'distance_to_mesh': _distance_to_mesh, 'color_solids': _color_solids},
+    'hybrid_render.cu': {'update_xyz_lookup': _update_xyz_lookup, 'update_xyz_image': _update_xyz_image,
+                         'process_image': _process_image},
 }
 
 

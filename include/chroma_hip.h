@@ -435,6 +435,35 @@ int chroma_hits_sort(chroma_ctx *ctx, const chroma_photon_arrays *hits, int32_t 
  * front to back over bg_color into d_pixels [n] (0xAARRGGBB).  Directions are used as given (not normalised). */
 int chroma_render(chroma_ctx *ctx, chroma_geometry *geom, int32_t nthreads, const float *d_origin, const float *d_direction,
                   uint32_t alpha_depth, uint32_t *d_pixels, float *d_dx, uint32_t *d_dxlen, float *d_color, uint32_t bg_color);
+/* The hybrid render (chroma/cuda/hybrid_render.cu; chroma/camera.py:188-249 drives it).  Both sample passes follow a photon
+ * with the propagate physics (all models, no weights) to its FIRST diffuse reflection, and stop there, on any terminal
+ * outcome, on a miss, on the NaN abort or after max_steps steps.  Thread k draws from the Philox stream
+ * (rng.seed, rng.photon_id_base + k) starting at d_rng_counters[k], and writes the advanced counter back: the caller's
+ * counter array (ncounters entries) plays the part of the reference's rng_states.  Lookup tables and images are float3
+ * arrays; the tables hold one entry per triangle (nlookup must equal the triangle count).  Optional per-thread sample
+ * outputs (give all or none): the diffusing triangle or -1, its side (1 = inside to outside, the reference's
+ * State::inside_to_outside), the final history, and (lookup) cos_theta.  Sizes, ranges and max_steps >= 0 are checked
+ * before any launch (CHROMA_ERR_INVALID; CHROMA_ERR_STACK for a BVH deeper than the walk supports).
+ *
+ * chroma_hybrid_lookup (update_xyz_lookup): thread k samples triangle offset + k, for k < nthreads and offset + k below
+ * both total_threads and the triangle count (other threads draw nothing).  A sample whose ray from `position` first hits
+ * its own triangle and then diffuses adds cos_theta * xyz to the diffusing triangle's entry of d_lookup1 (inside to
+ * outside) or d_lookup2.  Deterministic: the contributions of one call are summed per (triangle, side) in sample order in
+ * f32, and each sum is added once to its entry.
+ * chroma_hybrid_image (update_xyz_image): ray k (k < nthreads <= nimage) adds xyz * lookup[triangle] / nlookup_calls
+ * (nlookup_calls >= 1) to d_image[k].
+ * chroma_hybrid_pixels (process_image): d_pixels[k] = 0xFF << 24 | r << 16 | g << 8 | b of d_image[k] / nimages
+ * (nimages >= 1), each channel clamped to [0, 1] (NaN to 0) and floorf(x * 255). */
+int chroma_hybrid_lookup(chroma_ctx *ctx, chroma_geometry *geom, int32_t nthreads, int32_t total_threads, int32_t offset,
+                         const float position[3], chroma_rng rng, uint32_t *d_rng_counters, uint32_t ncounters, float wavelength,
+                         const float xyz[3], float *d_lookup1, float *d_lookup2, uint32_t nlookup, int32_t max_steps,
+                         int32_t *d_sample_triangle, uint32_t *d_sample_side, uint32_t *d_sample_history, float *d_sample_cos);
+int chroma_hybrid_image(chroma_ctx *ctx, chroma_geometry *geom, int32_t nthreads, chroma_rng rng, uint32_t *d_rng_counters,
+                        uint32_t ncounters, const float *d_positions, const float *d_directions, float wavelength, const float xyz[3],
+                        const float *d_lookup1, const float *d_lookup2, uint32_t nlookup, float *d_image, uint32_t nimage,
+                        int32_t nlookup_calls, int32_t max_steps, int32_t *d_sample_triangle, uint32_t *d_sample_side,
+                        uint32_t *d_sample_history);
+int chroma_hybrid_pixels(chroma_ctx *ctx, int32_t nthreads, const float *d_image, uint32_t *d_pixels, int32_t nimages);
 /* `color_solids` (chroma/cuda/mesh.h:153-166; host: GPUGeometry.color_solids, chroma/gpu/geometry.py:283-298): triangle t of
  * [first_triangle, first_triangle + ntriangles) takes d_solid_colors[solid_id_map[t]] where d_solid_hit[solid_id_map[t]] is set
  * (one byte per solid, as numpy bool); both arrays hold `nsolids` entries, a triangle of a solid beyond them keeps its colour.
