@@ -32,6 +32,7 @@
 #include <mutex>
 #include <unordered_map>
 #include <map>
+#include <type_traits>
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>          // types and prototypes only: RCCL itself is found with dlopen at first use
@@ -126,11 +127,10 @@ struct chroma_ctx {
     uint2 *coop_spill = nullptr;           // [coop_waves][8][COOP_SPILL]
     int ray_chunk = 256, coop_chunk = 64;  // rays a persistent wave takes from the queue per atomic (big batches)
     int claim_static = 5 | 8 << 4;                  // eighths of a wave's share of a launch's rays that it takes without the counter (k_raycast_quad; CHROMA_CLAIM_STATIC)
-    int fused_tail = 1;                    // 0 (CHROMA_TAIL=split): the last photons also take one launch set per step
-    int split_tail = 1;                    // 0 (CHROMA_TAIL=fused): chroma_propagate launches the fused kernel only, as the reference does
+    int tail_mode = CHROMA_TAIL_COOP;      // CHROMA_TAIL_*: the last photons in k_tail_coop | one launch set per step to the end | k_propagate only
     int autosort_mode = 0;                 // the order a large call takes its photons up in: 0 as they come (default: the index sort + gather cost more than they gain, profiles/r03/ab_autosort.txt), 1 by direction cell, 2 decided by a probe (propagate_order)
     int packet_mode = 0;                   // k_raycast_packet for the first step: 0 never (default: it is not faster, profiles/r03/ab_packet_first_step.txt), 1 always, 2 when the photons are coherent (CHROMA_PACKET=off|on|auto)
-    int wide_walk = CHROMA_WALK_QUAD;      // CHROMA_WALK_*: reference tree | wide tree with 1, 8 or 4 (default) lanes per ray
+    int walk = CHROMA_WALK_QUAD;           // CHROMA_WALK_*: reference tree | wide tree with 1, 8 or 4 (default) lanes per ray
     hipEvent_t ev_start = nullptr, ev_stop = nullptr, ev_mid = nullptr;
     // the one exchange of the path (per-channel hit arrays): an RCCL communicator over the node's GPUs
     ncclComm_t comm = nullptr;
@@ -174,18 +174,6 @@ struct chroma_geometry {
     uint32_t stack_need = 0, wide_depth = 0, wide_stack_need = 0;
     size_t device_bytes = 0;
 };
-
-// What one call does, fixed when it starts: the context's settings (chroma_set_walk / _tail / _packet / _autosort / _counting,
-// the CHROMA_* environment) overridden by the call's own chroma_propagate_options.  Every function below a public entry
-// point reads THIS, never the context's mutable settings, so a call's behaviour cannot change under it.
-struct CallOpts {
-    int walk, packet, autosort, counting;
-    int fused_tail, split_tail;
-};
-static CallOpts call_opts(const chroma_ctx *ctx)
-{
-    return CallOpts{ctx->wide_walk, ctx->packet_mode, ctx->autosort_mode, ctx->counting, ctx->fused_tail, ctx->split_tail};
-}
 
 // hipMalloc for the library's own working buffers: when the device is out of memory, everything parked in the pool
 // behind chroma_malloc / chroma_free is given back first (defined next to the pool)
@@ -265,60 +253,138 @@ static int check_photons(const chroma_photon_arrays *a, bool need_rng)
 }
 
 
-template <bool COUNT>
-static int launch_propagate_t(chroma_ctx *ctx, const CallOpts &co, chroma_geometry *geom, PhotonView pv, int first, int nthreads,
-                              const uint32_t *in_q, uint32_t *out_q, chroma_rng rng, int max_steps, int use_weights,
-                              int scatter_first)
+// f(std::integral_constant<bool, B>{}): one launch site for both instantiations of a kernel template
+template <class F>
+static void with_bool(bool b, F &&f)
 {
-    dim3 grid((unsigned)((nthreads + PROP_BLOCK - 1) / PROP_BLOCK)), block(PROP_BLOCK);
-    uint32_t need = geom->stack_need;
-#define LAUNCH(N)                                                                                         \
-    hipLaunchKernelGGL((k_propagate<N, COUNT>), grid, block, 0, ctx->stream, geom->view, pv, first, nthreads, \
-                       in_q, out_q, rng.seed, rng.photon_id_base, max_steps, use_weights, scatter_first, ctx->d_counters)
-    if (need <= STACK_LDS + STACK_SCRATCH) LAUNCH(STACK_LDS);
-    else return set_error(CHROMA_ERR_STACK, "BVH needs %u traversal stack entries, more than the %d supported", need, STACK_LDS + STACK_SCRATCH);
-#undef LAUNCH
+    if (b) f(std::true_type{}); else f(std::false_type{});
+}
+
+// the reference's tree with STACK_LDS entries in LDS and the rest in scratch: k_propagate, the persistent cast and the strict
+// retry loop walk it, so every call may
+static int check_stack(const chroma_geometry *geom)
+{
+    if (geom->stack_need <= STACK_LDS + STACK_SCRATCH) return CHROMA_OK;
+    return set_error(CHROMA_ERR_STACK, "BVH needs %u traversal stack entries, more than the %d supported", geom->stack_need,
+                     STACK_LDS + STACK_SCRATCH);
+}
+
+// The ray cast of a device step.  The exact walks run the reference's own loop for every ray (mesh.h:42-118 as it stands:
+// its tree, its order, its box arithmetic, every triangle tested the moment its leaf box is entered) and k_physics takes
+// their results as they are: LITERAL with four lanes per ray (k_raycast_literal) and the strict lane-per-ray loop for the few
+// rays whose 1/d is not moderate, LITERAL_LANE with the strict loop for every ray (the cross-check).  The others walk the
+// wide tree (WIDE 1, COOP 8, QUAD 4, PAIR 2 lanes per ray) or the reference's tree (PERSISTENT) and hand the rays they cannot
+// settle to k_raycast_retry.
+enum class Cast { PERSISTENT, WIDE, COOP, QUAD, PAIR, LITERAL, LITERAL_LANE };
+enum SpillKind : unsigned { SPILL_COOP = 1, SPILL_WIDE = 2 };
+
+// What one call runs, fixed when it starts: the context's settings (chroma_set_walk / _tail / _packet / _autosort / _counting,
+// the CHROMA_* environment) overridden by the call's own chroma_propagate_options, resolved against the geometry.  Every
+// function below a public entry point reads THIS, never the context's mutable settings, so a call cannot change under it.
+struct CallPlan {
+    int tail_mode;       // CHROMA_TAIL_*
+    bool counting;
+    Cast cast;           // what every device step runs
+    bool chain;          // the ray records go from kernel to kernel (k_load_working -> ray cast -> k_physics -> ...): no k_ray_setup
+    bool tail_watch;     // near the end the host reads the survivor count every step, to start the tail when the reference does
+    bool tail;           // ... and k_tail_coop can walk this geometry: it takes the last photons
+    bool isect_quad;     // chroma_intersect_mesh casts with k_raycast_quad
+    unsigned spill;      // SpillKind buffers the steps and the tail use
+    int packet;          // experimental: k_raycast_packet offered for the first step (chroma_set_packet's mode), or 0
+    int autosort;        // experimental: chroma_set_autosort's mode, or 0
+};
+
+// `walk`, `tail`, `counting`: the call's choice, or -1 for the context's
+static int make_plan(const chroma_ctx *ctx, const chroma_geometry *geom, int walk, int tail, int counting, CallPlan *plan)
+{
+    if (walk > CHROMA_WALK_LITERAL_LANE) return set_error(CHROMA_ERR_INVALID, "unknown walk mode %d", walk);
+    if (tail > CHROMA_TAIL_FUSED) return set_error(CHROMA_ERR_INVALID, "unknown tail mode %d", tail);
+    const int w = walk >= 0 ? walk : ctx->walk;
+    CallPlan p = {};
+    p.tail_mode = tail >= 0 ? tail : ctx->tail_mode;
+    p.counting = counting >= 0 ? counting != 0 : ctx->counting != 0;
+    // which fast walks' stacks (LDS part + global spill) hold the wide tree
+    const bool wide = geom->view.wnodes != nullptr;
+    const uint32_t ws = geom->wide_stack_need;
+    const bool fits_pair = wide && ws <= PAIR_STACK + COOP_SPILL, fits_quad = wide && ws <= QUAD_STACK + COOP_SPILL,
+               fits_coop = wide && ws <= COOP_STACK + COOP_SPILL, fits_wide = wide && ws <= WIDE_STACK + WIDE_SPILL;
+    // a fast walk whose stack is too shallow for the tree falls back to the next one (PAIR never to COOP)
+    p.cast = w == CHROMA_WALK_LITERAL ? Cast::LITERAL
+           : w == CHROMA_WALK_LITERAL_LANE ? Cast::LITERAL_LANE
+           : w == CHROMA_WALK_PAIR && fits_pair ? Cast::PAIR
+           : (w == CHROMA_WALK_QUAD || w == CHROMA_WALK_PAIR) && fits_quad ? Cast::QUAD
+           : (w == CHROMA_WALK_COOP || w == CHROMA_WALK_QUAD) && fits_coop ? Cast::COOP
+           : w != CHROMA_WALK_REFERENCE && fits_wide ? Cast::WIDE
+           : Cast::PERSISTENT;
+    // (a PAIR walk that fell back to the quad kernel keeps the k_ray_setup pass)
+    p.chain = p.cast == Cast::LITERAL || (p.cast == Cast::QUAD && w == CHROMA_WALK_QUAD);
+    // (the cross-check walks keep per-step launches to the end)
+    p.tail_watch = p.tail_mode == CHROMA_TAIL_COOP && (w == CHROMA_WALK_COOP || w == CHROMA_WALK_QUAD || w == CHROMA_WALK_PAIR ||
+                                                      w == CHROMA_WALK_LITERAL);
+    p.tail = p.tail_watch && fits_coop;
+    p.isect_quad = fits_coop && w != CHROMA_WALK_REFERENCE && w != CHROMA_WALK_LITERAL && w != CHROMA_WALK_LITERAL_LANE;
+    if (p.tail_mode != CHROMA_TAIL_FUSED) {
+        const bool coop_stack = p.cast == Cast::COOP || p.cast == Cast::QUAD || p.cast == Cast::PAIR || p.cast == Cast::LITERAL;
+        p.spill = (coop_stack || p.tail ? SPILL_COOP : 0u) | (p.cast == Cast::WIDE ? SPILL_WIDE : 0u);
+    }
+    if (p.chain && p.cast == Cast::QUAD) {
+        p.autosort = ctx->autosort_mode;
+#if CHROMA_EXPERIMENTAL
+        if (ws <= PACKET_STACK) p.packet = ctx->packet_mode;
+#endif
+    }
+    *plan = p;
+    return CHROMA_OK;
+}
+
+// the global-memory parts of the fast walks' stacks, allocated at first use.  Every cooperative walk indexes the coop one
+// with (wave * rays-per-wave + ray) * COOP_SPILL, so it is sized for the largest grid of any of them.
+static int ensure_spill(chroma_ctx *ctx, unsigned kinds)
+{
+    if ((kinds & SPILL_COOP) && !ctx->coop_spill) {
+        const size_t rays = std::max(std::max((size_t)ctx->coop_waves * 8, (size_t)ctx->quad_waves * 16), (size_t)ctx->pair_waves * 32);
+        HIP_TRY(hipSetDevice(ctx->device));
+        HIP_TRY(ctx_malloc(ctx, (void **)&ctx->coop_spill, rays * COOP_SPILL * sizeof(uint2)));
+    }
+    if ((kinds & SPILL_WIDE) && !ctx->wide_spill) {
+        HIP_TRY(hipSetDevice(ctx->device));
+        HIP_TRY(ctx_malloc(ctx, (void **)&ctx->wide_spill, (size_t)ctx->wide_waves * WIDE_SPILL * PROP_BLOCK * sizeof(uint2)));
+    }
+    return CHROMA_OK;
+}
+
+// the ray cast's grid: one wave per 8 (COOP), 16 (QUAD, LITERAL), 32 (PAIR) or 64 rays, up to the kernel's resident waves
+static unsigned cast_waves(const chroma_ctx *ctx, Cast cast, long long n)
+{
+    long long per = PROP_BLOCK, cap = ctx->persistent_waves;
+    switch (cast) {
+    case Cast::PAIR: per = 32; cap = ctx->pair_waves; break;
+    case Cast::QUAD: case Cast::LITERAL: per = 16; cap = ctx->quad_waves; break;
+    case Cast::COOP: per = 8; cap = ctx->coop_waves; break;
+    case Cast::WIDE: cap = ctx->wide_waves; break;
+    default: break;
+    }
+    return (unsigned)std::min<long long>((n + per - 1) / per, cap);
+}
+
+// the lane-per-photon kernel with the reference's launch shape (CHROMA_TAIL=fused, chroma_propagate_step)
+static int launch_propagate(chroma_ctx *ctx, bool counting, chroma_geometry *geom, PhotonView pv, int first, int nthreads,
+                            const uint32_t *in_q, uint32_t *out_q, chroma_rng rng, int max_steps, int use_weights, int scatter_first)
+{
+    const dim3 grid((unsigned)((nthreads + PROP_BLOCK - 1) / PROP_BLOCK)), block(PROP_BLOCK);
+    with_bool(counting, [&](auto C) {
+        hipLaunchKernelGGL((k_propagate<STACK_LDS, C>), grid, block, 0, ctx->stream, geom->view, pv, first, nthreads, in_q, out_q,
+                           rng.seed, rng.photon_id_base, max_steps, use_weights, scatter_first, ctx->d_counters);
+    });
     HIP_TRY(hipGetLastError());
     return CHROMA_OK;
 }
 
-static int launch_propagate(chroma_ctx *ctx, const CallOpts &co, chroma_geometry *geom, PhotonView pv, int first, int nthreads,
-                            const uint32_t *in_q, uint32_t *out_q, chroma_rng rng, int max_steps, int use_weights,
-                            int scatter_first)
-{
-    if (nthreads <= 0) return CHROMA_OK;
-    if (co.counting)
-        return launch_propagate_t<true>(ctx, co, geom, pv, first, nthreads, in_q, out_q, rng, max_steps, use_weights, scatter_first);
-    return launch_propagate_t<false>(ctx, co, geom, pv, first, nthreads, in_q, out_q, rng, max_steps, use_weights, scatter_first);
-}
-
-// the per-ray slices of global memory for stack entries beyond the LDS part: every cooperative walk indexes
-// it with (wave * rays-per-wave + ray) * COOP_SPILL, so it is sized for the largest grid of any of them
-static size_t spill_entries(const chroma_ctx *ctx)
-{
-    size_t rays = std::max(std::max((size_t)ctx->coop_waves * 8, (size_t)ctx->quad_waves * 16), (size_t)ctx->pair_waves * 32);
-    return rays * COOP_SPILL;
-}
-
-// one step for many photons: ray cast and physics as two launches
-// One step as ray set-up + ray cast + physics (+ the strict walk and the physics of the few rays that
-// need it), all reading the photon count and the launch policy from ctx->d_step (k_step_begin).
-// `n_upper` bounds the count and sizes the grids; `in_q`/`out_q` are whole queues (slot 0 = tail) and
-// `work_in`/`work_out` the working sets that go with them.  With `ev` (SIX events per step, indices 0..5): [0] step start,
-// [3] ray-cast kernels start, [5] start of the step's own ray cast (after an experimental packet launch), [1] its end,
-// [4] end of the main physics pass, [2] step end.
-// The walk whose steps chain their ray records from kernel to kernel (k_load_working -> k_raycast_quad -> k_physics ->
-// k_raycast_quad ...) instead of running k_ray_setup: the default one.
-static bool step_uses_quad_walk(const CallOpts &co, const chroma_geometry *geom)
-{
-    return geom->view.wnodes != nullptr && co.walk == CHROMA_WALK_QUAD && geom->wide_stack_need <= QUAD_STACK + COOP_SPILL;
-}
-
 // k_physics for one pass of a step.  `fixup`: 0 the main pass over every slot, 1 the slots k_raycast_retry has walked again
-// (a short list: a small grid), 2 every slot with the ray cast's results taken as they are (the exact walk).
-static void launch_physics(chroma_ctx *ctx, const CallOpts &co, chroma_geometry *geom, const PhotonView &pv, long long n_upper,
+// (a short list: a small grid), 2 every slot with the ray cast's results taken as they are (the exact walks).
+static void launch_physics(chroma_ctx *ctx, const CallPlan &plan, chroma_geometry *geom, const PhotonView &pv, long long n_upper,
                            const float4 *work_in, uint32_t *out_q, float4 *work_out, chroma_rng rng, int use_weights, int scatter_first,
-                           int fixup, float4 *rays_next, int literal_rays = 0)
+                           int fixup, float4 *rays_next)
 {
     StepState *st = ctx->d_step;
     const bool plain = geom->view.plain_optics != 0;      // (no re-emitting component, default surface model only)
@@ -332,7 +398,7 @@ static void launch_physics(chroma_ctx *ctx, const CallOpts &co, chroma_geometry 
     //  launch of 2048 blocks that find nothing to do costs 0.07 ms, 29 times per batch; a plain geometry with faces on the
     //  world box lists a good part of its hits for the exact check, so not less than that)
     if (fixup == 1 && plain) blocks = std::max(std::min(blocks, 64u), blocks / 8);
-    DeviceCounters *pc = co.counting ? ctx->d_counters : nullptr;
+    DeviceCounters *pc = plan.counting ? ctx->d_counters : nullptr;
 #if PHYS_DEAL
     if (deal) {
         hipLaunchKernelGGL(k_physics_deal, dim3(blocks), dim3(PHYS_DEAL_BLOCK), 0, ctx->stream, geom->view, pv, st, work_in, out_q, work_out,
@@ -341,191 +407,127 @@ static void launch_physics(chroma_ctx *ctx, const CallOpts &co, chroma_geometry 
         return;
     }
 #endif
-    if (plain)
-        hipLaunchKernelGGL((k_physics<false>), dim3(blocks), dim3(PHYS_BLOCK_OF(false)), 0, ctx->stream, geom->view, pv, st, work_in, out_q, work_out,
-                           ctx->hit_triangle, ctx->hit_distance, rng.seed, rng.photon_id_base, use_weights, scatter_first,
+    const int literal_rays = fixup == 2 ? 1 : 0;          // (the exact walks' ray records)
+    with_bool(!plain, [&](auto FULL) {
+        hipLaunchKernelGGL((k_physics<FULL>), dim3(blocks), dim3(PHYS_BLOCK_OF(FULL)), 0, ctx->stream, geom->view, pv, st, work_in, out_q,
+                           work_out, ctx->hit_triangle, ctx->hit_distance, rng.seed, rng.photon_id_base, use_weights, scatter_first,
                            ctx->retry_list, fixup, pc, rays_next, ctx->final_use, ctx->final_epoch, literal_rays);
-    else
-        hipLaunchKernelGGL((k_physics<true>), dim3(blocks), dim3(PHYS_BLOCK), 0, ctx->stream, geom->view, pv, st, work_in, out_q, work_out,
-                           ctx->hit_triangle, ctx->hit_distance, rng.seed, rng.photon_id_base, use_weights, scatter_first,
-                           ctx->retry_list, fixup, pc, rays_next, ctx->final_use, ctx->final_epoch, literal_rays);
+    });
 }
 
-// `rays_ready`: the records of this step are in ctx->rays already (written by k_load_working or by the k_physics of
-// the step before).  With the default walk the records of the next step go to ctx->rays_b, and the two are swapped.
-static int launch_split_step(chroma_ctx *ctx, const CallOpts &co, chroma_geometry *geom, PhotonView pv, long long n_upper, const uint32_t *in_q,
-                             uint32_t *out_q, const float4 *work_in, float4 *work_out, chroma_rng rng, int use_weights,
-                             int scatter_first, hipEvent_t *ev = nullptr, uint32_t first_n = 0, bool rays_ready = false, bool packet = false)
+// the timing events of one step, in the order they are recorded (EV_PER_STEP per step when a call times its kernels)
+enum { EV_STEP_BEGIN, EV_PACKET_BEGIN, EV_CAST_BEGIN, EV_CAST_END, EV_PHYSICS_END, EV_STEP_END, EV_PER_STEP };
+
+// One step as ray set-up + ray cast + physics (+ the strict walk and the physics of the few rays that need it), all reading the
+// photon count and the launch policy from ctx->d_step (k_step_begin).  `n_upper` bounds the count and sizes the grids;
+// `in_q`/`out_q` are whole queues (slot 0 = tail) and `work_in`/`work_out` the working sets that go with them.  `ev`: the
+// step's EV_PER_STEP events, or NULL.  When the rays chain, this step's records are in ctx->rays already (written by
+// k_load_working or by the k_physics of the step before), k_physics writes the next step's to ctx->rays_b, and the two swap.
+// `packet` (experimental): the first step of a call whose k_load_working looked at the photons' coherence -- k_raycast_packet
+// is launched before k_raycast_quad, and the word k_packet_decide wrote tells the two which of them has the step.
+static int launch_split_step(chroma_ctx *ctx, const CallPlan &plan, chroma_geometry *geom, PhotonView pv, long long n_upper,
+                             const uint32_t *in_q, uint32_t *out_q, const float4 *work_in, float4 *work_out, chroma_rng rng,
+                             int use_weights, int scatter_first, hipEvent_t *ev, uint32_t first_n, bool packet)
 {
-    // (`packet`: the first step of a call whose k_load_working looked at the photons' coherence: k_raycast_packet is
-    //  launched before k_raycast_quad, and the word k_packet_decide wrote tells the two which of them has the step)
     if (n_upper <= 0) return CHROMA_OK;
-    uint32_t need = geom->stack_need;
-    if (need > STACK_LDS + STACK_SCRATCH)
-        return set_error(CHROMA_ERR_STACK, "BVH needs %u traversal stack entries, more than the %d supported", need, STACK_LDS + STACK_SCRATCH);
-    const bool have_wide = geom->view.wnodes != nullptr;
-    if (co.walk == CHROMA_WALK_LITERAL || co.walk == CHROMA_WALK_LITERAL_LANE) {
-        // the reference's own loop for every ray (mesh.h:42-118 as it stands: its tree, its order, its box arithmetic,
-        // every triangle tested the moment its leaf box is entered), then the physics on the results as they are.
-        // LITERAL: k_raycast_literal (four lanes per ray, persistent waves; raycast_literal.h) + the strict lane-per-ray
-        // loop for the few rays whose 1/d is not moderate; LITERAL_LANE: the strict loop for every ray (the cross-check).
-        const bool lane_walk = co.walk == CHROMA_WALK_LITERAL_LANE;
-        StepState *st = ctx->d_step;
-        hipLaunchKernelGGL(k_step_begin, dim3(1), dim3(1), 0, ctx->stream, in_q, out_q, st,
-                           use_weights ? 0xFFFFFFFFu : (uint32_t)(PROP_BLOCK * 16 * 8), first_n);
-        if (ev) HIP_TRY(hipEventRecord(ev[0], ctx->stream));
-        if (!lane_walk && !ctx->coop_spill) {
-            HIP_TRY(hipSetDevice(ctx->device));
-            HIP_TRY(ctx_malloc(ctx, (void **)&ctx->coop_spill, spill_entries(ctx) * sizeof(uint2)));
-        }
-        // (the exact walk chains its ray records from kernel to kernel like the default walk: k_load_working writes the first
-        //  step's, k_physics the next step's while the photon is in its registers; LITERAL_LANE keeps the k_ray_setup pass)
-        const bool chained_lit = !lane_walk && rays_ready;
-        if (!chained_lit) {
-            unsigned sblocks = (unsigned)std::min<long long>((n_upper + 255) / 256, (long long)ctx->physics_blocks * 4);
-            hipLaunchKernelGGL(k_ray_setup, dim3(sblocks), dim3(256), 0, ctx->stream, geom->view, work_in, st, ctx->rays,
-                               ctx->hit_triangle, ctx->hit_distance, ctx->retry_list, &st->retry, lane_walk ? 0 : 1);
-        }
-        if (ev) { HIP_TRY(hipEventRecord(ev[3], ctx->stream)); HIP_TRY(hipEventRecord(ev[5], ctx->stream)); }
-        if (lane_walk) {
-            const unsigned lblocks = (unsigned)std::min<long long>((n_upper + PROP_BLOCK - 1) / PROP_BLOCK, (long long)ctx->persistent_waves);
-            if (co.counting)
-                hipLaunchKernelGGL((k_raycast_retry<true, true>), dim3(lblocks), dim3(PROP_BLOCK), 0, ctx->stream, geom->view, ctx->rays, st,
-                                   ctx->hit_triangle, ctx->hit_distance, ctx->retry_list, ctx->d_counters);
-            else
-                hipLaunchKernelGGL((k_raycast_retry<false, true>), dim3(lblocks), dim3(PROP_BLOCK), 0, ctx->stream, geom->view, ctx->rays, st,
-                                   ctx->hit_triangle, ctx->hit_distance, ctx->retry_list, ctx->d_counters);
-        } else {
-            const unsigned lwaves = (unsigned)std::min<long long>((n_upper + 15) / 16, (long long)ctx->quad_waves);
-            const unsigned rblocks = (unsigned)std::min<long long>((n_upper + PROP_BLOCK - 1) / PROP_BLOCK, 8 * 256);
-            if (co.counting) {
-                hipLaunchKernelGGL((k_raycast_literal<true>), dim3(lwaves), dim3(PROP_BLOCK), 0, ctx->stream, geom->view, ctx->rays, st,
-                                   ctx->hit_triangle, ctx->hit_distance, ctx->coop_spill, ctx->d_counters, ctx->coop_chunk, chained_lit ? 1 : 0, ctx->retry_list, ctx->claim_static);
-                hipLaunchKernelGGL((k_raycast_retry<true>), dim3(rblocks), dim3(PROP_BLOCK), 0, ctx->stream, geom->view, ctx->rays, st,
-                                   ctx->hit_triangle, ctx->hit_distance, ctx->retry_list, ctx->d_counters);
-            } else {
-                hipLaunchKernelGGL((k_raycast_literal<false>), dim3(lwaves), dim3(PROP_BLOCK), 0, ctx->stream, geom->view, ctx->rays, st,
-                                   ctx->hit_triangle, ctx->hit_distance, ctx->coop_spill, ctx->d_counters, ctx->coop_chunk, chained_lit ? 1 : 0, ctx->retry_list, ctx->claim_static);
-                hipLaunchKernelGGL((k_raycast_retry<false>), dim3(rblocks), dim3(PROP_BLOCK), 0, ctx->stream, geom->view, ctx->rays, st,
-                                   ctx->hit_triangle, ctx->hit_distance, ctx->retry_list, ctx->d_counters);
-            }
-        }
-        if (ev) HIP_TRY(hipEventRecord(ev[1], ctx->stream));
-        launch_physics(ctx, co, geom, pv, n_upper, work_in, out_q, work_out, rng, use_weights, scatter_first, 2, lane_walk ? nullptr : ctx->rays_b, 1);
-        if (ev) { HIP_TRY(hipEventRecord(ev[4], ctx->stream)); HIP_TRY(hipEventRecord(ev[2], ctx->stream)); }
-        HIP_TRY(hipGetLastError());
-        if (!lane_walk) std::swap(ctx->rays, ctx->rays_b);       // (what k_physics wrote is the next step's input)
-        return CHROMA_OK;
-    }
-    const bool pair = co.walk == CHROMA_WALK_PAIR && have_wide && geom->wide_stack_need <= PAIR_STACK + COOP_SPILL;
-    const bool quad = !pair && (co.walk == CHROMA_WALK_QUAD || co.walk == CHROMA_WALK_PAIR) && have_wide &&
-                      geom->wide_stack_need <= QUAD_STACK + COOP_SPILL;
-    const bool coop = !pair && !quad && (co.walk == CHROMA_WALK_COOP || co.walk == CHROMA_WALK_QUAD) && have_wide &&
-                      geom->wide_stack_need <= COOP_STACK + COOP_SPILL;
-    const bool wide = !pair && !coop && !quad && co.walk != CHROMA_WALK_REFERENCE && have_wide && geom->wide_stack_need <= WIDE_STACK + WIDE_SPILL;
-    if (wide && !ctx->wide_spill) {
-        HIP_TRY(hipSetDevice(ctx->device));
-        HIP_TRY(ctx_malloc(ctx, (void **)&ctx->wide_spill, (size_t)ctx->wide_waves * WIDE_SPILL * PROP_BLOCK * sizeof(uint2)));
-    }
-    if ((coop || quad || pair) && !ctx->coop_spill) {
-        HIP_TRY(hipSetDevice(ctx->device));
-        HIP_TRY(ctx_malloc(ctx, (void **)&ctx->coop_spill, spill_entries(ctx) * sizeof(uint2)));
-    }
-    // persistent ray cast: enough waves to fill the chip, each pulling rays from the queue
-    unsigned waves = pair ? (unsigned)std::min<long long>((n_upper + 31) / 32, (long long)ctx->pair_waves)
-                   : quad ? (unsigned)std::min<long long>((n_upper + 15) / 16, (long long)ctx->quad_waves)
-                   : coop ? (unsigned)std::min<long long>((n_upper + 7) / 8, (long long)ctx->coop_waves)
-                          : (unsigned)std::min<long long>((n_upper + PROP_BLOCK - 1) / PROP_BLOCK,
-                                                          (long long)(wide ? ctx->wide_waves : ctx->persistent_waves));
-    dim3 grid(waves), block(PROP_BLOCK);
     StepState *st = ctx->d_step;
+    const Cast cast = plan.cast;
+    const bool exact = cast == Cast::LITERAL || cast == Cast::LITERAL_LANE;
+    float4 *rays_next = plan.chain ? ctx->rays_b : nullptr;
+    const dim3 block(PROP_BLOCK);
+    auto record = [&](int slot) { return ev ? hipEventRecord(ev[slot], ctx->stream) : hipSuccess; };
+    // (both passes of the strict walk stride over the list and leave at once when it is short -- the usual case -- but a plain
+    //  geometry with faces on the world box lists a good part of its hits for the exact check: grids for that)
+    const unsigned rblocks = (unsigned)std::min<long long>((n_upper + PROP_BLOCK - 1) / PROP_BLOCK, 8 * 256);
+    auto retry = [&](auto C) {
+        hipLaunchKernelGGL((k_raycast_retry<C>), dim3(rblocks), block, 0, ctx->stream, geom->view, ctx->rays, st, ctx->hit_triangle,
+                           ctx->hit_distance, ctx->retry_list, ctx->d_counters);
+    };
     // (with weights the reference runs ALL steps in one launch: every count is "few")
     hipLaunchKernelGGL(k_step_begin, dim3(1), dim3(1), 0, ctx->stream, in_q, out_q, st,
                        use_weights ? 0xFFFFFFFFu : (uint32_t)(PROP_BLOCK * 16 * 8), first_n);
-    if (ev) HIP_TRY(hipEventRecord(ev[0], ctx->stream));
-    const bool chained = quad && step_uses_quad_walk(co, geom);
-    if (!(chained && rays_ready)) {
+    HIP_TRY(record(EV_STEP_BEGIN));
+    if (!plan.chain) {
         unsigned sblocks = (unsigned)std::min<long long>((n_upper + 255) / 256, (long long)ctx->physics_blocks * 4);
         hipLaunchKernelGGL(k_ray_setup, dim3(sblocks), dim3(256), 0, ctx->stream, geom->view, work_in, st, ctx->rays,
-                           ctx->hit_triangle, ctx->hit_distance, ctx->retry_list, &st->retry);
+                           ctx->hit_triangle, ctx->hit_distance, ctx->retry_list, &st->retry, cast == Cast::LITERAL ? 1 : 0);
     }
-    const int settle = (chained && rays_ready) ? 1 : 0;
-    float4 *rays_next = chained ? ctx->rays_b : nullptr;
-    if (ev) HIP_TRY(hipEventRecord(ev[3], ctx->stream));        // the ray-cast kernels proper are timed from here
+    HIP_TRY(record(EV_PACKET_BEGIN));                             // the ray-cast kernels proper are timed from here
     const uint32_t *skip_quad = nullptr;
 #if CHROMA_EXPERIMENTAL
-    const bool offer_packet = packet && chained && rays_ready;
-    skip_quad = offer_packet ? ctx->d_words + 4 : nullptr;
-    if (offer_packet) {
+    if (packet) {
+        skip_quad = ctx->d_words + 4;
         const unsigned pwaves = (unsigned)std::min<long long>((n_upper + WAVE - 1) / WAVE, (long long)ctx->quad_waves);
-        if (co.counting)
-            hipLaunchKernelGGL((k_raycast_packet<true>), dim3(pwaves), block, 0, ctx->stream, geom->view, ctx->rays, st, ctx->hit_triangle,
+        with_bool(plan.counting, [&](auto C) {
+            hipLaunchKernelGGL((k_raycast_packet<C>), dim3(pwaves), block, 0, ctx->stream, geom->view, ctx->rays, st, ctx->hit_triangle,
                                ctx->hit_distance, ctx->retry_list, ctx->d_counters, ctx->d_words + 4);
-        else
-            hipLaunchKernelGGL((k_raycast_packet<false>), dim3(pwaves), block, 0, ctx->stream, geom->view, ctx->rays, st, ctx->hit_triangle,
-                               ctx->hit_distance, ctx->retry_list, ctx->d_counters, ctx->d_words + 4);
+        });
     }
 #else
     (void)packet;
 #endif
-    if (ev) HIP_TRY(hipEventRecord(ev[5], ctx->stream));        // (k_raycast_packet before, the step's other ray cast after)
-#define RAYCAST_LAUNCH(COUNT)                                                                                          \
-    do {                                                                                                               \
-        if (pair)                                                                                                      \
-            hipLaunchKernelGGL((k_raycast_pair<COUNT>), grid, block, 0, ctx->stream, geom->view, ctx->rays, 0, st,      \
-                               ctx->hit_triangle, ctx->hit_distance, ctx->retry_list, ctx->coop_spill, ctx->d_counters, ctx->coop_chunk); \
-        else if (quad)                                                                                                 \
-            hipLaunchKernelGGL((k_raycast_quad<COUNT>), grid, block, 0, ctx->stream, geom->view, ctx->rays, 0, st,      \
-                               ctx->hit_triangle, ctx->hit_distance, ctx->retry_list, ctx->coop_spill, ctx->d_counters, ctx->coop_chunk, settle, skip_quad, ctx->claim_static); \
-        else if (coop)                                                                                                 \
-            hipLaunchKernelGGL((k_raycast_coop<COUNT>), grid, block, 0, ctx->stream, geom->view, ctx->rays, 0, st,      \
-                               ctx->hit_triangle, ctx->hit_distance, ctx->retry_list, ctx->coop_spill, ctx->d_counters, ctx->coop_chunk); \
-        else if (wide)                                                                                                 \
-            hipLaunchKernelGGL((k_raycast_wide<COUNT>), grid, block, 0, ctx->stream, geom->view, ctx->rays, 0, st,      \
-                               ctx->hit_triangle, ctx->hit_distance, ctx->retry_list, ctx->wide_spill, ctx->d_counters, ctx->ray_chunk); \
-        else                                                                                                           \
-            hipLaunchKernelGGL((k_raycast_persistent<COUNT>), grid, block, 0, ctx->stream, geom->view, ctx->rays, 0, st, \
-                               ctx->hit_triangle, ctx->hit_distance, ctx->retry_list, ctx->d_counters);                \
-        if (ev) HIP_TRY(hipEventRecord(ev[1], ctx->stream));                                                            \
-    } while (0)
-    if (co.counting) RAYCAST_LAUNCH(true); else RAYCAST_LAUNCH(false);
-#undef RAYCAST_LAUNCH
+    HIP_TRY(record(EV_CAST_BEGIN));
+    const dim3 grid(cast_waves(ctx, cast, n_upper));
+    const int chained = plan.chain ? 1 : 0;
+    with_bool(plan.counting, [&](auto C) {
+        switch (cast) {
+        case Cast::PAIR:
+            hipLaunchKernelGGL((k_raycast_pair<C>), grid, block, 0, ctx->stream, geom->view, ctx->rays, 0, st, ctx->hit_triangle,
+                               ctx->hit_distance, ctx->retry_list, ctx->coop_spill, ctx->d_counters, ctx->coop_chunk);
+            break;
+        case Cast::QUAD:
+            hipLaunchKernelGGL((k_raycast_quad<C>), grid, block, 0, ctx->stream, geom->view, ctx->rays, 0, st, ctx->hit_triangle,
+                               ctx->hit_distance, ctx->retry_list, ctx->coop_spill, ctx->d_counters, ctx->coop_chunk, chained, skip_quad,
+                               ctx->claim_static);
+            break;
+        case Cast::COOP:
+            hipLaunchKernelGGL((k_raycast_coop<C>), grid, block, 0, ctx->stream, geom->view, ctx->rays, 0, st, ctx->hit_triangle,
+                               ctx->hit_distance, ctx->retry_list, ctx->coop_spill, ctx->d_counters, ctx->coop_chunk);
+            break;
+        case Cast::WIDE:
+            hipLaunchKernelGGL((k_raycast_wide<C>), grid, block, 0, ctx->stream, geom->view, ctx->rays, 0, st, ctx->hit_triangle,
+                               ctx->hit_distance, ctx->retry_list, ctx->wide_spill, ctx->d_counters, ctx->ray_chunk);
+            break;
+        case Cast::PERSISTENT:
+            hipLaunchKernelGGL((k_raycast_persistent<C>), grid, block, 0, ctx->stream, geom->view, ctx->rays, 0, st, ctx->hit_triangle,
+                               ctx->hit_distance, ctx->retry_list, ctx->d_counters);
+            break;
+        case Cast::LITERAL:
+            hipLaunchKernelGGL((k_raycast_literal<C>), grid, block, 0, ctx->stream, geom->view, ctx->rays, st, ctx->hit_triangle,
+                               ctx->hit_distance, ctx->coop_spill, ctx->d_counters, ctx->coop_chunk, chained, ctx->retry_list,
+                               ctx->claim_static);
+            retry(C);
+            break;
+        case Cast::LITERAL_LANE:
+            hipLaunchKernelGGL((k_raycast_retry<C, true>), grid, block, 0, ctx->stream, geom->view, ctx->rays, st, ctx->hit_triangle,
+                               ctx->hit_distance, ctx->retry_list, ctx->d_counters);
+            break;
+        }
+    });
+    HIP_TRY(record(EV_CAST_END));
     // physics for every slot whose hit is regular; then the strict walk and the physics of the rest
-    launch_physics(ctx, co, geom, pv, n_upper, work_in, out_q, work_out, rng, use_weights, scatter_first, 0, rays_next);
-    if (ev) HIP_TRY(hipEventRecord(ev[4], ctx->stream));          // end of the main physics pass
-    // (both passes stride over the list and leave at once when it is short -- the usual case -- but a plain geometry
-    //  with faces on the world box lists a good part of its hits for the exact check: grids for that)
-    const unsigned rblocks = (unsigned)std::min<long long>((n_upper + PROP_BLOCK - 1) / PROP_BLOCK, 8 * 256);
-    if (co.counting)
-        hipLaunchKernelGGL((k_raycast_retry<true>), dim3(rblocks), block, 0, ctx->stream, geom->view, ctx->rays, st,
-                           ctx->hit_triangle, ctx->hit_distance, ctx->retry_list, ctx->d_counters);
-    else
-        hipLaunchKernelGGL((k_raycast_retry<false>), dim3(rblocks), block, 0, ctx->stream, geom->view, ctx->rays, st,
-                           ctx->hit_triangle, ctx->hit_distance, ctx->retry_list, ctx->d_counters);
-    launch_physics(ctx, co, geom, pv, n_upper, work_in, out_q, work_out, rng, use_weights, scatter_first, 1, rays_next);
-    if (ev) HIP_TRY(hipEventRecord(ev[2], ctx->stream));
+    launch_physics(ctx, plan, geom, pv, n_upper, work_in, out_q, work_out, rng, use_weights, scatter_first, exact ? 2 : 0, rays_next);
+    HIP_TRY(record(EV_PHYSICS_END));
+    if (!exact) {
+        with_bool(plan.counting, retry);
+        launch_physics(ctx, plan, geom, pv, n_upper, work_in, out_q, work_out, rng, use_weights, scatter_first, 1, rays_next);
+    }
+    HIP_TRY(record(EV_STEP_END));
     HIP_TRY(hipGetLastError());
-    if (chained) std::swap(ctx->rays, ctx->rays_b);       // (what k_physics wrote is the next step's input)
+    if (plan.chain) std::swap(ctx->rays, ctx->rays_b);       // (what k_physics wrote is the next step's input)
     return CHROMA_OK;
 }
 
-// All remaining steps of the last photons in one launch (k_tail_coop).  Returns CHROMA_OK and sets
-// *done when the geometry has a wide tree the kernel can walk; otherwise leaves *done false.
-static int launch_tail(chroma_ctx *ctx, const CallOpts &co, chroma_geometry *geom, PhotonView pv, long long n_upper, const uint32_t *in_q,
+// All remaining steps of the last photons in one launch (k_tail_coop), for a plan with `tail`.  Sets *done when it launched.
+static int launch_tail(chroma_ctx *ctx, const CallPlan &plan, chroma_geometry *geom, PhotonView pv, long long n_upper, const uint32_t *in_q,
                        uint32_t *out_q, const float4 *work_in, chroma_rng rng, int nsteps, int use_weights, int scatter_first,
-                       hipEvent_t *ev, bool *done, uint32_t first_n = 0, const HitsOut *beside = nullptr, uint64_t nphotons = 0)
+                       hipEvent_t *ev, bool *done, uint32_t first_n, const HitsOut *beside, uint64_t nphotons)
 {
     // (`beside`: a call that ends in k_finalize_hits -- that pass runs on the context's auxiliary stream WHILE the tail kernel
     //  finishes the last photons, which are stamped first so that it leaves them to the tail kernel; the two meet again
     //  before the call reads its result words)
     *done = false;
-    if (!geom->view.wnodes || geom->wide_stack_need > COOP_STACK + COOP_SPILL || geom->stack_need > STACK_LDS + STACK_SCRATCH)
-        return CHROMA_OK;
-    if (!ctx->coop_spill) {
-        HIP_TRY(hipSetDevice(ctx->device));
-        HIP_TRY(ctx_malloc(ctx, (void **)&ctx->coop_spill, spill_entries(ctx) * sizeof(uint2)));
-    }
-    unsigned waves = (unsigned)std::min<long long>((n_upper + 7) / 8, (long long)ctx->coop_waves);
+    const unsigned waves = cast_waves(ctx, Cast::COOP, n_upper);            // (8 lanes per photon)
     if ((long long)waves * 8 < n_upper) return CHROMA_OK;          // (cannot happen below 8192 photons)
     StepState *st = ctx->d_step;
     hipLaunchKernelGGL(k_step_begin, dim3(1), dim3(1), 0, ctx->stream, in_q, out_q, st,
@@ -546,13 +548,14 @@ static int launch_tail(chroma_ctx *ctx, const CallOpts &co, chroma_geometry *geo
                            nphotons, ho, ctx->d_words, tail_mark);
         HIP_TRY(hipEventRecord(ctx->ev_join, ctx->aux_stream));
     }
-    if (ev) { HIP_TRY(hipEventRecord(ev[0], ctx->stream)); HIP_TRY(hipEventRecord(ev[1], ctx->stream)); }
-#define TAIL_LAUNCH(C, L) hipLaunchKernelGGL((k_tail_coop<C, L>), dim3(waves), dim3(PROP_BLOCK), 0, ctx->stream, geom->view, pv, st, work_in, \
-                                             rng.seed, rng.photon_id_base, nsteps, use_weights, scatter_first, ctx->coop_spill, ctx->d_counters, ho, words)
-    if (co.walk == CHROMA_WALK_LITERAL) { if (co.counting) TAIL_LAUNCH(true, true); else TAIL_LAUNCH(false, true); }
-    else { if (co.counting) TAIL_LAUNCH(true, false); else TAIL_LAUNCH(false, false); }
-#undef TAIL_LAUNCH
-    if (ev) HIP_TRY(hipEventRecord(ev[2], ctx->stream));
+    if (ev) HIP_TRY(hipEventRecord(ev[EV_STEP_BEGIN], ctx->stream));
+    with_bool(plan.cast == Cast::LITERAL, [&](auto L) {
+        with_bool(plan.counting, [&](auto C) {
+            hipLaunchKernelGGL((k_tail_coop<C, L>), dim3(waves), dim3(PROP_BLOCK), 0, ctx->stream, geom->view, pv, st, work_in,
+                               rng.seed, rng.photon_id_base, nsteps, use_weights, scatter_first, ctx->coop_spill, ctx->d_counters, ho, words);
+        });
+    });
+    if (ev) HIP_TRY(hipEventRecord(ev[EV_STEP_END], ctx->stream));
     if (beside) HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
     HIP_TRY(hipGetLastError());
     *done = true;
@@ -840,10 +843,10 @@ int chroma_init(int device, chroma_ctx **out)
         if (const char *e = getenv("CHROMA_PAIR_WAVES_PER_CU")) pair_per_cu = std::max(1, atoi(e));
         ctx->pair_waves = prop.multiProcessorCount * pair_per_cu;
         if (const char *e = getenv("CHROMA_WALK"))
-            ctx->wide_walk = !strcmp(e, "reference") ? CHROMA_WALK_REFERENCE : !strcmp(e, "wide") ? CHROMA_WALK_WIDE
-                           : !strcmp(e, "coop") ? CHROMA_WALK_COOP : !strcmp(e, "pair") ? CHROMA_WALK_PAIR
-                           : (!strcmp(e, "literal") || !strcmp(e, "exact")) ? CHROMA_WALK_LITERAL
-                           : !strcmp(e, "literal_lane") ? CHROMA_WALK_LITERAL_LANE : CHROMA_WALK_QUAD;
+            ctx->walk = !strcmp(e, "reference") ? CHROMA_WALK_REFERENCE : !strcmp(e, "wide") ? CHROMA_WALK_WIDE
+                      : !strcmp(e, "coop") ? CHROMA_WALK_COOP : !strcmp(e, "pair") ? CHROMA_WALK_PAIR
+                      : (!strcmp(e, "literal") || !strcmp(e, "exact")) ? CHROMA_WALK_LITERAL
+                      : !strcmp(e, "literal_lane") ? CHROMA_WALK_LITERAL_LANE : CHROMA_WALK_QUAD;
 #if CHROMA_EXPERIMENTAL
         if (const char *e = getenv("CHROMA_PACKET")) ctx->packet_mode = !strcmp(e, "on") ? 1 : !strcmp(e, "auto") ? 2 : 0;
         if (const char *e = getenv("CHROMA_AUTOSORT")) ctx->autosort_mode = !strcmp(e, "on") || !strcmp(e, "1") ? 1 : !strcmp(e, "off") || !strcmp(e, "0") ? 0 : 2;
@@ -851,10 +854,8 @@ int chroma_init(int device, chroma_ctx **out)
         if (const char *e = getenv("CHROMA_RAY_CHUNK")) ctx->ray_chunk = std::max(64, atoi(e));
         if (const char *e = getenv("CHROMA_COOP_CHUNK")) ctx->coop_chunk = std::max(8, atoi(e));
         if (const char *e = getenv("CHROMA_CLAIM_STATIC")) { int big = 0, small = 0; if (sscanf(e, "%d:%d", &big, &small) < 2) small = big; ctx->claim_static = std::min(8, std::max(0, big)) | std::min(8, std::max(0, small)) << 4; }
-        if (const char *e = getenv("CHROMA_TAIL")) {      // coop (default) | split | fused (the lane-per-photon k_propagate)
-            ctx->split_tail = (strcmp(e, "fused") != 0);
-            ctx->fused_tail = (strcmp(e, "split") != 0 && strcmp(e, "fused") != 0);
-        }
+        if (const char *e = getenv("CHROMA_TAIL"))        // coop (default) | split | fused (the lane-per-photon k_propagate)
+            ctx->tail_mode = !strcmp(e, "fused") ? CHROMA_TAIL_FUSED : !strcmp(e, "split") ? CHROMA_TAIL_SPLIT : CHROMA_TAIL_COOP;
     }
     HIP_TRY(hipEventCreate(&ctx->ev_start));
     HIP_TRY(hipEventCreate(&ctx->ev_stop));
@@ -1515,7 +1516,9 @@ int chroma_propagate_step(chroma_ctx *ctx, chroma_geometry *geom, int32_t first_
     int rc = check_photons(photons, true);
     if (rc) return rc;
     if (first_photon < 0 || nthreads < 0) return set_error(CHROMA_ERR_INVALID, "negative photon range");
-    return launch_propagate(ctx, call_opts(ctx), geom, to_view(photons), first_photon, nthreads, d_input_queue, d_output_queue, rng,
+    if (nthreads == 0) return CHROMA_OK;
+    if ((rc = check_stack(geom))) return rc;
+    return launch_propagate(ctx, ctx->counting != 0, geom, to_view(photons), first_photon, nthreads, d_input_queue, d_output_queue, rng,
                             max_steps, use_weights, scatter_first);
 }
 
@@ -1620,8 +1623,6 @@ int chroma_copy_photon_hits(chroma_ctx *ctx, chroma_geometry *geom, int32_t firs
 }
 
 static int ensure_queues(chroma_ctx *ctx, size_t n);
-static int distance_to_mesh_fast(chroma_ctx *ctx, chroma_geometry *geom, int32_t n, const float *d_origin,
-                                 const float *d_direction, const int32_t *d_last_hit, float *d_distance, int32_t *d_triangle);
 
 int chroma_distance_to_mesh(chroma_ctx *ctx, chroma_geometry *geom, int32_t nthreads, const float *d_origin,
                             const float *d_direction, float *d_distance, int32_t *d_triangle)
@@ -1629,54 +1630,49 @@ int chroma_distance_to_mesh(chroma_ctx *ctx, chroma_geometry *geom, int32_t nthr
     return chroma_intersect_mesh(ctx, geom, nthreads, d_origin, d_direction, nullptr, d_distance, d_triangle);
 }
 
-int chroma_intersect_mesh(chroma_ctx *ctx, chroma_geometry *geom, int32_t nthreads, const float *d_origin,
-                          const float *d_direction, const int32_t *d_last_hit, float *d_distance, int32_t *d_triangle)
-{
-    if (!ctx || !geom || !d_origin || !d_direction || !d_distance) return set_error(CHROMA_ERR_INVALID, "bad argument");
-    if (nthreads <= 0) return CHROMA_OK;
-    uint32_t need = geom->stack_need;
-    if (need > STACK_LDS + STACK_SCRATCH)
-        return set_error(CHROMA_ERR_STACK, "BVH needs %u traversal stack entries, more than the %d supported", need, STACK_LDS + STACK_SCRATCH);
-    std::lock_guard<std::mutex> call_lock(ctx->call_mu);          // (the fast path uses the context's queues and ray records, as a propagate call does)
-    if (geom->view.wnodes && geom->wide_stack_need <= COOP_STACK + COOP_SPILL && ctx->wide_walk != CHROMA_WALK_REFERENCE &&
-        ctx->wide_walk != CHROMA_WALK_LITERAL && ctx->wide_walk != CHROMA_WALK_LITERAL_LANE)
-        return distance_to_mesh_fast(ctx, geom, nthreads, d_origin, d_direction, d_last_hit, d_distance, d_triangle);
-    dim3 grid((unsigned)((nthreads + PROP_BLOCK - 1) / PROP_BLOCK)), block(PROP_BLOCK);
-#define LAUNCH(N, C) hipLaunchKernelGGL((k_distance_to_mesh<N, C>), grid, block, 0, ctx->stream, geom->view, nthreads, \
-                                        d_origin, d_direction, d_last_hit, d_distance, d_triangle, ctx->d_counters)
-    if (ctx->counting) LAUNCH(STACK_LDS, true); else LAUNCH(STACK_LDS, false);
-#undef LAUNCH
-    HIP_TRY(hipGetLastError());
-    return CHROMA_OK;
-}
-
-static int distance_to_mesh_fast(chroma_ctx *ctx, chroma_geometry *geom, int32_t n, const float *d_origin,
+// the quad walk of the default propagate step over a caller's rays: k_raycast_quad, then the strict loop for the rays it hands over
+static int distance_to_mesh_fast(chroma_ctx *ctx, bool counting, chroma_geometry *geom, int32_t n, const float *d_origin,
                                  const float *d_direction, const int32_t *d_last_hit, float *d_distance, int32_t *d_triangle)
 {
     HIP_TRY(hipSetDevice(ctx->device));
     int rc = ensure_queues(ctx, (size_t)n); if (rc) return rc;
-    if (!ctx->coop_spill)
-        HIP_TRY(ctx_malloc(ctx, (void **)&ctx->coop_spill, spill_entries(ctx) * sizeof(uint2)));
+    rc = ensure_spill(ctx, SPILL_COOP); if (rc) return rc;
     StepState *st = ctx->d_step;
     const unsigned blocks = (unsigned)((n + 255) / 256);
     hipLaunchKernelGGL(k_step_set, dim3(1), dim3(1), 0, ctx->stream, st, (uint32_t)n);
     hipLaunchKernelGGL(k_rays_from_arrays, dim3(blocks), dim3(256), 0, ctx->stream, geom->view, (int)n, d_origin, d_direction,
                        d_last_hit, ctx->rays, ctx->hit_triangle, ctx->hit_distance, ctx->retry_list, st);
-    const unsigned waves = (unsigned)std::min<long long>(((long long)n + 15) / 16, (long long)ctx->quad_waves);
-    if (ctx->counting)
-        hipLaunchKernelGGL((k_raycast_quad<true>), dim3(waves), dim3(PROP_BLOCK), 0, ctx->stream, geom->view, ctx->rays, 0, st,
+    const unsigned waves = cast_waves(ctx, Cast::QUAD, n);
+    with_bool(counting, [&](auto C) {
+        hipLaunchKernelGGL((k_raycast_quad<C>), dim3(waves), dim3(PROP_BLOCK), 0, ctx->stream, geom->view, ctx->rays, 0, st,
                            ctx->hit_triangle, ctx->hit_distance, ctx->retry_list, ctx->coop_spill, ctx->d_counters, ctx->coop_chunk, 0, nullptr, ctx->claim_static);
-    else
-        hipLaunchKernelGGL((k_raycast_quad<false>), dim3(waves), dim3(PROP_BLOCK), 0, ctx->stream, geom->view, ctx->rays, 0, st,
-                           ctx->hit_triangle, ctx->hit_distance, ctx->retry_list, ctx->coop_spill, ctx->d_counters, ctx->coop_chunk, 0, nullptr, ctx->claim_static);
+    });
     hipLaunchKernelGGL(k_distance_finish, dim3(blocks), dim3(256), 0, ctx->stream, geom->view, (int)n, ctx->rays, ctx->hit_triangle,
                        ctx->hit_distance, d_distance, d_triangle, ctx->retry_list, st);
-    if (ctx->counting)
-        hipLaunchKernelGGL((k_distance_retry<true>), dim3(256), dim3(PROP_BLOCK), 0, ctx->stream, geom->view, ctx->rays, st,
+    with_bool(counting, [&](auto C) {
+        hipLaunchKernelGGL((k_distance_retry<C>), dim3(256), dim3(PROP_BLOCK), 0, ctx->stream, geom->view, ctx->rays, st,
                            ctx->retry_list, d_distance, d_triangle, ctx->d_counters);
-    else
-        hipLaunchKernelGGL((k_distance_retry<false>), dim3(256), dim3(PROP_BLOCK), 0, ctx->stream, geom->view, ctx->rays, st,
-                           ctx->retry_list, d_distance, d_triangle, ctx->d_counters);
+    });
+    HIP_TRY(hipGetLastError());
+    return CHROMA_OK;
+}
+
+int chroma_intersect_mesh(chroma_ctx *ctx, chroma_geometry *geom, int32_t nthreads, const float *d_origin,
+                          const float *d_direction, const int32_t *d_last_hit, float *d_distance, int32_t *d_triangle)
+{
+    if (!ctx || !geom || !d_origin || !d_direction || !d_distance) return set_error(CHROMA_ERR_INVALID, "bad argument");
+    if (nthreads <= 0) return CHROMA_OK;
+    CallPlan plan;
+    int rc = make_plan(ctx, geom, -1, -1, -1, &plan); if (rc) return rc;
+    if ((rc = check_stack(geom))) return rc;
+    std::lock_guard<std::mutex> call_lock(ctx->call_mu);          // (the fast path uses the context's queues and ray records, as a propagate call does)
+    if (plan.isect_quad)
+        return distance_to_mesh_fast(ctx, plan.counting, geom, nthreads, d_origin, d_direction, d_last_hit, d_distance, d_triangle);
+    const dim3 grid((unsigned)((nthreads + PROP_BLOCK - 1) / PROP_BLOCK)), block(PROP_BLOCK);
+    with_bool(plan.counting, [&](auto C) {
+        hipLaunchKernelGGL((k_distance_to_mesh<STACK_LDS, C>), grid, block, 0, ctx->stream, geom->view, nthreads, d_origin, d_direction,
+                           d_last_hit, d_distance, d_triangle, ctx->d_counters);
+    });
     HIP_TRY(hipGetLastError());
     return CHROMA_OK;
 }
@@ -1745,7 +1741,7 @@ int chroma_set_walk(chroma_ctx *ctx, int32_t mode)
     if (mode != CHROMA_WALK_REFERENCE && mode != CHROMA_WALK_WIDE && mode != CHROMA_WALK_COOP && mode != CHROMA_WALK_QUAD &&
         mode != CHROMA_WALK_PAIR && mode != CHROMA_WALK_LITERAL && mode != CHROMA_WALK_LITERAL_LANE)
         return set_error(CHROMA_ERR_INVALID, "unknown walk mode %d", mode);
-    ctx->wide_walk = mode;
+    ctx->walk = mode;
     return CHROMA_OK;
 }
 
@@ -1776,8 +1772,7 @@ int chroma_set_tail(chroma_ctx *ctx, int32_t mode)
     if (!ctx) return set_error(CHROMA_ERR_INVALID, "null ctx");
     if (mode != CHROMA_TAIL_COOP && mode != CHROMA_TAIL_SPLIT && mode != CHROMA_TAIL_FUSED)
         return set_error(CHROMA_ERR_INVALID, "unknown tail mode %d", mode);
-    ctx->split_tail = mode != CHROMA_TAIL_FUSED;
-    ctx->fused_tail = mode == CHROMA_TAIL_COOP;
+    ctx->tail_mode = mode;
     return CHROMA_OK;
 }
 
@@ -1785,7 +1780,7 @@ int chroma_set_tail(chroma_ctx *ctx, int32_t mode)
 #include "experimental/autosort.h"
 #else
 // (product build: a call takes its photons as they come -- the engine-side direction sort lives in experimental/autosort.h)
-static int propagate_order(chroma_ctx *, const CallOpts &, const PhotonView &, uint64_t, uint32_t, uint32_t **d_order) { *d_order = nullptr; return CHROMA_OK; }
+static int propagate_order(chroma_ctx *, const CallPlan &, const PhotonView &, uint64_t, uint32_t, uint32_t **d_order) { *d_order = nullptr; return CHROMA_OK; }
 #endif
 
 // the photons' final records (chroma_propagate_hits): 64 bytes per photon of the largest batch seen, zeroed once -- a record
@@ -1803,6 +1798,204 @@ static int ensure_final_records(chroma_ctx *ctx, size_t n)
     return CHROMA_OK;
 }
 
+// the live photons into the dense working set (k_load_working), with the first step's ray records when the rays chain
+static int load_working(chroma_ctx *ctx, const CallPlan &plan, chroma_geometry *geom, const PhotonView &pv, uint64_t nphotons,
+                        uint32_t ncopies, uint32_t *in_q, float4 *work_in, chroma_propagate_stats *acc)
+{
+    const unsigned blocks = (unsigned)std::min<uint64_t>((nphotons + PHYS_BLOCK - 1) / PHYS_BLOCK, (uint64_t)ctx->physics_blocks);
+    HIP_TRY(hipMemsetAsync(ctx->d_words + 4, 0, 12, ctx->stream));          // [4] use_packet, [5] coherent waves, [6] waves
+    uint32_t *d_order = nullptr;
+    int rc = propagate_order(ctx, plan, pv, nphotons, ncopies, &d_order); if (rc) return rc;
+    hipLaunchKernelGGL(k_load_working, dim3(blocks), dim3(PHYS_BLOCK), 0, ctx->stream, geom->view, pv, in_q, work_in,
+                       (uint64_t)nphotons, ncopies, (uint32_t)(nphotons / ncopies), plan.chain ? ctx->rays : nullptr,
+                       plan.packet == 2 ? ctx->d_words + 5 : nullptr, (const uint32_t *)d_order, plan.cast == Cast::LITERAL ? 1 : 0);
+    if (d_order) { chroma_free(ctx, d_order); acc->reordered += nphotons; }      // (parked until the stream has passed this point)
+#if CHROMA_EXPERIMENTAL
+    if (plan.packet)
+        hipLaunchKernelGGL(k_packet_decide, dim3(1), dim3(1), 0, ctx->stream, ctx->d_words + 5, ctx->d_words + 4, (uint64_t)nphotons, plan.packet);
+#endif
+    HIP_TRY(hipGetLastError());
+    return CHROMA_OK;
+}
+
+// kernel, ray-cast, packet and physics times of a call's first `steps` steps from their events (time_kernels)
+static int read_step_times(chroma_ctx *ctx, int steps, int tail_step, bool packet, chroma_propagate_stats *acc)
+{
+    for (int k = 0; k < steps; k++) {
+        const hipEvent_t *ev = ctx->step_events.data() + EV_PER_STEP * k;
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, ev[EV_STEP_BEGIN], ev[EV_STEP_END]));
+        acc->kernel_ms += ms;
+        if (k == tail_step) continue;             // the fused tail is not a ray-cast launch
+        HIP_TRY(hipEventElapsedTime(&ms, ev[EV_CAST_BEGIN], ev[EV_CAST_END]));
+        acc->raycast_ms += ms;
+        acc->raycast_launches++;
+        if (k == 0 && packet) {                   // the first step's k_raycast_packet launch (an empty one when the photons are not coherent)
+            HIP_TRY(hipEventElapsedTime(&ms, ev[EV_PACKET_BEGIN], ev[EV_CAST_BEGIN]));
+            acc->packet_ms += ms;
+            acc->packet_launches++;
+        }
+        HIP_TRY(hipEventElapsedTime(&ms, ev[EV_CAST_END], ev[EV_PHYSICS_END]));
+        acc->physics_ms += ms;                    // the main pass of k_physics (not the fix-up pass)
+        acc->physics_launches++;
+    }
+    return CHROMA_OK;
+}
+
+// Launch policy of the reference (chroma/gpu/photon.py:225-252): one step per launch while many
+// photons are alive, and ONE launch for all remaining steps once fewer than 64*16*8 are left (or
+// with weights).  A launch re-normalises dir/pol when it loads a photon (propagate.cu:248,250), so
+// the policy is part of the arithmetic.  Here every step is a ray cast + physics pair that gets the
+// whole chip; a step that the reference would run inside its last launch skips the re-normalisation
+// instead (same numbers; with weights that is every step but the first).  The policy is evaluated ON
+// THE DEVICE (k_step_begin), so the steps are enqueued back to back; the host looks at the survivor
+// count only now and then, to stop early, to shrink the grids and to hand the last photons to the
+// fused tail kernel.  The live photons travel in the dense working set (k_load_working).
+// `beside`: the hits request of a call that ends in k_finalize_hits (*finalized: the tail kernel has run it already).
+static int run_device_steps(chroma_ctx *ctx, const CallPlan &plan, chroma_geometry *geom, const PhotonView &pv, uint64_t nphotons,
+                            uint32_t ncopies, chroma_rng rng, const chroma_propagate_options &opt, const HitsOut *beside,
+                            chroma_propagate_stats *acc, bool *finalized)
+{
+    const int max_steps = opt.max_steps, use_weights = opt.use_weights;
+    uint32_t *in_q = ctx->queue_a, *out_q = ctx->queue_b;
+    float4 *work_in = ctx->work_a, *work_out = ctx->work_b;
+    HIP_TRY(hipMemsetAsync(ctx->d_step, 0, sizeof(StepState), ctx->stream));
+    hipLaunchKernelGGL(k_set_word, dim3(1), dim3(1), 0, ctx->stream, in_q, 1u);
+    hipLaunchKernelGGL(k_set_word, dim3(1), dim3(1), 0, ctx->stream, out_q, 1u);
+    int rc = load_working(ctx, plan, geom, pv, nphotons, ncopies, in_q, work_in, acc); if (rc) return rc;
+    const int nev = opt.time_kernels ? EV_PER_STEP * max_steps : 0;
+    while ((int)ctx->step_events.size() < nev) { hipEvent_t e; HIP_TRY(hipEventCreate(&e)); ctx->step_events.push_back(e); }
+    auto events = [&](int step) { return opt.time_kernels ? ctx->step_events.data() + EV_PER_STEP * step : nullptr; };
+    const long long few = (long long)PROP_BLOCK * 16 * 8;
+    long long n_upper = (long long)nphotons;
+    int step = 0, next_check = 1, tail_step = -1;          // (tail_step: the step at which the fused tail was launched)
+    bool done = false;
+    while (step < max_steps && !done) {
+        const int scatter_first = step == 0 ? opt.scatter_first : 0;
+        const uint32_t first_n = step == 0 ? (uint32_t)nphotons : 0u;
+        if (plan.tail && n_upper < few) {
+            // the reference's last launch: all remaining steps at once, 8 lanes per photon
+            rc = launch_tail(ctx, plan, geom, pv, n_upper, in_q, out_q, work_in, rng, max_steps - step, use_weights, scatter_first,
+                             events(step), &done, first_n, beside, nphotons);
+            if (rc) return rc;
+            if (done) { *finalized = beside != nullptr; tail_step = step++; break; }     // (it wrote every photon it held back)
+        }
+        rc = launch_split_step(ctx, plan, geom, pv, n_upper, in_q, out_q, work_in, work_out, rng, use_weights, scatter_first,
+                               events(step), first_n, step == 0 && plan.packet != 0);
+        if (rc) return rc;
+        step++;
+        std::swap(in_q, out_q);
+        std::swap(work_in, work_out);
+        if (step == next_check && step < max_steps) {
+            // survivors = tail - 1 of what is now the input queue
+            HIP_TRY(hipMemcpyAsync(ctx->h_words + 1, in_q, 4, hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(hipStreamSynchronize(ctx->stream));
+            n_upper = (long long)ctx->h_words[1] - 1;
+            if (n_upper <= 0) done = true;
+            // look every step once the tail is near, so that it starts when the reference's does
+            next_check = (plan.tail_watch && n_upper < 16 * few) ? step + 1 : (step < 8) ? step * 2 : step + 8;
+        }
+    }
+    if (!done) {
+        // max_steps reached with photons still alive: they go back to the caller's arrays
+        unsigned blocks = (unsigned)std::min<long long>((n_upper + 255) / 256, 4096);
+        hipLaunchKernelGGL(k_store_working, dim3(std::max(blocks, 1u)), dim3(256), 0, ctx->stream, geom->view, pv, in_q, work_in);
+    }
+    HIP_TRY(hipMemcpyAsync(ctx->h_step, ctx->d_step, sizeof(StepState), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    acc->launches += ((const StepState *)ctx->h_step)->launches;
+    return opt.time_kernels ? read_step_times(ctx, step, tail_step, plan.packet != 0, acc) : CHROMA_OK;
+}
+
+// CHROMA_TAIL=fused: the lane-per-photon kernel with the reference's own launch shapes
+static int run_fused(chroma_ctx *ctx, const CallPlan &plan, chroma_geometry *geom, const PhotonView &pv, uint64_t nphotons,
+                     uint32_t ncopies, chroma_rng rng, const chroma_propagate_options &opt, chroma_propagate_stats *acc)
+{
+    uint32_t *in_q = ctx->queue_a, *out_q = ctx->queue_b;
+    hipLaunchKernelGGL(k_init_queue, dim3((unsigned)((nphotons + 255) / 256)), dim3(256), 0, ctx->stream, in_q,
+                       (uint64_t)nphotons, ncopies, (uint32_t)(nphotons / ncopies));
+    hipLaunchKernelGGL(k_set_word, dim3(1), dim3(1), 0, ctx->stream, out_q, 1u);
+    HIP_TRY(hipGetLastError());
+    const int max_steps = opt.max_steps;
+    int scatter_first = opt.scatter_first;
+    uint64_t n = nphotons;
+    int step = 0;
+    while (step < max_steps) {
+        const bool few = n < (uint64_t)PROP_BLOCK * 16 * 8;
+        int nsteps = (few || opt.use_weights) ? (max_steps - step) : 1;
+        if (opt.time_kernels) HIP_TRY(hipEventRecord(ctx->ev_start, ctx->stream));
+        int rc = launch_propagate(ctx, plan.counting, geom, pv, 0, (int)n, in_q + 1, out_q, rng, nsteps, opt.use_weights, scatter_first);
+        if (rc) return rc;
+        acc->launches++;
+        if (opt.time_kernels) {
+            HIP_TRY(hipEventRecord(ctx->ev_stop, ctx->stream));
+            HIP_TRY(hipEventSynchronize(ctx->ev_stop));
+            float ms = 0.f;
+            HIP_TRY(hipEventElapsedTime(&ms, ctx->ev_start, ctx->ev_stop));
+            acc->kernel_ms += ms;
+        }
+        step += nsteps;
+        scatter_first = 0;
+        if (step < max_steps) {
+            std::swap(in_q, out_q);
+            // survivors = tail - 1 (one 4-byte read per step, as photon.py:250)
+            HIP_TRY(hipMemcpyAsync(ctx->h_words + 1, in_q, 4, hipMemcpyDeviceToHost, ctx->stream));
+            hipLaunchKernelGGL(k_set_word, dim3(1), dim3(1), 0, ctx->stream, out_q, 1u);
+            HIP_TRY(hipStreamSynchronize(ctx->stream));
+            n = (uint64_t)ctx->h_words[1] - 1;
+            if (n == 0) break;
+        }
+    }
+    return CHROMA_OK;
+}
+
+// The call's last pass and its report.  `finalize` (a hits request, or final records): one pass takes the records to the
+// caller's arrays and writes the abort word, the hit count, the compacted hits and the per-channel arrays (k_finalize_hits),
+// unless it has run beside the tail kernel already (`finalized`, launch_tail).  Otherwise the abort word alone (photon.py:254-255).
+static int finish_call(chroma_ctx *ctx, chroma_geometry *geom, const chroma_photon_arrays *photons, uint64_t nphotons,
+                       const HitsOut *finalize, bool finalized, chroma_hits_request *hr, const chroma_propagate_stats &acc,
+                       chroma_propagate_stats *stats, int32_t *aborted)
+{
+    uint32_t word = 0;
+    if (finalize) {
+        if (!finalized) {
+            HIP_TRY(hipMemsetAsync(ctx->d_words, 0, 12, ctx->stream));
+            const unsigned blocks = (unsigned)((nphotons + COPY_ITEMS * 256 - 1) / (COPY_ITEMS * 256));
+            hipLaunchKernelGGL(k_finalize_hits, dim3(blocks), dim3(256), 0, ctx->stream, geom->view, to_view(photons), (const float4 *)ctx->final_use,
+                               ctx->final_epoch, (uint64_t)nphotons, *finalize, ctx->d_words, 0u);
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipMemcpyAsync(ctx->h_words, ctx->d_words, 12, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        word = ctx->h_words[2];
+        if (hr) hr->nhits = ctx->h_words[0];
+    } else {
+        HIP_TRY(hipMemsetAsync(ctx->d_words + 2, 0, 4, ctx->stream));
+        const unsigned blocks = (unsigned)std::min<uint64_t>((nphotons + 255) / 256, 4096);
+        hipLaunchKernelGGL(k_flags_or, dim3(blocks), dim3(256), 0, ctx->stream, photons->flags, (uint64_t)nphotons, CHROMA_NAN_ABORT,
+                           ctx->d_words + 2);
+        HIP_TRY(hipGetLastError());
+        int rc = read_word(ctx, 2, &word); if (rc) return rc;
+    }
+    if (aborted) *aborted = (word & CHROMA_NAN_ABORT) ? 1 : 0;
+    chroma_propagate_stats tmp; memset(&tmp, 0, sizeof tmp);
+    chroma_propagate_stats *s = stats ? stats : &tmp;
+    int rc = chroma_propagate_stats_read(ctx, s); if (rc) return rc;
+    if (stats) {
+        stats->launches += acc.launches;
+        stats->kernel_ms += acc.kernel_ms;
+        stats->raycast_ms += acc.raycast_ms;
+        stats->raycast_launches += acc.raycast_launches;
+        stats->physics_ms += acc.physics_ms;
+        stats->physics_launches += acc.physics_launches;
+        stats->packet_ms += acc.packet_ms;
+        stats->packet_launches += acc.packet_launches;
+        stats->reordered += acc.reordered;
+    }
+    if (s->stack_overflows) return set_error(CHROMA_ERR_STACK, "traversal stack overflowed for %llu rays", (unsigned long long)s->stack_overflows);
+    return CHROMA_OK;
+}
+
 static int propagate_impl(chroma_ctx *ctx, chroma_geometry *geom, const chroma_photon_arrays *photons, uint64_t nphotons,
                           uint32_t ncopies, chroma_rng rng, const chroma_propagate_options &opt,
                           chroma_propagate_stats *stats, int32_t *aborted, chroma_hits_request *hr)
@@ -1810,19 +2003,8 @@ static int propagate_impl(chroma_ctx *ctx, chroma_geometry *geom, const chroma_p
     if (!ctx || !geom) return set_error(CHROMA_ERR_INVALID, "bad argument");
     int rc = check_photons(photons, true); if (rc) return rc;
     // what this call does: the context's settings as they are NOW, overridden by the call's own options
-    CallOpts co = call_opts(ctx);
-    if (opt.walk >= 0) {
-        if (opt.walk > CHROMA_WALK_LITERAL_LANE) return set_error(CHROMA_ERR_INVALID, "unknown walk mode %d", opt.walk);
-        co.walk = opt.walk;
-    }
-    if (opt.tail >= 0) {
-        if (opt.tail > CHROMA_TAIL_FUSED) return set_error(CHROMA_ERR_INVALID, "unknown tail mode %d", opt.tail);
-        co.split_tail = opt.tail != CHROMA_TAIL_FUSED;
-        co.fused_tail = opt.tail == CHROMA_TAIL_COOP;
-    }
-    if (opt.counting >= 0) co.counting = opt.counting ? 1 : 0;
-    const int32_t max_steps = opt.max_steps, use_weights = opt.use_weights, time_kernels = opt.time_kernels;
-    int32_t scatter_first = opt.scatter_first;
+    CallPlan plan;
+    rc = make_plan(ctx, geom, opt.walk, opt.tail, opt.counting, &plan); if (rc) return rc;
     // one call at a time per context: the queues, working sets, step block and final records are the context's own
     std::lock_guard<std::mutex> call_lock(ctx->call_mu);
     if (hr) {
@@ -1834,15 +2016,14 @@ static int propagate_impl(chroma_ctx *ctx, chroma_geometry *geom, const chroma_p
     if (nphotons >= 0x7fffffffull) return set_error(CHROMA_ERR_INVALID, "at most 2^31-2 photons per call");
     if (ncopies == 0 || nphotons % ncopies) return set_error(CHROMA_ERR_INVALID, "nphotons must be a multiple of ncopies");
     if (aborted) *aborted = 0;
-    if (nphotons == 0 || max_steps <= 0) return CHROMA_OK;
+    if (nphotons == 0 || opt.max_steps <= 0) return CHROMA_OK;
+    if ((rc = check_stack(geom))) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     rc = ensure_queues(ctx, nphotons); if (rc) return rc;
-    PhotonView pv = to_view(photons);
-    uint32_t *in_q = ctx->queue_a, *out_q = ctx->queue_b;
-    float4 *work_in = ctx->work_a, *work_out = ctx->work_b;
+    rc = ensure_spill(ctx, plan.spill); if (rc) return rc;
     // (final records: with a hit request, or for every call under CHROMA_FINAL_RECORDS=1 -- an A/B switch)
     static const bool records_always = getenv("CHROMA_FINAL_RECORDS") && atoi(getenv("CHROMA_FINAL_RECORDS")) != 0;
-    const bool use_records = (hr != nullptr || records_always) && co.split_tail != 0;
+    const bool use_records = (hr != nullptr || records_always) && plan.tail_mode != CHROMA_TAIL_FUSED;
     ctx->final_use = nullptr;
     if (use_records) {
         rc = ensure_final_records(ctx, nphotons); if (rc) return rc;
@@ -1855,8 +2036,6 @@ static int propagate_impl(chroma_ctx *ctx, chroma_geometry *geom, const chroma_p
     }
     struct FinalGuard { chroma_ctx *c; ~FinalGuard() { c->final_use = nullptr; } } final_guard{ctx};
     // where the call's last pass (k_finalize_hits) puts the hits, if it runs at all
-    const bool finalize = use_records || hr != nullptr;
-    bool finalized = false;              // it has been launched already, beside the tail kernel (launch_tail)
     HitsOut ho; memset(&ho, 0, sizeof ho);
     if (hr) {
         ho.want = 1;
@@ -1864,197 +2043,14 @@ static int propagate_impl(chroma_ctx *ctx, chroma_geometry *geom, const chroma_p
         if (hr->dst) { ho.dst = to_view(hr->dst); ho.channels = hr->d_channels; ho.capacity = hr->capacity; }
         ho.hit_count = hr->d_hit_count; ho.earliest = hr->d_hit_count ? hr->d_earliest_time_bits : nullptr;
     }
-
-    double kernel_ms = 0.0, raycast_ms = 0.0, physics_ms = 0.0, packet_ms = 0.0;
-    uint64_t launches = 0, raycast_launches = 0, physics_launches = 0, packet_launches = 0;
-    bool packet_offered = false;
-    uint64_t reordered = 0;
-    // Launch policy of the reference (chroma/gpu/photon.py:225-252): one step per launch while many
-    // photons are alive, and ONE launch for all remaining steps once fewer than 64*16*8 are left (or
-    // with weights).  A launch re-normalises dir/pol when it loads a photon (propagate.cu:248,250), so
-    // the policy is part of the arithmetic.  Here every step is a ray cast + physics pair that gets the
-    // whole chip; a step that the reference would run inside its last launch skips the re-normalisation
-    // instead (same numbers; with weights that is every step but the first).  The policy is evaluated ON
-    // THE DEVICE (k_step_begin), so the steps are enqueued back to back; the host looks at the survivor
-    // count only now and then, to stop early, to shrink the grids and to hand the last photons to the
-    // fused tail kernel.  The live photons travel in the dense working set (k_load_working).
-    const bool device_steps = co.split_tail != 0;
-    // the walks whose steps chain their ray records from kernel to kernel (k_load_working -> ray cast -> k_physics -> ...)
-    const bool chains_rays = step_uses_quad_walk(co, geom) || co.walk == CHROMA_WALK_LITERAL;
-    if (device_steps) {
-        HIP_TRY(hipMemsetAsync(ctx->d_step, 0, sizeof(StepState), ctx->stream));
-        hipLaunchKernelGGL(k_set_word, dim3(1), dim3(1), 0, ctx->stream, in_q, 1u);
-        hipLaunchKernelGGL(k_set_word, dim3(1), dim3(1), 0, ctx->stream, out_q, 1u);
-        {
-            unsigned blocks = (unsigned)std::min<uint64_t>((nphotons + PHYS_BLOCK - 1) / PHYS_BLOCK, (uint64_t)ctx->physics_blocks);
-#if CHROMA_EXPERIMENTAL
-            const bool probe = step_uses_quad_walk(co, geom) && co.packet != 0 && geom->wide_stack_need <= PACKET_STACK;
-#else
-            const bool probe = false;
-#endif
-            packet_offered = probe;
-            HIP_TRY(hipMemsetAsync(ctx->d_words + 4, 0, 12, ctx->stream));          // [4] use_packet, [5] coherent waves, [6] waves
-            uint32_t *d_order = nullptr;
-            if (step_uses_quad_walk(co, geom)) { rc = propagate_order(ctx, co, pv, nphotons, ncopies, &d_order); if (rc) return rc; }
-            hipLaunchKernelGGL(k_load_working, dim3(blocks), dim3(PHYS_BLOCK), 0, ctx->stream, geom->view, pv, in_q, work_in,
-                               (uint64_t)nphotons, ncopies, (uint32_t)(nphotons / ncopies),
-                               chains_rays ? ctx->rays : nullptr, (probe && co.packet == 2) ? ctx->d_words + 5 : nullptr,
-                               (const uint32_t *)d_order, co.walk == CHROMA_WALK_LITERAL ? 1 : 0);
-            if (d_order) { chroma_free(ctx, d_order); reordered = nphotons; }      // (parked until the stream has passed this point)
-#if CHROMA_EXPERIMENTAL
-            if (probe)
-                hipLaunchKernelGGL(k_packet_decide, dim3(1), dim3(1), 0, ctx->stream, ctx->d_words + 5, ctx->d_words + 4, (uint64_t)nphotons, co.packet);
-#endif
-        }
-        HIP_TRY(hipGetLastError());
-        const int nev = time_kernels ? 6 * max_steps : 0;
-        while ((int)ctx->step_events.size() < nev) { hipEvent_t e; HIP_TRY(hipEventCreate(&e)); ctx->step_events.push_back(e); }
-        long long n_upper = (long long)nphotons;
-        int step = 0, next_check = 1, steps_timed = 0;
-        bool done = false, tail_done = false;
-        const long long few = (long long)PROP_BLOCK * 16 * 8;
-        const bool fused_tail = co.fused_tail && (co.walk == CHROMA_WALK_COOP || co.walk == CHROMA_WALK_QUAD ||
-                                                    co.walk == CHROMA_WALK_PAIR || co.walk == CHROMA_WALK_LITERAL);    // (the cross-check walks keep per-step launches)
-        int tail_step = -1;                  // the step at which the fused tail was launched
-        while (step < max_steps && !done) {
-            if (fused_tail && n_upper < few) {
-                // the reference's last launch: all remaining steps at once, 8 lanes per photon
-                bool launched = false;
-                rc = launch_tail(ctx, co, geom, pv, n_upper, in_q, out_q, work_in, rng, max_steps - step, use_weights,
-                                 step == 0 ? scatter_first : 0, time_kernels ? ctx->step_events.data() + 6 * step : nullptr, &launched,
-                                 step == 0 ? (uint32_t)nphotons : 0u, finalize ? &ho : nullptr, (uint64_t)nphotons);
-                if (rc) return rc;
-                if (launched) {
-                    finalized = finalize;
-                    if (time_kernels) { tail_step = step; steps_timed = step + 1; }
-                    step = max_steps;
-                    tail_done = true;            // (it wrote every photon it held back to the caller's arrays)
-                    break;
-                }
-            }
-            rc = launch_split_step(ctx, co, geom, pv, n_upper, in_q, out_q, work_in, work_out, rng, use_weights,
-                                   step == 0 ? scatter_first : 0, time_kernels ? ctx->step_events.data() + 6 * step : nullptr,
-                                   step == 0 ? (uint32_t)nphotons : 0u, chains_rays, step == 0 && packet_offered);
-            if (rc) return rc;
-            if (time_kernels) steps_timed = step + 1;
-            step++;
-            std::swap(in_q, out_q);
-            std::swap(work_in, work_out);
-            if (step == next_check && step < max_steps) {
-                // survivors = tail - 1 of what is now the input queue
-                HIP_TRY(hipMemcpyAsync(ctx->h_words + 1, in_q, 4, hipMemcpyDeviceToHost, ctx->stream));
-                HIP_TRY(hipStreamSynchronize(ctx->stream));
-                n_upper = (long long)ctx->h_words[1] - 1;
-                if (n_upper <= 0) done = true;
-                // look every step once the tail is near, so that it starts when the reference's does
-                next_check = (fused_tail && n_upper < 16 * few) ? step + 1 : (step < 8) ? step * 2 : step + 8;
-            }
-        }
-        if (!tail_done && !done) {
-            // max_steps reached with photons still alive: they go back to the caller's arrays
-            unsigned blocks = (unsigned)std::min<long long>((n_upper + 255) / 256, 4096);
-            hipLaunchKernelGGL(k_store_working, dim3(std::max(blocks, 1u)), dim3(256), 0, ctx->stream, geom->view, pv, in_q, work_in);
-        }
-        HIP_TRY(hipMemcpyAsync(ctx->h_step, ctx->d_step, sizeof(StepState), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        launches = ((const StepState *)ctx->h_step)->launches;
-        for (int k = 0; k < steps_timed; k++) {
-            float ms = 0.f;
-            HIP_TRY(hipEventElapsedTime(&ms, ctx->step_events[6 * k], ctx->step_events[6 * k + 2]));
-            kernel_ms += ms;
-            if (k == tail_step) continue;             // the fused tail is not a ray-cast launch
-            HIP_TRY(hipEventElapsedTime(&ms, ctx->step_events[6 * k + 5], ctx->step_events[6 * k + 1]));
-            raycast_ms += ms;
-            raycast_launches++;
-            if (k == 0 && packet_offered) {           // the first step's k_raycast_packet launch (an empty one when the photons are not coherent)
-                HIP_TRY(hipEventElapsedTime(&ms, ctx->step_events[6 * k + 3], ctx->step_events[6 * k + 5]));
-                packet_ms += ms;
-                packet_launches++;
-            }
-            HIP_TRY(hipEventElapsedTime(&ms, ctx->step_events[6 * k + 1], ctx->step_events[6 * k + 4]));
-            physics_ms += ms;                         // the main pass of k_physics (not the fix-up pass)
-            physics_launches++;
-        }
-    } else {
-        // CHROMA_TAIL=fused: the lane-per-photon kernel with the reference's own launch shapes
-        hipLaunchKernelGGL(k_init_queue, dim3((unsigned)((nphotons + 255) / 256)), dim3(256), 0, ctx->stream, in_q,
-                           (uint64_t)nphotons, ncopies, (uint32_t)(nphotons / ncopies));
-        hipLaunchKernelGGL(k_set_word, dim3(1), dim3(1), 0, ctx->stream, out_q, 1u);
-        HIP_TRY(hipGetLastError());
-        uint64_t n = nphotons;
-        int step = 0;
-        while (step < max_steps) {
-            const bool few = n < (uint64_t)PROP_BLOCK * 16 * 8;
-            int nsteps = (few || use_weights) ? (max_steps - step) : 1;
-            if (time_kernels) HIP_TRY(hipEventRecord(ctx->ev_start, ctx->stream));
-            rc = launch_propagate(ctx, co, geom, pv, 0, (int)n, in_q + 1, out_q, rng, nsteps, use_weights, scatter_first);
-            if (rc) return rc;
-            launches++;
-            if (time_kernels) {
-                HIP_TRY(hipEventRecord(ctx->ev_stop, ctx->stream));
-                HIP_TRY(hipEventSynchronize(ctx->ev_stop));
-                float ms = 0.f;
-                HIP_TRY(hipEventElapsedTime(&ms, ctx->ev_start, ctx->ev_stop));
-                kernel_ms += ms;
-            }
-            step += nsteps;
-            scatter_first = 0;
-            if (step < max_steps) {
-                std::swap(in_q, out_q);
-                // survivors = tail - 1 (one 4-byte read per step, as photon.py:250)
-                HIP_TRY(hipMemcpyAsync(ctx->h_words + 1, in_q, 4, hipMemcpyDeviceToHost, ctx->stream));
-                hipLaunchKernelGGL(k_set_word, dim3(1), dim3(1), 0, ctx->stream, out_q, 1u);
-                HIP_TRY(hipStreamSynchronize(ctx->stream));
-                n = (uint64_t)ctx->h_words[1] - 1;
-                if (n == 0) break;
-            }
-        }
-    }
-    uint32_t word = 0;
-    if (finalize) {
-        // one pass: records -> the caller's arrays, abort word, hit count + compaction + per-channel arrays (k_finalize_hits);
-        // a call that ended in the tail kernel has run it beside that kernel already (launch_tail)
-        if (!finalized) {
-            HIP_TRY(hipMemsetAsync(ctx->d_words, 0, 12, ctx->stream));
-            const unsigned blocks = (unsigned)((nphotons + COPY_ITEMS * 256 - 1) / (COPY_ITEMS * 256));
-            hipLaunchKernelGGL(k_finalize_hits, dim3(blocks), dim3(256), 0, ctx->stream, geom->view, pv, (const float4 *)ctx->final_use, ctx->final_epoch,
-                               (uint64_t)nphotons, ho, ctx->d_words, 0u);
-            HIP_TRY(hipGetLastError());
-        }
-        HIP_TRY(hipMemcpyAsync(ctx->h_words, ctx->d_words, 12, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        word = ctx->h_words[2];
-        if (hr) hr->nhits = ctx->h_words[0];
-    } else {
-        // abort warning word (photon.py:254-255)
-        HIP_TRY(hipMemsetAsync(ctx->d_words + 2, 0, 4, ctx->stream));
-        {
-            unsigned blocks = (unsigned)std::min<uint64_t>((nphotons + 255) / 256, 4096);
-            hipLaunchKernelGGL(k_flags_or, dim3(blocks), dim3(256), 0, ctx->stream, photons->flags, (uint64_t)nphotons,
-                               CHROMA_NAN_ABORT, ctx->d_words + 2);
-            HIP_TRY(hipGetLastError());
-        }
-        rc = read_word(ctx, 2, &word); if (rc) return rc;
-    }
-    if (aborted) *aborted = (word & CHROMA_NAN_ABORT) ? 1 : 0;
-    if (stats) {
-        rc = chroma_propagate_stats_read(ctx, stats); if (rc) return rc;
-        stats->launches += launches;
-        stats->kernel_ms += kernel_ms;
-        stats->raycast_ms += raycast_ms;
-        stats->raycast_launches += raycast_launches;
-        stats->physics_ms += physics_ms;
-        stats->physics_launches += physics_launches;
-        stats->packet_ms += packet_ms;
-        stats->packet_launches += packet_launches;
-        stats->reordered += reordered;
-        if (stats->stack_overflows) return set_error(CHROMA_ERR_STACK, "traversal stack overflowed for %llu rays", (unsigned long long)stats->stack_overflows);
-    } else {
-        chroma_propagate_stats tmp; memset(&tmp, 0, sizeof tmp);
-        rc = chroma_propagate_stats_read(ctx, &tmp); if (rc) return rc;
-        if (tmp.stack_overflows) return set_error(CHROMA_ERR_STACK, "traversal stack overflowed for %llu rays", (unsigned long long)tmp.stack_overflows);
-    }
-    return CHROMA_OK;
+    const HitsOut *finalize = (use_records || hr) ? &ho : nullptr;
+    const PhotonView pv = to_view(photons);
+    chroma_propagate_stats acc; memset(&acc, 0, sizeof acc);
+    bool finalized = false;
+    rc = plan.tail_mode == CHROMA_TAIL_FUSED ? run_fused(ctx, plan, geom, pv, nphotons, ncopies, rng, opt, &acc)
+                                             : run_device_steps(ctx, plan, geom, pv, nphotons, ncopies, rng, opt, finalize, &acc, &finalized);
+    if (rc) return rc;
+    return finish_call(ctx, geom, photons, nphotons, finalize, finalized, hr, acc, stats, aborted);
 }
 
 static chroma_propagate_options default_options(int32_t max_steps, int32_t use_weights, int32_t scatter_first, int32_t time_kernels)

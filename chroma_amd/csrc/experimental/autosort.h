@@ -43,10 +43,10 @@ __global__ void k_order_probe(PhotonView pv, uint64_t n, uint32_t nsamples, uint
 #define AUTOSORT_MIN (1u << 21)
 #endif
 // *d_order: nullptr (take the photons as they come) or a chroma_malloc'ed permutation the caller frees after k_load_working
-static int propagate_order(chroma_ctx *ctx, const CallOpts &co, const PhotonView &pv, uint64_t nphotons, uint32_t ncopies, uint32_t **d_order)
+static int propagate_order(chroma_ctx *ctx, const CallPlan &plan, const PhotonView &pv, uint64_t nphotons, uint32_t ncopies, uint32_t **d_order)
 {
     *d_order = nullptr;
-    const int mode = co.autosort;
+    const int mode = plan.autosort;
     if (mode == 0 || ncopies != 1 || nphotons < AUTOSORT_MIN) return CHROMA_OK;
     if (mode == 2) {
         const uint32_t nsamples = 1024;
