@@ -27,22 +27,13 @@
 
 #include "../../include/chroma_hip.h"
 #include "bvh_result.h"
-#include "ctx_access.h"
+#include "chroma_internal.h"
 #include "device_common.h"
 
 using chroma_host::Node;
 using chroma_host::BvhResult;
 
 namespace {
-
-#define DEV_TRY(expr)                                                                                     \
-    do {                                                                                                  \
-        hipError_t e_ = (expr);                                                                           \
-        if (e_ != hipSuccess) {                                                                           \
-            chroma_internal_set_error((int)e_, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-            return (int)e_;                                                                               \
-        }                                                                                                 \
-    } while (0)
 
 const int MAX_CHILD = 15;          // 2^(32-28) - 1, chroma/bvh/grid.py:6
 
@@ -237,9 +228,9 @@ int chroma_bvh_build_device(chroma_ctx *ctx, const float *vertices, uint32_t nve
                             void **handle, uint64_t *nnodes, uint32_t *nlayers)
 {
     if (!ctx || !vertices || !triangles || !handle || ntriangles == 0 || ntriangles >= (1u << CHROMA_CHILD_BITS) || target_degree < 1)
-        return chroma_internal_set_error(CHROMA_ERR_INVALID, "chroma_bvh_build_device: bad argument");
-    hipStream_t stream = chroma_internal_stream(ctx);
-    DEV_TRY(hipSetDevice(chroma_internal_device(ctx)));
+        return set_error(CHROMA_ERR_INVALID, "chroma_bvh_build_device: bad argument");
+    hipStream_t stream = ctx->stream;
+    HIP_TRY(hipSetDevice(ctx->device));
     Lap lap(stream);
     Arena arena;
     arena.ctx = ctx;
@@ -247,50 +238,50 @@ int chroma_bvh_build_device(chroma_ctx *ctx, const float *vertices, uint32_t nve
     const float ox = world_origin[0], oy = world_origin[1], oz = world_origin[2], ws = world_scale;
 
     float *d_vertices; uint32_t *d_triangles;
-    DEV_TRY(arena.get(&d_vertices, 3 * (size_t)nvertices));
-    DEV_TRY(arena.get(&d_triangles, 3 * (size_t)n));
-    DEV_TRY(hipMemcpyAsync(d_vertices, vertices, 3 * (size_t)nvertices * sizeof(float), hipMemcpyHostToDevice, stream));
-    DEV_TRY(hipMemcpyAsync(d_triangles, triangles, 3 * (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    HIP_TRY(arena.get(&d_vertices, 3 * (size_t)nvertices));
+    HIP_TRY(arena.get(&d_triangles, 3 * (size_t)n));
+    HIP_TRY(hipMemcpyAsync(d_vertices, vertices, 3 * (size_t)nvertices * sizeof(float), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(d_triangles, triangles, 3 * (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
     unsigned long long *d_hist; uint32_t *d_word;
-    DEV_TRY(arena.get(&d_hist, 64));
-    DEV_TRY(arena.get(&d_word, 4));
-    DEV_TRY(hipMemsetAsync(d_word, 0, 16, stream));
+    HIP_TRY(arena.get(&d_hist, 64));
+    HIP_TRY(arena.get(&d_word, 4));
+    HIP_TRY(hipMemsetAsync(d_word, 0, 16, stream));
     hipLaunchKernelGGL(k_bvh_check_indices, dim3(std::min(blocks_for(3 * (size_t)n), 65535u)), dim3(256), 0, stream, d_triangles, 3 * (size_t)n, nvertices, d_word);
     uint32_t h_word[4] = {0, 0, 0, 0};
-    DEV_TRY(hipMemcpyAsync(h_word, d_word, 4, hipMemcpyDeviceToHost, stream));
-    DEV_TRY(hipStreamSynchronize(stream));
-    if (h_word[0]) return chroma_internal_set_error(CHROMA_ERR_INVALID, "chroma_bvh_build_device: a triangle names a vertex outside the mesh");
+    HIP_TRY(hipMemcpyAsync(h_word, d_word, 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (h_word[0]) return set_error(CHROMA_ERR_INVALID, "chroma_bvh_build_device: a triangle names a vertex outside the mesh");
     lap.lap("upload + validate");
 
     // make_leaves: Morton codes, then the stable sort (grid.py:26-28)
     uint64_t *d_codes, *d_codes_sorted; uint32_t *d_ids, *d_ids_sorted;
-    DEV_TRY(arena.get(&d_codes, n)); DEV_TRY(arena.get(&d_codes_sorted, n));
-    DEV_TRY(arena.get(&d_ids, n)); DEV_TRY(arena.get(&d_ids_sorted, n));
+    HIP_TRY(arena.get(&d_codes, n)); HIP_TRY(arena.get(&d_codes_sorted, n));
+    HIP_TRY(arena.get(&d_ids, n)); HIP_TRY(arena.get(&d_ids_sorted, n));
     hipLaunchKernelGGL(k_bvh_leaf_codes, dim3(blocks_for(n)), dim3(256), 0, stream, d_vertices, d_triangles, n, ox, oy, oz, ws, d_codes, d_ids);
     size_t tmp_bytes = 0;
-    DEV_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, d_codes, d_codes_sorted, d_ids, d_ids_sorted, (int)n, 0, 48, stream));
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, d_codes, d_codes_sorted, d_ids, d_ids_sorted, (int)n, 0, 48, stream));
     // the scans below reuse this scratch area: size it for the largest request
     size_t scan_bytes = 0, sum_bytes = 0;
     {
         uint32_t *nul = nullptr;
-        DEV_TRY(hipcub::DeviceScan::InclusiveScan(nullptr, scan_bytes, nul, nul, MaxOp(), (int)n, stream));
-        DEV_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, sum_bytes, nul, nul, (int)n, stream));
+        HIP_TRY(hipcub::DeviceScan::InclusiveScan(nullptr, scan_bytes, nul, nul, MaxOp(), (int)n, stream));
+        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, sum_bytes, nul, nul, (int)n, stream));
     }
     tmp_bytes = std::max(tmp_bytes, std::max(scan_bytes, sum_bytes));
     uint8_t *d_tmp;
-    DEV_TRY(arena.get(&d_tmp, tmp_bytes));
+    HIP_TRY(arena.get(&d_tmp, tmp_bytes));
     {
         size_t b = tmp_bytes;
-        DEV_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp, b, d_codes, d_codes_sorted, d_ids, d_ids_sorted, (int)n, 0, 48, stream));
+        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp, b, d_codes, d_codes_sorted, d_ids, d_ids_sorted, (int)n, 0, 48, stream));
     }
     lap.lap("leaf codes + morton sort");
     std::vector<uint4 *> layers;            // leaves first
     std::vector<uint32_t> layer_size;
     uint4 *d_leaves;
-    DEV_TRY(arena.get(&d_leaves, n));
+    HIP_TRY(arena.get(&d_leaves, n));
     hipLaunchKernelGGL(k_bvh_gather_leaves, dim3(blocks_for(n)), dim3(256), 0, stream, d_vertices, d_triangles, n, ox, oy, oz, ws, d_ids_sorted, d_leaves);
-    DEV_TRY(hipGetLastError());
-    DEV_TRY(hipStreamSynchronize(stream));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(stream));
     arena.release(d_vertices); arena.release(d_triangles); arena.release(d_codes); arena.release(d_ids);
     layers.push_back(d_leaves); layer_size.push_back(n);
     lap.lap("gather leaves");
@@ -298,18 +289,18 @@ int chroma_bvh_build_device(chroma_ctx *ctx, const float *vertices, uint32_t nve
     // the parent layers.  d_codes_sorted holds the codes of the top layer; the parents' codes go to d_next_codes.
     uint64_t *d_cur_codes = d_codes_sorted, *d_next_codes;
     uint32_t *d_run, *d_flag, *d_pos, *d_first;
-    DEV_TRY(arena.get(&d_next_codes, n));
-    DEV_TRY(arena.get(&d_run, n)); DEV_TRY(arena.get(&d_flag, n)); DEV_TRY(arena.get(&d_pos, n)); DEV_TRY(arena.get(&d_first, n));
+    HIP_TRY(arena.get(&d_next_codes, n));
+    HIP_TRY(arena.get(&d_run, n)); HIP_TRY(arena.get(&d_flag, n)); HIP_TRY(arena.get(&d_pos, n)); HIP_TRY(arena.get(&d_first, n));
     d_ids = d_ids_sorted;                    // (kept only because the arena owns it)
     while (layer_size.back() > 1) {
         const uint32_t nn = layer_size.back();
         const uint4 *top = layers.back();
         // grid.py:37-42: shift the codes until the mean group size reaches target_degree
-        DEV_TRY(hipMemsetAsync(d_hist, 0, 64 * sizeof(unsigned long long), stream));
+        HIP_TRY(hipMemsetAsync(d_hist, 0, 64 * sizeof(unsigned long long), stream));
         hipLaunchKernelGGL(k_bvh_diff_histogram, dim3(std::min(blocks_for(nn), 4096u)), dim3(256), 0, stream, d_cur_codes, nn, d_hist);
         unsigned long long hist[64];
-        DEV_TRY(hipMemcpyAsync(hist, d_hist, sizeof hist, hipMemcpyDeviceToHost, stream));
-        DEV_TRY(hipStreamSynchronize(stream));
+        HIP_TRY(hipMemcpyAsync(hist, d_hist, sizeof hist, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
         unsigned long long above[65];
         above[64] = 0;
         for (int d = 63; d >= 0; d--) above[d] = above[d + 1] + hist[d];
@@ -321,20 +312,20 @@ int chroma_bvh_build_device(chroma_ctx *ctx, const float *vertices, uint32_t nve
         }
         // grid.py:45-76: one parent per run of equal codes, runs cut at MAX_CHILD
         hipLaunchKernelGGL(k_bvh_run_keys, dim3(blocks_for(nn)), dim3(256), 0, stream, d_cur_codes, nn, shift, d_run);
-        { size_t b = tmp_bytes; DEV_TRY(hipcub::DeviceScan::InclusiveScan(d_tmp, b, d_run, d_run, MaxOp(), (int)nn, stream)); }
+        { size_t b = tmp_bytes; HIP_TRY(hipcub::DeviceScan::InclusiveScan(d_tmp, b, d_run, d_run, MaxOp(), (int)nn, stream)); }
         hipLaunchKernelGGL(k_bvh_parent_flags, dim3(blocks_for(nn)), dim3(256), 0, stream, d_run, nn, d_flag);
-        { size_t b = tmp_bytes; DEV_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp, b, d_flag, d_pos, (int)nn, stream)); }
+        { size_t b = tmp_bytes; HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp, b, d_flag, d_pos, (int)nn, stream)); }
         uint32_t last[2];
-        DEV_TRY(hipMemcpyAsync(&last[0], d_pos + (nn - 1), 4, hipMemcpyDeviceToHost, stream));
-        DEV_TRY(hipMemcpyAsync(&last[1], d_flag + (nn - 1), 4, hipMemcpyDeviceToHost, stream));
-        DEV_TRY(hipStreamSynchronize(stream));
+        HIP_TRY(hipMemcpyAsync(&last[0], d_pos + (nn - 1), 4, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipMemcpyAsync(&last[1], d_flag + (nn - 1), 4, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
         const uint32_t np = last[0] + last[1];
-        if (np == 0 || np >= nn + (nn == 1)) return chroma_internal_set_error(CHROMA_ERR_INTERNAL, "chroma_bvh_build_device: a layer of %u nodes got %u parents", nn, np);
+        if (np == 0 || np >= nn + (nn == 1)) return set_error(CHROMA_ERR_INTERNAL, "chroma_bvh_build_device: a layer of %u nodes got %u parents", nn, np);
         hipLaunchKernelGGL(k_bvh_first_children, dim3(blocks_for(nn)), dim3(256), 0, stream, d_flag, d_pos, nn, d_first);
         uint4 *d_parents;
-        DEV_TRY(arena.get(&d_parents, np));
+        HIP_TRY(arena.get(&d_parents, np));
         hipLaunchKernelGGL(k_bvh_make_parents, dim3(blocks_for(np)), dim3(256), 0, stream, top, nn, d_first, np, d_cur_codes, shift, d_parents, d_next_codes);
-        DEV_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         std::swap(d_cur_codes, d_next_codes);
         layers.push_back(d_parents); layer_size.push_back(np);
     }
@@ -346,9 +337,9 @@ int chroma_bvh_build_device(chroma_ctx *ctx, const float *vertices, uint32_t nve
     res->layer_bounds.assign(nl + 1, 0);
     for (size_t l = 0; l < nl; l++) res->layer_bounds[l + 1] = res->layer_bounds[l] + layer_size[nl - 1 - l];
     const uint64_t total = res->layer_bounds[nl];
-    if (total >= (1ull << CHROMA_CHILD_BITS)) { delete res; return chroma_internal_set_error(CHROMA_ERR_INVALID, "chroma_bvh_build_device: %llu nodes do not fit 28-bit child indices", (unsigned long long)total); }
+    if (total >= (1ull << CHROMA_CHILD_BITS)) { delete res; return set_error(CHROMA_ERR_INVALID, "chroma_bvh_build_device: %llu nodes do not fit 28-bit child indices", (unsigned long long)total); }
     uint4 *d_nodes;
-    if (arena.get(&d_nodes, total) != hipSuccess) { delete res; return chroma_internal_set_error(CHROMA_ERR_INTERNAL, "chroma_bvh_build_device: out of device memory"); }
+    if (arena.get(&d_nodes, total) != hipSuccess) { delete res; return set_error(CHROMA_ERR_INTERNAL, "chroma_bvh_build_device: out of device memory"); }
     for (size_t l = 0; l < nl; l++) {
         const uint32_t cnt = layer_size[nl - 1 - l];
         const uint32_t offset = (l + 1 < nl) ? (uint32_t)res->layer_bounds[l + 1] : 0u;
@@ -361,9 +352,9 @@ int chroma_bvh_build_device(chroma_ctx *ctx, const float *vertices, uint32_t nve
     }
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (e != hipSuccess) { delete res; return chroma_internal_set_error((int)e, "chroma_bvh_build_device: %s", hipGetErrorString(e)); }
+    if (e != hipSuccess) { delete res; return set_error((int)e, "chroma_bvh_build_device: %s", hipGetErrorString(e)); }
     res->nodes.resize(total);
-    { const int rc_ = chroma_internal_dtoh(ctx, res->nodes.data(), d_nodes, total * sizeof(uint4)); if (rc_ != CHROMA_OK) { delete res; return rc_; } }
+    { const int rc_ = chroma_memcpy_dtoh(ctx, res->nodes.data(), d_nodes, total * sizeof(uint4)); if (rc_ != CHROMA_OK) { delete res; return rc_; } }
     lap.lap("concatenate + collapse + download");
     *handle = res;
     if (nnodes) *nnodes = total;
@@ -408,40 +399,40 @@ __global__ void k_gather_words(const uint32_t *src, const uint32_t *order, uint3
 
 extern "C" int chroma_photons_sort_direction(chroma_ctx *ctx, const chroma_photon_arrays *photons, uint64_t nphotons)
 {
-    if (!ctx || !photons || !photons->dir) return chroma_internal_set_error(CHROMA_ERR_INVALID, "chroma_photons_sort_direction: bad argument");
-    if (nphotons >= 0x7fffffffull) return chroma_internal_set_error(CHROMA_ERR_INVALID, "at most 2^31-2 photons per call");
+    if (!ctx || !photons || !photons->dir) return set_error(CHROMA_ERR_INVALID, "chroma_photons_sort_direction: bad argument");
+    if (nphotons >= 0x7fffffffull) return set_error(CHROMA_ERR_INVALID, "at most 2^31-2 photons per call");
     if (nphotons < 2) return CHROMA_OK;
-    hipStream_t stream = chroma_internal_stream(ctx);
-    DEV_TRY(hipSetDevice(chroma_internal_device(ctx)));
+    hipStream_t stream = ctx->stream;
+    HIP_TRY(hipSetDevice(ctx->device));
     const uint32_t n = (uint32_t)nphotons;
     Arena arena;
     arena.ctx = ctx;
     uint32_t *d_codes, *d_codes_sorted, *d_ids, *d_order, *d_buf;
-    DEV_TRY(arena.get(&d_codes, n)); DEV_TRY(arena.get(&d_codes_sorted, n));
-    DEV_TRY(arena.get(&d_ids, n)); DEV_TRY(arena.get(&d_order, n));
+    HIP_TRY(arena.get(&d_codes, n)); HIP_TRY(arena.get(&d_codes_sorted, n));
+    HIP_TRY(arena.get(&d_ids, n)); HIP_TRY(arena.get(&d_order, n));
     hipLaunchKernelGGL(k_direction_codes, dim3(blocks_for(n)), dim3(256), 0, stream, photons->dir, n, d_codes, d_ids);
     size_t tmp_bytes = 0;
-    DEV_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, d_codes, d_codes_sorted, d_ids, d_order, (int)n, 0, 32, stream));
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, d_codes, d_codes_sorted, d_ids, d_order, (int)n, 0, 32, stream));
     uint8_t *d_tmp;
-    DEV_TRY(arena.get(&d_tmp, tmp_bytes));
-    DEV_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp, tmp_bytes, d_codes, d_codes_sorted, d_ids, d_order, (int)n, 0, 32, stream));
-    DEV_TRY(hipStreamSynchronize(stream));
+    HIP_TRY(arena.get(&d_tmp, tmp_bytes));
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp, tmp_bytes, d_codes, d_codes_sorted, d_ids, d_order, (int)n, 0, 32, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
     arena.release(d_codes); arena.release(d_codes_sorted); arena.release(d_ids); arena.release(d_tmp);
-    DEV_TRY(arena.get(&d_buf, 3 * (size_t)n));
+    HIP_TRY(arena.get(&d_buf, 3 * (size_t)n));
     float *f3[3] = {photons->pos, photons->dir, photons->pol};
     for (float *a : f3) {
         if (!a) continue;
         hipLaunchKernelGGL((k_gather_words<3>), dim3(blocks_for(n)), dim3(256), 0, stream, (const uint32_t *)a, d_order, n, d_buf);
-        DEV_TRY(hipMemcpyAsync(a, d_buf, 3 * (size_t)n * 4, hipMemcpyDeviceToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(a, d_buf, 3 * (size_t)n * 4, hipMemcpyDeviceToDevice, stream));
     }
     void *w1[7] = {photons->wavelengths, photons->t, photons->flags, photons->last_hit_triangles, photons->weights, photons->evidx, photons->rng_counters};
     for (void *a : w1) {
         if (!a) continue;
         hipLaunchKernelGGL((k_gather_words<1>), dim3(blocks_for(n)), dim3(256), 0, stream, (const uint32_t *)a, d_order, n, d_buf);
-        DEV_TRY(hipMemcpyAsync(a, d_buf, (size_t)n * 4, hipMemcpyDeviceToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(a, d_buf, (size_t)n * 4, hipMemcpyDeviceToDevice, stream));
     }
-    DEV_TRY(hipGetLastError());
-    DEV_TRY(hipStreamSynchronize(stream));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(stream));
     return CHROMA_OK;
 }
 
@@ -462,39 +453,39 @@ __global__ void k_hit_keys(const uint32_t *evidx, const int32_t *channels, uint3
 
 extern "C" int chroma_hits_sort(chroma_ctx *ctx, const chroma_photon_arrays *hits, int32_t *d_channels, uint64_t nhits)
 {
-    if (!ctx || !hits || !d_channels) return chroma_internal_set_error(CHROMA_ERR_INVALID, "chroma_hits_sort: bad argument");
-    if (nhits >= 0x7fffffffull) return chroma_internal_set_error(CHROMA_ERR_INVALID, "at most 2^31-2 hits per call");
+    if (!ctx || !hits || !d_channels) return set_error(CHROMA_ERR_INVALID, "chroma_hits_sort: bad argument");
+    if (nhits >= 0x7fffffffull) return set_error(CHROMA_ERR_INVALID, "at most 2^31-2 hits per call");
     if (nhits < 2) return CHROMA_OK;
-    hipStream_t stream = chroma_internal_stream(ctx);
-    DEV_TRY(hipSetDevice(chroma_internal_device(ctx)));
+    hipStream_t stream = ctx->stream;
+    HIP_TRY(hipSetDevice(ctx->device));
     const uint32_t n = (uint32_t)nhits;
     Arena arena;
     arena.ctx = ctx;
     unsigned long long *d_keys, *d_keys_sorted;
     uint32_t *d_ids, *d_order, *d_buf;
-    DEV_TRY(arena.get(&d_keys, n)); DEV_TRY(arena.get(&d_keys_sorted, n));
-    DEV_TRY(arena.get(&d_ids, n)); DEV_TRY(arena.get(&d_order, n));
+    HIP_TRY(arena.get(&d_keys, n)); HIP_TRY(arena.get(&d_keys_sorted, n));
+    HIP_TRY(arena.get(&d_ids, n)); HIP_TRY(arena.get(&d_order, n));
     hipLaunchKernelGGL(k_hit_keys, dim3(blocks_for(n)), dim3(256), 0, stream, (const uint32_t *)hits->evidx, (const int32_t *)d_channels, n, d_keys, d_ids);
     size_t tmp_bytes = 0;
-    DEV_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, d_keys, d_keys_sorted, d_ids, d_order, (int)n, 0, 64, stream));
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, d_keys, d_keys_sorted, d_ids, d_order, (int)n, 0, 64, stream));
     uint8_t *d_tmp;
-    DEV_TRY(arena.get(&d_tmp, tmp_bytes));
-    DEV_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp, tmp_bytes, d_keys, d_keys_sorted, d_ids, d_order, (int)n, 0, 64, stream));
-    DEV_TRY(arena.get(&d_buf, 3 * (size_t)n));
+    HIP_TRY(arena.get(&d_tmp, tmp_bytes));
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp, tmp_bytes, d_keys, d_keys_sorted, d_ids, d_order, (int)n, 0, 64, stream));
+    HIP_TRY(arena.get(&d_buf, 3 * (size_t)n));
     float *f3[3] = {hits->pos, hits->dir, hits->pol};
     for (float *a : f3) {
         if (!a) continue;
         hipLaunchKernelGGL((k_gather_words<3>), dim3(blocks_for(n)), dim3(256), 0, stream, (const uint32_t *)a, d_order, n, d_buf);
-        DEV_TRY(hipMemcpyAsync(a, d_buf, 3 * (size_t)n * 4, hipMemcpyDeviceToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(a, d_buf, 3 * (size_t)n * 4, hipMemcpyDeviceToDevice, stream));
     }
     void *w1[8] = {hits->wavelengths, hits->t, hits->flags, hits->last_hit_triangles, hits->weights, hits->evidx, hits->rng_counters, d_channels};
     for (void *a : w1) {
         if (!a) continue;
         hipLaunchKernelGGL((k_gather_words<1>), dim3(blocks_for(n)), dim3(256), 0, stream, (const uint32_t *)a, d_order, n, d_buf);
-        DEV_TRY(hipMemcpyAsync(a, d_buf, (size_t)n * 4, hipMemcpyDeviceToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(a, d_buf, (size_t)n * 4, hipMemcpyDeviceToDevice, stream));
     }
-    DEV_TRY(hipGetLastError());
-    DEV_TRY(hipStreamSynchronize(stream));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(stream));
     return CHROMA_OK;
 }
 
@@ -523,7 +514,7 @@ __global__ void k_order_codes(const float *dir, uint32_t n, uint32_t *codes, uin
 
 extern "C" int chroma_internal_direction_order(chroma_ctx *ctx, const float *d_dir, uint32_t n, uint32_t *d_order)
 {
-    hipStream_t stream = chroma_internal_stream(ctx);
+    hipStream_t stream = ctx->stream;
     void *codes = nullptr, *sorted = nullptr, *ids = nullptr, *tmp = nullptr;
     int rc = chroma_malloc(ctx, (size_t)n * 4, &codes);
     if (rc == CHROMA_OK) rc = chroma_malloc(ctx, (size_t)n * 4, &sorted);
@@ -541,7 +532,7 @@ extern "C" int chroma_internal_direction_order(chroma_ctx *ctx, const float *d_d
     }
     chroma_free(ctx, codes); chroma_free(ctx, sorted); chroma_free(ctx, ids); chroma_free(ctx, tmp);      // (parked behind the stream's work)
     if (rc != CHROMA_OK) return rc;
-    if (e != hipSuccess) return chroma_internal_set_error((int)e, "direction order: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return set_error((int)e, "direction order: %s", hipGetErrorString(e));
     return CHROMA_OK;
 }
 
@@ -551,16 +542,16 @@ extern "C" int chroma_internal_sort_pairs(chroma_ctx *ctx, const uint32_t *d_key
                                           uint32_t *d_values_out, uint32_t n, int end_bit)
 {
     if (n == 0) return CHROMA_OK;
-    if (n >= 0x7fffffffu || end_bit < 1 || end_bit > 32) return chroma_internal_set_error(CHROMA_ERR_INVALID, "sort_pairs: bad argument");
-    hipStream_t stream = chroma_internal_stream(ctx);
+    if (n >= 0x7fffffffu || end_bit < 1 || end_bit > 32) return set_error(CHROMA_ERR_INVALID, "sort_pairs: bad argument");
+    hipStream_t stream = ctx->stream;
     size_t tmp_bytes = 0;
     hipError_t e = hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, d_keys, d_keys_out, d_values, d_values_out, (int)n, 0, end_bit, stream);
-    if (e != hipSuccess) return chroma_internal_set_error((int)e, "sort_pairs: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return set_error((int)e, "sort_pairs: %s", hipGetErrorString(e));
     void *tmp = nullptr;
     int rc = chroma_malloc(ctx, std::max<size_t>(tmp_bytes, 4), &tmp);
     if (rc != CHROMA_OK) return rc;
     e = hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, d_keys, d_keys_out, d_values, d_values_out, (int)n, 0, end_bit, stream);
     chroma_free(ctx, tmp);                 // (parked behind the sort)
-    if (e != hipSuccess) return chroma_internal_set_error((int)e, "sort_pairs: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return set_error((int)e, "sort_pairs: %s", hipGetErrorString(e));
     return CHROMA_OK;
 }

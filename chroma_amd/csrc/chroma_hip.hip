@@ -1,8 +1,11 @@
-// chroma_hip.hip -- the C ABI of libchroma_hip.so (gfx950 / MI355X only): contexts, device memory, geometry upload, the host
-// side of chroma_propagate* (step loop, launch policy) and of every other entry point of include/chroma_hip.h.
+// chroma_hip.hip -- the propagate path of libchroma_hip.so (gfx950 / MI355X only): what a chroma_propagate* call runs (CallPlan),
+// its launches, step loop and tail, the settings and statistics that go with it, and the two calls that run this path's device
+// code on rays of their own: chroma_intersect_mesh (the same ray-cast kernels) and the hybrid render (k_propagate's step functions:
+// the compiler specialises those for their callers, so the family compiles as it did only beside k_propagate).  The other entry points of include/chroma_hip.h: context.hip, geometry.hip, kernel_calls.hip, comm.hip,
+// bvh_device.hip, wide_device.hip.
 //
-// The kernels live in one header per family, included below in dependency order (one translation unit: the families share
-// device helpers and launch-time constants):
+// The kernels of this path live in one header per family, included below in dependency order (each family is compiled in
+// this translation unit alone):
 //   kernel_propagate_fused.h      k_propagate -- lane-per-photon fused multi-step kernel
 //   kernel_step_control.h         hit codes, k_step_begin, ray records, k_ray_setup
 //   kernels_raycast_crosscheck.h  k_raycast_persistent / _wide / _coop -- cross-check walks (+ the eight-lane helpers)
@@ -13,29 +16,15 @@
 //   kernel_raycast_retry.h        k_raycast_retry -- the strict loop for rays the fast walks hand over
 //   kernel_physics.h              k_physics
 //   kernels_working_set.h         k_load_working, k_store_working
-//   kernels_photons_hits.h        photon-array kernels, hit extraction, k_finalize_hits
-//   kernels_daq_render.h          DAQ, distance_to_mesh, render, transforms, bomb generator, probe
-//   kernels_pdf.h                 per-channel PDFs over DAQ output: binning, PDF evaluation, moments, kernel estimate
+//   kernels_propagate_ends.h      the initial queue, the abort-flag reduction, k_finalize_hits
+//   kernels_distance.h            k_distance_to_mesh, and the fast path of chroma_intersect_mesh around k_raycast_quad
+//   kernels_hybrid_render.h       the hybrid render: k_propagate's step functions, one lane per sample
 //   experimental/*.h              measured-and-not-faster kernels: ONLY in build_variants/libchroma_hip_experimental.so
 // See DESIGN.md for the data layout and what bounds each kernel.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
 #include <stdio.h>
-#include <stdarg.h>
 #include <stdlib.h>
 #include <string.h>
-#include <string>
-#include <vector>
 #include <algorithm>
-#include <chrono>
-#include <atomic>
-#include <mutex>
-#include <unordered_map>
-#include <map>
-#include <type_traits>
-
-#include <dlfcn.h>
-#include <rccl/rccl.h>          // types and prototypes only: RCCL itself is found with dlopen at first use
 
 #ifndef CHROMA_EXPERIMENTAL
 #define CHROMA_EXPERIMENTAL 0      // 1: build_variants/libchroma_hip_experimental.so (csrc/experimental/: packet ray cast, dealt physics, autosort)
@@ -43,154 +32,12 @@
 #ifndef CHROMA_HYBRID_RENDER
 #define CHROMA_HYBRID_RENDER 1     // 0 only for tests/test_hybrid_isa.py: the other kernels compiled without the hybrid render's
 #endif
+#include "chroma_internal.h"
 #include "propagate_device.h"
-#include "wide_build.h"
-#include "host_utils.h"
-
-// ---------------------------------------------------------------------------------------------------
-// error handling
-// ---------------------------------------------------------------------------------------------------
-static thread_local std::string g_last_error;
-
-static int set_error(int code, const char *fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_last_error = buf;
-    return code;
-}
-
-#include "ctx_access.h"
-extern "C" int chroma_internal_set_error(int code, const char *fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_last_error = buf;
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                          \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess)                                                                  \
-            return set_error((int)e_, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-
-struct StepState {
-    uint32_t n;          // photons queued for this step
-    uint32_t renorm;     // this step opens a launch in the reference's sense: re-normalise dir/pol on load
-    uint32_t in_tail;    // the reference's last launch (all remaining steps) has begun
-    uint32_t launches;   // launches in the reference's sense so far
-    uint32_t work;       // next unclaimed ray of the persistent ray cast
-    uint32_t retry;      // rays left for k_raycast_retry
-    uint32_t pad[2];
-};
-
-struct chroma_ctx {
-    int device;
-    hipStream_t stream;
-    // queue ping-pong buffers for chroma_propagate (n+1 words each)
-    uint32_t *queue_a = nullptr, *queue_b = nullptr;
-    size_t queue_capacity = 0;
-    // (triangle, distance) per queue slot handed from k_raycast to k_physics
-    int32_t *hit_triangle = nullptr;
-    float *hit_distance = nullptr;
-    uint32_t *retry_list = nullptr;        // [capacity] queue slots handed to k_raycast_retry
-    float4 *rays = nullptr;                // [capacity][4] ray records (k_ray_setup / k_load_working / k_physics)
-    float4 *rays_b = nullptr;              // the records of the NEXT step while k_physics writes them (default walk)
-    float4 *work_a = nullptr, *work_b = nullptr;    // [capacity][4] the dense working sets that go with queue_a / queue_b
-    // chroma_propagate_hits: photons that end in k_physics leave as one 64-byte record at their id (final_rec, stamped with the
-    // call's epoch); k_finalize_hits fills the caller's arrays from the records and extracts the hits in one pass
-    float4 *final_rec = nullptr; size_t final_capacity = 0; uint32_t final_epoch = 0;
-    float4 *final_use = nullptr;           // final_rec while a call uses the records, else NULL (k_physics stores to the arrays)
-    // small device scratch: [0..3] DeviceCounters, then misc words
-    DeviceCounters *d_counters = nullptr;
-    uint32_t *d_words = nullptr;        // 16 words
-    uint32_t *h_words = nullptr;        // pinned mirror
-    int counting = 0;
-    StepState *d_step = nullptr;           // device-side step control block (k_step_begin)
-    uint32_t *h_step = nullptr;            // pinned copy for the occasional read-back
-    int physics_blocks = 256 * 8;          // grid cap of k_physics (blocks stride over the queue)
-    std::vector<hipEvent_t> step_events;   // 4 per step when kernels are timed
-    int persistent_waves = 256 * 20 * 4;   // grid of the persistent ray-cast kernel (set from the device at init)
-    int wide_waves = 256 * 14;             // same for k_raycast_wide (11 KB of LDS per wave)
-    uint2 *wide_spill = nullptr;           // [wide_waves][WIDE_SPILL][64] stack entries beyond the LDS part
-    int coop_waves = 256 * 32;             // grid of k_raycast_coop (2 KB of LDS per wave: wave slots limit residency)
-    int quad_waves = 256 * 24;             // grid of k_raycast_quad
-    int pair_waves = 256 * 20;             // grid of k_raycast_pair (32 rays per wave)
-    uint2 *coop_spill = nullptr;           // [coop_waves][8][COOP_SPILL]
-    int ray_chunk = 256, coop_chunk = 64;  // rays a persistent wave takes from the queue per atomic (big batches)
-    int claim_static = 5 | 8 << 4;                  // eighths of a wave's share of a launch's rays that it takes without the counter (k_raycast_quad; CHROMA_CLAIM_STATIC)
-    int tail_mode = CHROMA_TAIL_COOP;      // CHROMA_TAIL_*: the last photons in k_tail_coop | one launch set per step to the end | k_propagate only
-    int autosort_mode = 0;                 // the order a large call takes its photons up in: 0 as they come (default: the index sort + gather cost more than they gain, profiles/r03/ab_autosort.txt), 1 by direction cell, 2 decided by a probe (propagate_order)
-    int packet_mode = 0;                   // k_raycast_packet for the first step: 0 never (default: it is not faster, profiles/r03/ab_packet_first_step.txt), 1 always, 2 when the photons are coherent (CHROMA_PACKET=off|on|auto)
-    int walk = CHROMA_WALK_QUAD;           // CHROMA_WALK_*: reference tree | wide tree with 1, 8 or 4 (default) lanes per ray
-    hipEvent_t ev_start = nullptr, ev_stop = nullptr, ev_mid = nullptr;
-    // the one exchange of the path (per-channel hit arrays): an RCCL communicator over the node's GPUs
-    ncclComm_t comm = nullptr;
-    int comm_nranks = 1, comm_rank = 0;
-    uint32_t *gather_buf = nullptr;        // [comm_nranks][n] words for the OR reduction (all-gather + local OR)
-    size_t gather_capacity = 0;
-    // ---- device-memory pool behind chroma_malloc / chroma_free (see there) ----
-    struct PoolBlock { void *ptr; hipEvent_t ev; };
-    std::mutex call_mu;                                    // one chroma_propagate* call at a time per context (see propagate_impl)
-    std::mutex pool_mu;
-    std::multimap<size_t, PoolBlock> pool;                 // free blocks by size
-    std::unordered_map<void *, size_t> live;               // size of every block handed out
-    std::vector<hipEvent_t> pool_events;                   // spare events
-    size_t pool_bytes = 0, pool_limit = 0;
-    uint64_t pool_hits = 0, pool_misses = 0;
-    // ---- host -> device uploads: a second stream and a ring of pinned staging buffers (chroma_upload) ----
-    hipStream_t copy_stream = nullptr;
-    hipStream_t aux_stream = nullptr;          // k_finalize_hits beside the tail kernel (launch_tail)
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    std::mutex stage_mu;
-    static constexpr int STAGE_N = 3;
-    static constexpr size_t STAGE_BYTES = 64u << 20;
-    void *stage[STAGE_N] = {nullptr, nullptr, nullptr};
-    hipEvent_t stage_ev[STAGE_N] = {nullptr, nullptr, nullptr};
-    // the same ring for device -> host copies, with its own lock: a hit download does not queue behind the next batch's upload
-    std::mutex stage_down_mu;
-    void *stage_down[STAGE_N] = {nullptr, nullptr, nullptr};
-    hipEvent_t stage_down_ev[STAGE_N] = {nullptr, nullptr, nullptr};
-};
-
-extern "C" hipStream_t chroma_internal_stream(chroma_ctx *ctx) { return ctx->stream; }
-extern "C" int chroma_internal_device(chroma_ctx *ctx) { return ctx->device; }
-
-struct chroma_geometry {
-    chroma_ctx *ctx;
-    GeoView view;
-    std::vector<void *> allocations;
-    void *d_vertices = nullptr, *d_triangles = nullptr, *d_material_codes = nullptr, *d_colors = nullptr;
-    void *d_nodes_api = nullptr;       // nodes exactly as passed in (GPUGeometry.nodes)
-    size_t nvertices = 0, ntriangles = 0, nnodes = 0, nwide = 0, nrecords = 0;
-    uint32_t stack_need = 0, wide_depth = 0, wide_stack_need = 0;
-    size_t device_bytes = 0;
-};
-
-// hipMalloc for the library's own working buffers: when the device is out of memory, everything parked in the pool
-// behind chroma_malloc / chroma_free is given back first (defined next to the pool)
-static hipError_t ctx_malloc(chroma_ctx *ctx, void **ptr, size_t bytes);
-extern "C" hipError_t chroma_internal_malloc(chroma_ctx *ctx, void **ptr, size_t bytes) { return ctx_malloc(ctx, ptr, bytes); }
 
 // ---------------------------------------------------------------------------------------------------
 // kernels
 // ---------------------------------------------------------------------------------------------------
-#define PROP_BLOCK 64
-#ifndef STACK_LDS
-#define STACK_LDS 24      // traversal stack entries kept in LDS (6 KB per wave); deeper ones spill to scratch
-#endif
-#ifndef RAY_WAVES
-#define RAY_WAVES 1        // __launch_bounds__ waves/SIMD hint for the ray-cast kernel
-#endif
-
 #include "kernel_propagate_fused.h"
 
 #include "kernel_step_control.h"
@@ -222,11 +69,9 @@ extern "C" hipError_t chroma_internal_malloc(chroma_ctx *ctx, void **ptr, size_t
 
 #include "kernels_working_set.h"
 
-#include "kernels_photons_hits.h"
+#include "kernels_propagate_ends.h"
 
-#include "kernels_daq_render.h"
-
-#include "kernels_pdf.h"
+#include "kernels_distance.h"
 
 #if CHROMA_HYBRID_RENDER
 #include "kernels_hybrid_render.h"
@@ -235,31 +80,6 @@ extern "C" hipError_t chroma_internal_malloc(chroma_ctx *ctx, void **ptr, size_t
 // ---------------------------------------------------------------------------------------------------
 // host helpers
 // ---------------------------------------------------------------------------------------------------
-static PhotonView to_view(const chroma_photon_arrays *a)
-{
-    PhotonView v;
-    v.pos = a->pos; v.dir = a->dir; v.pol = a->pol; v.wavelengths = a->wavelengths; v.t = a->t;
-    v.flags = a->flags; v.last_hit_triangles = a->last_hit_triangles; v.weights = a->weights;
-    v.evidx = a->evidx; v.rng_counters = a->rng_counters;
-    return v;
-}
-
-static int check_photons(const chroma_photon_arrays *a, bool need_rng)
-{
-    if (!a || !a->pos || !a->dir || !a->pol || !a->wavelengths || !a->t || !a->flags || !a->last_hit_triangles ||
-        !a->weights || !a->evidx || (need_rng && !a->rng_counters))
-        return set_error(CHROMA_ERR_INVALID, "photon arrays: null pointer");
-    return CHROMA_OK;
-}
-
-
-// f(std::integral_constant<bool, B>{}): one launch site for both instantiations of a kernel template
-template <class F>
-static void with_bool(bool b, F &&f)
-{
-    if (b) f(std::true_type{}); else f(std::false_type{});
-}
-
 // the reference's tree with STACK_LDS entries in LDS and the rest in scratch: k_propagate, the persistent cast and the strict
 // retry loop walk it, so every call may
 static int check_stack(const chroma_geometry *geom)
@@ -562,949 +382,50 @@ static int launch_tail(chroma_ctx *ctx, const CallPlan &plan, chroma_geometry *g
     return CHROMA_OK;
 }
 
-template <class T>
-static int upload(chroma_geometry *g, const T *host, size_t count, const T **dev_out)
+// chroma_init's share of this file: the grids of the ray-cast kernels from their residency, the walk and the launch policy
+// from the CHROMA_* environment
+int propagate_settings(chroma_ctx *ctx)
 {
-    *dev_out = nullptr;
-    size_t bytes = std::max(count, (size_t)1) * sizeof(T);
-    void *d = nullptr;
-    HIP_TRY(ctx_malloc(g->ctx, &d, bytes));
-    g->allocations.push_back(d);
-    g->device_bytes += bytes;
-    if (count && host) HIP_TRY(hipMemcpy(d, host, count * sizeof(T), hipMemcpyHostToDevice));
-    else HIP_TRY(hipMemset(d, 0, bytes));
-    *dev_out = (const T *)d;
+    const int device = ctx->device;
+    hipDeviceProp_t prop;
+    HIP_TRY(hipGetDeviceProperties(&prop, device));
+    int per_cu = 20;                     // LDS-limited residency of k_raycast_persistent (8 KB per wave)
+    if (const char *e = getenv("CHROMA_RAY_WAVES_PER_CU")) per_cu = std::max(1, atoi(e));
+    ctx->persistent_waves = prop.multiProcessorCount * per_cu;
+    ctx->physics_blocks = prop.multiProcessorCount * 8;          // (for blocks of PHYS_BLOCK threads)
+    int wide_per_cu = 14;                // LDS-limited residency of k_raycast_wide
+    if (const char *e = getenv("CHROMA_WIDE_WAVES_PER_CU")) wide_per_cu = std::max(1, atoi(e));
+    ctx->wide_waves = prop.multiProcessorCount * wide_per_cu;
+    int coop_per_cu = 28;                // 71 VGPRs (amdgpu_waves_per_eu 7): 7 waves per SIMD
+    if (const char *e = getenv("CHROMA_COOP_WAVES_PER_CU")) coop_per_cu = std::max(1, atoi(e));
+    ctx->coop_waves = prop.multiProcessorCount * coop_per_cu;
+    int quad_per_cu = 4 * QUAD_WAVES_PER_EU;
+    if (const char *e = getenv("CHROMA_QUAD_WAVES_PER_CU")) quad_per_cu = std::max(1, atoi(e));
+    ctx->quad_waves = prop.multiProcessorCount * quad_per_cu;
+    int pair_per_cu = 4 * PAIR_WAVES_PER_EU;
+    if (const char *e = getenv("CHROMA_PAIR_WAVES_PER_CU")) pair_per_cu = std::max(1, atoi(e));
+    ctx->pair_waves = prop.multiProcessorCount * pair_per_cu;
+    if (const char *e = getenv("CHROMA_WALK"))
+        ctx->walk = !strcmp(e, "reference") ? CHROMA_WALK_REFERENCE : !strcmp(e, "wide") ? CHROMA_WALK_WIDE
+                  : !strcmp(e, "coop") ? CHROMA_WALK_COOP : !strcmp(e, "pair") ? CHROMA_WALK_PAIR
+                  : (!strcmp(e, "literal") || !strcmp(e, "exact")) ? CHROMA_WALK_LITERAL
+                  : !strcmp(e, "literal_lane") ? CHROMA_WALK_LITERAL_LANE : CHROMA_WALK_QUAD;
+#if CHROMA_EXPERIMENTAL
+    if (const char *e = getenv("CHROMA_PACKET")) ctx->packet_mode = !strcmp(e, "on") ? 1 : !strcmp(e, "auto") ? 2 : 0;
+    if (const char *e = getenv("CHROMA_AUTOSORT")) ctx->autosort_mode = !strcmp(e, "on") || !strcmp(e, "1") ? 1 : !strcmp(e, "off") || !strcmp(e, "0") ? 0 : 2;
+#endif
+    if (const char *e = getenv("CHROMA_RAY_CHUNK")) ctx->ray_chunk = std::max(64, atoi(e));
+    if (const char *e = getenv("CHROMA_COOP_CHUNK")) ctx->coop_chunk = std::max(8, atoi(e));
+    if (const char *e = getenv("CHROMA_CLAIM_STATIC")) { int big = 0, small = 0; if (sscanf(e, "%d:%d", &big, &small) < 2) small = big; ctx->claim_static = std::min(8, std::max(0, big)) | std::min(8, std::max(0, small)) << 4; }
+    if (const char *e = getenv("CHROMA_TAIL"))        // coop (default) | split | fused (the lane-per-photon k_propagate)
+        ctx->tail_mode = !strcmp(e, "fused") ? CHROMA_TAIL_FUSED : !strcmp(e, "split") ? CHROMA_TAIL_SPLIT : CHROMA_TAIL_COOP;
     return CHROMA_OK;
-}
-
-// chroma_geometry_create's two derived arrays, made on the device from what has just been uploaded
-__global__ void k_traversal_nodes(const uint4 *nodes, uint32_t nnodes, const uint32_t *tri_to_dev, uint32_t ntriangles, uint4 *out)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nnodes) return;
-    uint4 n = nodes[i];
-    if ((n.w >> CHROMA_CHILD_BITS) == 0) { const uint32_t t = n.w & ~CHROMA_NCHILD_MASK; n.w = t < ntriangles ? tri_to_dev[t] : n.w; }
-    out[i] = n;
-}
-__global__ void k_triangle_records(const float *vertices, const uint32_t *triangles, const uint32_t *codes, const uint32_t *rank,
-                                   const uint32_t *dev_to_tri, uint32_t nrecords, float4 *tri)
-{
-    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= nrecords) return;
-    const uint32_t t = dev_to_tri[k];
-    const uint32_t extra[3] = {codes[t], t, rank[t]};
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-        const float *vv = vertices + 3 * (size_t)triangles[3 * (size_t)t + c];
-        tri[(size_t)TRI_STRIDE * k + c] = make_float4(vv[0], vv[1], vv[2], __uint_as_float(extra[c]));
-    }
-}
-// the 32-byte physics records (TriPhys, device_common.h), one per 48-byte record and in the same order: the normal by
-// fill_state's expression and the leaf box by the reference's rule, from the record's vertices, in k_physics's arithmetic
-__global__ void k_triangle_phys(GeoView g, uint32_t nrecords, uint4 *out)
-{
-    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= nrecords) return;
-    const float4 *t = g.tri + (size_t)TRI_STRIDE * k;
-    const float4 a = t[0], b = t[1], c = t[2];
-    const v3 v0 = mk3(a.x, a.y, a.z), v1 = mk3(b.x, b.y, b.z), v2 = mk3(c.x, c.y, c.z);
-    const v3 n = triangle_normal(v0, v1, v2);
-    uint32_t bx, by, bz;
-    leaf_words(g, v0, v1, v2, bx, by, bz);
-    out[2 * (size_t)k] = make_uint4(__float_as_uint(n.x), __float_as_uint(n.y), __float_as_uint(n.z), __float_as_uint(a.w));
-    out[2 * (size_t)k + 1] = make_uint4(__float_as_uint(b.w), bx, by, bz);
-}
-// the 48-byte intersection records (GeoView::tri_isect, device_common.h), one per triangle record and in the same order:
-// the edges by intersect_triangle's expressions (v1 - v0, v2 - v0 in float), laid out for intersect_triangle_edges
-__global__ void k_triangle_isect(GeoView g, uint32_t nrecords, float4 *out)
-{
-    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= nrecords) return;
-    const float4 *t = g.tri + (size_t)TRI_STRIDE * k;
-    const float4 a = t[0], b = t[1], c = t[2];
-    const v3 v0 = mk3(a.x, a.y, a.z), e1 = mk3(b.x, b.y, b.z) - v0, e2 = mk3(c.x, c.y, c.z) - v0;
-    out[3 * (size_t)k] = make_float4(e1.x, e2.x, e1.y, e2.y);
-    out[3 * (size_t)k + 1] = make_float4(e1.z, e2.z, v0.x, v0.y);
-    out[3 * (size_t)k + 2] = make_float4(v0.z, c.w, 0.0f, 0.0f);
-}
-// Worst-case number of simultaneously live stack entries of the depth-first walk in
-// intersect_mesh for this tree (every box test succeeding).  Children always have larger
-// indices than their parent (layers are stored root first), so one backward sweep suffices.
-// Most entries a walk's stack can hold at once, for the two trees of a geometry, from the arrays AS UPLOADED.
-// need(node) = max over its inner children c, in push order, of (inner children before c) + need(c) [reference walk, mesh.h:68-110],
-// need(node) = inner children - 1 + max need(child) [nearest-first wide walk].  Children follow their parents in both arrays, so
-// the values are the least fixed point of these rules: every pass over the array only raises entries, and after (depth of the
-// tree) passes nothing changes -- ~30 passes of a few milliseconds instead of a second-long backward sweep on one host core.
-__global__ void k_stack_need_ref(const uint4 *nodes, uint32_t nnodes, uint32_t *need, uint32_t *changed)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nnodes) return;
-    const uint32_t w = nodes[i].w, nchild = w >> CHROMA_CHILD_BITS, first = w & ~CHROMA_NCHILD_MASK;
-    if (nchild == 0) return;
-    uint32_t best = 0;
-    if ((uint64_t)first + nchild > nnodes || first <= i) best = 0xFFFFu;
-    else {
-        uint32_t rank = 0;
-        for (uint32_t j = 0; j < nchild; j++)
-            if ((nodes[first + j].w >> CHROMA_CHILD_BITS) != 0) { best = max(best, rank + need[first + j]); rank++; }
-        best = min(max(best, rank), 0xFFFFu);
-    }
-    if (best != need[i]) { need[i] = best; *changed = 1u; }
-}
-__global__ void k_stack_need_wide(const uint4 *wnodes, uint32_t nwide, uint32_t *need, uint32_t *changed)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nwide) return;
-    uint32_t inner = 0, below = 0;
-    for (int j = 0; j < 8; j++) {
-        const uint32_t w = wnodes[8 * (size_t)i + j].w;
-        if (w == 0xFFFFFFFFu || (w & 0x80000000u)) continue;
-        inner++;
-        if (w < nwide && w > i) below = max(below, need[w]);
-    }
-    const uint32_t v = min(0xFFFFu, inner ? inner - 1u + below : 0u);
-    if (v != need[i]) { need[i] = v; *changed = 1u; }
-}
-// runs `pass` until an entry no longer changes; returns need[0]
-template <class Pass>
-static int stack_need_fixed_point(chroma_ctx *ctx, size_t n, Pass pass, uint32_t *result)
-{
-    uint32_t *d_need = nullptr, *d_changed = nullptr;
-    HIP_TRY(ctx_malloc(ctx, (void **)&d_need, std::max<size_t>(n, 1) * 4));
-    if (hipMalloc(&d_changed, 4) != hipSuccess) { hipFree(d_need); return set_error(CHROMA_ERR_INTERNAL, "out of device memory"); }
-    hipError_t e = hipMemsetAsync(d_need, 0, std::max<size_t>(n, 1) * 4, ctx->stream);
-    uint32_t changed = 1, h_need = 0;
-    for (int it = 0; e == hipSuccess && changed && it < 8192; it++) {
-        e = hipMemsetAsync(d_changed, 0, 4, ctx->stream);
-        for (int k = 0; k < 4; k++) pass(d_need, d_changed);                    // (four passes per question)
-        if (e == hipSuccess) e = hipMemcpyAsync(&changed, d_changed, 4, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    }
-    if (e == hipSuccess) e = hipMemcpy(&h_need, d_need, 4, hipMemcpyDeviceToHost);
-    hipFree(d_need); hipFree(d_changed);
-    if (e != hipSuccess) return set_error((int)e, "stack need: %s", hipGetErrorString(e));
-    if (changed) return set_error(CHROMA_ERR_INVALID, "stack need: the tree does not settle (a child range that points back?)");
-    *result = h_need;
-    return CHROMA_OK;
-}
-
-// ---- distance_to_mesh through the fast ray cast --------------------------------------------------------
-// mesh.h:124-151 asks for the nearest triangle along free rays.  Same pipeline as a propagation step:
-// ray records, k_raycast_quad, the check that the reference tests the winner (record_hit_is_regular),
-// the literal reference walk for the rays that fail it or that the fast walk cannot take.
-__global__ void k_rays_from_arrays(GeoView g, int n, const float *origin_in, const float *direction_in, const int32_t *last_hit_in,
-                                   float4 *rays, int32_t *hit_triangle, float *hit_distance, uint32_t *retry_list, StepState *st)
-{
-    int slot = blockIdx.x * blockDim.x + threadIdx.x;
-    if (slot >= n) return;
-    int last_hit = last_hit_in ? last_hit_in[slot] : -1;          // a triangle id (mesh.h:82) -> its record
-    last_hit = (last_hit >= 0 && (uint32_t)last_hit < g.ntriangles) ? (int)g.tri_to_dev[last_hit] : -1;
-    v3 origin = load3(origin_in, slot), direction = load3(direction_in, slot);
-    direction = direction / norm(direction);
-    v3 noid = (-origin) / direction;
-    v3 inv_dir = 1.0f / direction;
-    bool moderate = cm_fabsf(inv_dir.x) < 1e30f && cm_fabsf(inv_dir.y) < 1e30f && cm_fabsf(inv_dir.z) < 1e30f &&
-                    cm_fabsf(noid.x) < 1e30f && cm_fabsf(noid.y) < 1e30f && cm_fabsf(noid.z) < 1e30f;
-    int status = moderate ? 0 : HIT_RETRY;                 // (a NaN ray is not moderate: the literal walk answers)
-    v3 a = mk3(0.f, 0.f, 0.f), b = mk3(0.f, 0.f, 0.f);
-    if (moderate) {
-        a = ray_fast(g, noid, inv_dir, 1.0f).a;
-        b = mk3(cm_fmaf(g.world_origin[0], inv_dir.x, noid.x), cm_fmaf(g.world_origin[1], inv_dir.y, noid.y),
-                cm_fmaf(g.world_origin[2], inv_dir.z, noid.z));
-    }
-    float4 *r = rays + 4 * (size_t)slot;
-    r[0] = make_float4(origin.x, origin.y, origin.z, __int_as_float(last_hit));
-    r[1] = make_float4(direction.x, direction.y, direction.z, __int_as_float(status));
-    r[2] = make_float4(a.x, a.y, a.z, ray_growth(g, origin));
-    r[3] = make_float4(b.x, b.y, b.z, 0.0f);
-    if (status != 0) {
-        hit_triangle[slot] = status;
-        hit_distance[slot] = 0.0f;
-        retry_list[atomicAdd(&st->retry, 1u)] = (uint32_t)slot;
-    }
-}
-__global__ void k_step_set(StepState *st, uint32_t n) { st->n = n; st->renorm = 0u; st->in_tail = 0u; st->launches = 0u; st->work = 0u; st->retry = 0u; }
-
-// results of the fast cast: checked, translated to triangle ids, or handed to the literal walk
-__global__ void k_distance_finish(GeoView g, int n, const float4 *rays, const int32_t *hit_triangle, const float *hit_distance,
-                                  float *distance_out, int32_t *triangle_out, uint32_t *retry_list, StepState *st)
-{
-    int slot = blockIdx.x * blockDim.x + threadIdx.x;
-    if (slot >= n) return;
-    int rec = hit_triangle[slot];
-    if (rec == HIT_RETRY) return;                          // already listed
-    if (rec >= 0) {
-        const float4 *r = rays + 4 * (size_t)slot;
-        const float4 r0 = r[0], r1 = r[1];
-        const float4 *t = g.tri + TRI_STRIDE * (size_t)rec;
-        const float4 a = t[0], b = t[1], c = t[2];
-        const float dist = hit_distance[slot];
-        if (!record_hit_is_regular(g, a, b, c, mk3(r0.x, r0.y, r0.z), mk3(r1.x, r1.y, r1.z), dist)) {
-            retry_list[atomicAdd(&st->retry, 1u)] = (uint32_t)slot;
-            return;
-        }
-        distance_out[slot] = dist;
-        if (triangle_out) triangle_out[slot] = (int32_t)__float_as_uint(b.w);
-    } else if (triangle_out) {
-        triangle_out[slot] = -1;                           // a miss leaves the distance untouched (mesh.h:145-148)
-    }
-}
-template <bool COUNT>
-__global__ __launch_bounds__(PROP_BLOCK) void
-k_distance_retry(GeoView g, const float4 *rays, const StepState *st, const uint32_t *retry_list, float *distance_out,
-                 int32_t *triangle_out, DeviceCounters *counters)
-{
-    __shared__ uint32_t s_lds[TRAV_LDS_WORDS(STACK_LDS, PROP_BLOCK)];
-    const int nretry = (int)st->retry;
-    LaneCounters cnt = {0, 0, 0, 0};
-    for (int k = blockIdx.x * PROP_BLOCK + threadIdx.x; k < nretry; k += gridDim.x * PROP_BLOCK) {
-        const int slot = (int)retry_list[k];
-        const float4 *r = rays + 4 * (size_t)slot;
-        const float4 r0 = r[0], r1 = r[1];
-        float dist;
-        int rec = intersect_mesh_dev<STACK_LDS, PROP_BLOCK, COUNT>(g, mk3(r0.x, r0.y, r0.z), mk3(r1.x, r1.y, r1.z), dist,
-                                                                   __float_as_int(r0.w), s_lds + threadIdx.x, cnt, true);
-        if (rec >= 0) distance_out[slot] = dist;
-        if (triangle_out) triangle_out[slot] = rec >= 0 ? (int32_t)g.dev_to_tri[rec] : -1;
-    }
-    unsigned long long ov = wave_sum_u64(cnt.overflows);
-    if (COUNT) {
-        unsigned long long nd = wave_sum_u64(cnt.nodes), tr = wave_sum_u64(cnt.tris);
-        if (lane_id() == 0) { atomicAdd(&counters->nodes_visited, nd); atomicAdd(&counters->triangles_tested, tr); }
-    }
-    if (lane_id() == 0 && ov) atomicAdd(&counters->stack_overflows, ov);
 }
 
 // ---------------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------------
 extern "C" {
-
-const char *chroma_last_error(void) { return g_last_error.c_str(); }
-const char *chroma_version(void) { return "chroma_hip 0.1 (gfx950)"; }
-
-int chroma_device_count(int *count)
-{
-    if (!count) return set_error(CHROMA_ERR_INVALID, "null count");
-    int n = 0;
-    hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess) { *count = 0; return set_error(CHROMA_ERR_NO_DEVICE, "hipGetDeviceCount: %s", hipGetErrorString(e)); }
-    *count = n;
-    return CHROMA_OK;
-}
-
-int chroma_init(int device, chroma_ctx **out)
-{
-    if (!out) return set_error(CHROMA_ERR_INVALID, "null ctx");
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n == 0)
-        return set_error(CHROMA_ERR_NO_DEVICE, "no HIP device available (libchroma_hip needs an MI355X/gfx950 GPU)");
-    if (device < 0) device = 0;
-    if (device >= n) return set_error(CHROMA_ERR_INVALID, "device %d out of range (%d devices)", device, n);
-    HIP_TRY(hipSetDevice(device));
-    chroma_ctx *ctx = new chroma_ctx;
-    ctx->device = device;
-    HIP_TRY(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
-    HIP_TRY(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
-    HIP_TRY(hipStreamCreateWithFlags(&ctx->aux_stream, hipStreamNonBlocking));
-    HIP_TRY(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
-    {
-        size_t free_b = 0, total_b = 0;
-        HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-        ctx->pool_limit = (size_t)(0.4 * (double)total_b);
-        if (const char *e = getenv("CHROMA_POOL_MB")) ctx->pool_limit = (size_t)std::max(0ll, atoll(e)) << 20;
-    }
-    HIP_TRY(hipMalloc((void **)&ctx->d_counters, sizeof(DeviceCounters)));
-    HIP_TRY(hipMemset(ctx->d_counters, 0, sizeof(DeviceCounters)));
-    HIP_TRY(hipMalloc((void **)&ctx->d_words, 16 * sizeof(uint32_t)));
-    HIP_TRY(hipMemset(ctx->d_words, 0, 16 * sizeof(uint32_t)));
-    HIP_TRY(hipHostMalloc((void **)&ctx->h_words, 16 * sizeof(uint32_t), hipHostMallocDefault));
-    HIP_TRY(hipMalloc((void **)&ctx->d_step, sizeof(StepState)));
-    HIP_TRY(hipMemset(ctx->d_step, 0, sizeof(StepState)));
-    HIP_TRY(hipHostMalloc((void **)&ctx->h_step, sizeof(StepState), hipHostMallocDefault));
-    {
-        hipDeviceProp_t prop;
-        HIP_TRY(hipGetDeviceProperties(&prop, device));
-        int per_cu = 20;                     // LDS-limited residency of k_raycast_persistent (8 KB per wave)
-        if (const char *e = getenv("CHROMA_RAY_WAVES_PER_CU")) per_cu = std::max(1, atoi(e));
-        ctx->persistent_waves = prop.multiProcessorCount * per_cu;
-        ctx->physics_blocks = prop.multiProcessorCount * 8;          // (for blocks of PHYS_BLOCK threads)
-        int wide_per_cu = 14;                // LDS-limited residency of k_raycast_wide
-        if (const char *e = getenv("CHROMA_WIDE_WAVES_PER_CU")) wide_per_cu = std::max(1, atoi(e));
-        ctx->wide_waves = prop.multiProcessorCount * wide_per_cu;
-        int coop_per_cu = 28;                // 71 VGPRs (amdgpu_waves_per_eu 7): 7 waves per SIMD
-        if (const char *e = getenv("CHROMA_COOP_WAVES_PER_CU")) coop_per_cu = std::max(1, atoi(e));
-        ctx->coop_waves = prop.multiProcessorCount * coop_per_cu;
-        int quad_per_cu = 4 * QUAD_WAVES_PER_EU;
-        if (const char *e = getenv("CHROMA_QUAD_WAVES_PER_CU")) quad_per_cu = std::max(1, atoi(e));
-        ctx->quad_waves = prop.multiProcessorCount * quad_per_cu;
-        int pair_per_cu = 4 * PAIR_WAVES_PER_EU;
-        if (const char *e = getenv("CHROMA_PAIR_WAVES_PER_CU")) pair_per_cu = std::max(1, atoi(e));
-        ctx->pair_waves = prop.multiProcessorCount * pair_per_cu;
-        if (const char *e = getenv("CHROMA_WALK"))
-            ctx->walk = !strcmp(e, "reference") ? CHROMA_WALK_REFERENCE : !strcmp(e, "wide") ? CHROMA_WALK_WIDE
-                      : !strcmp(e, "coop") ? CHROMA_WALK_COOP : !strcmp(e, "pair") ? CHROMA_WALK_PAIR
-                      : (!strcmp(e, "literal") || !strcmp(e, "exact")) ? CHROMA_WALK_LITERAL
-                      : !strcmp(e, "literal_lane") ? CHROMA_WALK_LITERAL_LANE : CHROMA_WALK_QUAD;
-#if CHROMA_EXPERIMENTAL
-        if (const char *e = getenv("CHROMA_PACKET")) ctx->packet_mode = !strcmp(e, "on") ? 1 : !strcmp(e, "auto") ? 2 : 0;
-        if (const char *e = getenv("CHROMA_AUTOSORT")) ctx->autosort_mode = !strcmp(e, "on") || !strcmp(e, "1") ? 1 : !strcmp(e, "off") || !strcmp(e, "0") ? 0 : 2;
-#endif
-        if (const char *e = getenv("CHROMA_RAY_CHUNK")) ctx->ray_chunk = std::max(64, atoi(e));
-        if (const char *e = getenv("CHROMA_COOP_CHUNK")) ctx->coop_chunk = std::max(8, atoi(e));
-        if (const char *e = getenv("CHROMA_CLAIM_STATIC")) { int big = 0, small = 0; if (sscanf(e, "%d:%d", &big, &small) < 2) small = big; ctx->claim_static = std::min(8, std::max(0, big)) | std::min(8, std::max(0, small)) << 4; }
-        if (const char *e = getenv("CHROMA_TAIL"))        // coop (default) | split | fused (the lane-per-photon k_propagate)
-            ctx->tail_mode = !strcmp(e, "fused") ? CHROMA_TAIL_FUSED : !strcmp(e, "split") ? CHROMA_TAIL_SPLIT : CHROMA_TAIL_COOP;
-    }
-    HIP_TRY(hipEventCreate(&ctx->ev_start));
-    HIP_TRY(hipEventCreate(&ctx->ev_stop));
-    HIP_TRY(hipEventCreate(&ctx->ev_mid));
-    *out = ctx;
-    return CHROMA_OK;
-}
-
-static void pool_release_all(chroma_ctx *ctx);
-int chroma_shutdown(chroma_ctx *ctx)
-{
-    if (!ctx) return CHROMA_OK;
-    hipSetDevice(ctx->device);
-    hipStreamSynchronize(ctx->stream);
-    hipStreamSynchronize(ctx->copy_stream);
-    chroma_comm_destroy(ctx);
-    { std::lock_guard<std::mutex> lock(ctx->pool_mu); pool_release_all(ctx); for (hipEvent_t e : ctx->pool_events) hipEventDestroy(e); ctx->pool_events.clear(); }
-    for (int i = 0; i < chroma_ctx::STAGE_N; i++) { if (ctx->stage[i]) hipHostFree(ctx->stage[i]); if (ctx->stage_ev[i]) hipEventDestroy(ctx->stage_ev[i]); }
-    for (int i = 0; i < chroma_ctx::STAGE_N; i++) { if (ctx->stage_down[i]) hipHostFree(ctx->stage_down[i]); if (ctx->stage_down_ev[i]) hipEventDestroy(ctx->stage_down_ev[i]); }
-    hipStreamDestroy(ctx->copy_stream);
-    if (ctx->aux_stream) { hipStreamSynchronize(ctx->aux_stream); hipStreamDestroy(ctx->aux_stream); }
-    if (ctx->ev_fork) hipEventDestroy(ctx->ev_fork);
-    if (ctx->ev_join) hipEventDestroy(ctx->ev_join);
-    if (ctx->queue_a) hipFree(ctx->queue_a);
-    if (ctx->queue_b) hipFree(ctx->queue_b);
-    if (ctx->wide_spill) hipFree(ctx->wide_spill);
-    if (ctx->coop_spill) hipFree(ctx->coop_spill);
-    if (ctx->d_step) hipFree(ctx->d_step);
-    if (ctx->h_step) hipHostFree(ctx->h_step);
-    for (hipEvent_t e : ctx->step_events) hipEventDestroy(e);
-    if (ctx->hit_triangle) hipFree(ctx->hit_triangle);
-    if (ctx->hit_distance) hipFree(ctx->hit_distance);
-    if (ctx->retry_list) hipFree(ctx->retry_list);
-    if (ctx->rays) hipFree(ctx->rays);
-    if (ctx->rays_b) hipFree(ctx->rays_b);
-    if (ctx->work_a) hipFree(ctx->work_a);
-    if (ctx->work_b) hipFree(ctx->work_b);
-    hipFree(ctx->d_counters);
-    hipFree(ctx->d_words);
-    hipHostFree(ctx->h_words);
-    hipEventDestroy(ctx->ev_start);
-    hipEventDestroy(ctx->ev_stop);
-    hipEventDestroy(ctx->ev_mid);
-    hipStreamDestroy(ctx->stream);
-    delete ctx;
-    return CHROMA_OK;
-}
-
-int chroma_synchronize(chroma_ctx *ctx)
-{
-    if (!ctx) return set_error(CHROMA_ERR_INVALID, "null ctx");
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return CHROMA_OK;
-}
-
-int chroma_mem_info(chroma_ctx *ctx, size_t *free_bytes, size_t *total_bytes)
-{
-    if (!ctx) return set_error(CHROMA_ERR_INVALID, "null ctx");
-    HIP_TRY(hipSetDevice(ctx->device));
-    size_t f = 0, t = 0;
-    HIP_TRY(hipMemGetInfo(&f, &t));
-    if (free_bytes) *free_bytes = f;
-    if (total_bytes) *total_bytes = t;
-    return CHROMA_OK;
-}
-
-int chroma_device_name(chroma_ctx *ctx, char *buf, size_t buflen)
-{
-    if (!ctx || !buf || !buflen) return set_error(CHROMA_ERR_INVALID, "bad argument");
-    hipDeviceProp_t prop;
-    HIP_TRY(hipGetDeviceProperties(&prop, ctx->device));
-    snprintf(buf, buflen, "%s (%s, %d CUs)", prop.name, prop.gcnArchName, prop.multiProcessorCount);
-    return CHROMA_OK;
-}
-
-// ---- device memory: a pool -----------------------------------------------------------------------------------
-// Simulation builds a GPUPhotons per event batch: ten arrays allocated, used for one propagate, dropped.  hipMalloc and
-// hipFree each cost ~0.1-1 ms for blocks of hundreds of MB and hipFree synchronises the device, so blocks are kept
-// instead: chroma_free parks a block (with an event recorded on the context's stream: work already queued on it may
-// still use the block), chroma_malloc hands a parked block of exactly the requested size back once that event has
-// completed -- no waiting, no new allocation.  Capped at CHROMA_POOL_MB (default: 40 % of the device's memory);
-// chroma_pool_trim releases everything parked (also done by itself when hipMalloc runs out of memory).
-static size_t pool_round(size_t nbytes) { return (std::max(nbytes, (size_t)4) + 255) & ~(size_t)255; }
-
-static void pool_release_all(chroma_ctx *ctx)       // (pool_mu held)
-{
-    for (auto &kv : ctx->pool) { hipEventSynchronize(kv.second.ev); hipFree(kv.second.ptr); ctx->pool_events.push_back(kv.second.ev); }
-    ctx->pool.clear();
-    ctx->pool_bytes = 0;
-}
-
-static hipError_t ctx_malloc(chroma_ctx *ctx, void **ptr, size_t bytes)
-{
-    hipError_t e = hipMalloc(ptr, bytes);
-    if (e == hipErrorOutOfMemory) {
-        (void)hipGetLastError();
-        std::lock_guard<std::mutex> lock(ctx->pool_mu);
-        if (!ctx->pool.empty()) { pool_release_all(ctx); e = hipMalloc(ptr, bytes); }
-    }
-    return e;
-}
-
-int chroma_malloc(chroma_ctx *ctx, size_t nbytes, void **d_ptr)
-{
-    if (!ctx || !d_ptr) return set_error(CHROMA_ERR_INVALID, "bad argument");
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t size = pool_round(nbytes);
-    std::lock_guard<std::mutex> lock(ctx->pool_mu);
-    auto range = ctx->pool.equal_range(size);
-    for (auto it = range.first; it != range.second; ++it) {
-        // (still in use by queued work: hipErrorNotReady is not an error here, and must not stay behind as the thread's
-        //  "last error" for the next hipGetLastError() after a kernel launch to find)
-        if (hipEventQuery(it->second.ev) != hipSuccess) { (void)hipGetLastError(); continue; }
-        *d_ptr = it->second.ptr;
-        ctx->pool_events.push_back(it->second.ev);
-        ctx->pool.erase(it);
-        ctx->pool_bytes -= size;
-        ctx->live[*d_ptr] = size;
-        ctx->pool_hits++;
-        return CHROMA_OK;
-    }
-    hipError_t e = hipMalloc(d_ptr, size);
-    if (e == hipErrorOutOfMemory && !ctx->pool.empty()) {
-        (void)hipGetLastError();
-        pool_release_all(ctx);
-        e = hipMalloc(d_ptr, size);
-    }
-    if (e != hipSuccess) return set_error((int)e, "hipMalloc(%zu bytes) failed: %s", size, hipGetErrorString(e));
-    ctx->live[*d_ptr] = size;
-    ctx->pool_misses++;
-    return CHROMA_OK;
-}
-
-int chroma_free(chroma_ctx *ctx, void *d_ptr)
-{
-    if (!ctx) return set_error(CHROMA_ERR_INVALID, "null ctx");
-    if (!d_ptr) return CHROMA_OK;
-    // (a Python __del__ or the prefetch worker may call this from a thread whose current device is another GPU's)
-    HIP_TRY(hipSetDevice(ctx->device));
-    std::lock_guard<std::mutex> lock(ctx->pool_mu);
-    auto it = ctx->live.find(d_ptr);
-    if (it == ctx->live.end()) {                   // not one of ours (should not happen): the old behaviour
-        HIP_TRY(hipStreamSynchronize(ctx->stream)); HIP_TRY(hipFree(d_ptr));
-        return CHROMA_OK;
-    }
-    const size_t size = it->second;
-    ctx->live.erase(it);
-    bool park = ctx->pool_bytes + size <= ctx->pool_limit;
-    hipEvent_t ev = nullptr;
-    if (park) {
-        // a block is parked behind an event on the context's stream; should the event not come about, the block is
-        // simply freed (after the stream has drained) -- it must never be left neither parked nor freed
-        if (!ctx->pool_events.empty()) { ev = ctx->pool_events.back(); ctx->pool_events.pop_back(); }
-        else if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) { ev = nullptr; park = false; }
-        if (park && hipEventRecord(ev, ctx->stream) != hipSuccess) { ctx->pool_events.push_back(ev); park = false; }
-    }
-    if (!park) {
-        (void)hipGetLastError();
-        HIP_TRY(hipStreamSynchronize(ctx->stream)); HIP_TRY(hipFree(d_ptr));
-        return CHROMA_OK;
-    }
-    ctx->pool.emplace(size, chroma_ctx::PoolBlock{d_ptr, ev});
-    ctx->pool_bytes += size;
-    return CHROMA_OK;
-}
-
-int chroma_pool_trim(chroma_ctx *ctx)
-{
-    if (!ctx) return set_error(CHROMA_ERR_INVALID, "null ctx");
-    std::lock_guard<std::mutex> lock(ctx->pool_mu);
-    pool_release_all(ctx);
-    return CHROMA_OK;
-}
-
-int chroma_pool_stats(chroma_ctx *ctx, uint64_t *parked_bytes, uint64_t *reused, uint64_t *allocated)
-{
-    if (!ctx) return set_error(CHROMA_ERR_INVALID, "null ctx");
-    std::lock_guard<std::mutex> lock(ctx->pool_mu);
-    if (parked_bytes) *parked_bytes = ctx->pool_bytes;
-    if (reused) *reused = ctx->pool_hits;
-    if (allocated) *allocated = ctx->pool_misses;
-    return CHROMA_OK;
-}
-
-// ---- host -> device ------------------------------------------------------------------------------------------
-// A copy from pageable host memory runs at ~11 GB/s through the runtime's own bounce buffer (one thread).  Large copies
-// are staged here instead: the host threads copy 64 MB pieces into a ring of PINNED buffers in parallel and each piece
-// goes to the device by DMA while the next is being staged.  (r03: 11.2 -> 16 GB/s with 32 MB pieces and 64 threads on
-// a 16-core quota; the thread count now follows the quota.)
-static int staged_htod(chroma_ctx *ctx, hipStream_t stream, void *d_dst, const void *h_src, size_t nbytes)
-{
-    std::lock_guard<std::mutex> lock(ctx->stage_mu);
-    for (int i = 0; i < chroma_ctx::STAGE_N; i++)
-        if (!ctx->stage[i]) {
-            HIP_TRY(hipHostMalloc(&ctx->stage[i], chroma_ctx::STAGE_BYTES, hipHostMallocDefault));
-            HIP_TRY(hipEventCreateWithFlags(&ctx->stage_ev[i], hipEventDisableTiming));
-        }
-    size_t off = 0;
-    int k = 0;
-    while (off < nbytes) {
-        const size_t len = std::min(chroma_ctx::STAGE_BYTES, nbytes - off);
-        HIP_TRY(hipEventSynchronize(ctx->stage_ev[k]));            // (the DMA that last read this buffer is done)
-        char *dst = (char *)ctx->stage[k];
-        const char *src = (const char *)h_src + off;
-        chroma_host::parallel_for(len, [&](size_t a, size_t b) { memcpy(dst + a, src + a, b - a); }, 1u << 20);
-        HIP_TRY(hipMemcpyAsync((char *)d_dst + off, dst, len, hipMemcpyHostToDevice, stream));
-        HIP_TRY(hipEventRecord(ctx->stage_ev[k], stream));
-        off += len;
-        k = (k + 1) % chroma_ctx::STAGE_N;
-    }
-    HIP_TRY(hipStreamSynchronize(stream));
-    return CHROMA_OK;
-}
-
-int chroma_memcpy_htod(chroma_ctx *ctx, void *d_dst, const void *h_src, size_t nbytes)
-{
-    if (!ctx) return set_error(CHROMA_ERR_INVALID, "null ctx");
-    if (nbytes == 0) return CHROMA_OK;
-    if (nbytes >= (8u << 20)) return staged_htod(ctx, ctx->stream, d_dst, h_src, nbytes);
-    HIP_TRY(hipMemcpyAsync(d_dst, h_src, nbytes, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return CHROMA_OK;
-}
-
-// The same copy on the context's SECOND stream: not ordered with the work queued on the main stream, so that the
-// photons of the next event batch can go up while the current batch propagates (Simulation, one thread ahead).  The
-// destination must not be in use by queued work: a block fresh from chroma_malloc never is.  Returns when the data is
-// on the device.
-int chroma_upload(chroma_ctx *ctx, void *d_dst, const void *h_src, size_t nbytes)
-{
-    if (!ctx) return set_error(CHROMA_ERR_INVALID, "null ctx");
-    if (nbytes == 0) return CHROMA_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (nbytes >= (8u << 20)) return staged_htod(ctx, ctx->copy_stream, d_dst, h_src, nbytes);
-    HIP_TRY(hipMemcpyAsync(d_dst, h_src, nbytes, hipMemcpyHostToDevice, ctx->copy_stream));
-    HIP_TRY(hipStreamSynchronize(ctx->copy_stream));
-    return CHROMA_OK;
-}
-
-// ---- device -> host: the same ring the other way round -- a piece comes down by DMA into a pinned buffer while the host
-// threads copy the previous one out to (pageable, possibly never touched) destination memory in parallel
-static int staged_dtoh(chroma_ctx *ctx, hipStream_t stream, void *h_dst, const void *d_src, size_t nbytes)
-{
-    std::lock_guard<std::mutex> lock(ctx->stage_down_mu);
-    for (int i = 0; i < chroma_ctx::STAGE_N; i++)
-        if (!ctx->stage_down[i]) {
-            HIP_TRY(hipHostMalloc(&ctx->stage_down[i], chroma_ctx::STAGE_BYTES, hipHostMallocDefault));
-            HIP_TRY(hipEventCreateWithFlags(&ctx->stage_down_ev[i], hipEventDisableTiming));
-        }
-    const size_t npieces = (nbytes + chroma_ctx::STAGE_BYTES - 1) / chroma_ctx::STAGE_BYTES;
-    auto issue = [&](size_t i) -> hipError_t {
-        const size_t off = i * chroma_ctx::STAGE_BYTES, len = std::min(chroma_ctx::STAGE_BYTES, nbytes - off);
-        const int k = (int)(i % chroma_ctx::STAGE_N);
-        hipError_t e = hipMemcpyAsync(ctx->stage_down[k], (const char *)d_src + off, len, hipMemcpyDeviceToHost, stream);
-        return e != hipSuccess ? e : hipEventRecord(ctx->stage_down_ev[k], stream);
-    };
-    HIP_TRY(issue(0));
-    for (size_t i = 0; i < npieces; i++) {
-        if (i + 1 < npieces) HIP_TRY(issue(i + 1));               // (its buffer was copied out two pieces ago)
-        const size_t off = i * chroma_ctx::STAGE_BYTES, len = std::min(chroma_ctx::STAGE_BYTES, nbytes - off);
-        const int k = (int)(i % chroma_ctx::STAGE_N);
-        HIP_TRY(hipEventSynchronize(ctx->stage_down_ev[k]));
-        const char *src = (const char *)ctx->stage_down[k];
-        char *dst = (char *)h_dst + off;
-        chroma_host::parallel_for(len, [&](size_t a, size_t b) { memcpy(dst + a, src + a, b - a); }, 1u << 20);
-    }
-    return CHROMA_OK;
-}
-// for the other translation units of the library (ctx_access.h): a large download on the context's stream
-extern "C" int chroma_internal_dtoh(chroma_ctx *ctx, void *h_dst, const void *d_src, size_t nbytes)
-{
-    if (nbytes == 0) return CHROMA_OK;
-    if (nbytes >= (8u << 20)) return staged_dtoh(ctx, ctx->stream, h_dst, d_src, nbytes);
-    HIP_TRY(hipMemcpyAsync(h_dst, d_src, nbytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return CHROMA_OK;
-}
-extern "C" int chroma_internal_htod(chroma_ctx *ctx, void *d_dst, const void *h_src, size_t nbytes)
-{
-    if (nbytes == 0) return CHROMA_OK;
-    if (nbytes >= (8u << 20)) return staged_htod(ctx, ctx->stream, d_dst, h_src, nbytes);
-    HIP_TRY(hipMemcpyAsync(d_dst, h_src, nbytes, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return CHROMA_OK;
-}
-
-int chroma_memcpy_dtoh(chroma_ctx *ctx, void *h_dst, const void *d_src, size_t nbytes)
-{
-    if (!ctx) return set_error(CHROMA_ERR_INVALID, "null ctx");
-    return chroma_internal_dtoh(ctx, h_dst, d_src, nbytes);
-}
-
-int chroma_memcpy_dtod(chroma_ctx *ctx, void *d_dst, const void *d_src, size_t nbytes)
-{
-    if (!ctx) return set_error(CHROMA_ERR_INVALID, "null ctx");
-    if (nbytes == 0) return CHROMA_OK;
-    HIP_TRY(hipMemcpyAsync(d_dst, d_src, nbytes, hipMemcpyDeviceToDevice, ctx->stream));
-    return CHROMA_OK;
-}
-
-int chroma_memset32(chroma_ctx *ctx, void *d_dst, uint32_t value, size_t count)
-{
-    if (!ctx) return set_error(CHROMA_ERR_INVALID, "null ctx");
-    if (count == 0) return CHROMA_OK;
-    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)d_dst, (int)value, count, ctx->stream));
-    return CHROMA_OK;
-}
-
-// ---- geometry -------------------------------------------------------------------------------------
-int chroma_geometry_create(chroma_ctx *ctx, const chroma_geometry_desc *d, chroma_geometry **out)
-{
-    if (!ctx || !d || !out) return set_error(CHROMA_ERR_INVALID, "bad argument");
-    if (!d->vertices || !d->triangles || !d->material_codes || !d->nodes || d->nnodes == 0 || d->ntriangles == 0)
-        return set_error(CHROMA_ERR_INVALID, "geometry: missing mesh or BVH arrays");
-    if (d->wavelength_n < 2 || d->nmaterials == 0 || d->nmaterials > 127 || d->nsurfaces > 127)
-        return set_error(CHROMA_ERR_INVALID, "geometry: bad optics table sizes (8-bit signed material/surface indices)");
-    if (!d->mat_refractive_index || !d->mat_absorption_length || !d->mat_scattering_length || !d->mat_num_comp || !d->mat_comp_offset)
-        return set_error(CHROMA_ERR_INVALID, "geometry: missing material tables");
-    // host-side shape checks the kernels rely on (all cores; the first offender in index order is reported)
-    {
-        using chroma_host::parallel_for;
-        std::atomic<size_t> bad_tri(SIZE_MAX), bad_node(SIZE_MAX), bad_code(SIZE_MAX);
-        auto note = [](std::atomic<size_t> &slot, size_t i) { size_t cur = slot.load(); while (i < cur && !slot.compare_exchange_weak(cur, i)) {} };
-        parallel_for((size_t)d->ntriangles * 3, [&](size_t lo, size_t hi) {
-            for (size_t i = lo; i < hi; i++) if (d->triangles[i] >= d->nvertices) { note(bad_tri, i); break; }
-        });
-        if (bad_tri != SIZE_MAX) { size_t i = bad_tri; return set_error(CHROMA_ERR_INVALID, "triangle %zu references vertex %u >= %u", i / 3, d->triangles[i], d->nvertices); }
-        parallel_for((size_t)d->nnodes, [&](size_t lo, size_t hi) {
-            for (size_t i = lo; i < hi; i++) {
-                uint32_t w = d->nodes[4 * i + 3];
-                uint32_t nchild = w >> CHROMA_CHILD_BITS, child = w & ~CHROMA_NCHILD_MASK;
-                bool bad = nchild == 0 ? child >= d->ntriangles : ((size_t)child + nchild > d->nnodes || child <= i);
-                if (bad) { note(bad_node, i); break; }
-            }
-        });
-        if (bad_node != SIZE_MAX) {
-            size_t i = bad_node;
-            uint32_t w = d->nodes[4 * i + 3], nchild = w >> CHROMA_CHILD_BITS, child = w & ~CHROMA_NCHILD_MASK;
-            if (nchild == 0) return set_error(CHROMA_ERR_INVALID, "leaf node %zu references triangle %u >= %u", i, child, d->ntriangles);
-            return set_error(CHROMA_ERR_INVALID, "node %zu has a bad child range [%u, %u)", i, child, child + nchild);
-        }
-        parallel_for((size_t)d->ntriangles, [&](size_t lo, size_t hi) {
-            for (size_t i = lo; i < hi; i++) {
-                uint32_t code = d->material_codes[i];
-                int inner = (int8_t)(code >> 24), outer = (int8_t)(code >> 16), surf = (int8_t)(code >> 8);
-                bool bad = inner < 0 || outer < 0 || inner >= (int)d->nmaterials || outer >= (int)d->nmaterials || surf < -1 || surf >= (int)d->nsurfaces;
-                if (!bad && d->nsolids && d->solid_id_map && d->solid_id_map[i] >= d->nsolids) bad = true;
-                if (bad) { note(bad_code, i); break; }
-            }
-        });
-        if (bad_code != SIZE_MAX) {
-            size_t i = bad_code;
-            uint32_t code = d->material_codes[i];
-            int inner = (int8_t)(code >> 24), outer = (int8_t)(code >> 16), surf = (int8_t)(code >> 8);
-            if (inner < 0 || outer < 0 || inner >= (int)d->nmaterials || outer >= (int)d->nmaterials || surf < -1 || surf >= (int)d->nsurfaces)
-                return set_error(CHROMA_ERR_INVALID, "triangle %zu has material code 0x%08x outside the tables", i, code);
-            return set_error(CHROMA_ERR_INVALID, "triangle %zu has solid id %u >= %u", i, d->solid_id_map[i], d->nsolids);
-        }
-    }
-    for (uint32_t m = 0; m < d->nmaterials; m++)
-        if (d->mat_num_comp[m] && d->mat_comp_offset[m] + d->mat_num_comp[m] > d->ncomp_total)
-            return set_error(CHROMA_ERR_INVALID, "material %u: component rows out of range", m);
-    for (uint32_t s = 0; s < d->nsurfaces; s++) {
-        if (d->surf_model[s] == CHROMA_SURFACE_DICHROIC) {
-            int di = d->surf_dichroic_index ? d->surf_dichroic_index[s] : -1;
-            if (di < 0 || di >= (int)d->ndichroic || d->dichroic_nangles[di] < 2 ||
-                d->dichroic_offset[di] + d->dichroic_nangles[di] > d->ndichroic_angles_total)
-                return set_error(CHROMA_ERR_INVALID, "surface %u: dichroic tables missing or out of range", s);
-        }
-    }
-
-    const bool timing = getenv("CHROMA_TIMING") != nullptr;
-    auto t_phase = std::chrono::steady_clock::now();
-    auto phase = [&](const char *what) {
-        if (!timing) return;
-        auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "[chroma_geometry_create] %-28s %.2f s\n", what, std::chrono::duration<double>(now - t_phase).count());
-        t_phase = now;
-    };
-    phase("validation");
-    HIP_TRY(hipSetDevice(ctx->device));
-    chroma_geometry *g = new chroma_geometry;
-    g->ctx = ctx;
-    g->nvertices = d->nvertices; g->ntriangles = d->ntriangles; g->nnodes = d->nnodes;
-    GeoView &v = g->view;
-    memset(&v, 0, sizeof v);
-    int rc;
-#define UP(field, src, count) if ((rc = upload(g, src, (size_t)(count), &v.field)) != CHROMA_OK) { chroma_geometry_destroy(g); return rc; }
-    // nodes as passed in (what GPUGeometry.nodes shows)
-    { const uint4 *p; if ((rc = upload(g, (const uint4 *)d->nodes, d->nnodes, &p)) != CHROMA_OK) { chroma_geometry_destroy(g); return rc; } g->d_nodes_api = (void *)p; }
-    // derived 8-wide tree, device triangle order and reference test ranks (csrc/wide_build.cpp)
-    chroma_host::WideTree wt;
-    const bool wide_given = d->wide_nodes != nullptr;
-    if (wide_given) {
-        if (!d->wide_tri_to_record || !d->wide_record_to_tri || !d->wide_rank || d->nwide == 0 || d->nrecords == 0) {
-            chroma_geometry_destroy(g);
-            return set_error(CHROMA_ERR_INVALID, "geometry: a supplied wide tree needs its nodes, both record maps and the ranks");
-        }
-    } else {
-        // the default topology is built where the reference builds its tree: on the device (csrc/wide_device.hip);
-        // the others, and CHROMA_WIDE_BUILD=host, on the host cores (csrc/wide_build.cpp) -- "levels" gives the same tree either way
-        std::string werr;
-        const int topology = chroma_host::wide_topology_from_env();
-        const char *where = getenv("CHROMA_WIDE_BUILD");
-        if (topology == chroma_host::WIDE_TOPOLOGY_LEVELS && !(where && !strcmp(where, "host"))) {
-            void *h = nullptr;
-            rc = chroma_wide_build_device(ctx, d->nodes, d->nnodes, d->ntriangles, &h, nullptr, nullptr, nullptr);
-            if (rc == (int)hipErrorOutOfMemory) {
-                // (the builder's scratch -- ~150 bytes per triangle -- did not fit beside what the caller keeps on the card:
-                //  give the pool's parked blocks back and try once more; then the host cores build the SAME tree)
-                (void)hipGetLastError();
-                chroma_pool_trim(ctx);
-                rc = chroma_wide_build_device(ctx, d->nodes, d->nnodes, d->ntriangles, &h, nullptr, nullptr, nullptr);
-            }
-            if (rc == (int)hipErrorOutOfMemory) {
-                (void)hipGetLastError();
-                fprintf(stderr, "chroma_geometry_create: no room on the device for the tree builder's scratch: building the same tree on the host cores\n");
-                if (chroma_host::build_wide_tree(d->nodes, d->nnodes, d->ntriangles, wt, werr, topology) != 0) {
-                    chroma_geometry_destroy(g);
-                    return set_error(CHROMA_ERR_INVALID, "%s", werr.c_str());
-                }
-            } else if (rc != CHROMA_OK) { chroma_geometry_destroy(g); return rc; }
-            else {
-                wt = std::move(*(chroma_host::WideTree *)h);
-                delete (chroma_host::WideTree *)h;
-            }
-        } else if (chroma_host::build_wide_tree(d->nodes, d->nnodes, d->ntriangles, wt, werr, topology) != 0) {
-            chroma_geometry_destroy(g);
-            return set_error(CHROMA_ERR_INVALID, "%s", werr.c_str());
-        }
-    }
-    phase(wide_given ? "nodes upload" : "nodes upload + wide tree");
-    const uint32_t *wide_nodes = wide_given ? d->wide_nodes : wt.wnodes.data();
-    const uint32_t *tri_to_dev = wide_given ? d->wide_tri_to_record : wt.tri_to_dev.data();
-    const uint32_t *dev_to_tri = wide_given ? d->wide_record_to_tri : wt.dev_to_tri.data();
-    const uint32_t *tri_rank = wide_given ? d->wide_rank : wt.rank.data();
-    const size_t nwide = wide_given ? (size_t)d->nwide : wt.nwide;
-    const size_t nrecords = wide_given ? (size_t)d->nrecords : wt.dev_to_tri.size();
-    {   // the walks index the wide nodes and the records with what this tree holds: check it before any upload
-        std::string werr;
-        if (chroma_host::validate_wide_tree(wide_nodes, nwide, tri_to_dev, d->ntriangles, dev_to_tri, nrecords, werr) != 0) {
-            chroma_geometry_destroy(g);
-            return set_error(CHROMA_ERR_INVALID, "%s", werr.c_str());
-        }
-    }
-    phase("wide tree index checks");
-    { const uint4 *p; if ((rc = upload(g, (const uint4 *)wide_nodes, nwide * 8, &p)) != CHROMA_OK) { chroma_geometry_destroy(g); return rc; } v.wnodes = p; }
-    v.nwide = (uint32_t)nwide;
-    g->nwide = nwide; g->wide_depth = wt.depth; g->nrecords = nrecords;
-    {
-        const uint4 *dw = v.wnodes;
-        const uint32_t nw = (uint32_t)nwide;
-        hipStream_t st = ctx->stream;
-        if ((rc = stack_need_fixed_point(ctx, nwide, [&](uint32_t *need, uint32_t *changed) {
-                 hipLaunchKernelGGL(k_stack_need_wide, dim3((nw + 255) / 256), dim3(256), 0, st, dw, nw, need, changed); }, &g->wide_stack_need)) != CHROMA_OK) {
-            chroma_geometry_destroy(g);
-            return rc;
-        }
-    }
-    { chroma_host::WordBuffer().swap(wt.wnodes); }
-    UP(tri_to_dev, tri_to_dev, d->ntriangles);
-    UP(dev_to_tri, dev_to_tri, nrecords);
-    // traversal copy of the nodes: leaf child -> device triangle index (a pass over the array uploaded above)
-    {
-        void *dn = nullptr;
-        size_t bytes = (size_t)d->nnodes * 16;
-        hipError_t e = ctx_malloc(ctx, &dn, bytes);
-        if (e != hipSuccess) { chroma_geometry_destroy(g); return set_error((int)e, "hipMalloc(%zu) for nodes: %s", bytes, hipGetErrorString(e)); }
-        g->allocations.push_back(dn);
-        g->device_bytes += bytes;
-        hipLaunchKernelGGL(k_traversal_nodes, dim3((unsigned)((d->nnodes + 255) / 256)), dim3(256), 0, ctx->stream, (const uint4 *)g->d_nodes_api, (uint32_t)d->nnodes,
-                           v.tri_to_dev, d->ntriangles, (uint4 *)dn);
-        v.nodes = (const uint4 *)dn;
-    }
-    phase("wide nodes + traversal copy");
-    // API-visible copies of the mesh arrays (GPUGeometry.vertices/.triangles/.material_codes/.colors)
-    { const float *p; if ((rc = upload(g, d->vertices, (size_t)d->nvertices * 3, &p)) != CHROMA_OK) { chroma_geometry_destroy(g); return rc; } g->d_vertices = (void *)p; }
-    { const uint32_t *p; if ((rc = upload(g, d->triangles, (size_t)d->ntriangles * 3, &p)) != CHROMA_OK) { chroma_geometry_destroy(g); return rc; } g->d_triangles = (void *)p; }
-    { const uint32_t *p; if ((rc = upload(g, d->material_codes, d->ntriangles, &p)) != CHROMA_OK) { chroma_geometry_destroy(g); return rc; } g->d_material_codes = (void *)p; }
-    memcpy(v.world_origin, d->world_origin, sizeof v.world_origin);   // (the leaf boxes of the physics records need them)
-    v.world_scale = d->world_scale;
-    // 48-byte triangle records in device order: gathered on the device from those arrays (+ the ranks, uploaded for this only)
-    {
-        void *dtri = nullptr;
-        size_t bytes = nrecords * (16 * TRI_STRIDE);
-        hipError_t e = ctx_malloc(ctx, &dtri, bytes);
-        if (e != hipSuccess) { chroma_geometry_destroy(g); return set_error((int)e, "hipMalloc(%zu) for triangle records: %s", bytes, hipGetErrorString(e)); }
-        g->allocations.push_back(dtri);
-        g->device_bytes += bytes;
-        uint32_t *d_rank = nullptr;
-        e = ctx_malloc(ctx, (void **)&d_rank, std::max<size_t>(d->ntriangles, 1) * 4);
-        if (e != hipSuccess) { chroma_geometry_destroy(g); return set_error((int)e, "hipMalloc for triangle ranks: %s", hipGetErrorString(e)); }
-        rc = chroma_internal_htod(ctx, d_rank, tri_rank, (size_t)d->ntriangles * 4);
-        if (rc == CHROMA_OK) {
-            hipLaunchKernelGGL(k_triangle_records, dim3((unsigned)((nrecords + 255) / 256)), dim3(256), 0, ctx->stream, (const float *)g->d_vertices, (const uint32_t *)g->d_triangles,
-                               (const uint32_t *)g->d_material_codes, d_rank, v.dev_to_tri, (uint32_t)nrecords, (float4 *)dtri);
-            e = hipStreamSynchronize(ctx->stream);
-            if (e != hipSuccess) rc = set_error((int)e, "triangle records: %s", hipGetErrorString(e));
-        }
-        hipFree(d_rank);
-        if (rc != CHROMA_OK) { chroma_geometry_destroy(g); return rc; }
-        v.tri = (const float4 *)dtri;
-    }
-    // 32-byte physics records, in the same order: derived from the 48-byte ones (k_physics reads only these)
-    {
-        void *dphys = nullptr;
-        size_t bytes = std::max<size_t>(nrecords, 1) * 32;
-        hipError_t e = ctx_malloc(ctx, &dphys, bytes);
-        if (e != hipSuccess) { chroma_geometry_destroy(g); return set_error((int)e, "hipMalloc(%zu) for physics records: %s", bytes, hipGetErrorString(e)); }
-        g->allocations.push_back(dphys);
-        g->device_bytes += bytes;
-        if (nrecords) hipLaunchKernelGGL(k_triangle_phys, dim3((unsigned)((nrecords + 255) / 256)), dim3(256), 0, ctx->stream, v, (uint32_t)nrecords, (uint4 *)dphys);
-        e = hipStreamSynchronize(ctx->stream);
-        if (e == hipSuccess) e = hipGetLastError();
-        if (e != hipSuccess) { chroma_geometry_destroy(g); return set_error((int)e, "physics records: %s", hipGetErrorString(e)); }
-        v.tri_phys = (const uint4 *)dphys;
-    }
-    // 48-byte intersection records, in the same order: the edge form of the fast walks' triangle test
-    {
-        void *disect = nullptr;
-        size_t bytes = std::max<size_t>(nrecords, 1) * 48;
-        hipError_t e = ctx_malloc(ctx, &disect, bytes);
-        if (e != hipSuccess) { chroma_geometry_destroy(g); return set_error((int)e, "hipMalloc(%zu) for intersection records: %s", bytes, hipGetErrorString(e)); }
-        g->allocations.push_back(disect);
-        g->device_bytes += bytes;
-        if (nrecords) hipLaunchKernelGGL(k_triangle_isect, dim3((unsigned)((nrecords + 255) / 256)), dim3(256), 0, ctx->stream, v, (uint32_t)nrecords, (float4 *)disect);
-        e = hipStreamSynchronize(ctx->stream);
-        if (e == hipSuccess) e = hipGetLastError();
-        if (e != hipSuccess) { chroma_geometry_destroy(g); return set_error((int)e, "intersection records: %s", hipGetErrorString(e)); }
-        v.tri_isect = (const float4 *)disect;
-    }
-    phase("triangle records");
-    { const uint32_t *p; if ((rc = upload(g, d->colors, d->colors ? d->ntriangles : 0, &p)) != CHROMA_OK) { chroma_geometry_destroy(g); return rc; } g->d_colors = (void *)p; }
-    UP(solid_id_map, d->solid_id_map, d->solid_id_map ? d->ntriangles : 0);
-    size_t wn = d->wavelength_n;
-    UP(mat_refractive_index, d->mat_refractive_index, d->nmaterials * wn);
-    UP(mat_absorption_length, d->mat_absorption_length, d->nmaterials * wn);
-    UP(mat_scattering_length, d->mat_scattering_length, d->nmaterials * wn);
-    UP(mat_num_comp, d->mat_num_comp, d->nmaterials);
-    UP(mat_comp_offset, d->mat_comp_offset, d->nmaterials);
-    UP(comp_reemission_prob, d->comp_reemission_prob, d->ncomp_total * wn);
-    UP(comp_reemission_wvl_cdf, d->comp_reemission_wvl_cdf, d->ncomp_total * wn);
-    UP(comp_absorption_length, d->comp_absorption_length, d->ncomp_total * wn);
-    UP(comp_reemission_time_cdf, d->comp_reemission_time_cdf, (size_t)d->ncomp_total * d->time_n);
-    UP(surf_detect, d->surf_detect, d->nsurfaces * wn);
-    UP(surf_absorb, d->surf_absorb, d->nsurfaces * wn);
-    UP(surf_reemit, d->surf_reemit, d->nsurfaces * wn);
-    UP(surf_reflect_diffuse, d->surf_reflect_diffuse, d->nsurfaces * wn);
-    UP(surf_reflect_specular, d->surf_reflect_specular, d->nsurfaces * wn);
-    UP(surf_eta, d->surf_eta, d->nsurfaces * wn);
-    UP(surf_k, d->surf_k, d->nsurfaces * wn);
-    UP(surf_reemission_cdf, d->surf_reemission_cdf, d->nsurfaces * wn);
-    {
-        std::vector<SurfaceInfo> info(std::max<uint32_t>(d->nsurfaces, 1));
-        for (uint32_t s = 0; s < d->nsurfaces; s++)
-            info[s] = SurfaceInfo{d->surf_model[s], d->surf_transmissive[s], d->surf_thickness[s],
-                                  d->surf_dichroic_index ? d->surf_dichroic_index[s] : -1};
-        UP(surf_info, info.data(), info.size());
-    }
-    UP(dichroic_nangles, d->dichroic_nangles, d->ndichroic);
-    UP(dichroic_offset, d->dichroic_offset, d->ndichroic);
-    UP(dichroic_angles, d->dichroic_angles, d->ndichroic_angles_total);
-    UP(dichroic_reflect, d->dichroic_reflect, d->ndichroic_angles_total * wn);
-    UP(dichroic_transmit, d->dichroic_transmit, d->ndichroic_angles_total * wn);
-    UP(solid_id_to_channel_index, d->solid_id_to_channel_index, d->nsolids);
-#undef UP
-    {   // ~16 ulp of the largest world coordinate (record_hit_is_regular)
-        float maxabs = 0.0f;
-        for (int a = 0; a < 3; a++)
-            maxabs = std::max(maxabs, std::max(fabsf(d->world_origin[a]), fabsf(d->world_origin[a] + 65535.0f * d->world_scale)));
-        v.suspect_margin = 2e-6f * maxabs;
-        // growth of the boxes in the fast slab test (ray_growth, propagate_device.h): four times the bound on what the fused
-        // evaluation can differ from the reference's, at least a quarter of a quantum, at most the whole quantum of rounds 1-2
-        // (CHROMA_SLAB_GROW overrides: A/B runs)
-        const double bound = ldexp(1.0, -24) * (10.0 * 65534.0 + 2.0 * (double)maxabs / std::max((double)d->world_scale, 1e-30));
-        v.slab_grow = (float)std::min(1.0, std::max(0.25, 4.0 * bound));
-        if (const char *e = getenv("CHROMA_SLAB_GROW")) v.slab_grow = (float)std::min(1.0, std::max(0.0625, atof(e)));
-    }
-    v.wavelength_n = d->wavelength_n; v.wavelength_start = d->wavelength_start; v.wavelength_step = d->wavelength_step;
-    v.time_n = d->time_n; v.time_start = d->time_start; v.time_step = d->time_step;
-    v.nnodes = d->nnodes; v.ntriangles = d->ntriangles; v.nsolids = d->nsolids; v.nchannels = d->nchannels;
-    v.plain_optics = 1u;
-    for (uint32_t m = 0; m < d->nmaterials; m++) if (d->mat_num_comp[m]) v.plain_optics = 0u;
-    for (uint32_t k = 0; k < d->nsurfaces; k++) if (d->surf_model[k] != CHROMA_SURFACE_DEFAULT) v.plain_optics = 0u;
-    if (getenv("CHROMA_FULL_PHYSICS")) v.plain_optics = 0u;          // (A/B: the all-models kernel on a plain geometry)
-
-    phase("mesh arrays + tables");
-    {
-        const uint4 *dn = (const uint4 *)g->d_nodes_api;
-        const uint32_t nn = (uint32_t)d->nnodes;
-        hipStream_t st = ctx->stream;
-        uint32_t need = 0;
-        if ((rc = stack_need_fixed_point(ctx, d->nnodes, [&](uint32_t *nd, uint32_t *changed) {
-                 hipLaunchKernelGGL(k_stack_need_ref, dim3((nn + 255) / 256), dim3(256), 0, st, dn, nn, nd, changed); }, &need)) != CHROMA_OK) {
-            chroma_geometry_destroy(g);
-            return rc;
-        }
-        g->stack_need = std::max<uint32_t>(1, need);
-    }
-    phase("stack need");
-    if (g->stack_need > STACK_LDS + STACK_SCRATCH) {
-        uint32_t need = g->stack_need;
-        chroma_geometry_destroy(g);
-        return set_error(CHROMA_ERR_STACK, "BVH needs %u traversal stack entries, more than the %d supported", need, STACK_LDS + STACK_SCRATCH);
-    }
-    *out = g;
-    return CHROMA_OK;
-}
-
-int chroma_geometry_destroy(chroma_geometry *g)
-{
-    if (!g) return CHROMA_OK;
-    hipSetDevice(g->ctx->device);
-    hipStreamSynchronize(g->ctx->stream);
-    for (void *p : g->allocations) hipFree(p);
-    delete g;
-    return CHROMA_OK;
-}
-
-int chroma_geometry_device_ptr(chroma_geometry *g, const char *name, void **d_ptr, size_t *nbytes)
-{
-    if (!g || !name || !d_ptr) return set_error(CHROMA_ERR_INVALID, "bad argument");
-    std::string n(name);
-    size_t bytes = 0; void *p = nullptr;
-    if (n == "nodes") { p = g->d_nodes_api; bytes = g->nnodes * 16; }
-    else if (n == "vertices") { p = g->d_vertices; bytes = g->nvertices * 12; }
-    else if (n == "triangles") { p = g->d_triangles; bytes = g->ntriangles * 12; }
-    else if (n == "material_codes") { p = g->d_material_codes; bytes = g->ntriangles * 4; }
-    else if (n == "colors") { p = g->d_colors; bytes = g->ntriangles * 4; }
-    else if (n == "solid_id_map") { p = (void *)g->view.solid_id_map; bytes = g->ntriangles * 4; }
-    else if (n == "solid_id_to_channel_index") { p = (void *)g->view.solid_id_to_channel_index; bytes = (size_t)g->view.nsolids * 4; }
-    else if (n == "triangle_records") { p = (void *)g->view.tri; bytes = g->nrecords * (16 * TRI_STRIDE); }
-    else if (n == "triangle_phys") { p = (void *)g->view.tri_phys; bytes = g->nrecords * 32; }
-    else if (n == "triangle_isect") { p = (void *)g->view.tri_isect; bytes = g->nrecords * 48; }
-    else if (n == "wide_nodes") { p = (void *)g->view.wnodes; bytes = g->nwide * 128; }
-    else if (n == "tri_to_dev") { p = (void *)g->view.tri_to_dev; bytes = g->ntriangles * 4; }
-    else if (n == "dev_to_tri") { p = (void *)g->view.dev_to_tri; bytes = g->nrecords * 4; }
-    else return set_error(CHROMA_ERR_INVALID, "unknown geometry array '%s'", name);
-    *d_ptr = p;
-    if (nbytes) *nbytes = bytes;
-    return CHROMA_OK;
-}
-
-int chroma_geometry_stack_need(chroma_geometry *g, uint32_t *entries)
-{
-    if (!g || !entries) return set_error(CHROMA_ERR_INVALID, "bad argument");
-    *entries = g->stack_need;
-    return CHROMA_OK;
-}
 
 // ---- kernel-level entry points ------------------------------------------------------------------------
 int chroma_propagate_step(chroma_ctx *ctx, chroma_geometry *geom, int32_t first_photon, int32_t nthreads,
@@ -1520,106 +441,6 @@ int chroma_propagate_step(chroma_ctx *ctx, chroma_geometry *geom, int32_t first_
     if ((rc = check_stack(geom))) return rc;
     return launch_propagate(ctx, ctx->counting != 0, geom, to_view(photons), first_photon, nthreads, d_input_queue, d_output_queue, rng,
                             max_steps, use_weights, scatter_first);
-}
-
-int chroma_photon_duplicate(chroma_ctx *ctx, int32_t first_photon, int32_t nthreads,
-                            const chroma_photon_arrays *photons, int32_t copies, int32_t stride)
-{
-    if (!ctx) return set_error(CHROMA_ERR_INVALID, "null ctx");
-    int rc = check_photons(photons, false);
-    if (rc) return rc;
-    if (nthreads <= 0 || copies <= 0) return CHROMA_OK;
-    hipLaunchKernelGGL(k_photon_duplicate, dim3((nthreads + 255) / 256), dim3(256), 0, ctx->stream, to_view(photons),
-                       first_photon, nthreads, copies, stride);
-    HIP_TRY(hipGetLastError());
-    return CHROMA_OK;
-}
-
-static int read_word(chroma_ctx *ctx, int slot, uint32_t *out)
-{
-    HIP_TRY(hipMemcpyAsync(ctx->h_words + slot, ctx->d_words + slot, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    *out = ctx->h_words[slot];
-    return CHROMA_OK;
-}
-
-int chroma_count_photons(chroma_ctx *ctx, int32_t first_photon, int32_t nthreads, uint32_t target_flag,
-                         const uint32_t *d_flags, uint32_t *count)
-{
-    if (!ctx || !d_flags || !count) return set_error(CHROMA_ERR_INVALID, "bad argument");
-    HIP_TRY(hipMemsetAsync(ctx->d_words, 0, 4, ctx->stream));
-    if (nthreads > 0) {
-        hipLaunchKernelGGL(k_count_photons, dim3((unsigned)std::min((nthreads + 255) / 256, 4096)), dim3(256), 0, ctx->stream, d_flags, first_photon,
-                           nthreads, target_flag, ctx->d_words);
-        HIP_TRY(hipGetLastError());
-    }
-    return read_word(ctx, 0, count);
-}
-
-int chroma_copy_photons(chroma_ctx *ctx, int32_t first_photon, int32_t nthreads, uint32_t target_flag,
-                        const chroma_photon_arrays *src, const chroma_photon_arrays *dst, uint32_t *ncopied)
-{
-    if (!ctx) return set_error(CHROMA_ERR_INVALID, "null ctx");
-    int rc = check_photons(src, false); if (rc) return rc;
-    rc = check_photons(dst, false); if (rc) return rc;
-    HIP_TRY(hipMemsetAsync(ctx->d_words, 0, 4, ctx->stream));
-    if (nthreads > 0) {
-        hipLaunchKernelGGL(k_copy_photons, dim3((unsigned)(((long long)nthreads + 16 * 256 - 1) / (16 * 256))), dim3(256), 0, ctx->stream, to_view(src), to_view(dst),
-                           first_photon, nthreads, target_flag, ctx->d_words);
-        HIP_TRY(hipGetLastError());
-    }
-    uint32_t n = 0;
-    rc = read_word(ctx, 0, &n);
-    if (ncopied) *ncopied = n;
-    return rc;
-}
-
-int chroma_copy_photon_queue(chroma_ctx *ctx, int32_t first_photon, int32_t nthreads, const uint32_t *d_queue,
-                             const chroma_photon_arrays *src, const chroma_photon_arrays *dst)
-{
-    if (!ctx || !d_queue) return set_error(CHROMA_ERR_INVALID, "bad argument");
-    int rc = check_photons(src, false); if (rc) return rc;
-    rc = check_photons(dst, false); if (rc) return rc;
-    if (nthreads <= 0) return CHROMA_OK;
-    hipLaunchKernelGGL(k_copy_photon_queue, dim3((nthreads + 255) / 256), dim3(256), 0, ctx->stream, to_view(src), to_view(dst),
-                       first_photon, nthreads, d_queue);
-    HIP_TRY(hipGetLastError());
-    return CHROMA_OK;
-}
-
-int chroma_count_photon_hits(chroma_ctx *ctx, chroma_geometry *geom, int32_t first_photon, int32_t nphotons,
-                             uint32_t detection_state, const chroma_photon_arrays *photons, uint32_t *count)
-{
-    if (!ctx || !geom || !count) return set_error(CHROMA_ERR_INVALID, "bad argument");
-    if (!geom->view.nsolids) return set_error(CHROMA_ERR_INVALID, "geometry has no detector channel map");
-    int rc = check_photons(photons, false); if (rc) return rc;
-    HIP_TRY(hipMemsetAsync(ctx->d_words, 0, 4, ctx->stream));
-    if (nphotons > 0) {
-        hipLaunchKernelGGL(k_count_hits, dim3((unsigned)std::min((nphotons + 255) / 256, 4096)), dim3(256), 0, ctx->stream, geom->view, photons->flags,
-                           photons->last_hit_triangles, first_photon, nphotons, detection_state, ctx->d_words);
-        HIP_TRY(hipGetLastError());
-    }
-    return read_word(ctx, 0, count);
-}
-
-int chroma_copy_photon_hits(chroma_ctx *ctx, chroma_geometry *geom, int32_t first_photon, int32_t nphotons,
-                            uint32_t detection_state, const chroma_photon_arrays *src, const chroma_photon_arrays *dst,
-                            int32_t *d_channels, uint32_t *ncopied)
-{
-    if (!ctx || !geom || !d_channels) return set_error(CHROMA_ERR_INVALID, "bad argument");
-    if (!geom->view.nsolids) return set_error(CHROMA_ERR_INVALID, "geometry has no detector channel map");
-    int rc = check_photons(src, false); if (rc) return rc;
-    rc = check_photons(dst, false); if (rc) return rc;
-    HIP_TRY(hipMemsetAsync(ctx->d_words, 0, 4, ctx->stream));
-    if (nphotons > 0) {
-        hipLaunchKernelGGL(k_copy_hits, dim3((unsigned)(((long long)nphotons + COPY_ITEMS * 256 - 1) / (COPY_ITEMS * 256))), dim3(256), 0, ctx->stream, geom->view, to_view(src),
-                           to_view(dst), d_channels, first_photon, nphotons, detection_state, ctx->d_words);
-        HIP_TRY(hipGetLastError());
-    }
-    uint32_t n = 0;
-    rc = read_word(ctx, 0, &n);
-    if (ncopied) *ncopied = n;
-    return rc;
 }
 
 static int ensure_queues(chroma_ctx *ctx, size_t n);
@@ -2084,189 +905,6 @@ int chroma_propagate_opt(chroma_ctx *ctx, chroma_geometry *geom, const chroma_ph
     return propagate_impl(ctx, geom, photons, nphotons, ncopies, rng, *options, stats, aborted, hits);
 }
 
-int chroma_channel_hits(chroma_ctx *ctx, chroma_geometry *geom, uint64_t nphotons, uint32_t detection_state,
-                        const chroma_photon_arrays *photons, uint32_t *d_hit_count, uint32_t *d_earliest_time_bits)
-{
-    if (!ctx || !geom || !d_hit_count) return set_error(CHROMA_ERR_INVALID, "bad argument");
-    if (!geom->view.nsolids) return set_error(CHROMA_ERR_INVALID, "geometry has no detector channel map");
-    int rc = check_photons(photons, false); if (rc) return rc;
-    if (nphotons == 0) return CHROMA_OK;
-    hipLaunchKernelGGL(k_channel_hits, dim3((unsigned)((nphotons + 255) / 256)), dim3(256), 0, ctx->stream, geom->view,
-                       photons->flags, photons->last_hit_triangles, photons->t, (uint64_t)nphotons, detection_state,
-                       d_hit_count, d_earliest_time_bits);
-    HIP_TRY(hipGetLastError());
-    return CHROMA_OK;
-}
-
-int chroma_daq_reset(chroma_ctx *ctx, float maxtime, uint32_t nchannels, uint32_t *d_earliest_time_int,
-                     uint32_t *d_channel_q_int, uint32_t *d_channel_histories)
-{
-    if (!ctx || !d_earliest_time_int || !d_channel_q_int || !d_channel_histories) return set_error(CHROMA_ERR_INVALID, "bad argument");
-    if (nchannels == 0) return CHROMA_OK;
-    hipLaunchKernelGGL(k_daq_reset, dim3((nchannels + 255) / 256), dim3(256), 0, ctx->stream, maxtime, nchannels,
-                       d_earliest_time_int, d_channel_q_int, d_channel_histories);
-    HIP_TRY(hipGetLastError());
-    return CHROMA_OK;
-}
-
-int chroma_daq_acquire(chroma_ctx *ctx, chroma_geometry *geom, const chroma_daq_tables *tables, int32_t first_photon,
-                       int32_t nphotons, uint32_t detection_state, const chroma_photon_arrays *photons, chroma_rng rng,
-                       uint32_t acquisition, float global_weight, uint32_t *d_earliest_time_int,
-                       uint32_t *d_channel_q_int, uint32_t *d_channel_histories)
-{
-    if (!ctx || !geom || !tables || !d_earliest_time_int || !d_channel_q_int || !d_channel_histories)
-        return set_error(CHROMA_ERR_INVALID, "bad argument");
-    if (!geom->view.nsolids) return set_error(CHROMA_ERR_INVALID, "geometry has no detector channel map");
-    if (tables->time_cdf_len < 2 || tables->charge_cdf_len < 2 || !tables->d_time_cdf_x || !tables->d_time_cdf_y ||
-        !tables->d_charge_cdf_x || !tables->d_charge_cdf_y || !(tables->charge_unit > 0.0f))
-        return set_error(CHROMA_ERR_INVALID, "DAQ tables: need two CDFs of at least 2 points and a positive charge unit");
-    int rc = check_photons(photons, false); if (rc) return rc;
-    if (nphotons <= 0) return CHROMA_OK;
-    hipLaunchKernelGGL(k_run_daq, dim3((nphotons + 255) / 256), dim3(256), 0, ctx->stream, geom->view, *tables, first_photon,
-                       nphotons, detection_state, photons->t, photons->flags, photons->last_hit_triangles, photons->weights,
-                       rng.seed, rng.photon_id_base, acquisition, global_weight, d_earliest_time_int, d_channel_q_int,
-                       d_channel_histories);
-    HIP_TRY(hipGetLastError());
-    return CHROMA_OK;
-}
-
-int chroma_daq_acquire_many(chroma_ctx *ctx, chroma_geometry *geom, const chroma_daq_tables *tables, int32_t first_photon,
-                            int32_t nphotons, uint32_t detection_state, const chroma_photon_arrays *photons, chroma_rng rng,
-                            uint32_t acquisition, float global_weight, int32_t ndaq, int32_t channel_stride,
-                            uint32_t *d_earliest_time_int, uint32_t *d_channel_q_int, uint32_t *d_channel_histories)
-{
-    if (!ctx || !geom || !tables || !d_earliest_time_int || !d_channel_q_int || !d_channel_histories)
-        return set_error(CHROMA_ERR_INVALID, "bad argument");
-    if (!geom->view.nsolids) return set_error(CHROMA_ERR_INVALID, "geometry has no detector channel map");
-    if (ndaq < 1 || channel_stride < (int32_t)geom->view.nchannels)
-        return set_error(CHROMA_ERR_INVALID, "ndaq must be positive and the channel stride at least the number of channels");
-    if (tables->time_cdf_len < 2 || tables->charge_cdf_len < 2 || !tables->d_time_cdf_x || !tables->d_time_cdf_y ||
-        !tables->d_charge_cdf_x || !tables->d_charge_cdf_y || !(tables->charge_unit > 0.0f))
-        return set_error(CHROMA_ERR_INVALID, "DAQ tables: need two CDFs of at least 2 points and a positive charge unit");
-    int rc = check_photons(photons, false); if (rc) return rc;
-    if (nphotons <= 0) return CHROMA_OK;
-    const long long total = (long long)nphotons * ndaq;
-    hipLaunchKernelGGL(k_run_daq_many, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, geom->view, *tables,
-                       first_photon, nphotons, detection_state, photons->t, photons->flags, photons->last_hit_triangles,
-                       photons->weights, rng.seed, rng.photon_id_base, acquisition, global_weight, ndaq, channel_stride,
-                       d_earliest_time_int, d_channel_q_int, d_channel_histories);
-    HIP_TRY(hipGetLastError());
-    return CHROMA_OK;
-}
-
-int chroma_daq_convert(chroma_ctx *ctx, uint32_t nchannels, float charge_unit, const uint32_t *d_earliest_time_int,
-                       const uint32_t *d_channel_q_int, float *d_earliest_time, float *d_channel_q)
-{
-    if (!ctx || !d_earliest_time_int || !d_channel_q_int || !d_earliest_time || !d_channel_q)
-        return set_error(CHROMA_ERR_INVALID, "bad argument");
-    if (nchannels == 0) return CHROMA_OK;
-    hipLaunchKernelGGL(k_daq_convert, dim3((nchannels + 255) / 256), dim3(256), 0, ctx->stream, nchannels, charge_unit,
-                       d_earliest_time_int, d_channel_q_int, d_earliest_time, d_channel_q);
-    HIP_TRY(hipGetLastError());
-    return CHROMA_OK;
-}
-
-// ---- PDFs over DAQ output (kernels_pdf.h) ----
-static int check_pdf_layout(uint32_t nchannels, int32_t ndaq, uint32_t stride)
-{
-    if (ndaq < 1 || stride < nchannels)
-        return set_error(CHROMA_ERR_INVALID, "ndaq must be positive and the channel stride at least the number of channels");
-    return CHROMA_OK;
-}
-
-int chroma_pdf_bin_hits(chroma_ctx *ctx, uint32_t nchannels, int32_t ndaq, uint32_t stride, const float *d_channel_q,
-                        const float *d_channel_t, int32_t tbins, float tmin, float tmax, int32_t qbins, float qmin, float qmax,
-                        uint32_t *d_hitcount, uint32_t *d_pdf)
-{
-    if (!ctx || !d_channel_q || !d_channel_t || !d_hitcount || !d_pdf) return set_error(CHROMA_ERR_INVALID, "bad argument");
-    int rc = check_pdf_layout(nchannels, ndaq, stride); if (rc) return rc;
-    if (tbins < 1 || qbins < 1 || (int64_t)tbins * qbins > INT32_MAX)
-        return set_error(CHROMA_ERR_INVALID, "need at least one time and one charge bin (and fewer than 2^31 per channel)");
-    if (!(tmin < tmax) || !(qmin < qmax)) return set_error(CHROMA_ERR_INVALID, "empty or inverted time or charge range");
-    if (nchannels == 0) return CHROMA_OK;
-    std::lock_guard<std::mutex> call_lock(ctx->call_mu);
-    hipLaunchKernelGGL(k_pdf_bin_hits, dim3((nchannels + 255) / 256), dim3(256), 0, ctx->stream, nchannels, (int)ndaq, stride,
-                       d_channel_q, d_channel_t, d_hitcount, (int)tbins, tmin, tmax, (int)qbins, qmin, qmax, d_pdf);
-    HIP_TRY(hipGetLastError());
-    return CHROMA_OK;
-}
-
-int chroma_pdf_eval_accumulate(chroma_ctx *ctx, uint32_t nchannels, int32_t ndaq, uint32_t stride, const uint32_t *d_event_hit,
-                               const float *d_event_time, const float *d_mc_time, uint32_t nhit, const uint32_t *d_hit_channels,
-                               float min_twidth, float tmin, float tmax, int32_t min_bin_content, uint32_t *d_hitcount,
-                               uint32_t *d_bincount, float *d_nearest)
-{
-    if (!ctx || !d_event_hit || !d_event_time || !d_mc_time || !d_hitcount || !d_bincount || (nhit && (!d_hit_channels || !d_nearest)))
-        return set_error(CHROMA_ERR_INVALID, "bad argument");
-    int rc = check_pdf_layout(nchannels, ndaq, stride); if (rc) return rc;
-    if (min_bin_content < 1 || min_bin_content > 1024) return set_error(CHROMA_ERR_INVALID, "min_bin_content must be in 1 .. 1024");
-    if (!(tmin < tmax)) return set_error(CHROMA_ERR_INVALID, "empty or inverted time range");
-    if (nhit > nchannels) return set_error(CHROMA_ERR_INVALID, "more hit channels than channels");
-    if (nchannels == 0) return CHROMA_OK;
-    std::lock_guard<std::mutex> call_lock(ctx->call_mu);
-    hipLaunchKernelGGL(k_pdf_eval_hitcount, dim3((nchannels + 255) / 256), dim3(256), 0, ctx->stream, nchannels, (int)ndaq, stride,
-                       d_event_hit, d_mc_time, tmin, tmax, d_hitcount);
-    HIP_TRY(hipGetLastError());
-    if (nhit == 0) return CHROMA_OK;          // an event with no hit channel: nothing to sort
-    hipLaunchKernelGGL(k_pdf_eval_accumulate, dim3((nhit + PDF_EVAL_WAVES - 1) / PDF_EVAL_WAVES), dim3(64 * PDF_EVAL_WAVES), 0,
-                       ctx->stream, nchannels, (int)ndaq, stride, nhit, d_hit_channels, d_event_hit, d_event_time, d_mc_time,
-                       0.5f * min_twidth, tmin, tmax, (int)min_bin_content, d_hitcount, d_bincount, d_nearest);
-    HIP_TRY(hipGetLastError());
-    return CHROMA_OK;
-}
-
-int chroma_pdf_moments(chroma_ctx *ctx, int32_t time_only, uint32_t nchannels, int32_t ndaq, uint32_t stride, const float *d_mc_time,
-                       const float *d_mc_charge, float tmin, float tmax, float qmin, float qmax, uint32_t *d_mom0, float *d_t_mom1,
-                       float *d_t_mom2, float *d_q_mom1, float *d_q_mom2)
-{
-    if (!ctx || !d_mc_time || !d_mom0 || !d_t_mom1 || !d_t_mom2 || (!time_only && (!d_mc_charge || !d_q_mom1 || !d_q_mom2)))
-        return set_error(CHROMA_ERR_INVALID, "bad argument");
-    int rc = check_pdf_layout(nchannels, ndaq, stride); if (rc) return rc;
-    if (!(tmin < tmax) || (!time_only && !(qmin < qmax))) return set_error(CHROMA_ERR_INVALID, "empty or inverted time or charge range");
-    if (nchannels == 0) return CHROMA_OK;
-    std::lock_guard<std::mutex> call_lock(ctx->call_mu);
-    hipLaunchKernelGGL(k_pdf_moments, dim3((nchannels + 255) / 256), dim3(256), 0, ctx->stream, (int)(time_only != 0), nchannels,
-                       (int)ndaq, stride, d_mc_time, d_mc_charge, tmin, tmax, qmin, qmax, d_mom0, d_t_mom1, d_t_mom2, d_q_mom1, d_q_mom2);
-    HIP_TRY(hipGetLastError());
-    return CHROMA_OK;
-}
-
-int chroma_pdf_kernel_eval(chroma_ctx *ctx, int32_t time_only, uint32_t nchannels, int32_t ndaq, uint32_t stride,
-                           const uint32_t *d_event_hit, const float *d_event_time, const float *d_event_charge, const float *d_mc_time,
-                           const float *d_mc_charge, float tmin, float tmax, float qmin, float qmax, const float *d_inv_time_bandwidths,
-                           const float *d_inv_charge_bandwidths, uint32_t *d_hitcount, float *d_time_pdf_values,
-                           float *d_charge_pdf_values)
-{
-    if (!ctx || !d_event_hit || !d_event_time || !d_mc_time || !d_inv_time_bandwidths || !d_hitcount || !d_time_pdf_values ||
-        (!time_only && (!d_event_charge || !d_mc_charge || !d_inv_charge_bandwidths || !d_charge_pdf_values)))
-        return set_error(CHROMA_ERR_INVALID, "bad argument");
-    int rc = check_pdf_layout(nchannels, ndaq, stride); if (rc) return rc;
-    if (!(tmin < tmax) || (!time_only && !(qmin < qmax))) return set_error(CHROMA_ERR_INVALID, "empty or inverted time or charge range");
-    if (nchannels == 0) return CHROMA_OK;
-    std::lock_guard<std::mutex> call_lock(ctx->call_mu);
-    hipLaunchKernelGGL(k_pdf_kernel_eval, dim3((nchannels + 255) / 256), dim3(256), 0, ctx->stream, (int)(time_only != 0), nchannels,
-                       (int)ndaq, stride, d_event_hit, d_event_time, d_event_charge, d_mc_time, d_mc_charge, tmin, tmax, qmin, qmax,
-                       d_inv_time_bandwidths, d_inv_charge_bandwidths, d_hitcount, d_time_pdf_values, d_charge_pdf_values);
-    HIP_TRY(hipGetLastError());
-    return CHROMA_OK;
-}
-
-int chroma_render(chroma_ctx *ctx, chroma_geometry *geom, int32_t nthreads, const float *d_origin, const float *d_direction,
-                  uint32_t alpha_depth, uint32_t *d_pixels, float *d_dx, uint32_t *d_dxlen, float *d_color, uint32_t bg_color)
-{
-    if (!ctx || !geom || !d_origin || !d_direction || !d_pixels || !d_dx || !d_dxlen || !d_color)
-        return set_error(CHROMA_ERR_INVALID, "bad argument");
-    if (alpha_depth < 1) return set_error(CHROMA_ERR_INVALID, "alpha_depth must be at least 1");
-    if (nthreads <= 0) return CHROMA_OK;
-    if (geom->stack_need > STACK_LDS + STACK_SCRATCH)
-        return set_error(CHROMA_ERR_STACK, "BVH needs %u traversal stack entries, more than the %d supported", geom->stack_need, STACK_LDS + STACK_SCRATCH);
-    hipLaunchKernelGGL((k_render<STACK_LDS>), dim3((unsigned)((nthreads + PROP_BLOCK - 1) / PROP_BLOCK)), dim3(PROP_BLOCK), 0, ctx->stream,
-                       geom->view, (const uint32_t *)geom->d_colors, (int)nthreads, d_origin, d_direction, alpha_depth, d_pixels, d_dx,
-                       d_dxlen, (float4 *)d_color, bg_color, ctx->d_counters);
-    HIP_TRY(hipGetLastError());
-    return CHROMA_OK;
-}
-
 #if CHROMA_HYBRID_RENDER
 // ---- the hybrid render (chroma/cuda/hybrid_render.cu as chroma/camera.py:188-249 drives it; kernels_hybrid_render.h) ----
 // Everything is checked before the first launch.  The two sample passes take the context's call lock: they run the step
@@ -2363,205 +1001,5 @@ int chroma_hybrid_pixels(chroma_ctx *ctx, int32_t nthreads, const float *d_image
     return CHROMA_OK;
 }
 #endif  // CHROMA_HYBRID_RENDER
-
-int chroma_color_solids(chroma_ctx *ctx, chroma_geometry *geom, int32_t first_triangle, int32_t ntriangles, const uint8_t *d_solid_hit,
-                        const uint32_t *d_solid_colors, uint32_t nsolids)
-{
-    if (!ctx || !geom || !d_solid_hit || !d_solid_colors) return set_error(CHROMA_ERR_INVALID, "bad argument");
-    if (!geom->d_colors || !geom->view.solid_id_map) return set_error(CHROMA_ERR_INVALID, "geometry was created without colors / solid_id_map");
-    if (first_triangle < 0 || ntriangles < 0 || (uint64_t)first_triangle + (uint64_t)ntriangles > (uint64_t)geom->ntriangles)
-        return set_error(CHROMA_ERR_INVALID, "triangles %d .. %lld of %llu", first_triangle, (long long)first_triangle + ntriangles, (unsigned long long)geom->ntriangles);
-    if (ntriangles == 0) return CHROMA_OK;
-    hipLaunchKernelGGL(k_color_solids, dim3((unsigned)((ntriangles + 255) / 256)), dim3(256), 0, ctx->stream, (int)first_triangle, (int)ntriangles,
-                       geom->view.solid_id_map, d_solid_hit, d_solid_colors, nsolids, (uint32_t *)geom->d_colors);
-    HIP_TRY(hipGetLastError());
-    return CHROMA_OK;
-}
-
-static int rays_transform(chroma_ctx *ctx, int32_t n, float *d_a, int mode, float phi, const float axis[3], const float point[3])
-{
-    if (!ctx || !d_a) return set_error(CHROMA_ERR_INVALID, "bad argument");
-    if (n <= 0) return CHROMA_OK;
-    const float zero[3] = {0.f, 0.f, 0.f};
-    if (!axis) axis = zero;
-    if (!point) point = zero;
-    hipLaunchKernelGGL(k_rays_transform, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (int)n, d_a, mode, phi,
-                       axis[0], axis[1], axis[2], point[0], point[1], point[2]);
-    HIP_TRY(hipGetLastError());
-    return CHROMA_OK;
-}
-int chroma_points_translate(chroma_ctx *ctx, int32_t n, float *d_a, const float v[3]) { return rays_transform(ctx, n, d_a, 0, 0.f, nullptr, v); }
-int chroma_points_rotate(chroma_ctx *ctx, int32_t n, float *d_a, float phi, const float axis[3]) { return rays_transform(ctx, n, d_a, 1, phi, axis, nullptr); }
-int chroma_points_rotate_around_point(chroma_ctx *ctx, int32_t n, float *d_a, float phi, const float axis[3], const float point[3])
-{ return rays_transform(ctx, n, d_a, 2, phi, axis, point); }
-
-int chroma_probe(chroma_ctx *ctx, int32_t fn, uint64_t n, const float *d_x, const float *d_tab_x, const float *d_tab_f,
-                 uint32_t ntab, float start, float step, float *d_out)
-{
-    if (!ctx || !d_x || !d_out || fn < 0 || fn > 4) return set_error(CHROMA_ERR_INVALID, "bad argument");
-    if ((fn == 0 && (!d_tab_f || ntab < 2)) || (fn == 1 && (!d_tab_x || ntab < 2)) || (fn == 2 && (!d_tab_x || !d_tab_f || ntab < 2)))
-        return set_error(CHROMA_ERR_INVALID, "probe %d: table missing", fn);
-    if (n == 0) return CHROMA_OK;
-    hipLaunchKernelGGL(k_probe, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (int)fn, n, d_x, d_tab_x, d_tab_f,
-                       ntab, start, step, d_out);
-    HIP_TRY(hipGetLastError());
-    return CHROMA_OK;
-}
-
-int chroma_generate_bomb(chroma_ctx *ctx, const chroma_photon_arrays *photons, uint64_t nphotons, uint64_t seed,
-                         uint64_t id_base, const float pos[3], float wavelength_lo, float wavelength_hi)
-{
-    if (!ctx || !pos) return set_error(CHROMA_ERR_INVALID, "bad argument");
-    int rc = check_photons(photons, true); if (rc) return rc;
-    if (nphotons == 0) return CHROMA_OK;
-    hipLaunchKernelGGL(k_generate_bomb, dim3((unsigned)((nphotons + 255) / 256)), dim3(256), 0, ctx->stream, to_view(photons),
-                       (uint64_t)nphotons, seed, id_base, pos[0], pos[1], pos[2], wavelength_lo, wavelength_hi);
-    HIP_TRY(hipGetLastError());
-    return CHROMA_OK;
-}
-
-// ---- the hit reduction across GPUs ----------------------------------------------------
-// Photons never interact and every GPU holds the whole geometry, so a batch sharded over the GPUs of a
-// node needs exactly one exchange: its per-channel arrays.  That exchange is RCCL on the library's own
-// stream, on the device arrays the hit kernels filled -- nothing is staged through the host.  RCCL is
-// found with dlopen when the first communicator call is made (a process that already holds an RCCL, e.g.
-// torch's, gets that one through the shared-object name), so single-GPU users never load it.
-struct RcclApi {
-    void *handle = nullptr;
-    ncclResult_t (*GetUniqueId)(ncclUniqueId *) = nullptr;
-    ncclResult_t (*CommInitRank)(ncclComm_t *, int, ncclUniqueId, int) = nullptr;
-    ncclResult_t (*CommDestroy)(ncclComm_t) = nullptr;
-    ncclResult_t (*AllReduce)(const void *, void *, size_t, ncclDataType_t, ncclRedOp_t, ncclComm_t, hipStream_t) = nullptr;
-    ncclResult_t (*AllGather)(const void *, void *, size_t, ncclDataType_t, ncclComm_t, hipStream_t) = nullptr;
-    ncclResult_t (*GroupStart)() = nullptr;
-    ncclResult_t (*GroupEnd)() = nullptr;
-    const char *(*GetErrorString)(ncclResult_t) = nullptr;
-};
-static RcclApi g_rccl;
-
-static int rccl_load()
-{
-    if (g_rccl.handle) return CHROMA_OK;
-    void *h = nullptr;
-    for (const char *name : {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"}) {
-        h = dlopen(name, RTLD_NOW | RTLD_GLOBAL);
-        if (h) break;
-    }
-    if (!h) return set_error(CHROMA_ERR_INVALID, "RCCL not found (dlopen librccl.so.1): %s", dlerror());
-#define SYM(field, name) \
-    do { *(void **)(&g_rccl.field) = dlsym(h, name); \
-         if (!g_rccl.field) { dlclose(h); return set_error(CHROMA_ERR_INVALID, "RCCL: symbol %s missing", name); } } while (0)
-    SYM(GetUniqueId, "ncclGetUniqueId"); SYM(CommInitRank, "ncclCommInitRank"); SYM(CommDestroy, "ncclCommDestroy");
-    SYM(AllReduce, "ncclAllReduce"); SYM(AllGather, "ncclAllGather"); SYM(GroupStart, "ncclGroupStart");
-    SYM(GroupEnd, "ncclGroupEnd"); SYM(GetErrorString, "ncclGetErrorString");
-#undef SYM
-    g_rccl.handle = h;
-    return CHROMA_OK;
-}
-#define RCCL_TRY(expr)                                                                             \
-    do {                                                                                           \
-        ncclResult_t r_ = (expr);                                                                  \
-        if (r_ != ncclSuccess)                                                                     \
-            return set_error(CHROMA_ERR_INVALID, "%s failed: %s", #expr, g_rccl.GetErrorString(r_)); \
-    } while (0)
-
-__global__ void k_or_gathered(uint32_t *out, const uint32_t *gathered, uint32_t n, int nranks)
-{
-    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    uint32_t acc = 0;
-    for (int r = 0; r < nranks; r++) acc |= gathered[(size_t)r * n + i];
-    out[i] = acc;
-}
-
-int chroma_comm_unique_id(uint8_t id[CHROMA_COMM_ID_BYTES])
-{
-    if (!id) return set_error(CHROMA_ERR_INVALID, "null id");
-    static_assert(CHROMA_COMM_ID_BYTES == NCCL_UNIQUE_ID_BYTES, "id size");
-    int rc = rccl_load(); if (rc) return rc;
-    ncclUniqueId u;
-    RCCL_TRY(g_rccl.GetUniqueId(&u));
-    memcpy(id, u.internal, NCCL_UNIQUE_ID_BYTES);
-    return CHROMA_OK;
-}
-
-int chroma_comm_init(chroma_ctx *ctx, int32_t nranks, int32_t rank, const uint8_t id[CHROMA_COMM_ID_BYTES])
-{
-    if (!ctx || !id || nranks < 1 || rank < 0 || rank >= nranks) return set_error(CHROMA_ERR_INVALID, "bad argument");
-    if (ctx->comm) return set_error(CHROMA_ERR_INVALID, "this context already has a communicator");
-    int rc = rccl_load(); if (rc) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
-    ncclUniqueId u;
-    memcpy(u.internal, id, NCCL_UNIQUE_ID_BYTES);
-    RCCL_TRY(g_rccl.CommInitRank(&ctx->comm, nranks, u, rank));
-    ctx->comm_nranks = nranks;
-    ctx->comm_rank = rank;
-    return CHROMA_OK;
-}
-
-int chroma_comm_destroy(chroma_ctx *ctx)
-{
-    if (!ctx) return set_error(CHROMA_ERR_INVALID, "null ctx");
-    if (ctx->comm) {
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        RCCL_TRY(g_rccl.CommDestroy(ctx->comm));
-        ctx->comm = nullptr;
-        ctx->comm_nranks = 1;
-        ctx->comm_rank = 0;
-    }
-    if (ctx->gather_buf) { hipFree(ctx->gather_buf); ctx->gather_buf = nullptr; ctx->gather_capacity = 0; }
-    return CHROMA_OK;
-}
-
-// hit_count: sum; earliest-time bit patterns: min (non-negative times order like their bits,
-// chroma/cuda/daq.cu:5-20).  In place, on the library's stream; without a communicator the arrays
-// already are the whole job's.
-int chroma_allreduce_hits(chroma_ctx *ctx, uint32_t *d_hit_count, uint32_t *d_earliest_time_bits, uint32_t nchannels)
-{
-    if (!ctx || !d_hit_count) return set_error(CHROMA_ERR_INVALID, "bad argument");
-    if (!ctx->comm || nchannels == 0) return CHROMA_OK;
-    // (the first error is kept and the group is ALWAYS closed: an early return between GroupStart and GroupEnd would
-    //  leave the group open for every later RCCL call of the process -- torch's included, the library is shared)
-    RCCL_TRY(g_rccl.GroupStart());
-    ncclResult_t first = g_rccl.AllReduce(d_hit_count, d_hit_count, nchannels, ncclUint32, ncclSum, ctx->comm, ctx->stream);
-    if (first == ncclSuccess && d_earliest_time_bits)
-        first = g_rccl.AllReduce(d_earliest_time_bits, d_earliest_time_bits, nchannels, ncclUint32, ncclMin, ctx->comm, ctx->stream);
-    const ncclResult_t end = g_rccl.GroupEnd();
-    if (first == ncclSuccess) first = end;
-    if (first != ncclSuccess) return set_error(CHROMA_ERR_INVALID, "chroma_allreduce_hits: %s", g_rccl.GetErrorString(first));
-    return CHROMA_OK;
-}
-
-// The three integer arrays a DAQ acquisition accumulates (chroma/cuda/daq.cu:73-75) over sharded photons:
-// earliest time bits (min), integer charge (sum), channel histories (bitwise OR -- not an RCCL reduction:
-// all-gather, then OR locally).
-int chroma_allreduce_daq(chroma_ctx *ctx, uint32_t *d_earliest_time_int, uint32_t *d_channel_q_int,
-                         uint32_t *d_channel_histories, uint32_t nchannels)
-{
-    if (!ctx || !d_earliest_time_int || !d_channel_q_int || !d_channel_histories) return set_error(CHROMA_ERR_INVALID, "bad argument");
-    if (!ctx->comm || nchannels == 0) return CHROMA_OK;
-    const size_t need = (size_t)ctx->comm_nranks * nchannels;
-    if (ctx->gather_capacity < need) {
-        HIP_TRY(hipSetDevice(ctx->device));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (ctx->gather_buf) hipFree(ctx->gather_buf);
-        ctx->gather_buf = nullptr; ctx->gather_capacity = 0;
-        HIP_TRY(hipMalloc((void **)&ctx->gather_buf, need * sizeof(uint32_t)));
-        ctx->gather_capacity = need;
-    }
-    RCCL_TRY(g_rccl.GroupStart());
-    ncclResult_t first = g_rccl.AllReduce(d_earliest_time_int, d_earliest_time_int, nchannels, ncclUint32, ncclMin, ctx->comm, ctx->stream);
-    if (first == ncclSuccess)
-        first = g_rccl.AllReduce(d_channel_q_int, d_channel_q_int, nchannels, ncclUint32, ncclSum, ctx->comm, ctx->stream);
-    if (first == ncclSuccess)
-        first = g_rccl.AllGather(d_channel_histories, ctx->gather_buf, nchannels, ncclUint32, ctx->comm, ctx->stream);
-    const ncclResult_t end = g_rccl.GroupEnd();          // (always: see chroma_allreduce_hits)
-    if (first == ncclSuccess) first = end;
-    if (first != ncclSuccess) return set_error(CHROMA_ERR_INVALID, "chroma_allreduce_daq: %s", g_rccl.GetErrorString(first));
-    hipLaunchKernelGGL(k_or_gathered, dim3((nchannels + 255) / 256), dim3(256), 0, ctx->stream, d_channel_histories,
-                       ctx->gather_buf, nchannels, ctx->comm_nranks);
-    HIP_TRY(hipGetLastError());
-    return CHROMA_OK;
-}
 
 }  // extern "C"

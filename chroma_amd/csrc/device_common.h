@@ -121,6 +121,17 @@ struct DeviceCounters {   // accumulated with one atomic per wave
     unsigned long long packet_rays, packet_nodes, packet_tris;      // k_raycast_packet's share of the two counts above (counting builds)
 };
 
+// the device-side step control block of chroma_propagate (k_step_begin, kernel_step_control.h)
+struct StepState {
+    uint32_t n;          // photons queued for this step
+    uint32_t renorm;     // this step opens a launch in the reference's sense: re-normalise dir/pol on load
+    uint32_t in_tail;    // the reference's last launch (all remaining steps) has begun
+    uint32_t launches;   // launches in the reference's sense so far
+    uint32_t work;       // next unclaimed ray of the persistent ray cast
+    uint32_t retry;      // rays left for k_raycast_retry
+    uint32_t pad[2];
+};
+
 // ---- hits ---------------------------------------------------------------------------------------------------------
 // the channel a photon was detected on, or -1 (propagate.cu:157-171: the flag, a last hit triangle, a solid with a channel)
 __device__ inline int hit_channel(const GeoView &g, uint32_t history, int triangle_id, uint32_t detection_state)
@@ -137,6 +148,23 @@ struct HitsOut {
     uint32_t *hit_count, *earliest;
     uint32_t detection_state; int want;
 };
+
+__device__ inline void copy_photon(const PhotonView &src, size_t i, const PhotonView &dst, size_t o)
+{
+    store3(dst.pos, o, load3(src.pos, i));
+    store3(dst.dir, o, load3(src.dir, i));
+    store3(dst.pol, o, load3(src.pol, i));
+    dst.wavelengths[o] = src.wavelengths[i];
+    dst.t[o] = src.t[i];
+    dst.flags[o] = src.flags[i];
+    dst.last_hit_triangles[o] = src.last_hit_triangles[i];
+    dst.weights[o] = src.weights[i];
+    dst.evidx[o] = src.evidx[i];
+    if (dst.rng_counters && src.rng_counters) dst.rng_counters[o] = src.rng_counters[i];
+}
+
+// photons a thread of k_copy_hits / k_finalize_hits looks at (blocks of 256 threads)
+#define COPY_ITEMS 16
 
 // ---- wave-level helpers --------------------------------------------------------------------
 __device__ inline unsigned lane_id() { return __lane_id(); }

@@ -1,6 +1,5 @@
-// kernels_daq_render.h -- DAQ (chroma/cuda/daq.cu), distance_to_mesh, render (chroma/cuda/render.cu), point transforms, the bomb generator, the probe kernel.
-// One of the kernel families of libchroma_hip.so; included by chroma_hip.hip (one translation unit: the families share
-// device helpers and launch-time constants, and are included in dependency order).
+// kernels_daq_render.h -- DAQ (chroma/cuda/daq.cu), render (chroma/cuda/render.cu), point transforms, the bomb generator, the probe kernel.
+// One of the kernel families of libchroma_hip.so; included by kernel_calls.hip alone, so that each kernel is compiled once.
 #pragma once
 
 // ---- DAQ (chroma/cuda/daq.cu) ------------------------------------------------------------------
@@ -100,37 +99,6 @@ __global__ void k_daq_convert(uint32_t n, float charge_unit, const uint32_t *tim
         t_out[id] = __uint_as_float(time_ints[id]);
         q_out[id] = (float)q_ints[id] * charge_unit;
     }
-}
-
-// distance_to_mesh (chroma/cuda/mesh.h:124-151)
-template <int LDS_N, bool COUNT>
-__global__ __launch_bounds__(PROP_BLOCK) void
-k_distance_to_mesh(GeoView g, int nthreads, const float *origin, const float *direction, const int32_t *last_hit_in,
-                   float *distance_out, int32_t *triangle_out, DeviceCounters *counters)
-{
-    __shared__ uint32_t s_lds[TRAV_LDS_WORDS(LDS_N, PROP_BLOCK)];
-    int id = blockIdx.x * PROP_BLOCK + threadIdx.x;
-    LaneCounters cnt = {0, 0, 0, 0};
-    bool on = id < nthreads;
-    v3 o = mk3(0.f, 0.f, 0.f), d = mk3(0.f, 0.f, 1.f);
-    if (on) {
-        o = load3(origin, id);
-        d = load3(direction, id);
-        d = d / norm(d);
-    }
-    float dist;
-    const int last_hit = (on && last_hit_in) ? last_hit_in[id] : -1;
-    int tri = intersect_mesh<LDS_N, PROP_BLOCK, COUNT>(g, o, d, dist, last_hit, s_lds + threadIdx.x, cnt, on);
-    if (on) {
-        if (tri != -1) distance_out[id] = dist;
-        if (triangle_out) triangle_out[id] = tri;
-    }
-    unsigned long long ov = wave_sum_u64(cnt.overflows);
-    if (COUNT) {
-        unsigned long long nd = wave_sum_u64(cnt.nodes), tr = wave_sum_u64(cnt.tris);
-        if (lane_id() == 0) { atomicAdd(&counters->nodes_visited, nd); atomicAdd(&counters->triangles_tested, tr); }
-    }
-    if (lane_id() == 0 && ov) atomicAdd(&counters->stack_overflows, ov);
 }
 
 // ---- render (chroma/cuda/render.cu:37-181) ---------------------------------------------------------------

@@ -296,6 +296,13 @@ __device__ inline bool node_passes(float tmin, float min_distance)
 // live in LDS ([entry][lane]: one bank per lane), deeper ones -- rare: the observed depth is
 // ~20 -- in a per-lane scratch array, so LDS use stays at LDS_N*256 B per wave.
 #define STACK_SCRATCH 104
+#define PROP_BLOCK 64
+#ifndef STACK_LDS
+#define STACK_LDS 24      // traversal stack entries kept in LDS (6 KB per wave); deeper ones spill to scratch
+#endif
+#ifndef RAY_WAVES
+#define RAY_WAVES 1        // __launch_bounds__ waves/SIMD hint for the ray-cast kernel
+#endif
 #ifndef TRAV_PENDING
 #define TRAV_PENDING 8      // postponed leaf (triangle) tests per lane, kept in LDS
 #endif

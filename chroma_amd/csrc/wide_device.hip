@@ -38,21 +38,12 @@
 #include <vector>
 
 #include "../../include/chroma_hip.h"
-#include "ctx_access.h"
+#include "chroma_internal.h"
 #include "wide_build.h"
 
 using chroma_host::WideTree;
 
 namespace {
-
-#define DEV_TRY(expr)                                                                                     \
-    do {                                                                                                  \
-        hipError_t e_ = (expr);                                                                           \
-        if (e_ != hipSuccess) {                                                                           \
-            chroma_internal_set_error((int)e_, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-            return (int)e_;                                                                               \
-        }                                                                                                 \
-    } while (0)
 
 struct Arena {          // every device buffer of one build; freed together whatever happens
     chroma_ctx *ctx = nullptr;       // (blocks come from and go back to the context's pool -- chroma_malloc / chroma_free: a repeated call
@@ -769,21 +760,21 @@ extern "C" {
 int chroma_wide_build_device(chroma_ctx *ctx, const uint32_t *nodes, uint64_t nnodes, uint32_t ntriangles, void **handle,
                              uint64_t *nwide, uint64_t *nrecords, uint32_t *depth)
 {
-    if (!ctx || !nodes || !handle || nnodes == 0) return chroma_internal_set_error(CHROMA_ERR_INVALID, "chroma_wide_build_device: bad argument");
-    hipStream_t stream = chroma_internal_stream(ctx);
-    DEV_TRY(hipSetDevice(chroma_internal_device(ctx)));
+    if (!ctx || !nodes || !handle || nnodes == 0) return set_error(CHROMA_ERR_INVALID, "chroma_wide_build_device: bad argument");
+    hipStream_t stream = ctx->stream;
+    HIP_TRY(hipSetDevice(ctx->device));
     Lap lap(stream);
     WideTree *t = new WideTree;
     struct Guard { WideTree *t; ~Guard() { delete t; } } guard{t};
-    if (nnodes >= 0xFFFFFFFFull) return chroma_internal_set_error(CHROMA_ERR_INVALID, "chroma_wide_build_device: too many nodes");
+    if (nnodes >= 0xFFFFFFFFull) return set_error(CHROMA_ERR_INVALID, "chroma_wide_build_device: too many nodes");
     Arena arena;
     arena.ctx = ctx;
     uint4 *d_nodes; uint32_t *d_leaf_node, *d_flag, *d_rank, *d_counters;
-    DEV_TRY(arena.get(&d_nodes, (size_t)nnodes));
-    DEV_TRY(arena.get(&d_leaf_node, ntriangles));
-    DEV_TRY(arena.get(&d_flag, ntriangles)); DEV_TRY(arena.get(&d_rank, ntriangles));
-    DEV_TRY(arena.get(&d_counters, 8));
-    { const int rc_ = chroma_internal_htod(ctx, d_nodes, nodes, (size_t)nnodes * 16u); if (rc_ != CHROMA_OK) return rc_; }
+    HIP_TRY(arena.get(&d_nodes, (size_t)nnodes));
+    HIP_TRY(arena.get(&d_leaf_node, ntriangles));
+    HIP_TRY(arena.get(&d_flag, ntriangles)); HIP_TRY(arena.get(&d_rank, ntriangles));
+    HIP_TRY(arena.get(&d_counters, 8));
+    { const int rc_ = chroma_memcpy_htod(ctx, d_nodes, nodes, (size_t)nnodes * 16u); if (rc_ != CHROMA_OK) return rc_; }
     lap.lap("nodes upload");
 
     // ---- the reference's test order: leaves under every node, then ranks (passes until nothing changes)
@@ -791,47 +782,47 @@ int chroma_wide_build_device(chroma_ctx *ctx, const uint32_t *nodes, uint64_t nn
     {
         const uint32_t nn = (uint32_t)nnodes;
         uint32_t *d_leaves, *d_base; unsigned long long *d_rank_leaf;
-        DEV_TRY(arena.get(&d_leaves, nn)); DEV_TRY(arena.get(&d_base, nn)); DEV_TRY(arena.get(&d_rank_leaf, ntriangles));
-        DEV_TRY(hipMemsetAsync(d_leaves, 0, (size_t)nn * 4u, stream));
-        DEV_TRY(hipMemsetAsync(d_base, 0xFF, (size_t)nn * 4u, stream));
-        DEV_TRY(hipMemsetAsync(d_base, 0, 4, stream));
-        DEV_TRY(hipMemsetAsync(d_rank_leaf, 0xFF, (size_t)ntriangles * 8u, stream));
+        HIP_TRY(arena.get(&d_leaves, nn)); HIP_TRY(arena.get(&d_base, nn)); HIP_TRY(arena.get(&d_rank_leaf, ntriangles));
+        HIP_TRY(hipMemsetAsync(d_leaves, 0, (size_t)nn * 4u, stream));
+        HIP_TRY(hipMemsetAsync(d_base, 0xFF, (size_t)nn * 4u, stream));
+        HIP_TRY(hipMemsetAsync(d_base, 0, 4, stream));
+        HIP_TRY(hipMemsetAsync(d_rank_leaf, 0xFF, (size_t)ntriangles * 8u, stream));
         for (int phase = 0; phase < 2; phase++) {
             uint32_t h[2] = {1u, 0u};
             for (int it = 0; h[0] && !h[1]; it++) {
-                if (it > 4096) return chroma_internal_set_error(CHROMA_ERR_INVALID, "chroma_wide_build_device: the reference tree does not settle");
-                DEV_TRY(hipMemsetAsync(d_counters, 0, 2 * sizeof(uint32_t), stream));
+                if (it > 4096) return set_error(CHROMA_ERR_INVALID, "chroma_wide_build_device: the reference tree does not settle");
+                HIP_TRY(hipMemsetAsync(d_counters, 0, 2 * sizeof(uint32_t), stream));
                 for (int k = 0; k < 4; k++) {                    // (four passes per question)
                     if (phase == 0) hipLaunchKernelGGL(k_ref_count_leaves, dim3(blocks_for(nn)), dim3(256), 0, stream, d_nodes, nn, d_leaves, d_counters);
                     else hipLaunchKernelGGL(k_ref_assign, dim3(blocks_for(nn)), dim3(256), 0, stream, d_nodes, nn, d_leaves, d_base, ntriangles, d_rank_leaf, d_counters);
                 }
-                DEV_TRY(hipMemcpyAsync(h, d_counters, sizeof h, hipMemcpyDeviceToHost, stream));
-                DEV_TRY(hipStreamSynchronize(stream));
+                HIP_TRY(hipMemcpyAsync(h, d_counters, sizeof h, hipMemcpyDeviceToHost, stream));
+                HIP_TRY(hipStreamSynchronize(stream));
             }
-            if (h[1]) return chroma_internal_set_error(CHROMA_ERR_INVALID, phase == 0 ? "chroma_wide_build_device: wide tree: bad child range"
+            if (h[1]) return set_error(CHROMA_ERR_INVALID, phase == 0 ? "chroma_wide_build_device: wide tree: bad child range"
                                                                                         : "chroma_wide_build_device: wide tree: leaf references a triangle outside the mesh");
         }
         if (ntriangles) hipLaunchKernelGGL(k_ref_unpack, dim3(blocks_for(ntriangles)), dim3(256), 0, stream, d_rank_leaf, ntriangles, d_rank, d_leaf_node);
-        DEV_TRY(hipGetLastError());
-        DEV_TRY(hipStreamSynchronize(stream));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(stream));
         t->rank.resize(ntriangles);
-        { const int rc_ = chroma_internal_dtoh(ctx, t->rank.data(), d_rank, (size_t)ntriangles * 4u); if (rc_ != CHROMA_OK) return rc_; }
+        { const int rc_ = chroma_memcpy_dtoh(ctx, t->rank.data(), d_rank, (size_t)ntriangles * 4u); if (rc_ != CHROMA_OK) return rc_; }
         arena.release(d_leaves); arena.release(d_base); arena.release(d_rank_leaf);
         lap.lap("reference test order");
     }
     size_t tmp_bytes = 0;
-    { uint32_t *nul = nullptr; DEV_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, nul, nul, (int)std::max<uint32_t>(ntriangles, 1u), stream)); }
+    { uint32_t *nul = nullptr; HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, nul, nul, (int)std::max<uint32_t>(ntriangles, 1u), stream)); }
     uint8_t *d_tmp;
-    DEV_TRY(arena.get(&d_tmp, tmp_bytes));
+    HIP_TRY(arena.get(&d_tmp, tmp_bytes));
     uint32_t np = 0;
     if (ntriangles) {
         hipLaunchKernelGGL(k_prim_flags, dim3(blocks_for(ntriangles)), dim3(256), 0, stream, d_leaf_node, ntriangles, d_flag);
-        { size_t b = tmp_bytes; DEV_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp, b, d_flag, d_rank, (int)ntriangles, stream)); }
+        { size_t b = tmp_bytes; HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp, b, d_flag, d_rank, (int)ntriangles, stream)); }
         hipLaunchKernelGGL(k_last_sum, dim3(1), dim3(64), 0, stream, d_rank, d_flag, ntriangles, d_counters);
-        DEV_TRY(hipMemcpyAsync(&np, d_counters, 4, hipMemcpyDeviceToHost, stream));
-        DEV_TRY(hipStreamSynchronize(stream));
+        HIP_TRY(hipMemcpyAsync(&np, d_counters, 4, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
     }
-    if (np > 0x3FFFFFFFu) return chroma_internal_set_error(CHROMA_ERR_INVALID, "chroma_wide_build_device: too many triangles");
+    if (np > 0x3FFFFFFFu) return set_error(CHROMA_ERR_INVALID, "chroma_wide_build_device: too many triangles");
     if (np < 2) {
         // nothing to split: an empty node, or one leaf entry
         t->wnodes.assign(32, 0);
@@ -839,7 +830,7 @@ int chroma_wide_build_device(chroma_ctx *ctx, const uint32_t *nodes, uint64_t nn
         if (np == 1) {
             if (leaf_node.empty()) {
                 leaf_node.resize(ntriangles);
-                DEV_TRY(hipMemcpy(leaf_node.data(), d_leaf_node, (size_t)ntriangles * 4u, hipMemcpyDeviceToHost));
+                HIP_TRY(hipMemcpy(leaf_node.data(), d_leaf_node, (size_t)ntriangles * 4u, hipMemcpyDeviceToHost));
             }
             uint32_t tri = 0;
             while (leaf_node[tri] == 0xFFFFFFFFu) tri++;          // the one triangle under a reachable leaf
@@ -858,10 +849,10 @@ int chroma_wide_build_device(chroma_ctx *ctx, const uint32_t *nodes, uint64_t nn
     }
     { std::vector<uint32_t>().swap(leaf_node); }
     uint4 *d_prims_a, *d_prims_b;
-    DEV_TRY(arena.get(&d_prims_a, np)); DEV_TRY(arena.get(&d_prims_b, np));
+    HIP_TRY(arena.get(&d_prims_a, np)); HIP_TRY(arena.get(&d_prims_b, np));
     hipLaunchKernelGGL(k_make_prims, dim3(blocks_for(ntriangles)), dim3(256), 0, stream, d_nodes, d_leaf_node, d_rank, ntriangles, d_prims_a, wide_tight_leaves());
-    DEV_TRY(hipGetLastError());
-    DEV_TRY(hipStreamSynchronize(stream));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(stream));
     arena.release(d_nodes); arena.release(d_leaf_node); arena.release(d_flag); arena.release(d_rank); arena.release(d_tmp);
     lap.lap("upload + triangles");
 
@@ -869,36 +860,36 @@ int chroma_wide_build_device(chroma_ctx *ctx, const uint32_t *nodes, uint64_t nn
     const size_t nb = 2 * (size_t)np - 1;
     uint4 *d_bin, *d_segs_a, *d_segs_b, *d_lsplit;
     uint32_t *d_dev_to_tri, *d_list[4], *d_nch, *d_ch0, *d_chunk_l, *d_chunk_nl, *d_chunk_off, *d_lcb, *d_lbins;
-    DEV_TRY(arena.get(&d_bin, nb));
-    DEV_TRY(arena.get(&d_segs_a, np)); DEV_TRY(arena.get(&d_segs_b, np));
-    DEV_TRY(arena.get(&d_flag, np)); DEV_TRY(arena.get(&d_rank, np));
-    DEV_TRY(arena.get(&d_dev_to_tri, np));
-    for (int c = 0; c < 4; c++) DEV_TRY(arena.get(&d_list[c], c == 3 ? (size_t)np / 2 + 1 : c == 0 ? (size_t)np / (TINY_MAX + 1) + 1 : c == 1 ? (size_t)np / (SWEEP_MAX + 1) + 1 : (size_t)np / (WAVE_MAX + 1) + 1));
+    HIP_TRY(arena.get(&d_bin, nb));
+    HIP_TRY(arena.get(&d_segs_a, np)); HIP_TRY(arena.get(&d_segs_b, np));
+    HIP_TRY(arena.get(&d_flag, np)); HIP_TRY(arena.get(&d_rank, np));
+    HIP_TRY(arena.get(&d_dev_to_tri, np));
+    for (int c = 0; c < 4; c++) HIP_TRY(arena.get(&d_list[c], c == 3 ? (size_t)np / 2 + 1 : c == 0 ? (size_t)np / (TINY_MAX + 1) + 1 : c == 1 ? (size_t)np / (SWEEP_MAX + 1) + 1 : (size_t)np / (WAVE_MAX + 1) + 1));
     const size_t max_large = (size_t)np / (WAVE_MAX + 1) + 1, max_chunks = (size_t)np / CHUNK + max_large + 1;
-    DEV_TRY(arena.get(&d_nch, max_large)); DEV_TRY(arena.get(&d_ch0, max_large));
-    DEV_TRY(arena.get(&d_lcb, max_large * 6)); DEV_TRY(arena.get(&d_lbins, max_large * BINS_WORDS)); DEV_TRY(arena.get(&d_lsplit, max_large));
-    DEV_TRY(arena.get(&d_chunk_l, max_chunks)); DEV_TRY(arena.get(&d_chunk_nl, max_chunks)); DEV_TRY(arena.get(&d_chunk_off, max_chunks));
-    { uint32_t *nul = nullptr; DEV_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, nul, nul, (int)np, stream)); }
-    DEV_TRY(arena.get(&d_tmp, tmp_bytes));
+    HIP_TRY(arena.get(&d_nch, max_large)); HIP_TRY(arena.get(&d_ch0, max_large));
+    HIP_TRY(arena.get(&d_lcb, max_large * 6)); HIP_TRY(arena.get(&d_lbins, max_large * BINS_WORDS)); HIP_TRY(arena.get(&d_lsplit, max_large));
+    HIP_TRY(arena.get(&d_chunk_l, max_chunks)); HIP_TRY(arena.get(&d_chunk_nl, max_chunks)); HIP_TRY(arena.get(&d_chunk_off, max_chunks));
+    { uint32_t *nul = nullptr; HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, nul, nul, (int)np, stream)); }
+    HIP_TRY(arena.get(&d_tmp, tmp_bytes));
     {
         const uint4 root = make_uint4(0u, np, 0u, 0u);
-        DEV_TRY(hipMemcpyAsync(d_segs_a, &root, sizeof root, hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(d_segs_a, &root, sizeof root, hipMemcpyHostToDevice, stream));
     }
     std::vector<uint32_t> level_base, level_count;
     uint32_t nseg = 1, base = 0;
     for (;;) {
-        if (level_base.size() > 4096) return chroma_internal_set_error(CHROMA_ERR_INTERNAL, "chroma_wide_build_device: the binary tree does not end");
-        DEV_TRY(hipMemsetAsync(d_counters, 0, 8 * sizeof(uint32_t), stream));
+        if (level_base.size() > 4096) return set_error(CHROMA_ERR_INTERNAL, "chroma_wide_build_device: the binary tree does not end");
+        HIP_TRY(hipMemsetAsync(d_counters, 0, 8 * sizeof(uint32_t), stream));
         hipLaunchKernelGGL(k_classify, dim3(blocks_for(nseg)), dim3(256), 0, stream, d_segs_a, nseg, d_prims_a, d_bin, d_dev_to_tri, d_flag,
                            d_list[0], d_list[1], d_list[2], d_list[3], d_counters);
-        { size_t b = tmp_bytes; DEV_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp, b, d_flag, d_rank, (int)nseg, stream)); }
+        { size_t b = tmp_bytes; HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp, b, d_flag, d_rank, (int)nseg, stream)); }
         hipLaunchKernelGGL(k_last_sum, dim3(1), dim3(64), 0, stream, d_rank, d_flag, nseg, d_counters + 3);
         uint32_t h[6];                  // [0] small, [1] wave, [2] large, [3] sets to split, [4] chunks (below), [5] tiny
-        DEV_TRY(hipMemcpyAsync(h, d_counters, sizeof h, hipMemcpyDeviceToHost, stream));
-        DEV_TRY(hipStreamSynchronize(stream));
+        HIP_TRY(hipMemcpyAsync(h, d_counters, sizeof h, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
         level_base.push_back(base); level_count.push_back(nseg);
         const uint32_t nsmall = h[0], nwave = h[1], nlarge = h[2], nonleaf = h[3], ntiny = h[5];
-        if (ntiny + nsmall + nwave + nlarge != nonleaf) return chroma_internal_set_error(CHROMA_ERR_INTERNAL, "chroma_wide_build_device: level %zu: lists of %u + %u + %u + %u sets, %u to split", level_base.size() - 1, ntiny, nsmall, nwave, nlarge, nonleaf);
+        if (ntiny + nsmall + nwave + nlarge != nonleaf) return set_error(CHROMA_ERR_INTERNAL, "chroma_wide_build_device: level %zu: lists of %u + %u + %u + %u sets, %u to split", level_base.size() - 1, ntiny, nsmall, nwave, nlarge, nonleaf);
         if (nonleaf == 0) break;
         const uint32_t next_base = base + nseg;
         if (ntiny) hipLaunchKernelGGL(k_split_tiny, dim3(blocks_for(ntiny)), dim3(256), 0, stream, d_list[3], ntiny, d_segs_a, d_rank, d_prims_a, d_prims_b, d_bin, d_segs_b, next_base);
@@ -906,30 +897,30 @@ int chroma_wide_build_device(chroma_ctx *ctx, const uint32_t *nodes, uint64_t nn
         if (nwave) hipLaunchKernelGGL(k_split_wave, dim3(blocks_for(nwave, 4)), dim3(256), 0, stream, d_list[1], nwave, d_segs_a, d_rank, d_prims_a, d_prims_b, d_bin, d_segs_b, next_base);
         if (nlarge) {
             hipLaunchKernelGGL(k_large_nchunks, dim3(blocks_for(nlarge)), dim3(256), 0, stream, d_list[2], nlarge, d_segs_a, d_nch);
-            { size_t b = tmp_bytes; DEV_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp, b, d_nch, d_ch0, (int)nlarge, stream)); }
+            { size_t b = tmp_bytes; HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp, b, d_nch, d_ch0, (int)nlarge, stream)); }
             hipLaunchKernelGGL(k_last_sum, dim3(1), dim3(64), 0, stream, d_ch0, d_nch, nlarge, d_counters + 4);
             uint32_t nchunks = 0;
-            DEV_TRY(hipMemcpyAsync(&nchunks, d_counters + 4, 4, hipMemcpyDeviceToHost, stream));
-            DEV_TRY(hipStreamSynchronize(stream));
-            if (nchunks == 0 || nchunks > max_chunks) return chroma_internal_set_error(CHROMA_ERR_INTERNAL, "chroma_wide_build_device: %u chunks", nchunks);
+            HIP_TRY(hipMemcpyAsync(&nchunks, d_counters + 4, 4, hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipStreamSynchronize(stream));
+            if (nchunks == 0 || nchunks > max_chunks) return set_error(CHROMA_ERR_INTERNAL, "chroma_wide_build_device: %u chunks", nchunks);
             hipLaunchKernelGGL(k_large_init, dim3(blocks_for((size_t)nlarge * BINS_WORDS)), dim3(256), 0, stream, d_lcb, d_lbins, nlarge);
             hipLaunchKernelGGL(k_large_chunkmap, dim3(blocks_for(nchunks)), dim3(256), 0, stream, d_ch0, nlarge, nchunks, d_chunk_l);
             hipLaunchKernelGGL(k_large_bounds, dim3(nchunks), dim3(256), 0, stream, d_chunk_l, d_ch0, d_list[2], d_segs_a, d_prims_a, d_lcb);
             hipLaunchKernelGGL(k_large_bins, dim3(nchunks), dim3(256), 0, stream, d_chunk_l, d_ch0, d_list[2], d_segs_a, d_prims_a, d_lcb, d_lbins);
             hipLaunchKernelGGL(k_large_decide, dim3(blocks_for(nlarge, 4)), dim3(256), 0, stream, d_list[2], nlarge, d_segs_a, d_rank, d_lcb, d_lbins, d_lsplit, d_bin, d_segs_b, next_base);
             hipLaunchKernelGGL(k_large_count, dim3(nchunks), dim3(256), 0, stream, d_chunk_l, d_ch0, d_list[2], d_segs_a, d_prims_a, d_lcb, d_lsplit, d_chunk_nl);
-            { size_t b = tmp_bytes; DEV_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp, b, d_chunk_nl, d_chunk_off, (int)nchunks, stream)); }
+            { size_t b = tmp_bytes; HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp, b, d_chunk_nl, d_chunk_off, (int)nchunks, stream)); }
             hipLaunchKernelGGL(k_large_scatter, dim3(nchunks), dim3(256), 0, stream, d_chunk_l, d_ch0, d_list[2], d_segs_a, d_prims_a, d_prims_b, d_lcb, d_lsplit, d_chunk_off);
         }
-        DEV_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         std::swap(d_prims_a, d_prims_b);
         std::swap(d_segs_a, d_segs_b);
         base = next_base;
         nseg = 2u * nonleaf;
     }
-    if ((size_t)base + nseg != nb) return chroma_internal_set_error(CHROMA_ERR_INTERNAL, "chroma_wide_build_device: %zu binary nodes made, %zu expected", (size_t)base + nseg, nb);
+    if ((size_t)base + nseg != nb) return set_error(CHROMA_ERR_INTERNAL, "chroma_wide_build_device: %zu binary nodes made, %zu expected", (size_t)base + nseg, nb);
     t->dev_to_tri.resize(np);
-    { const int rc_ = chroma_internal_dtoh(ctx, t->dev_to_tri.data(), d_dev_to_tri, (size_t)np * 4u); if (rc_ != CHROMA_OK) return rc_; }
+    { const int rc_ = chroma_memcpy_dtoh(ctx, t->dev_to_tri.data(), d_dev_to_tri, (size_t)np * 4u); if (rc_ != CHROMA_OK) return rc_; }
     arena.release(d_prims_a); arena.release(d_prims_b); arena.release(d_segs_a); arena.release(d_segs_b); arena.release(d_flag); arena.release(d_rank);
     arena.release(d_dev_to_tri);
     for (int c = 0; c < 4; c++) arena.release(d_list[c]);
@@ -940,12 +931,12 @@ int chroma_wide_build_device(chroma_ctx *ctx, const uint32_t *nodes, uint64_t nn
 
     // ---- boxes and the least-area table, bottom-up
     float *d_cost; uint32_t *d_share;
-    DEV_TRY(arena.get(&d_cost, nb * 8)); DEV_TRY(arena.get(&d_share, nb));
-    DEV_TRY(hipMemsetAsync(d_cost, 0, nb * 8 * sizeof(float), stream));
+    HIP_TRY(arena.get(&d_cost, nb * 8)); HIP_TRY(arena.get(&d_share, nb));
+    HIP_TRY(hipMemsetAsync(d_cost, 0, nb * 8 * sizeof(float), stream));
     for (size_t l = level_base.size(); l-- > 0;)
         hipLaunchKernelGGL(k_dp, dim3(blocks_for(level_count[l])), dim3(256), 0, stream, d_bin, d_cost, d_share, level_base[l], level_count[l]);
-    DEV_TRY(hipGetLastError());
-    DEV_TRY(hipStreamSynchronize(stream));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(stream));
     arena.release(d_cost);
     lap.lap("boxes + least-area table");
 
@@ -953,33 +944,33 @@ int chroma_wide_build_device(chroma_ctx *ctx, const uint32_t *nodes, uint64_t nn
     uint32_t *d_level, *d_next, *d_items, *d_info, *d_ninner, *d_first;
     uint32_t cnt = 1;
     size_t cap = 1;                       // capacity of the per-level arrays
-    DEV_TRY(arena.get(&d_level, 1));
-    { const uint32_t root = 0; DEV_TRY(hipMemcpyAsync(d_level, &root, 4, hipMemcpyHostToDevice, stream)); }
+    HIP_TRY(arena.get(&d_level, 1));
+    { const uint32_t root = 0; HIP_TRY(hipMemcpyAsync(d_level, &root, 4, hipMemcpyHostToDevice, stream)); }
     size_t wbase = 0;
     uint32_t wdepth = 0;
     t->wnodes.reserve(((size_t)np / 3 + 1024) * 32);          // (address space only: a node per ~5.6 triangles at C3)
     d_items = d_info = d_ninner = d_first = nullptr;
     while (cnt) {
-        if (wbase + cnt > 0x7FFFFFFFull) return chroma_internal_set_error(CHROMA_ERR_INVALID, "chroma_wide_build_device: more than 2^31 wide nodes");
+        if (wbase + cnt > 0x7FFFFFFFull) return set_error(CHROMA_ERR_INVALID, "chroma_wide_build_device: more than 2^31 wide nodes");
         if (!d_items || cnt > cap) {
             arena.release(d_items); arena.release(d_info); arena.release(d_ninner); arena.release(d_first);
             cap = cnt;
-            DEV_TRY(arena.get(&d_items, cap * 8)); DEV_TRY(arena.get(&d_info, cap)); DEV_TRY(arena.get(&d_ninner, cap)); DEV_TRY(arena.get(&d_first, cap));
+            HIP_TRY(arena.get(&d_items, cap * 8)); HIP_TRY(arena.get(&d_info, cap)); HIP_TRY(arena.get(&d_ninner, cap)); HIP_TRY(arena.get(&d_first, cap));
         }
         hipLaunchKernelGGL(k_emit_count, dim3(blocks_for(cnt)), dim3(256), 0, stream, d_bin, d_share, d_level, cnt, d_items, d_info, d_ninner);
-        { size_t b = tmp_bytes; DEV_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp, b, d_ninner, d_first, (int)cnt, stream)); }
+        { size_t b = tmp_bytes; HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp, b, d_ninner, d_first, (int)cnt, stream)); }
         hipLaunchKernelGGL(k_last_sum, dim3(1), dim3(64), 0, stream, d_first, d_ninner, cnt, d_counters);
         uint32_t nnext = 0;
-        DEV_TRY(hipMemcpyAsync(&nnext, d_counters, 4, hipMemcpyDeviceToHost, stream));
-        DEV_TRY(hipStreamSynchronize(stream));
+        HIP_TRY(hipMemcpyAsync(&nnext, d_counters, 4, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
         uint4 *d_w;
-        DEV_TRY(arena.get(&d_w, (size_t)cnt * 8));
-        DEV_TRY(arena.get(&d_next, nnext));
+        HIP_TRY(arena.get(&d_w, (size_t)cnt * 8));
+        HIP_TRY(arena.get(&d_next, nnext));
         hipLaunchKernelGGL(k_emit_write, dim3(blocks_for((size_t)cnt * 8)), dim3(256), 0, stream, d_bin, d_items, d_info, d_first, cnt,
                            (uint32_t)(wbase + cnt), d_w, d_next);
-        DEV_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         t->wnodes.resize((wbase + cnt) * 32);
-        { const int rc_ = chroma_internal_dtoh(ctx, t->wnodes.data() + wbase * 32, d_w, (size_t)cnt * 128u); if (rc_ != CHROMA_OK) return rc_; }
+        { const int rc_ = chroma_memcpy_dtoh(ctx, t->wnodes.data() + wbase * 32, d_w, (size_t)cnt * 128u); if (rc_ != CHROMA_OK) return rc_; }
         arena.release(d_w); arena.release(d_level);
         d_level = d_next;
         wbase += cnt;

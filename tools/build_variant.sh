@@ -7,6 +7,7 @@ name=$1; shift
 mkdir -p $here/build_variants
 cd $here/chroma_amd/csrc
 make -s all >/dev/null
+# the flags reach the propagate unit, as those of `make variants` do; every other object is the in-tree build's
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -ffp-contract=off -fno-fast-math \
   -fhip-fp32-correctly-rounded-divide-sqrt -fno-gpu-flush-denormals-to-zero -Wno-unused-value -Wno-unused-result \
   "$@" -c chroma_hip.hip -o $here/build_variants/chroma_hip_$name.o
