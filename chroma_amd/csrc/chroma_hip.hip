@@ -345,7 +345,9 @@ static int launch_tail(chroma_ctx *ctx, const CallPlan &plan, chroma_geometry *g
 {
     // (`beside`: a call that ends in k_finalize_hits -- that pass runs on the context's auxiliary stream WHILE the tail kernel
     //  finishes the last photons, which are stamped first so that it leaves them to the tail kernel; the two meet again
-    //  before the call reads its result words)
+    //  before the call reads its result words.  The tail kernel is launched FIRST: its ~1000 waves are resident before the
+    //  24 000 blocks of the streaming pass fill every wave slot.  Launched second, its workgroups waited for slots behind them
+    //  and the tail ended 1.7 ms after the pass instead of with it: DESIGN.md section 3.2)
     *done = false;
     const unsigned waves = cast_waves(ctx, Cast::COOP, n_upper);            // (8 lanes per photon)
     if ((long long)waves * 8 < n_upper) return CHROMA_OK;          // (cannot happen below 8192 photons)
@@ -361,12 +363,7 @@ static int launch_tail(chroma_ctx *ctx, const CallPlan &plan, chroma_geometry *g
         HIP_TRY(hipMemsetAsync(ctx->d_words, 0, 12, ctx->stream));
         if (ctx->final_use)
             hipLaunchKernelGGL(k_mark_tail, dim3(32), dim3(256), 0, ctx->stream, in_q, ctx->final_use, tail_mark);
-        HIP_TRY(hipEventRecord(ctx->ev_fork, ctx->stream));
-        HIP_TRY(hipStreamWaitEvent(ctx->aux_stream, ctx->ev_fork, 0));
-        const unsigned blocks = (unsigned)((nphotons + COPY_ITEMS * 256 - 1) / (COPY_ITEMS * 256));
-        hipLaunchKernelGGL(k_finalize_hits, dim3(blocks), dim3(256), 0, ctx->aux_stream, geom->view, pv, (const float4 *)ctx->final_use, ctx->final_epoch,
-                           nphotons, ho, ctx->d_words, tail_mark);
-        HIP_TRY(hipEventRecord(ctx->ev_join, ctx->aux_stream));
+        HIP_TRY(hipEventRecord(ctx->ev_fork, ctx->stream));          // (the words are cleared and the tail's photons stamped: the pass may start)
     }
     if (ev) HIP_TRY(hipEventRecord(ev[EV_STEP_BEGIN], ctx->stream));
     with_bool(plan.cast == Cast::LITERAL, [&](auto L) {
@@ -376,7 +373,14 @@ static int launch_tail(chroma_ctx *ctx, const CallPlan &plan, chroma_geometry *g
         });
     });
     if (ev) HIP_TRY(hipEventRecord(ev[EV_STEP_END], ctx->stream));
-    if (beside) HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
+    if (beside) {
+        HIP_TRY(hipStreamWaitEvent(ctx->aux_stream, ctx->ev_fork, 0));
+        const unsigned blocks = (unsigned)((nphotons + COPY_ITEMS * 256 - 1) / (COPY_ITEMS * 256));
+        hipLaunchKernelGGL(k_finalize_hits, dim3(blocks), dim3(256), 0, ctx->aux_stream, geom->view, pv, (const float4 *)ctx->final_use, ctx->final_epoch,
+                           nphotons, ho, ctx->d_words, ctx->final_epoch | 0x80000000u);
+        HIP_TRY(hipEventRecord(ctx->ev_join, ctx->aux_stream));
+        HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
+    }
     HIP_TRY(hipGetLastError());
     *done = true;
     return CHROMA_OK;
