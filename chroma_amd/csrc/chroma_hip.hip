@@ -359,10 +359,9 @@ static int launch_tail(chroma_ctx *ctx, const CallPlan &plan, chroma_geometry *g
     if (beside) {
         ho = *beside;
         words = ctx->d_words;
-        const uint32_t tail_mark = ctx->final_epoch | 0x80000000u;
         HIP_TRY(hipMemsetAsync(ctx->d_words, 0, 12, ctx->stream));
         if (ctx->final_use)
-            hipLaunchKernelGGL(k_mark_tail, dim3(32), dim3(256), 0, ctx->stream, in_q, ctx->final_use, tail_mark);
+            hipLaunchKernelGGL(k_mark_tail, dim3(32), dim3(256), 0, ctx->stream, in_q, ctx->final_use, photon_tail_stamp(ctx->final_epoch));
         HIP_TRY(hipEventRecord(ctx->ev_fork, ctx->stream));          // (the words are cleared and the tail's photons stamped: the pass may start)
     }
     if (ev) HIP_TRY(hipEventRecord(ev[EV_STEP_BEGIN], ctx->stream));
@@ -377,7 +376,7 @@ static int launch_tail(chroma_ctx *ctx, const CallPlan &plan, chroma_geometry *g
         HIP_TRY(hipStreamWaitEvent(ctx->aux_stream, ctx->ev_fork, 0));
         const unsigned blocks = (unsigned)((nphotons + COPY_ITEMS * 256 - 1) / (COPY_ITEMS * 256));
         hipLaunchKernelGGL(k_finalize_hits, dim3(blocks), dim3(256), 0, ctx->aux_stream, geom->view, pv, (const float4 *)ctx->final_use, ctx->final_epoch,
-                           nphotons, ho, ctx->d_words, ctx->final_epoch | 0x80000000u);
+                           nphotons, ho, ctx->d_words, photon_tail_stamp(ctx->final_epoch));
         HIP_TRY(hipEventRecord(ctx->ev_join, ctx->aux_stream));
         HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
     }

@@ -1,4 +1,5 @@
-// device_common.h -- device-side types shared by the HIP kernels of libchroma_hip.so.
+// device_common.h -- device-side types shared by the HIP kernels of libchroma_hip.so: float3 algebra, the geometry and photon
+// views, the 64-byte photon record (PhotonRecord) and what stores a photon back (store_photon), wave and block helpers.
 //
 // Written for gfx950 (CDNA4) only: 64-wide wavefronts, one photon per lane.
 // Arithmetic follows include/chroma_math.h (the numeric contract) and is compiled with
@@ -148,6 +149,67 @@ struct HitsOut {
     uint32_t *hit_count, *earliest;
     uint32_t detection_state; int want;
 };
+
+// a photon in registers (chroma/cuda/photon.h:12-27)
+struct Photon {
+    v3 position, direction, polarization;
+    float wavelength, time, weight;
+    uint32_t history;
+    int last_hit_triangle;
+    uint32_t evidx;
+};
+
+// ---- the photon record --------------------------------------------------------------------------------------------
+// A photon outside the caller's arrays: 64 bytes, four float4 rows ("working set" and "final records")
+//   {position, wavelength} {direction, time} {polarization, weight} {flags, draw counter, last hit, tag}
+// The LAST HIT word (row 3, .z) is
+//   - the index of a triangle RECORD (GeoView::tri, -1: none) in a working-set record: what the next ray cast skips;
+//   - a triangle ID (-1: none) in a final record: what the caller's last_hit_triangles gets.
+// The TAG (row 3, .w) is
+//   - the photon id, in a working-set record (the record sits at its queue slot);
+//   - the call's epoch, in a final record (the record sits at its photon id; k_physics, chroma_propagate_hits only);
+//   - photon_tail_stamp(epoch) = epoch | 0x80000000, on the final-record slot of a photon k_tail_coop is about to finish
+//     (k_mark_tail): k_finalize_hits, which runs beside the tail kernel, leaves such a photon to it.
+// Used by k_load_working, k_ray_setup and k_mark_tail.  k_physics, k_physics_deal, k_tail_coop, k_store_working and
+// k_finalize_hits still pick the rows apart by hand, in this layout: taken through the struct they compile to other
+// registers, scratch or occupancy (profiles/r09/INDEX.md).
+CM_FN uint32_t photon_tail_stamp(uint32_t epoch) { return epoch | 0x80000000u; }
+
+struct PhotonRecord {
+    float4 row[4];
+
+    PhotonRecord() = default;
+    __device__ inline PhotonRecord(const Photon &p, uint32_t draw_counter, int last_hit, uint32_t tag)
+    {
+        row[0] = make_float4(p.position.x, p.position.y, p.position.z, p.wavelength);
+        row[1] = make_float4(p.direction.x, p.direction.y, p.direction.z, p.time);
+        row[2] = make_float4(p.polarization.x, p.polarization.y, p.polarization.z, p.weight);
+        row[3] = make_float4(__uint_as_float(p.history), __uint_as_float(draw_counter), __int_as_float(last_hit), __uint_as_float(tag));
+    }
+    __device__ static inline PhotonRecord load(const float4 *r) { PhotonRecord rec; rec.row[0] = r[0]; rec.row[1] = r[1]; rec.row[2] = r[2]; rec.row[3] = r[3]; return rec; }
+    __device__ inline void store(float4 *r) const { r[0] = row[0]; r[1] = row[1]; r[2] = row[2]; r[3] = row[3]; }
+    // row 3 of a record nothing else is known of: the stamp of k_mark_tail
+    __device__ static inline void store_tag(float4 *r, uint32_t tag) { r[3] = make_float4(0.f, 0.f, 0.f, __uint_as_float(tag)); }
+
+    // (accessors for what a caller reads today; the other words get theirs with the first kernel that reads them through the struct)
+    __device__ inline v3 position() const { return mk3(row[0].x, row[0].y, row[0].z); }
+    __device__ inline v3 direction() const { return mk3(row[1].x, row[1].y, row[1].z); }
+    __device__ inline int last_hit() const { return __float_as_int(row[3].z); }
+};
+
+// a photon goes back to the caller's arrays (evidx is the caller's own: no kernel of a step changes it)
+__device__ inline void store_photon(const PhotonView &pv, size_t id, const Photon &p, uint32_t draw_counter)
+{
+    pv.rng_counters[id] = draw_counter;
+    store3(pv.pos, id, p.position);
+    store3(pv.dir, id, p.direction);
+    store3(pv.pol, id, p.polarization);
+    pv.wavelengths[id] = p.wavelength;
+    pv.t[id] = p.time;
+    pv.flags[id] = p.history;
+    pv.last_hit_triangles[id] = p.last_hit_triangle;
+    pv.weights[id] = p.weight;
+}
 
 __device__ inline void copy_photon(const PhotonView &src, size_t i, const PhotonView &dst, size_t o)
 {

@@ -164,17 +164,7 @@ k_physics_deal(GeoView g, PhotonView pv, StepState *st, const float4 *work_in, u
             // (a photon scattered or absorbed in the bulk forgets the triangle, photon.h:232,262,283)
             last_hit_record = (p.last_hit_triangle < 0) ? -1 : tri;
             alive = (p.history & CHROMA_TERMINAL_MASK) == 0;
-            if (!alive) {
-                pv.rng_counters[photon_id] = counter;
-                store3(pv.pos, photon_id, p.position);
-                store3(pv.dir, photon_id, p.direction);
-                store3(pv.pol, photon_id, p.polarization);
-                pv.wavelengths[photon_id] = p.wavelength;
-                pv.t[photon_id] = p.time;
-                pv.flags[photon_id] = p.history;
-                pv.last_hit_triangles[photon_id] = p.last_hit_triangle;
-                pv.weights[photon_id] = p.weight;
-            }
+            if (!alive) store_photon(pv, photon_id, p, counter);
         }
         const uint32_t at = block_queue_append<NW>(output_queue, alive, photon_id, s_counts);
         if (alive) {

@@ -164,15 +164,7 @@ k_physics(GeoView g, PhotonView pv, StepState *st, const float4 *work_in, uint32
                     f[2] = make_float4(p.polarization.x, p.polarization.y, p.polarization.z, p.weight);
                     f[3] = make_float4(__uint_as_float(p.history), __uint_as_float(counter), __int_as_float(p.last_hit_triangle), __uint_as_float(epoch));
                 } else {
-                    pv.rng_counters[photon_id] = counter;
-                    store3(pv.pos, photon_id, p.position);
-                    store3(pv.dir, photon_id, p.direction);
-                    store3(pv.pol, photon_id, p.polarization);
-                    pv.wavelengths[photon_id] = p.wavelength;
-                    pv.t[photon_id] = p.time;
-                    pv.flags[photon_id] = p.history;
-                    pv.last_hit_triangles[photon_id] = p.last_hit_triangle;
-                    pv.weights[photon_id] = p.weight;
+                    store_photon(pv, photon_id, p, counter);
                 }
             }
         }

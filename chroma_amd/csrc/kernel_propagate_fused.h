@@ -69,15 +69,7 @@ k_propagate(GeoView g, PhotonView pv, int first_photon, int nthreads, const uint
     }
 
     if (loaded) {
-        pv.rng_counters[photon_id] = rng.counter;
-        store3(pv.pos, photon_id, p.position);
-        store3(pv.dir, photon_id, p.direction);
-        store3(pv.pol, photon_id, p.polarization);
-        pv.wavelengths[photon_id] = p.wavelength;
-        pv.t[photon_id] = p.time;
-        pv.flags[photon_id] = p.history;
-        pv.last_hit_triangles[photon_id] = p.last_hit_triangle;
-        pv.weights[photon_id] = p.weight;
+        store_photon(pv, photon_id, p, rng.counter);
         pv.evidx[photon_id] = p.evidx;
         alive = (p.history & CHROMA_TERMINAL_MASK) == 0;
     }

@@ -91,10 +91,8 @@ k_ray_setup(GeoView g, const float4 *work, const StepState *st, float4 *rays,
 {
     const int nthreads = (int)st->n, renorm = (int)st->renorm;
     for (int slot = blockIdx.x * blockDim.x + threadIdx.x; slot < nthreads; slot += gridDim.x * blockDim.x) {
-        const float4 *w = work + 4 * (size_t)slot;
-        const float4 w0 = w[0], w1 = w[1], w3 = w[3];
-        const int status = make_ray_record(g, rays + 4 * (size_t)slot, mk3(w0.x, w0.y, w0.z), mk3(w1.x, w1.y, w1.z), renorm,
-                                           __float_as_int(w3.z), literal != 0);
+        const PhotonRecord rec = PhotonRecord::load(work + 4 * (size_t)slot);
+        const int status = make_ray_record(g, rays + 4 * (size_t)slot, rec.position(), rec.direction(), renorm, rec.last_hit(), literal != 0);
         if (status != 0) {
             hit_triangle[slot] = status;
             hit_distance[slot] = 0.0f;

@@ -222,15 +222,7 @@ k_tail_coop(GeoView g, PhotonView pv, const StepState *st, const float4 *work_in
     }
 
     if (loaded && j == 0) {                                 // the call ends with this kernel: everything goes back
-        pv.rng_counters[photon_id] = rng.counter;
-        store3(pv.pos, photon_id, p.position);
-        store3(pv.dir, photon_id, p.direction);
-        store3(pv.pol, photon_id, p.polarization);
-        pv.wavelengths[photon_id] = p.wavelength;
-        pv.t[photon_id] = p.time;
-        pv.flags[photon_id] = p.history;
-        pv.last_hit_triangles[photon_id] = p.last_hit_triangle;
-        pv.weights[photon_id] = p.weight;
+        store_photon(pv, photon_id, p, rng.counter);
         if (words) {
             if (p.history & CHROMA_NAN_ABORT) atomicOr(words + 2, CHROMA_NAN_ABORT);
             const int ch = h.want ? hit_channel(g, p.history, p.last_hit_triangle, h.detection_state) : -1;
@@ -274,5 +266,5 @@ __global__ void k_mark_tail(const uint32_t *queue, float4 *final_rec, uint32_t t
 {
     const uint32_t n = queue[0] - 1u;
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
-        final_rec[4 * (size_t)queue[1 + i] + 3] = make_float4(0.f, 0.f, 0.f, __uint_as_float(tail_mark));
+        PhotonRecord::store_tag(final_rec + 4 * (size_t)queue[1 + i], tail_mark);
 }

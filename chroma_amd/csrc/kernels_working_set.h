@@ -4,8 +4,8 @@
 #pragma once
 
 // ---- the dense working set ----------------------------------------------------------------------------
-// While a batch propagates, its live photons are kept as 64-byte records ordered by queue slot:
-// {pos, wavelength} {dir, time} {pol, weight} {flags, draw counter, last hit record, photon id}.  Steps
+// While a batch propagates, its live photons are kept as 64-byte records ordered by queue slot (PhotonRecord,
+// device_common.h: last hit = triangle record, tag = photon id).  Steps
 // read and append these records (streaming), so their traffic follows the number of survivors; the
 // caller's SoA arrays are read once (here) and written once per photon (when it ends, or at the end of
 // the call).  Working through the arrays instead made steps 2..5 touch nearly every line of every array
@@ -13,9 +13,6 @@
 // k_load_working also is the initial queue of GPUPhotons.propagate (chroma/gpu/photon.py:206-216: the
 // ncopies clones of a photon next to each other); photons that are already terminal are left out -- and
 // thereby untouched (propagate.cu:258).
-#ifndef LOAD_STAGE_LDS
-#define LOAD_STAGE_LDS 1
-#endif
 __global__ __launch_bounds__(PHYS_BLOCK) void
 k_load_working(GeoView g, PhotonView pv, uint32_t *queue, float4 *work, uint64_t n, uint32_t ncopies, uint32_t true_n, float4 *rays,
                uint32_t *coherence, const uint32_t *order = nullptr, int literal_rays = 0)
@@ -27,9 +24,7 @@ k_load_working(GeoView g, PhotonView pv, uint32_t *queue, float4 *work, uint64_t
     // (`coherence`: [0] += waves whose photons share an origin and lie within a cone of 50 mrad, [1] += waves looked at:
     //  what decides between k_raycast_packet and k_raycast_quad for the first step.  A heuristic: it steers speed only.)
     __shared__ uint32_t s_counts[PHYS_BLOCK / WAVE + 1];
-#if LOAD_STAGE_LDS
     __shared__ float4 s_stage[PHYS_BLOCK / WAVE][WAVE * 4];
-#endif
 #if CHROMA_EXPERIMENTAL
     uint32_t coh_yes = 0, coh_all = 0;
 #endif
@@ -47,7 +42,6 @@ k_load_working(GeoView g, PhotonView pv, uint32_t *queue, float4 *work, uint64_t
             take = (flags & CHROMA_TERMINAL_MASK) == 0;
         }
         const uint32_t at = block_queue_append<PHYS_BLOCK / WAVE>(queue, take, photon_id, s_counts);
-#if LOAD_STAGE_LDS
         // The survivors of a wave land in consecutive slots (block_queue_append), 64 bytes each -- but a lane's four
         // 16-byte stores are 64 bytes apart from its neighbours': 64 partial lines per store instruction.  The records go
         // through LDS instead and leave as whole kilobytes: store i of the wave writes bytes [1024 i, 1024 (i + 1)) of
@@ -63,11 +57,8 @@ k_load_working(GeoView g, PhotonView pv, uint32_t *queue, float4 *work, uint64_t
             const v3 pol = load3(pv.pol, photon_id);
             lh = pv.last_hit_triangles[photon_id];
             lh = (lh >= 0 && (uint32_t)lh < g.ntriangles) ? (int)g.tri_to_dev[lh] : -1;
-            float4 *w = st + 4 * rnk;
-            w[0] = make_float4(pos.x, pos.y, pos.z, pv.wavelengths[photon_id]);
-            w[1] = make_float4(dir.x, dir.y, dir.z, pv.t[photon_id]);
-            w[2] = make_float4(pol.x, pol.y, pol.z, pv.weights[photon_id]);
-            w[3] = make_float4(__uint_as_float(flags), __uint_as_float(pv.rng_counters[photon_id]), __int_as_float(lh), __uint_as_float(photon_id));
+            const Photon p = {pos, dir, pol, pv.wavelengths[photon_id], pv.t[photon_id], pv.weights[photon_id], flags, -1, 0u};
+            PhotonRecord(p, pv.rng_counters[photon_id], lh, photon_id).store(st + 4 * rnk);
         }
         __builtin_amdgcn_wave_barrier();
         for (uint32_t q = lane_id(); q < 4u * nsurv; q += WAVE) work[4 * (size_t)first_slot + q] = st[q];
@@ -79,18 +70,6 @@ k_load_working(GeoView g, PhotonView pv, uint32_t *queue, float4 *work, uint64_t
             __builtin_amdgcn_wave_barrier();
         }
         if (take) {
-#else
-        if (take) {
-            v3 pos = load3(pv.pos, photon_id), dir = load3(pv.dir, photon_id), pol = load3(pv.pol, photon_id);
-            int lh = pv.last_hit_triangles[photon_id];
-            lh = (lh >= 0 && (uint32_t)lh < g.ntriangles) ? (int)g.tri_to_dev[lh] : -1;
-            float4 *w = work + 4 * (size_t)(at - 1u);
-            w[0] = make_float4(pos.x, pos.y, pos.z, pv.wavelengths[photon_id]);
-            w[1] = make_float4(dir.x, dir.y, dir.z, pv.t[photon_id]);
-            w[2] = make_float4(pol.x, pol.y, pol.z, pv.weights[photon_id]);
-            w[3] = make_float4(__uint_as_float(flags), __uint_as_float(pv.rng_counters[photon_id]), __int_as_float(lh), __uint_as_float(photon_id));
-            if (rays) make_ray_record(g, rays + 4 * (size_t)(at - 1u), pos, dir, 1, lh, literal_rays != 0);
-#endif
 #if CHROMA_EXPERIMENTAL
             if (coherence) {
                 // against the wave's first taken lane (the lanes of a wave land in consecutive slots)

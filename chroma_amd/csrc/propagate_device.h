@@ -15,14 +15,6 @@
 #define CHROMA_EPSILON 1e-6
 enum { CMD_BREAK = 0, CMD_CONTINUE = 1, CMD_PASS = 2 };
 
-struct Photon {
-    v3 position, direction, polarization;
-    float wavelength, time, weight;
-    uint32_t history;
-    int last_hit_triangle;
-    uint32_t evidx;
-};
-
 struct State {
     v3 surface_normal;
     float refractive_index1, refractive_index2;
