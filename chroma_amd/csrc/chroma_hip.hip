@@ -1,5 +1,6 @@
-// chroma_hip.hip -- the propagate path of libchroma_hip.so (gfx950 / MI355X only): what a chroma_propagate* call runs (CallPlan),
-// its launches, step loop and tail, the settings and statistics that go with it, and the two calls that run this path's device
+// chroma_hip.hip -- the propagate path of libchroma_hip.so (gfx950 / MI355X only): what a walk costs and falls back to (one row
+// of WALKS each), what a chroma_propagate* call runs (CallPlan, resolved from those rows), the call itself (PropagateCall: its
+// state in one object, its launches, step loop and tail as members), the settings and statistics that go with it, and the two calls that run this path's device
 // code on rays of their own: chroma_intersect_mesh (the same ray-cast kernels) and the hybrid render (k_propagate's step functions:
 // the compiler specialises those for their callers, so the family compiles as it did only beside k_propagate).  The other entry points of include/chroma_hip.h: context.hip, geometry.hip, kernel_calls.hip, comm.hip,
 // bvh_device.hip, wide_device.hip.
@@ -94,18 +95,52 @@ static int check_stack(const chroma_geometry *geom)
 // their results as they are: LITERAL with four lanes per ray (k_raycast_literal) and the strict lane-per-ray loop for the few
 // rays whose 1/d is not moderate, LITERAL_LANE with the strict loop for every ray (the cross-check).  The others walk the
 // wide tree (WIDE 1, COOP 8, QUAD 4, PAIR 2 lanes per ray) or the reference's tree (PERSISTENT) and hand the rays they cannot
-// settle to k_raycast_retry.
+// settle to k_raycast_retry.  A Cast has the number of its CHROMA_WALK_*.
 enum class Cast { PERSISTENT, WIDE, COOP, QUAD, PAIR, LITERAL, LITERAL_LANE };
-enum SpillKind : unsigned { SPILL_COOP = 1, SPILL_WIDE = 2 };
+enum SpillKind : unsigned { SPILL_NONE = 0, SPILL_COOP = 1, SPILL_WIDE = 2 };
+
+// Everything the host knows about a walk, one row per CHROMA_WALK_* in the order of their numbers.
+struct Walk {
+    const char *name, *alias;      // what CHROMA_WALK accepts
+    Cast cast;                     // the kernel of a device step
+    int rays_per_wave;             // one wave per so many rays ...
+    int waves_per_cu;              // ... up to the kernel's resident waves: a CU holds this many
+    const char *waves_env;         // ... unless this variable says otherwise (at least 1)
+    uint32_t stack;                // the deepest wide tree its stack holds, LDS part + global spill; 0: it walks the reference's tree (check_stack)
+    SpillKind spill;               // the context's buffer behind the global part of its stack
+    int fallback;                  // the walk that takes its place when the wide tree is deeper than `stack`
+    bool chain;                    // the ray records go from kernel to kernel (k_load_working -> ray cast -> k_physics -> ...): no k_ray_setup
+    bool tail;                     // under CHROMA_TAIL_COOP it hands the last photons to k_tail_coop (the cross-check walks keep per-step launches to the end)
+};
+static const Walk WALKS[] = {
+    // (waves per CU: LDS-limited residency with 8 KB per wave | 11 KB per wave | 71 VGPRs, amdgpu_waves_per_eu 7 | the kernels' own attribute)
+    {"reference", nullptr, Cast::PERSISTENT, PROP_BLOCK, 20, "CHROMA_RAY_WAVES_PER_CU", 0, SPILL_NONE, -1, false, false},
+    {"wide", nullptr, Cast::WIDE, PROP_BLOCK, 14, "CHROMA_WIDE_WAVES_PER_CU", WIDE_STACK + WIDE_SPILL, SPILL_WIDE, CHROMA_WALK_REFERENCE, false, false},
+    {"coop", nullptr, Cast::COOP, 8, 28, "CHROMA_COOP_WAVES_PER_CU", COOP_STACK + COOP_SPILL, SPILL_COOP, CHROMA_WALK_WIDE, false, true},
+    {"quad", nullptr, Cast::QUAD, 16, 4 * QUAD_WAVES_PER_EU, "CHROMA_QUAD_WAVES_PER_CU", QUAD_STACK + COOP_SPILL, SPILL_COOP, CHROMA_WALK_COOP, true, true},
+    {"pair", nullptr, Cast::PAIR, 32, 4 * PAIR_WAVES_PER_EU, "CHROMA_PAIR_WAVES_PER_CU", PAIR_STACK + COOP_SPILL, SPILL_COOP, CHROMA_WALK_QUAD, false, true},
+    // (the exact walks never fall back; k_raycast_literal has the quad kernel's grid and its slice of the coop spill buffer)
+    {"literal", "exact", Cast::LITERAL, 16, 4 * QUAD_WAVES_PER_EU, "CHROMA_QUAD_WAVES_PER_CU", 0, SPILL_COOP, -1, true, true},
+    {"literal_lane", nullptr, Cast::LITERAL_LANE, PROP_BLOCK, 20, "CHROMA_RAY_WAVES_PER_CU", 0, SPILL_NONE, -1, false, false},
+};
+static const int NWALKS = sizeof WALKS / sizeof WALKS[0];
+static_assert(NWALKS == CHROMA_WALK_LITERAL_LANE + 1, "one row per CHROMA_WALK_*");
+
+// whether the walk's stack holds the geometry's tree
+static bool walk_fits(const Walk &w, const chroma_geometry *geom)
+{
+    return w.stack == 0 || (geom->view.wnodes != nullptr && geom->wide_stack_need <= w.stack);
+}
 
 // What one call runs, fixed when it starts: the context's settings (chroma_set_walk / _tail / _packet / _autosort / _counting,
-// the CHROMA_* environment) overridden by the call's own chroma_propagate_options, resolved against the geometry.  Every
-// function below a public entry point reads THIS, never the context's mutable settings, so a call cannot change under it.
+// the CHROMA_* environment) overridden by the call's own chroma_propagate_options, resolved against the geometry through the
+// rows of WALKS.  Every function below a public entry point reads THIS (a propagate call: inside its PropagateCall), never
+// the context's mutable settings, so a call cannot change under it.
 struct CallPlan {
     int tail_mode;       // CHROMA_TAIL_*
     bool counting;
-    Cast cast;           // what every device step runs
-    bool chain;          // the ray records go from kernel to kernel (k_load_working -> ray cast -> k_physics -> ...): no k_ray_setup
+    Cast cast;           // what every device step runs: the chosen walk's, or that of the walk it fell back to
+    bool chain;          // Walk::chain of the chosen walk, when it did not fall back
     bool tail_watch;     // near the end the host reads the survivor count every step, to start the tail when the reference does
     bool tail;           // ... and k_tail_coop can walk this geometry: it takes the last photons
     bool isect_quad;     // chroma_intersect_mesh casts with k_raycast_quad
@@ -117,40 +152,31 @@ struct CallPlan {
 // `walk`, `tail`, `counting`: the call's choice, or -1 for the context's
 static int make_plan(const chroma_ctx *ctx, const chroma_geometry *geom, int walk, int tail, int counting, CallPlan *plan)
 {
-    if (walk > CHROMA_WALK_LITERAL_LANE) return set_error(CHROMA_ERR_INVALID, "unknown walk mode %d", walk);
+    if (walk >= NWALKS) return set_error(CHROMA_ERR_INVALID, "unknown walk mode %d", walk);
     if (tail > CHROMA_TAIL_FUSED) return set_error(CHROMA_ERR_INVALID, "unknown tail mode %d", tail);
     const int w = walk >= 0 ? walk : ctx->walk;
     CallPlan p = {};
     p.tail_mode = tail >= 0 ? tail : ctx->tail_mode;
     p.counting = counting >= 0 ? counting != 0 : ctx->counting != 0;
-    // which fast walks' stacks (LDS part + global spill) hold the wide tree
-    const bool wide = geom->view.wnodes != nullptr;
-    const uint32_t ws = geom->wide_stack_need;
-    const bool fits_pair = wide && ws <= PAIR_STACK + COOP_SPILL, fits_quad = wide && ws <= QUAD_STACK + COOP_SPILL,
-               fits_coop = wide && ws <= COOP_STACK + COOP_SPILL, fits_wide = wide && ws <= WIDE_STACK + WIDE_SPILL;
     // a fast walk whose stack is too shallow for the tree falls back to the next one (PAIR never to COOP)
-    p.cast = w == CHROMA_WALK_LITERAL ? Cast::LITERAL
-           : w == CHROMA_WALK_LITERAL_LANE ? Cast::LITERAL_LANE
-           : w == CHROMA_WALK_PAIR && fits_pair ? Cast::PAIR
-           : (w == CHROMA_WALK_QUAD || w == CHROMA_WALK_PAIR) && fits_quad ? Cast::QUAD
-           : (w == CHROMA_WALK_COOP || w == CHROMA_WALK_QUAD) && fits_coop ? Cast::COOP
-           : w != CHROMA_WALK_REFERENCE && fits_wide ? Cast::WIDE
-           : Cast::PERSISTENT;
-    // (a PAIR walk that fell back to the quad kernel keeps the k_ray_setup pass)
-    p.chain = p.cast == Cast::LITERAL || (p.cast == Cast::QUAD && w == CHROMA_WALK_QUAD);
-    // (the cross-check walks keep per-step launches to the end)
-    p.tail_watch = p.tail_mode == CHROMA_TAIL_COOP && (w == CHROMA_WALK_COOP || w == CHROMA_WALK_QUAD || w == CHROMA_WALK_PAIR ||
-                                                      w == CHROMA_WALK_LITERAL);
-    p.tail = p.tail_watch && fits_coop;
-    p.isect_quad = fits_coop && w != CHROMA_WALK_REFERENCE && w != CHROMA_WALK_LITERAL && w != CHROMA_WALK_LITERAL_LANE;
-    if (p.tail_mode != CHROMA_TAIL_FUSED) {
-        const bool coop_stack = p.cast == Cast::COOP || p.cast == Cast::QUAD || p.cast == Cast::PAIR || p.cast == Cast::LITERAL;
-        p.spill = (coop_stack || p.tail ? SPILL_COOP : 0u) | (p.cast == Cast::WIDE ? SPILL_WIDE : 0u);
+    int r = w;
+    while (!walk_fits(WALKS[r], geom)) {
+        r = WALKS[r].fallback;
+        if (w == CHROMA_WALK_PAIR && r == CHROMA_WALK_COOP) r = WALKS[r].fallback;
     }
+    p.cast = WALKS[r].cast;
+    // (a PAIR walk that fell back to the quad kernel keeps the k_ray_setup pass)
+    p.chain = r == w && WALKS[w].chain;
+    // (k_tail_coop and the quad cast of chroma_intersect_mesh have the coop walk's stack)
+    const bool fits_coop = walk_fits(WALKS[CHROMA_WALK_COOP], geom);
+    p.tail_watch = p.tail_mode == CHROMA_TAIL_COOP && WALKS[w].tail;
+    p.tail = p.tail_watch && fits_coop;
+    p.isect_quad = fits_coop && WALKS[w].stack != 0;
+    if (p.tail_mode != CHROMA_TAIL_FUSED) p.spill = WALKS[r].spill | (p.tail ? SPILL_COOP : SPILL_NONE);
     if (p.chain && p.cast == Cast::QUAD) {
         p.autosort = ctx->autosort_mode;
 #if CHROMA_EXPERIMENTAL
-        if (ws <= PACKET_STACK) p.packet = ctx->packet_mode;
+        if (geom->wide_stack_need <= PACKET_STACK) p.packet = ctx->packet_mode;
 #endif
     }
     *plan = p;
@@ -161,258 +187,453 @@ static int make_plan(const chroma_ctx *ctx, const chroma_geometry *geom, int wal
 // with (wave * rays-per-wave + ray) * COOP_SPILL, so it is sized for the largest grid of any of them.
 static int ensure_spill(chroma_ctx *ctx, unsigned kinds)
 {
-    if ((kinds & SPILL_COOP) && !ctx->coop_spill) {
-        const size_t rays = std::max(std::max((size_t)ctx->coop_waves * 8, (size_t)ctx->quad_waves * 16), (size_t)ctx->pair_waves * 32);
+    const struct { SpillKind kind; uint2 **buf; size_t depth; } bufs[] = {{SPILL_COOP, &ctx->coop_spill, COOP_SPILL},
+                                                                          {SPILL_WIDE, &ctx->wide_spill, WIDE_SPILL}};
+    for (const auto &b : bufs) {
+        if (!(kinds & b.kind) || *b.buf) continue;
+        size_t rays = 0;
+        for (const Walk &w : WALKS)
+            if (w.spill == b.kind) rays = std::max(rays, (size_t)ctx->waves[(int)w.cast] * w.rays_per_wave);
         HIP_TRY(hipSetDevice(ctx->device));
-        HIP_TRY(ctx_malloc(ctx, (void **)&ctx->coop_spill, rays * COOP_SPILL * sizeof(uint2)));
-    }
-    if ((kinds & SPILL_WIDE) && !ctx->wide_spill) {
-        HIP_TRY(hipSetDevice(ctx->device));
-        HIP_TRY(ctx_malloc(ctx, (void **)&ctx->wide_spill, (size_t)ctx->wide_waves * WIDE_SPILL * PROP_BLOCK * sizeof(uint2)));
+        HIP_TRY(ctx_malloc(ctx, (void **)b.buf, rays * b.depth * sizeof(uint2)));
     }
     return CHROMA_OK;
 }
 
-// the ray cast's grid: one wave per 8 (COOP), 16 (QUAD, LITERAL), 32 (PAIR) or 64 rays, up to the kernel's resident waves
+// the ray cast's grid: one wave per Walk::rays_per_wave rays, up to the kernel's resident waves
 static unsigned cast_waves(const chroma_ctx *ctx, Cast cast, long long n)
 {
-    long long per = PROP_BLOCK, cap = ctx->persistent_waves;
-    switch (cast) {
-    case Cast::PAIR: per = 32; cap = ctx->pair_waves; break;
-    case Cast::QUAD: case Cast::LITERAL: per = 16; cap = ctx->quad_waves; break;
-    case Cast::COOP: per = 8; cap = ctx->coop_waves; break;
-    case Cast::WIDE: cap = ctx->wide_waves; break;
-    default: break;
-    }
-    return (unsigned)std::min<long long>((n + per - 1) / per, cap);
+    const long long per = WALKS[(int)cast].rays_per_wave;
+    return (unsigned)std::min<long long>((n + per - 1) / per, ctx->waves[(int)cast]);
 }
 
 // the lane-per-photon kernel with the reference's launch shape (CHROMA_TAIL=fused, chroma_propagate_step)
-static int launch_propagate(chroma_ctx *ctx, bool counting, chroma_geometry *geom, PhotonView pv, int first, int nthreads,
-                            const uint32_t *in_q, uint32_t *out_q, chroma_rng rng, int max_steps, int use_weights, int scatter_first)
+struct FusedLaunch { int first, nthreads; const uint32_t *in_q; uint32_t *out_q; int max_steps, use_weights, scatter_first; };
+static int launch_propagate(chroma_ctx *ctx, bool counting, chroma_geometry *geom, const PhotonView &pv, chroma_rng rng, const FusedLaunch &a)
 {
-    const dim3 grid((unsigned)((nthreads + PROP_BLOCK - 1) / PROP_BLOCK)), block(PROP_BLOCK);
+    const dim3 grid((unsigned)((a.nthreads + PROP_BLOCK - 1) / PROP_BLOCK)), block(PROP_BLOCK);
     with_bool(counting, [&](auto C) {
-        hipLaunchKernelGGL((k_propagate<STACK_LDS, C>), grid, block, 0, ctx->stream, geom->view, pv, first, nthreads, in_q, out_q,
-                           rng.seed, rng.photon_id_base, max_steps, use_weights, scatter_first, ctx->d_counters);
+        hipLaunchKernelGGL((k_propagate<STACK_LDS, C>), grid, block, 0, ctx->stream, geom->view, pv, a.first, a.nthreads, a.in_q, a.out_q,
+                           rng.seed, rng.photon_id_base, a.max_steps, a.use_weights, a.scatter_first, ctx->d_counters);
     });
     HIP_TRY(hipGetLastError());
     return CHROMA_OK;
-}
-
-// k_physics for one pass of a step.  `fixup`: 0 the main pass over every slot, 1 the slots k_raycast_retry has walked again
-// (a short list: a small grid), 2 every slot with the ray cast's results taken as they are (the exact walks).
-static void launch_physics(chroma_ctx *ctx, const CallPlan &plan, chroma_geometry *geom, const PhotonView &pv, long long n_upper,
-                           const float4 *work_in, uint32_t *out_q, float4 *work_out, chroma_rng rng, int use_weights, int scatter_first,
-                           int fixup, float4 *rays_next)
-{
-    StepState *st = ctx->d_step;
-    const bool plain = geom->view.plain_optics != 0;      // (no re-emitting component, default surface model only)
-    bool deal = false;
-#if PHYS_DEAL
-    deal = plain && !ctx->final_use;                      // (photons of a block dealt by what happens to them: experimental/physics_deal.h)
-#endif
-    const int pb = deal ? PHYS_DEAL_BLOCK : PHYS_BLOCK_OF(!plain);
-    unsigned blocks = (unsigned)std::min<long long>((n_upper + pb - 1) / pb, std::max<long long>(1, (long long)ctx->physics_blocks * PHYS_BLOCK / pb));
-    // (the retry list is ~1e-3 of the slots with plain optics: an eighth of the grid strides over it in a round or two, and a
-    //  launch of 2048 blocks that find nothing to do costs 0.07 ms, 29 times per batch; a plain geometry with faces on the
-    //  world box lists a good part of its hits for the exact check, so not less than that)
-    if (fixup == 1 && plain) blocks = std::max(std::min(blocks, 64u), blocks / 8);
-    DeviceCounters *pc = plan.counting ? ctx->d_counters : nullptr;
-#if PHYS_DEAL
-    if (deal) {
-        hipLaunchKernelGGL(k_physics_deal, dim3(blocks), dim3(PHYS_DEAL_BLOCK), 0, ctx->stream, geom->view, pv, st, work_in, out_q, work_out,
-                           ctx->hit_triangle, ctx->hit_distance, rng.seed, rng.photon_id_base, use_weights, scatter_first,
-                           ctx->retry_list, fixup, pc, rays_next);
-        return;
-    }
-#endif
-    const int literal_rays = fixup == 2 ? 1 : 0;          // (the exact walks' ray records)
-    with_bool(!plain, [&](auto FULL) {
-        hipLaunchKernelGGL((k_physics<FULL>), dim3(blocks), dim3(PHYS_BLOCK_OF(FULL)), 0, ctx->stream, geom->view, pv, st, work_in, out_q,
-                           work_out, ctx->hit_triangle, ctx->hit_distance, rng.seed, rng.photon_id_base, use_weights, scatter_first,
-                           ctx->retry_list, fixup, pc, rays_next, ctx->final_use, ctx->final_epoch, literal_rays);
-    });
 }
 
 // the timing events of one step, in the order they are recorded (EV_PER_STEP per step when a call times its kernels)
 enum { EV_STEP_BEGIN, EV_PACKET_BEGIN, EV_CAST_BEGIN, EV_CAST_END, EV_PHYSICS_END, EV_STEP_END, EV_PER_STEP };
 
-// One step as ray set-up + ray cast + physics (+ the strict walk and the physics of the few rays that need it), all reading the
-// photon count and the launch policy from ctx->d_step (k_step_begin).  `n_upper` bounds the count and sizes the grids;
-// `in_q`/`out_q` are whole queues (slot 0 = tail) and `work_in`/`work_out` the working sets that go with them.  `ev`: the
-// step's EV_PER_STEP events, or NULL.  When the rays chain, this step's records are in ctx->rays already (written by
-// k_load_working or by the k_physics of the step before), k_physics writes the next step's to ctx->rays_b, and the two swap.
-// `packet` (experimental): the first step of a call whose k_load_working looked at the photons' coherence -- k_raycast_packet
-// is launched before k_raycast_quad, and the word k_packet_decide wrote tells the two which of them has the step.
-static int launch_split_step(chroma_ctx *ctx, const CallPlan &plan, chroma_geometry *geom, PhotonView pv, long long n_upper,
-                             const uint32_t *in_q, uint32_t *out_q, const float4 *work_in, float4 *work_out, chroma_rng rng,
-                             int use_weights, int scatter_first, hipEvent_t *ev, uint32_t first_n, bool packet)
-{
-    if (n_upper <= 0) return CHROMA_OK;
-    StepState *st = ctx->d_step;
-    const Cast cast = plan.cast;
-    const bool exact = cast == Cast::LITERAL || cast == Cast::LITERAL_LANE;
-    float4 *rays_next = plan.chain ? ctx->rays_b : nullptr;
-    const dim3 block(PROP_BLOCK);
-    auto record = [&](int slot) { return ev ? hipEventRecord(ev[slot], ctx->stream) : hipSuccess; };
-    // (both passes of the strict walk stride over the list and leave at once when it is short -- the usual case -- but a plain
-    //  geometry with faces on the world box lists a good part of its hits for the exact check: grids for that)
-    const unsigned rblocks = (unsigned)std::min<long long>((n_upper + PROP_BLOCK - 1) / PROP_BLOCK, 8 * 256);
-    auto retry = [&](auto C) {
-        hipLaunchKernelGGL((k_raycast_retry<C>), dim3(rblocks), block, 0, ctx->stream, geom->view, ctx->rays, st, ctx->hit_triangle,
-                           ctx->hit_distance, ctx->retry_list, ctx->d_counters);
-    };
-    // (with weights the reference runs ALL steps in one launch: every count is "few")
-    hipLaunchKernelGGL(k_step_begin, dim3(1), dim3(1), 0, ctx->stream, in_q, out_q, st,
-                       use_weights ? 0xFFFFFFFFu : (uint32_t)(PROP_BLOCK * 16 * 8), first_n);
-    HIP_TRY(record(EV_STEP_BEGIN));
-    if (!plan.chain) {
-        unsigned sblocks = (unsigned)std::min<long long>((n_upper + 255) / 256, (long long)ctx->physics_blocks * 4);
-        hipLaunchKernelGGL(k_ray_setup, dim3(sblocks), dim3(256), 0, ctx->stream, geom->view, work_in, st, ctx->rays,
-                           ctx->hit_triangle, ctx->hit_distance, ctx->retry_list, &st->retry, cast == Cast::LITERAL ? 1 : 0);
-    }
-    HIP_TRY(record(EV_PACKET_BEGIN));                             // the ray-cast kernels proper are timed from here
-    const uint32_t *skip_quad = nullptr;
-#if CHROMA_EXPERIMENTAL
-    if (packet) {
-        skip_quad = ctx->d_words + 4;
-        const unsigned pwaves = (unsigned)std::min<long long>((n_upper + WAVE - 1) / WAVE, (long long)ctx->quad_waves);
-        with_bool(plan.counting, [&](auto C) {
-            hipLaunchKernelGGL((k_raycast_packet<C>), dim3(pwaves), block, 0, ctx->stream, geom->view, ctx->rays, st, ctx->hit_triangle,
-                               ctx->hit_distance, ctx->retry_list, ctx->d_counters, ctx->d_words + 4);
-        });
-    }
-#else
-    (void)packet;
-#endif
-    HIP_TRY(record(EV_CAST_BEGIN));
-    const dim3 grid(cast_waves(ctx, cast, n_upper));
-    const int chained = plan.chain ? 1 : 0;
-    with_bool(plan.counting, [&](auto C) {
-        switch (cast) {
-        case Cast::PAIR:
-            hipLaunchKernelGGL((k_raycast_pair<C>), grid, block, 0, ctx->stream, geom->view, ctx->rays, 0, st, ctx->hit_triangle,
-                               ctx->hit_distance, ctx->retry_list, ctx->coop_spill, ctx->d_counters, ctx->coop_chunk);
-            break;
-        case Cast::QUAD:
-            hipLaunchKernelGGL((k_raycast_quad<C>), grid, block, 0, ctx->stream, geom->view, ctx->rays, 0, st, ctx->hit_triangle,
-                               ctx->hit_distance, ctx->retry_list, ctx->coop_spill, ctx->d_counters, ctx->coop_chunk, chained, skip_quad,
-                               ctx->claim_static);
-            break;
-        case Cast::COOP:
-            hipLaunchKernelGGL((k_raycast_coop<C>), grid, block, 0, ctx->stream, geom->view, ctx->rays, 0, st, ctx->hit_triangle,
-                               ctx->hit_distance, ctx->retry_list, ctx->coop_spill, ctx->d_counters, ctx->coop_chunk);
-            break;
-        case Cast::WIDE:
-            hipLaunchKernelGGL((k_raycast_wide<C>), grid, block, 0, ctx->stream, geom->view, ctx->rays, 0, st, ctx->hit_triangle,
-                               ctx->hit_distance, ctx->retry_list, ctx->wide_spill, ctx->d_counters, ctx->ray_chunk);
-            break;
-        case Cast::PERSISTENT:
-            hipLaunchKernelGGL((k_raycast_persistent<C>), grid, block, 0, ctx->stream, geom->view, ctx->rays, 0, st, ctx->hit_triangle,
-                               ctx->hit_distance, ctx->retry_list, ctx->d_counters);
-            break;
-        case Cast::LITERAL:
-            hipLaunchKernelGGL((k_raycast_literal<C>), grid, block, 0, ctx->stream, geom->view, ctx->rays, st, ctx->hit_triangle,
-                               ctx->hit_distance, ctx->coop_spill, ctx->d_counters, ctx->coop_chunk, chained, ctx->retry_list,
-                               ctx->claim_static);
-            retry(C);
-            break;
-        case Cast::LITERAL_LANE:
-            hipLaunchKernelGGL((k_raycast_retry<C, true>), grid, block, 0, ctx->stream, geom->view, ctx->rays, st, ctx->hit_triangle,
-                               ctx->hit_distance, ctx->retry_list, ctx->d_counters);
-            break;
-        }
-    });
-    HIP_TRY(record(EV_CAST_END));
-    // physics for every slot whose hit is regular; then the strict walk and the physics of the rest
-    launch_physics(ctx, plan, geom, pv, n_upper, work_in, out_q, work_out, rng, use_weights, scatter_first, exact ? 2 : 0, rays_next);
-    HIP_TRY(record(EV_PHYSICS_END));
-    if (!exact) {
-        with_bool(plan.counting, retry);
-        launch_physics(ctx, plan, geom, pv, n_upper, work_in, out_q, work_out, rng, use_weights, scatter_first, 1, rays_next);
-    }
-    HIP_TRY(record(EV_STEP_END));
-    HIP_TRY(hipGetLastError());
-    if (plan.chain) std::swap(ctx->rays, ctx->rays_b);       // (what k_physics wrote is the next step's input)
-    return CHROMA_OK;
-}
+namespace { struct PropagateCall; }
+// *d_order: nullptr (the call takes its photons as they come) or a chroma_malloc'ed permutation to free after k_load_working
+static int propagate_order(PropagateCall &call, uint32_t **d_order);
 
-// All remaining steps of the last photons in one launch (k_tail_coop), for a plan with `tail`.  Sets *done when it launched.
-static int launch_tail(chroma_ctx *ctx, const CallPlan &plan, chroma_geometry *geom, PhotonView pv, long long n_upper, const uint32_t *in_q,
-                       uint32_t *out_q, const float4 *work_in, chroma_rng rng, int nsteps, int use_weights, int scatter_first,
-                       hipEvent_t *ev, bool *done, uint32_t first_n, const HitsOut *beside, uint64_t nphotons)
-{
-    // (`beside`: a call that ends in k_finalize_hits -- that pass runs on the context's auxiliary stream WHILE the tail kernel
-    //  finishes the last photons, which are stamped first so that it leaves them to the tail kernel; the two meet again
-    //  before the call reads its result words.  The tail kernel is launched FIRST: its ~1000 waves are resident before the
-    //  24 000 blocks of the streaming pass fill every wave slot.  Launched second, its workgroups waited for slots behind them
-    //  and the tail ended 1.7 ms after the pass instead of with it: DESIGN.md section 3.2)
-    *done = false;
-    const unsigned waves = cast_waves(ctx, Cast::COOP, n_upper);            // (8 lanes per photon)
-    if ((long long)waves * 8 < n_upper) return CHROMA_OK;          // (cannot happen below 8192 photons)
-    StepState *st = ctx->d_step;
-    hipLaunchKernelGGL(k_step_begin, dim3(1), dim3(1), 0, ctx->stream, in_q, out_q, st,
-                       use_weights ? 0xFFFFFFFFu : (uint32_t)(PROP_BLOCK * 16 * 8), first_n);
-    HitsOut ho; memset(&ho, 0, sizeof ho);
-    uint32_t *words = nullptr;
-    if (beside) {
-        ho = *beside;
-        words = ctx->d_words;
-        HIP_TRY(hipMemsetAsync(ctx->d_words, 0, 12, ctx->stream));
-        if (ctx->final_use)
-            hipLaunchKernelGGL(k_mark_tail, dim3(32), dim3(256), 0, ctx->stream, in_q, ctx->final_use, photon_tail_stamp(ctx->final_epoch));
-        HIP_TRY(hipEventRecord(ctx->ev_fork, ctx->stream));          // (the words are cleared and the tail's photons stamped: the pass may start)
+// One chroma_propagate* call: what it was asked, what it runs (CallPlan), the context's buffers in the roles they have at the
+// moment, and what it has found out so far.  Built once by propagate_impl after its checks; the functions of the path are its
+// members and take only what varies from one invocation to the next.  The context's own pointers and settings are not changed
+// by a call: the pairs below swap HERE.  (Unnamed namespace: its members are not the library's symbols.)
+namespace {
+struct PropagateCall {
+    chroma_ctx *ctx; chroma_geometry *geom;
+    CallPlan plan;
+    PhotonView pv; chroma_rng rng; chroma_propagate_options opt;
+    uint64_t nphotons; uint32_t ncopies;
+    uint32_t *in_q, *out_q;            // whole queues (slot 0 = tail): this step's input and output
+    float4 *work_in, *work_out;        // ... and the dense working sets that go with them
+    float4 *rays, *rays_next;          // ray records: this step's, and where a chaining k_physics writes the next step's
+    float4 *final_rec;                 // the context's final records when this call uses them, else NULL (k_physics stores to the arrays)
+    uint32_t final_epoch;              // ... and what marks a record as this call's
+    HitsOut ho;                        // where the call's last pass (k_finalize_hits) puts the hits ...
+    bool finalize;                     // ... if it runs at all: a hits request, or final records
+    chroma_propagate_stats acc;        // launches and kernel times so far
+    long long n_upper;                 // bounds the live photons: sizes the grids
+    bool finalized;                    // k_finalize_hits has run already, beside the tail kernel (launch_tail)
+
+    hipEvent_t *events(int step) const { return opt.time_kernels ? ctx->step_events.data() + EV_PER_STEP * step : nullptr; }
+
+    // the live photons into the dense working set (k_load_working), with the first step's ray records when the rays chain
+    int load_working()
+    {
+        const unsigned blocks = (unsigned)std::min<uint64_t>((nphotons + PHYS_BLOCK - 1) / PHYS_BLOCK, (uint64_t)ctx->physics_blocks);
+        HIP_TRY(hipMemsetAsync(ctx->d_words + W_PACKET_USE, 0, (W_PACKET_END - W_PACKET_USE) * sizeof(uint32_t), ctx->stream));
+        uint32_t *d_order = nullptr;
+        int rc = propagate_order(*this, &d_order); if (rc) return rc;
+        hipLaunchKernelGGL(k_load_working, dim3(blocks), dim3(PHYS_BLOCK), 0, ctx->stream, geom->view, pv, in_q, work_in,
+                           (uint64_t)nphotons, ncopies, (uint32_t)(nphotons / ncopies), plan.chain ? rays : nullptr,
+                           plan.packet == 2 ? ctx->d_words + W_PACKET_COHERENT : nullptr, (const uint32_t *)d_order, plan.cast == Cast::LITERAL ? 1 : 0);
+        if (d_order) { chroma_free(ctx, d_order); acc.reordered += nphotons; }      // (parked until the stream has passed this point)
+#if CHROMA_EXPERIMENTAL
+        if (plan.packet)
+            hipLaunchKernelGGL(k_packet_decide, dim3(1), dim3(1), 0, ctx->stream, ctx->d_words + W_PACKET_COHERENT, ctx->d_words + W_PACKET_USE,
+                               (uint64_t)nphotons, plan.packet);
+#endif
+        HIP_TRY(hipGetLastError());
+        return CHROMA_OK;
     }
-    if (ev) HIP_TRY(hipEventRecord(ev[EV_STEP_BEGIN], ctx->stream));
-    with_bool(plan.cast == Cast::LITERAL, [&](auto L) {
-        with_bool(plan.counting, [&](auto C) {
-            hipLaunchKernelGGL((k_tail_coop<C, L>), dim3(waves), dim3(PROP_BLOCK), 0, ctx->stream, geom->view, pv, st, work_in,
-                               rng.seed, rng.photon_id_base, nsteps, use_weights, scatter_first, ctx->coop_spill, ctx->d_counters, ho, words);
+
+    // (with weights the reference runs ALL steps in one launch: every count is "few")
+    void launch_step_begin(uint32_t first_n)
+    {
+        hipLaunchKernelGGL(k_step_begin, dim3(1), dim3(1), 0, ctx->stream, in_q, out_q, ctx->d_step,
+                           opt.use_weights ? 0xFFFFFFFFu : (uint32_t)(PROP_BLOCK * 16 * 8), first_n);
+    }
+
+    // k_physics for one pass of a step.  `fixup`: 0 the main pass over every slot, 1 the slots k_raycast_retry has walked again
+    // (a short list: a small grid), 2 every slot with the ray cast's results taken as they are (the exact walks).
+    void launch_physics(int scatter_first, int fixup)
+    {
+        StepState *st = ctx->d_step;
+        float4 *chained = plan.chain ? rays_next : nullptr;
+        const bool plain = geom->view.plain_optics != 0;      // (no re-emitting component, default surface model only)
+        bool deal = false;
+#if PHYS_DEAL
+        deal = plain && !final_rec;                           // (photons of a block dealt by what happens to them: experimental/physics_deal.h)
+#endif
+        const int pb = deal ? PHYS_DEAL_BLOCK : PHYS_BLOCK_OF(!plain);
+        unsigned blocks = (unsigned)std::min<long long>((n_upper + pb - 1) / pb, std::max<long long>(1, (long long)ctx->physics_blocks * PHYS_BLOCK / pb));
+        // (the retry list is ~1e-3 of the slots with plain optics: an eighth of the grid strides over it in a round or two, and a
+        //  launch of 2048 blocks that find nothing to do costs 0.07 ms, 29 times per batch; a plain geometry with faces on the
+        //  world box lists a good part of its hits for the exact check, so not less than that)
+        if (fixup == 1 && plain) blocks = std::max(std::min(blocks, 64u), blocks / 8);
+        DeviceCounters *pc = plan.counting ? ctx->d_counters : nullptr;
+#if PHYS_DEAL
+        if (deal) {
+            hipLaunchKernelGGL(k_physics_deal, dim3(blocks), dim3(PHYS_DEAL_BLOCK), 0, ctx->stream, geom->view, pv, st, work_in, out_q, work_out,
+                               ctx->hit_triangle, ctx->hit_distance, rng.seed, rng.photon_id_base, opt.use_weights, scatter_first,
+                               ctx->retry_list, fixup, pc, chained);
+            return;
+        }
+#endif
+        const int literal_rays = fixup == 2 ? 1 : 0;          // (the exact walks' ray records)
+        with_bool(!plain, [&](auto FULL) {
+            hipLaunchKernelGGL((k_physics<FULL>), dim3(blocks), dim3(PHYS_BLOCK_OF(FULL)), 0, ctx->stream, geom->view, pv, st, work_in, out_q,
+                               work_out, ctx->hit_triangle, ctx->hit_distance, rng.seed, rng.photon_id_base, opt.use_weights, scatter_first,
+                               ctx->retry_list, fixup, pc, chained, final_rec, final_epoch, literal_rays);
         });
-    });
-    if (ev) HIP_TRY(hipEventRecord(ev[EV_STEP_END], ctx->stream));
-    if (beside) {
-        HIP_TRY(hipStreamWaitEvent(ctx->aux_stream, ctx->ev_fork, 0));
-        const unsigned blocks = (unsigned)((nphotons + COPY_ITEMS * 256 - 1) / (COPY_ITEMS * 256));
-        hipLaunchKernelGGL(k_finalize_hits, dim3(blocks), dim3(256), 0, ctx->aux_stream, geom->view, pv, (const float4 *)ctx->final_use, ctx->final_epoch,
-                           nphotons, ho, ctx->d_words, photon_tail_stamp(ctx->final_epoch));
-        HIP_TRY(hipEventRecord(ctx->ev_join, ctx->aux_stream));
-        HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
     }
-    HIP_TRY(hipGetLastError());
-    *done = true;
-    return CHROMA_OK;
+
+    // One step as ray set-up + ray cast + physics (+ the strict walk and the physics of the few rays that need it), all reading the
+    // photon count and the launch policy from ctx->d_step (k_step_begin).  `ev`: the step's EV_PER_STEP events, or NULL.  When the
+    // rays chain, this step's records are in `rays` already (written by k_load_working or by the k_physics of the step before),
+    // k_physics writes the next step's to `rays_next`, and the two swap.
+    // `packet` (experimental): the first step of a call whose k_load_working looked at the photons' coherence -- k_raycast_packet
+    // is launched before k_raycast_quad, and the word k_packet_decide wrote tells the two which of them has the step.
+    int launch_split_step(int scatter_first, hipEvent_t *ev, uint32_t first_n, bool packet)
+    {
+        if (n_upper <= 0) return CHROMA_OK;
+        StepState *st = ctx->d_step;
+        const Cast cast = plan.cast;
+        const bool exact = cast == Cast::LITERAL || cast == Cast::LITERAL_LANE;
+        const dim3 block(PROP_BLOCK);
+        auto record = [&](int slot) { return ev ? hipEventRecord(ev[slot], ctx->stream) : hipSuccess; };
+        // (both passes of the strict walk stride over the list and leave at once when it is short -- the usual case -- but a plain
+        //  geometry with faces on the world box lists a good part of its hits for the exact check: grids for that)
+        const unsigned rblocks = (unsigned)std::min<long long>((n_upper + PROP_BLOCK - 1) / PROP_BLOCK, 8 * 256);
+        auto retry = [&](auto C) {
+            hipLaunchKernelGGL((k_raycast_retry<C>), dim3(rblocks), block, 0, ctx->stream, geom->view, rays, st, ctx->hit_triangle,
+                               ctx->hit_distance, ctx->retry_list, ctx->d_counters);
+        };
+        launch_step_begin(first_n);
+        HIP_TRY(record(EV_STEP_BEGIN));
+        if (!plan.chain) {
+            unsigned sblocks = (unsigned)std::min<long long>((n_upper + 255) / 256, (long long)ctx->physics_blocks * 4);
+            hipLaunchKernelGGL(k_ray_setup, dim3(sblocks), dim3(256), 0, ctx->stream, geom->view, work_in, st, rays,
+                               ctx->hit_triangle, ctx->hit_distance, ctx->retry_list, &st->retry, cast == Cast::LITERAL ? 1 : 0);
+        }
+        HIP_TRY(record(EV_PACKET_BEGIN));                             // the ray-cast kernels proper are timed from here
+        const uint32_t *skip_quad = nullptr;
+#if CHROMA_EXPERIMENTAL
+        if (packet) {
+            skip_quad = ctx->d_words + W_PACKET_USE;
+            const unsigned pwaves = (unsigned)std::min<long long>((n_upper + WAVE - 1) / WAVE, (long long)ctx->waves[(int)Cast::QUAD]);
+            with_bool(plan.counting, [&](auto C) {
+                hipLaunchKernelGGL((k_raycast_packet<C>), dim3(pwaves), block, 0, ctx->stream, geom->view, rays, st, ctx->hit_triangle,
+                                   ctx->hit_distance, ctx->retry_list, ctx->d_counters, ctx->d_words + W_PACKET_USE);
+            });
+        }
+#else
+        (void)packet;
+#endif
+        HIP_TRY(record(EV_CAST_BEGIN));
+        const dim3 grid(cast_waves(ctx, cast, n_upper));
+        const int chained = plan.chain ? 1 : 0;
+        with_bool(plan.counting, [&](auto C) {
+            switch (cast) {
+            case Cast::PAIR:
+                hipLaunchKernelGGL((k_raycast_pair<C>), grid, block, 0, ctx->stream, geom->view, rays, 0, st, ctx->hit_triangle,
+                                   ctx->hit_distance, ctx->retry_list, ctx->coop_spill, ctx->d_counters, ctx->coop_chunk);
+                break;
+            case Cast::QUAD:
+                hipLaunchKernelGGL((k_raycast_quad<C>), grid, block, 0, ctx->stream, geom->view, rays, 0, st, ctx->hit_triangle,
+                                   ctx->hit_distance, ctx->retry_list, ctx->coop_spill, ctx->d_counters, ctx->coop_chunk, chained, skip_quad,
+                                   ctx->claim_static);
+                break;
+            case Cast::COOP:
+                hipLaunchKernelGGL((k_raycast_coop<C>), grid, block, 0, ctx->stream, geom->view, rays, 0, st, ctx->hit_triangle,
+                                   ctx->hit_distance, ctx->retry_list, ctx->coop_spill, ctx->d_counters, ctx->coop_chunk);
+                break;
+            case Cast::WIDE:
+                hipLaunchKernelGGL((k_raycast_wide<C>), grid, block, 0, ctx->stream, geom->view, rays, 0, st, ctx->hit_triangle,
+                                   ctx->hit_distance, ctx->retry_list, ctx->wide_spill, ctx->d_counters, ctx->ray_chunk);
+                break;
+            case Cast::PERSISTENT:
+                hipLaunchKernelGGL((k_raycast_persistent<C>), grid, block, 0, ctx->stream, geom->view, rays, 0, st, ctx->hit_triangle,
+                                   ctx->hit_distance, ctx->retry_list, ctx->d_counters);
+                break;
+            case Cast::LITERAL:
+                hipLaunchKernelGGL((k_raycast_literal<C>), grid, block, 0, ctx->stream, geom->view, rays, st, ctx->hit_triangle,
+                                   ctx->hit_distance, ctx->coop_spill, ctx->d_counters, ctx->coop_chunk, chained, ctx->retry_list,
+                                   ctx->claim_static);
+                retry(C);
+                break;
+            case Cast::LITERAL_LANE:
+                hipLaunchKernelGGL((k_raycast_retry<C, true>), grid, block, 0, ctx->stream, geom->view, rays, st, ctx->hit_triangle,
+                                   ctx->hit_distance, ctx->retry_list, ctx->d_counters);
+                break;
+            }
+        });
+        HIP_TRY(record(EV_CAST_END));
+        // physics for every slot whose hit is regular; then the strict walk and the physics of the rest
+        launch_physics(scatter_first, exact ? 2 : 0);
+        HIP_TRY(record(EV_PHYSICS_END));
+        if (!exact) {
+            with_bool(plan.counting, retry);
+            launch_physics(scatter_first, 1);
+        }
+        HIP_TRY(record(EV_STEP_END));
+        HIP_TRY(hipGetLastError());
+        if (plan.chain) std::swap(rays, rays_next);              // (what k_physics wrote is the next step's input)
+        return CHROMA_OK;
+    }
+
+    // All remaining `nsteps` steps of the last photons in one launch (k_tail_coop), for a plan with `tail`.  Sets *done when it launched.
+    int launch_tail(int nsteps, int scatter_first, hipEvent_t *ev, uint32_t first_n, bool *done)
+    {
+        // (a call that ends in k_finalize_hits: that pass runs on the context's auxiliary stream WHILE the tail kernel
+        //  finishes the last photons, which are stamped first so that it leaves them to the tail kernel; the two meet again
+        //  before the call reads its result words.  The tail kernel is launched FIRST: its ~1000 waves are resident before the
+        //  24 000 blocks of the streaming pass fill every wave slot.  Launched second, its workgroups waited for slots behind them
+        //  and the tail ended 1.7 ms after the pass instead of with it: DESIGN.md section 3.2)
+        *done = false;
+        const unsigned waves = cast_waves(ctx, Cast::COOP, n_upper);            // (8 lanes per photon)
+        if ((long long)waves * 8 < n_upper) return CHROMA_OK;          // (cannot happen below 8192 photons)
+        launch_step_begin(first_n);
+        HitsOut beside; memset(&beside, 0, sizeof beside);
+        uint32_t *words = nullptr;
+        if (finalize) {
+            beside = ho;
+            words = ctx->d_words;
+            HIP_TRY(hipMemsetAsync(ctx->d_words, 0, W_RESULT_END * sizeof(uint32_t), ctx->stream));
+            if (final_rec)
+                hipLaunchKernelGGL(k_mark_tail, dim3(32), dim3(256), 0, ctx->stream, in_q, final_rec, photon_tail_stamp(final_epoch));
+            HIP_TRY(hipEventRecord(ctx->ev_fork, ctx->stream));          // (the words are cleared and the tail's photons stamped: the pass may start)
+        }
+        if (ev) HIP_TRY(hipEventRecord(ev[EV_STEP_BEGIN], ctx->stream));
+        with_bool(plan.cast == Cast::LITERAL, [&](auto L) {
+            with_bool(plan.counting, [&](auto C) {
+                hipLaunchKernelGGL((k_tail_coop<C, L>), dim3(waves), dim3(PROP_BLOCK), 0, ctx->stream, geom->view, pv, ctx->d_step, work_in,
+                                   rng.seed, rng.photon_id_base, nsteps, opt.use_weights, scatter_first, ctx->coop_spill, ctx->d_counters, beside, words);
+            });
+        });
+        if (ev) HIP_TRY(hipEventRecord(ev[EV_STEP_END], ctx->stream));
+        if (finalize) {
+            HIP_TRY(hipStreamWaitEvent(ctx->aux_stream, ctx->ev_fork, 0));
+            launch_finalize(ctx->aux_stream, photon_tail_stamp(final_epoch));
+            HIP_TRY(hipEventRecord(ctx->ev_join, ctx->aux_stream));
+            HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
+            finalized = true;              // (the tail kernel writes every photon it held back)
+        }
+        HIP_TRY(hipGetLastError());
+        *done = true;
+        return CHROMA_OK;
+    }
+
+    // k_finalize_hits: the records to the caller's arrays, the abort word, the hit count, the compacted hits, the per-channel arrays
+    void launch_finalize(hipStream_t stream, uint32_t tail_mark)
+    {
+        const unsigned blocks = (unsigned)((nphotons + COPY_ITEMS * 256 - 1) / (COPY_ITEMS * 256));
+        hipLaunchKernelGGL(k_finalize_hits, dim3(blocks), dim3(256), 0, stream, geom->view, pv, (const float4 *)final_rec, final_epoch,
+                           (uint64_t)nphotons, ho, ctx->d_words, tail_mark);
+    }
+
+    // kernel, ray-cast, packet and physics times of a call's first `steps` steps from their events (time_kernels)
+    int read_step_times(int steps, int tail_step)
+    {
+        for (int k = 0; k < steps; k++) {
+            const hipEvent_t *ev = events(k);
+            float ms = 0.f;
+            HIP_TRY(hipEventElapsedTime(&ms, ev[EV_STEP_BEGIN], ev[EV_STEP_END]));
+            acc.kernel_ms += ms;
+            if (k == tail_step) continue;             // the fused tail is not a ray-cast launch
+            HIP_TRY(hipEventElapsedTime(&ms, ev[EV_CAST_BEGIN], ev[EV_CAST_END]));
+            acc.raycast_ms += ms;
+            acc.raycast_launches++;
+            if (k == 0 && plan.packet) {              // the first step's k_raycast_packet launch (an empty one when the photons are not coherent)
+                HIP_TRY(hipEventElapsedTime(&ms, ev[EV_PACKET_BEGIN], ev[EV_CAST_BEGIN]));
+                acc.packet_ms += ms;
+                acc.packet_launches++;
+            }
+            HIP_TRY(hipEventElapsedTime(&ms, ev[EV_CAST_END], ev[EV_PHYSICS_END]));
+            acc.physics_ms += ms;                    // the main pass of k_physics (not the fix-up pass)
+            acc.physics_launches++;
+        }
+        return CHROMA_OK;
+    }
+
+    // Launch policy of the reference (chroma/gpu/photon.py:225-252): one step per launch while many
+    // photons are alive, and ONE launch for all remaining steps once fewer than 64*16*8 are left (or
+    // with weights).  A launch re-normalises dir/pol when it loads a photon (propagate.cu:248,250), so
+    // the policy is part of the arithmetic.  Here every step is a ray cast + physics pair that gets the
+    // whole chip; a step that the reference would run inside its last launch skips the re-normalisation
+    // instead (same numbers; with weights that is every step but the first).  The policy is evaluated ON
+    // THE DEVICE (k_step_begin), so the steps are enqueued back to back; the host looks at the survivor
+    // count only now and then, to stop early, to shrink the grids and to hand the last photons to the
+    // fused tail kernel.  The live photons travel in the dense working set (k_load_working).
+    int run_device_steps()
+    {
+        const int max_steps = opt.max_steps;
+        HIP_TRY(hipMemsetAsync(ctx->d_step, 0, sizeof(StepState), ctx->stream));
+        hipLaunchKernelGGL(k_set_word, dim3(1), dim3(1), 0, ctx->stream, in_q, 1u);
+        hipLaunchKernelGGL(k_set_word, dim3(1), dim3(1), 0, ctx->stream, out_q, 1u);
+        int rc = load_working(); if (rc) return rc;
+        const int nev = opt.time_kernels ? EV_PER_STEP * max_steps : 0;
+        while ((int)ctx->step_events.size() < nev) { hipEvent_t e; HIP_TRY(hipEventCreate(&e)); ctx->step_events.push_back(e); }
+        const long long few = (long long)PROP_BLOCK * 16 * 8;
+        int step = 0, next_check = 1, tail_step = -1;          // (tail_step: the step at which the fused tail was launched)
+        bool done = false;
+        while (step < max_steps && !done) {
+            const int scatter_first = step == 0 ? opt.scatter_first : 0;
+            const uint32_t first_n = step == 0 ? (uint32_t)nphotons : 0u;
+            if (plan.tail && n_upper < few) {
+                // the reference's last launch: all remaining steps at once, 8 lanes per photon
+                rc = launch_tail(max_steps - step, scatter_first, events(step), first_n, &done); if (rc) return rc;
+                if (done) { tail_step = step++; break; }
+            }
+            rc = launch_split_step(scatter_first, events(step), first_n, step == 0 && plan.packet != 0); if (rc) return rc;
+            step++;
+            std::swap(in_q, out_q);
+            std::swap(work_in, work_out);
+            if (step == next_check && step < max_steps) {
+                // survivors = tail - 1 of what is now the input queue
+                HIP_TRY(hipMemcpyAsync(ctx->h_words + W_SURVIVORS, in_q, 4, hipMemcpyDeviceToHost, ctx->stream));
+                HIP_TRY(hipStreamSynchronize(ctx->stream));
+                n_upper = (long long)ctx->h_words[W_SURVIVORS] - 1;
+                if (n_upper <= 0) done = true;
+                // look every step once the tail is near, so that it starts when the reference's does
+                next_check = (plan.tail_watch && n_upper < 16 * few) ? step + 1 : (step < 8) ? step * 2 : step + 8;
+            }
+        }
+        if (!done) {
+            // max_steps reached with photons still alive: they go back to the caller's arrays
+            unsigned blocks = (unsigned)std::min<long long>((n_upper + 255) / 256, 4096);
+            hipLaunchKernelGGL(k_store_working, dim3(std::max(blocks, 1u)), dim3(256), 0, ctx->stream, geom->view, pv, in_q, work_in);
+        }
+        HIP_TRY(hipMemcpyAsync(ctx->h_step, ctx->d_step, sizeof(StepState), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        acc.launches += ((const StepState *)ctx->h_step)->launches;
+        return opt.time_kernels ? read_step_times(step, tail_step) : CHROMA_OK;
+    }
+
+    // CHROMA_TAIL=fused: the lane-per-photon kernel with the reference's own launch shapes
+    int run_fused()
+    {
+        hipLaunchKernelGGL(k_init_queue, dim3((unsigned)((nphotons + 255) / 256)), dim3(256), 0, ctx->stream, in_q,
+                           (uint64_t)nphotons, ncopies, (uint32_t)(nphotons / ncopies));
+        hipLaunchKernelGGL(k_set_word, dim3(1), dim3(1), 0, ctx->stream, out_q, 1u);
+        HIP_TRY(hipGetLastError());
+        const int max_steps = opt.max_steps;
+        int scatter_first = opt.scatter_first;
+        uint64_t n = nphotons;
+        int step = 0;
+        while (step < max_steps) {
+            const bool few = n < (uint64_t)PROP_BLOCK * 16 * 8;
+            int nsteps = (few || opt.use_weights) ? (max_steps - step) : 1;
+            if (opt.time_kernels) HIP_TRY(hipEventRecord(ctx->ev_start, ctx->stream));
+            int rc = launch_propagate(ctx, plan.counting, geom, pv, rng, {0, (int)n, in_q + 1, out_q, nsteps, opt.use_weights, scatter_first});
+            if (rc) return rc;
+            acc.launches++;
+            if (opt.time_kernels) {
+                HIP_TRY(hipEventRecord(ctx->ev_stop, ctx->stream));
+                HIP_TRY(hipEventSynchronize(ctx->ev_stop));
+                float ms = 0.f;
+                HIP_TRY(hipEventElapsedTime(&ms, ctx->ev_start, ctx->ev_stop));
+                acc.kernel_ms += ms;
+            }
+            step += nsteps;
+            scatter_first = 0;
+            if (step < max_steps) {
+                std::swap(in_q, out_q);
+                // survivors = tail - 1 (one 4-byte read per step, as photon.py:250)
+                HIP_TRY(hipMemcpyAsync(ctx->h_words + W_SURVIVORS, in_q, 4, hipMemcpyDeviceToHost, ctx->stream));
+                hipLaunchKernelGGL(k_set_word, dim3(1), dim3(1), 0, ctx->stream, out_q, 1u);
+                HIP_TRY(hipStreamSynchronize(ctx->stream));
+                n = (uint64_t)ctx->h_words[W_SURVIVORS] - 1;
+                if (n == 0) break;
+            }
+        }
+        return CHROMA_OK;
+    }
+
+    // The call's last pass and its report.  A finalizing call: one pass takes the records to the caller's arrays and writes the
+    // abort word, the hit count, the compacted hits and the per-channel arrays (k_finalize_hits), unless it has run beside the
+    // tail kernel already (`finalized`, launch_tail).  Otherwise the abort word alone (photon.py:254-255).
+    int finish(chroma_hits_request *hr, chroma_propagate_stats *stats, int32_t *aborted)
+    {
+        uint32_t word = 0;
+        if (finalize) {
+            if (!finalized) {
+                HIP_TRY(hipMemsetAsync(ctx->d_words, 0, W_RESULT_END * sizeof(uint32_t), ctx->stream));
+                launch_finalize(ctx->stream, 0u);
+                HIP_TRY(hipGetLastError());
+            }
+            HIP_TRY(hipMemcpyAsync(ctx->h_words, ctx->d_words, W_RESULT_END * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(hipStreamSynchronize(ctx->stream));
+            word = ctx->h_words[W_ABORT];
+            if (hr) hr->nhits = ctx->h_words[W_HIT_COUNT];
+        } else {
+            HIP_TRY(hipMemsetAsync(ctx->d_words + W_ABORT, 0, 4, ctx->stream));
+            const unsigned blocks = (unsigned)std::min<uint64_t>((nphotons + 255) / 256, 4096);
+            hipLaunchKernelGGL(k_flags_or, dim3(blocks), dim3(256), 0, ctx->stream, pv.flags, (uint64_t)nphotons, CHROMA_NAN_ABORT,
+                               ctx->d_words + W_ABORT);
+            HIP_TRY(hipGetLastError());
+            int rc = read_word(ctx, W_ABORT, &word); if (rc) return rc;
+        }
+        if (aborted) *aborted = (word & CHROMA_NAN_ABORT) ? 1 : 0;
+        chroma_propagate_stats tmp; memset(&tmp, 0, sizeof tmp);
+        chroma_propagate_stats *s = stats ? stats : &tmp;
+        int rc = chroma_propagate_stats_read(ctx, s); if (rc) return rc;
+        if (stats) {
+            stats->launches += acc.launches;
+            stats->kernel_ms += acc.kernel_ms;
+            stats->raycast_ms += acc.raycast_ms;
+            stats->raycast_launches += acc.raycast_launches;
+            stats->physics_ms += acc.physics_ms;
+            stats->physics_launches += acc.physics_launches;
+            stats->packet_ms += acc.packet_ms;
+            stats->packet_launches += acc.packet_launches;
+            stats->reordered += acc.reordered;
+        }
+        if (s->stack_overflows) return set_error(CHROMA_ERR_STACK, "traversal stack overflowed for %llu rays", (unsigned long long)s->stack_overflows);
+        return CHROMA_OK;
+    }
+};
 }
 
 // chroma_init's share of this file: the grids of the ray-cast kernels from their residency, the walk and the launch policy
 // from the CHROMA_* environment
 int propagate_settings(chroma_ctx *ctx)
 {
-    const int device = ctx->device;
     hipDeviceProp_t prop;
-    HIP_TRY(hipGetDeviceProperties(&prop, device));
-    int per_cu = 20;                     // LDS-limited residency of k_raycast_persistent (8 KB per wave)
-    if (const char *e = getenv("CHROMA_RAY_WAVES_PER_CU")) per_cu = std::max(1, atoi(e));
-    ctx->persistent_waves = prop.multiProcessorCount * per_cu;
+    HIP_TRY(hipGetDeviceProperties(&prop, ctx->device));
     ctx->physics_blocks = prop.multiProcessorCount * 8;          // (for blocks of PHYS_BLOCK threads)
-    int wide_per_cu = 14;                // LDS-limited residency of k_raycast_wide
-    if (const char *e = getenv("CHROMA_WIDE_WAVES_PER_CU")) wide_per_cu = std::max(1, atoi(e));
-    ctx->wide_waves = prop.multiProcessorCount * wide_per_cu;
-    int coop_per_cu = 28;                // 71 VGPRs (amdgpu_waves_per_eu 7): 7 waves per SIMD
-    if (const char *e = getenv("CHROMA_COOP_WAVES_PER_CU")) coop_per_cu = std::max(1, atoi(e));
-    ctx->coop_waves = prop.multiProcessorCount * coop_per_cu;
-    int quad_per_cu = 4 * QUAD_WAVES_PER_EU;
-    if (const char *e = getenv("CHROMA_QUAD_WAVES_PER_CU")) quad_per_cu = std::max(1, atoi(e));
-    ctx->quad_waves = prop.multiProcessorCount * quad_per_cu;
-    int pair_per_cu = 4 * PAIR_WAVES_PER_EU;
-    if (const char *e = getenv("CHROMA_PAIR_WAVES_PER_CU")) pair_per_cu = std::max(1, atoi(e));
-    ctx->pair_waves = prop.multiProcessorCount * pair_per_cu;
-    if (const char *e = getenv("CHROMA_WALK"))
-        ctx->walk = !strcmp(e, "reference") ? CHROMA_WALK_REFERENCE : !strcmp(e, "wide") ? CHROMA_WALK_WIDE
-                  : !strcmp(e, "coop") ? CHROMA_WALK_COOP : !strcmp(e, "pair") ? CHROMA_WALK_PAIR
-                  : (!strcmp(e, "literal") || !strcmp(e, "exact")) ? CHROMA_WALK_LITERAL
-                  : !strcmp(e, "literal_lane") ? CHROMA_WALK_LITERAL_LANE : CHROMA_WALK_QUAD;
+    const char *walk = getenv("CHROMA_WALK");
+    if (walk) ctx->walk = CHROMA_WALK_QUAD;                      // (what is no walk's name means the default)
+    for (int w = 0; w < NWALKS; w++) {
+        const Walk &row = WALKS[w];
+        int per_cu = row.waves_per_cu;
+        if (const char *e = getenv(row.waves_env)) per_cu = std::max(1, atoi(e));
+        ctx->waves[(int)row.cast] = prop.multiProcessorCount * per_cu;
+        if (walk && (!strcmp(walk, row.name) || (row.alias && !strcmp(walk, row.alias)))) ctx->walk = w;
+    }
 #if CHROMA_EXPERIMENTAL
     if (const char *e = getenv("CHROMA_PACKET")) ctx->packet_mode = !strcmp(e, "on") ? 1 : !strcmp(e, "auto") ? 2 : 0;
     if (const char *e = getenv("CHROMA_AUTOSORT")) ctx->autosort_mode = !strcmp(e, "on") || !strcmp(e, "1") ? 1 : !strcmp(e, "off") || !strcmp(e, "0") ? 0 : 2;
@@ -442,43 +663,26 @@ int chroma_propagate_step(chroma_ctx *ctx, chroma_geometry *geom, int32_t first_
     if (first_photon < 0 || nthreads < 0) return set_error(CHROMA_ERR_INVALID, "negative photon range");
     if (nthreads == 0) return CHROMA_OK;
     if ((rc = check_stack(geom))) return rc;
-    return launch_propagate(ctx, ctx->counting != 0, geom, to_view(photons), first_photon, nthreads, d_input_queue, d_output_queue, rng,
-                            max_steps, use_weights, scatter_first);
+    return launch_propagate(ctx, ctx->counting != 0, geom, to_view(photons), rng,
+                            {first_photon, nthreads, d_input_queue, d_output_queue, max_steps, use_weights, scatter_first});
 }
 
-static int ensure_queues(chroma_ctx *ctx, size_t n);
+static int ensure_queues(chroma_ctx *ctx, size_t n)
+{
+    if (ctx->queue_capacity >= n + 1) return CHROMA_OK;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    const auto buffers = queue_buffers(ctx);
+    for (const QueueBuffer &b : buffers) { if (*b.ptr) hipFree(*b.ptr); *b.ptr = nullptr; }
+    ctx->queue_capacity = 0;
+    for (const QueueBuffer &b : buffers) HIP_TRY(ctx_malloc(ctx, b.ptr, (n + 1) * b.bytes));
+    ctx->queue_capacity = n + 1;
+    return CHROMA_OK;
+}
 
 int chroma_distance_to_mesh(chroma_ctx *ctx, chroma_geometry *geom, int32_t nthreads, const float *d_origin,
                             const float *d_direction, float *d_distance, int32_t *d_triangle)
 {
     return chroma_intersect_mesh(ctx, geom, nthreads, d_origin, d_direction, nullptr, d_distance, d_triangle);
-}
-
-// the quad walk of the default propagate step over a caller's rays: k_raycast_quad, then the strict loop for the rays it hands over
-static int distance_to_mesh_fast(chroma_ctx *ctx, bool counting, chroma_geometry *geom, int32_t n, const float *d_origin,
-                                 const float *d_direction, const int32_t *d_last_hit, float *d_distance, int32_t *d_triangle)
-{
-    HIP_TRY(hipSetDevice(ctx->device));
-    int rc = ensure_queues(ctx, (size_t)n); if (rc) return rc;
-    rc = ensure_spill(ctx, SPILL_COOP); if (rc) return rc;
-    StepState *st = ctx->d_step;
-    const unsigned blocks = (unsigned)((n + 255) / 256);
-    hipLaunchKernelGGL(k_step_set, dim3(1), dim3(1), 0, ctx->stream, st, (uint32_t)n);
-    hipLaunchKernelGGL(k_rays_from_arrays, dim3(blocks), dim3(256), 0, ctx->stream, geom->view, (int)n, d_origin, d_direction,
-                       d_last_hit, ctx->rays, ctx->hit_triangle, ctx->hit_distance, ctx->retry_list, st);
-    const unsigned waves = cast_waves(ctx, Cast::QUAD, n);
-    with_bool(counting, [&](auto C) {
-        hipLaunchKernelGGL((k_raycast_quad<C>), dim3(waves), dim3(PROP_BLOCK), 0, ctx->stream, geom->view, ctx->rays, 0, st,
-                           ctx->hit_triangle, ctx->hit_distance, ctx->retry_list, ctx->coop_spill, ctx->d_counters, ctx->coop_chunk, 0, nullptr, ctx->claim_static);
-    });
-    hipLaunchKernelGGL(k_distance_finish, dim3(blocks), dim3(256), 0, ctx->stream, geom->view, (int)n, ctx->rays, ctx->hit_triangle,
-                       ctx->hit_distance, d_distance, d_triangle, ctx->retry_list, st);
-    with_bool(counting, [&](auto C) {
-        hipLaunchKernelGGL((k_distance_retry<C>), dim3(256), dim3(PROP_BLOCK), 0, ctx->stream, geom->view, ctx->rays, st,
-                           ctx->retry_list, d_distance, d_triangle, ctx->d_counters);
-    });
-    HIP_TRY(hipGetLastError());
-    return CHROMA_OK;
 }
 
 int chroma_intersect_mesh(chroma_ctx *ctx, chroma_geometry *geom, int32_t nthreads, const float *d_origin,
@@ -490,50 +694,40 @@ int chroma_intersect_mesh(chroma_ctx *ctx, chroma_geometry *geom, int32_t nthrea
     int rc = make_plan(ctx, geom, -1, -1, -1, &plan); if (rc) return rc;
     if ((rc = check_stack(geom))) return rc;
     std::lock_guard<std::mutex> call_lock(ctx->call_mu);          // (the fast path uses the context's queues and ray records, as a propagate call does)
-    if (plan.isect_quad)
-        return distance_to_mesh_fast(ctx, plan.counting, geom, nthreads, d_origin, d_direction, d_last_hit, d_distance, d_triangle);
-    const dim3 grid((unsigned)((nthreads + PROP_BLOCK - 1) / PROP_BLOCK)), block(PROP_BLOCK);
+    if (!plan.isect_quad) {
+        const dim3 grid((unsigned)((nthreads + PROP_BLOCK - 1) / PROP_BLOCK)), block(PROP_BLOCK);
+        with_bool(plan.counting, [&](auto C) {
+            hipLaunchKernelGGL((k_distance_to_mesh<STACK_LDS, C>), grid, block, 0, ctx->stream, geom->view, nthreads, d_origin, d_direction,
+                               d_last_hit, d_distance, d_triangle, ctx->d_counters);
+        });
+        HIP_TRY(hipGetLastError());
+        return CHROMA_OK;
+    }
+    // the quad walk of the default propagate step over the caller's rays: k_raycast_quad, then the strict loop for the rays it hands over
+    HIP_TRY(hipSetDevice(ctx->device));
+    rc = ensure_queues(ctx, (size_t)nthreads); if (rc) return rc;
+    rc = ensure_spill(ctx, SPILL_COOP); if (rc) return rc;
+    StepState *st = ctx->d_step;
+    const unsigned blocks = (unsigned)((nthreads + 255) / 256);
+    hipLaunchKernelGGL(k_step_set, dim3(1), dim3(1), 0, ctx->stream, st, (uint32_t)nthreads);
+    hipLaunchKernelGGL(k_rays_from_arrays, dim3(blocks), dim3(256), 0, ctx->stream, geom->view, (int)nthreads, d_origin, d_direction,
+                       d_last_hit, ctx->rays, ctx->hit_triangle, ctx->hit_distance, ctx->retry_list, st);
+    const unsigned waves = cast_waves(ctx, Cast::QUAD, nthreads);
     with_bool(plan.counting, [&](auto C) {
-        hipLaunchKernelGGL((k_distance_to_mesh<STACK_LDS, C>), grid, block, 0, ctx->stream, geom->view, nthreads, d_origin, d_direction,
-                           d_last_hit, d_distance, d_triangle, ctx->d_counters);
+        hipLaunchKernelGGL((k_raycast_quad<C>), dim3(waves), dim3(PROP_BLOCK), 0, ctx->stream, geom->view, ctx->rays, 0, st,
+                           ctx->hit_triangle, ctx->hit_distance, ctx->retry_list, ctx->coop_spill, ctx->d_counters, ctx->coop_chunk, 0, nullptr, ctx->claim_static);
+    });
+    hipLaunchKernelGGL(k_distance_finish, dim3(blocks), dim3(256), 0, ctx->stream, geom->view, (int)nthreads, ctx->rays, ctx->hit_triangle,
+                       ctx->hit_distance, d_distance, d_triangle, ctx->retry_list, st);
+    with_bool(plan.counting, [&](auto C) {
+        hipLaunchKernelGGL((k_distance_retry<C>), dim3(256), dim3(PROP_BLOCK), 0, ctx->stream, geom->view, ctx->rays, st,
+                           ctx->retry_list, d_distance, d_triangle, ctx->d_counters);
     });
     HIP_TRY(hipGetLastError());
     return CHROMA_OK;
 }
 
 // ---- fused host loops -----------------------------------------------------------------------------------
-static int ensure_queues(chroma_ctx *ctx, size_t n)
-{
-    if (ctx->queue_capacity >= n + 1) return CHROMA_OK;
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (ctx->queue_a) hipFree(ctx->queue_a);
-    if (ctx->queue_b) hipFree(ctx->queue_b);
-    if (ctx->hit_triangle) hipFree(ctx->hit_triangle);
-    if (ctx->hit_distance) hipFree(ctx->hit_distance);
-    if (ctx->retry_list) hipFree(ctx->retry_list);
-    if (ctx->rays) hipFree(ctx->rays);
-    if (ctx->rays_b) hipFree(ctx->rays_b);
-    if (ctx->work_a) hipFree(ctx->work_a);
-    if (ctx->work_b) hipFree(ctx->work_b);
-    ctx->work_a = ctx->work_b = nullptr;
-    ctx->queue_a = ctx->queue_b = nullptr;
-    ctx->hit_triangle = nullptr; ctx->hit_distance = nullptr; ctx->retry_list = nullptr;
-    ctx->rays = nullptr;
-    ctx->rays_b = nullptr;
-    ctx->queue_capacity = 0;
-    HIP_TRY(ctx_malloc(ctx, (void **)&ctx->queue_a, (n + 1) * sizeof(uint32_t)));
-    HIP_TRY(ctx_malloc(ctx, (void **)&ctx->queue_b, (n + 1) * sizeof(uint32_t)));
-    HIP_TRY(ctx_malloc(ctx, (void **)&ctx->hit_triangle, (n + 1) * sizeof(int32_t)));
-    HIP_TRY(ctx_malloc(ctx, (void **)&ctx->hit_distance, (n + 1) * sizeof(float)));
-    HIP_TRY(ctx_malloc(ctx, (void **)&ctx->retry_list, (n + 1) * sizeof(uint32_t)));
-    HIP_TRY(ctx_malloc(ctx, (void **)&ctx->rays, (n + 1) * 4 * sizeof(float4)));
-    HIP_TRY(ctx_malloc(ctx, (void **)&ctx->rays_b, (n + 1) * 4 * sizeof(float4)));
-    HIP_TRY(ctx_malloc(ctx, (void **)&ctx->work_a, (n + 1) * 4 * sizeof(float4)));
-    HIP_TRY(ctx_malloc(ctx, (void **)&ctx->work_b, (n + 1) * 4 * sizeof(float4)));
-    ctx->queue_capacity = n + 1;
-    return CHROMA_OK;
-}
-
 int chroma_propagate_stats_read(chroma_ctx *ctx, chroma_propagate_stats *stats)
 {
     if (!ctx || !stats) return set_error(CHROMA_ERR_INVALID, "bad argument");
@@ -562,9 +756,7 @@ int chroma_set_counting(chroma_ctx *ctx, int32_t enabled)
 int chroma_set_walk(chroma_ctx *ctx, int32_t mode)
 {
     if (!ctx) return set_error(CHROMA_ERR_INVALID, "null ctx");
-    if (mode != CHROMA_WALK_REFERENCE && mode != CHROMA_WALK_WIDE && mode != CHROMA_WALK_COOP && mode != CHROMA_WALK_QUAD &&
-        mode != CHROMA_WALK_PAIR && mode != CHROMA_WALK_LITERAL && mode != CHROMA_WALK_LITERAL_LANE)
-        return set_error(CHROMA_ERR_INVALID, "unknown walk mode %d", mode);
+    if (mode < 0 || mode >= NWALKS) return set_error(CHROMA_ERR_INVALID, "unknown walk mode %d", mode);
     ctx->walk = mode;
     return CHROMA_OK;
 }
@@ -604,7 +796,7 @@ int chroma_set_tail(chroma_ctx *ctx, int32_t mode)
 #include "experimental/autosort.h"
 #else
 // (product build: a call takes its photons as they come -- the engine-side direction sort lives in experimental/autosort.h)
-static int propagate_order(chroma_ctx *, const CallPlan &, const PhotonView &, uint64_t, uint32_t, uint32_t **d_order) { *d_order = nullptr; return CHROMA_OK; }
+static int propagate_order(PropagateCall &, uint32_t **d_order) { *d_order = nullptr; return CHROMA_OK; }
 #endif
 
 // the photons' final records (chroma_propagate_hits): 64 bytes per photon of the largest batch seen, zeroed once -- a record
@@ -619,204 +811,6 @@ static int ensure_final_records(chroma_ctx *ctx, size_t n)
     HIP_TRY(hipMemsetAsync(ctx->final_rec, 0, n * 4 * sizeof(float4), ctx->stream));
     ctx->final_capacity = n;
     ctx->final_epoch = 0;
-    return CHROMA_OK;
-}
-
-// the live photons into the dense working set (k_load_working), with the first step's ray records when the rays chain
-static int load_working(chroma_ctx *ctx, const CallPlan &plan, chroma_geometry *geom, const PhotonView &pv, uint64_t nphotons,
-                        uint32_t ncopies, uint32_t *in_q, float4 *work_in, chroma_propagate_stats *acc)
-{
-    const unsigned blocks = (unsigned)std::min<uint64_t>((nphotons + PHYS_BLOCK - 1) / PHYS_BLOCK, (uint64_t)ctx->physics_blocks);
-    HIP_TRY(hipMemsetAsync(ctx->d_words + 4, 0, 12, ctx->stream));          // [4] use_packet, [5] coherent waves, [6] waves
-    uint32_t *d_order = nullptr;
-    int rc = propagate_order(ctx, plan, pv, nphotons, ncopies, &d_order); if (rc) return rc;
-    hipLaunchKernelGGL(k_load_working, dim3(blocks), dim3(PHYS_BLOCK), 0, ctx->stream, geom->view, pv, in_q, work_in,
-                       (uint64_t)nphotons, ncopies, (uint32_t)(nphotons / ncopies), plan.chain ? ctx->rays : nullptr,
-                       plan.packet == 2 ? ctx->d_words + 5 : nullptr, (const uint32_t *)d_order, plan.cast == Cast::LITERAL ? 1 : 0);
-    if (d_order) { chroma_free(ctx, d_order); acc->reordered += nphotons; }      // (parked until the stream has passed this point)
-#if CHROMA_EXPERIMENTAL
-    if (plan.packet)
-        hipLaunchKernelGGL(k_packet_decide, dim3(1), dim3(1), 0, ctx->stream, ctx->d_words + 5, ctx->d_words + 4, (uint64_t)nphotons, plan.packet);
-#endif
-    HIP_TRY(hipGetLastError());
-    return CHROMA_OK;
-}
-
-// kernel, ray-cast, packet and physics times of a call's first `steps` steps from their events (time_kernels)
-static int read_step_times(chroma_ctx *ctx, int steps, int tail_step, bool packet, chroma_propagate_stats *acc)
-{
-    for (int k = 0; k < steps; k++) {
-        const hipEvent_t *ev = ctx->step_events.data() + EV_PER_STEP * k;
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, ev[EV_STEP_BEGIN], ev[EV_STEP_END]));
-        acc->kernel_ms += ms;
-        if (k == tail_step) continue;             // the fused tail is not a ray-cast launch
-        HIP_TRY(hipEventElapsedTime(&ms, ev[EV_CAST_BEGIN], ev[EV_CAST_END]));
-        acc->raycast_ms += ms;
-        acc->raycast_launches++;
-        if (k == 0 && packet) {                   // the first step's k_raycast_packet launch (an empty one when the photons are not coherent)
-            HIP_TRY(hipEventElapsedTime(&ms, ev[EV_PACKET_BEGIN], ev[EV_CAST_BEGIN]));
-            acc->packet_ms += ms;
-            acc->packet_launches++;
-        }
-        HIP_TRY(hipEventElapsedTime(&ms, ev[EV_CAST_END], ev[EV_PHYSICS_END]));
-        acc->physics_ms += ms;                    // the main pass of k_physics (not the fix-up pass)
-        acc->physics_launches++;
-    }
-    return CHROMA_OK;
-}
-
-// Launch policy of the reference (chroma/gpu/photon.py:225-252): one step per launch while many
-// photons are alive, and ONE launch for all remaining steps once fewer than 64*16*8 are left (or
-// with weights).  A launch re-normalises dir/pol when it loads a photon (propagate.cu:248,250), so
-// the policy is part of the arithmetic.  Here every step is a ray cast + physics pair that gets the
-// whole chip; a step that the reference would run inside its last launch skips the re-normalisation
-// instead (same numbers; with weights that is every step but the first).  The policy is evaluated ON
-// THE DEVICE (k_step_begin), so the steps are enqueued back to back; the host looks at the survivor
-// count only now and then, to stop early, to shrink the grids and to hand the last photons to the
-// fused tail kernel.  The live photons travel in the dense working set (k_load_working).
-// `beside`: the hits request of a call that ends in k_finalize_hits (*finalized: the tail kernel has run it already).
-static int run_device_steps(chroma_ctx *ctx, const CallPlan &plan, chroma_geometry *geom, const PhotonView &pv, uint64_t nphotons,
-                            uint32_t ncopies, chroma_rng rng, const chroma_propagate_options &opt, const HitsOut *beside,
-                            chroma_propagate_stats *acc, bool *finalized)
-{
-    const int max_steps = opt.max_steps, use_weights = opt.use_weights;
-    uint32_t *in_q = ctx->queue_a, *out_q = ctx->queue_b;
-    float4 *work_in = ctx->work_a, *work_out = ctx->work_b;
-    HIP_TRY(hipMemsetAsync(ctx->d_step, 0, sizeof(StepState), ctx->stream));
-    hipLaunchKernelGGL(k_set_word, dim3(1), dim3(1), 0, ctx->stream, in_q, 1u);
-    hipLaunchKernelGGL(k_set_word, dim3(1), dim3(1), 0, ctx->stream, out_q, 1u);
-    int rc = load_working(ctx, plan, geom, pv, nphotons, ncopies, in_q, work_in, acc); if (rc) return rc;
-    const int nev = opt.time_kernels ? EV_PER_STEP * max_steps : 0;
-    while ((int)ctx->step_events.size() < nev) { hipEvent_t e; HIP_TRY(hipEventCreate(&e)); ctx->step_events.push_back(e); }
-    auto events = [&](int step) { return opt.time_kernels ? ctx->step_events.data() + EV_PER_STEP * step : nullptr; };
-    const long long few = (long long)PROP_BLOCK * 16 * 8;
-    long long n_upper = (long long)nphotons;
-    int step = 0, next_check = 1, tail_step = -1;          // (tail_step: the step at which the fused tail was launched)
-    bool done = false;
-    while (step < max_steps && !done) {
-        const int scatter_first = step == 0 ? opt.scatter_first : 0;
-        const uint32_t first_n = step == 0 ? (uint32_t)nphotons : 0u;
-        if (plan.tail && n_upper < few) {
-            // the reference's last launch: all remaining steps at once, 8 lanes per photon
-            rc = launch_tail(ctx, plan, geom, pv, n_upper, in_q, out_q, work_in, rng, max_steps - step, use_weights, scatter_first,
-                             events(step), &done, first_n, beside, nphotons);
-            if (rc) return rc;
-            if (done) { *finalized = beside != nullptr; tail_step = step++; break; }     // (it wrote every photon it held back)
-        }
-        rc = launch_split_step(ctx, plan, geom, pv, n_upper, in_q, out_q, work_in, work_out, rng, use_weights, scatter_first,
-                               events(step), first_n, step == 0 && plan.packet != 0);
-        if (rc) return rc;
-        step++;
-        std::swap(in_q, out_q);
-        std::swap(work_in, work_out);
-        if (step == next_check && step < max_steps) {
-            // survivors = tail - 1 of what is now the input queue
-            HIP_TRY(hipMemcpyAsync(ctx->h_words + 1, in_q, 4, hipMemcpyDeviceToHost, ctx->stream));
-            HIP_TRY(hipStreamSynchronize(ctx->stream));
-            n_upper = (long long)ctx->h_words[1] - 1;
-            if (n_upper <= 0) done = true;
-            // look every step once the tail is near, so that it starts when the reference's does
-            next_check = (plan.tail_watch && n_upper < 16 * few) ? step + 1 : (step < 8) ? step * 2 : step + 8;
-        }
-    }
-    if (!done) {
-        // max_steps reached with photons still alive: they go back to the caller's arrays
-        unsigned blocks = (unsigned)std::min<long long>((n_upper + 255) / 256, 4096);
-        hipLaunchKernelGGL(k_store_working, dim3(std::max(blocks, 1u)), dim3(256), 0, ctx->stream, geom->view, pv, in_q, work_in);
-    }
-    HIP_TRY(hipMemcpyAsync(ctx->h_step, ctx->d_step, sizeof(StepState), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    acc->launches += ((const StepState *)ctx->h_step)->launches;
-    return opt.time_kernels ? read_step_times(ctx, step, tail_step, plan.packet != 0, acc) : CHROMA_OK;
-}
-
-// CHROMA_TAIL=fused: the lane-per-photon kernel with the reference's own launch shapes
-static int run_fused(chroma_ctx *ctx, const CallPlan &plan, chroma_geometry *geom, const PhotonView &pv, uint64_t nphotons,
-                     uint32_t ncopies, chroma_rng rng, const chroma_propagate_options &opt, chroma_propagate_stats *acc)
-{
-    uint32_t *in_q = ctx->queue_a, *out_q = ctx->queue_b;
-    hipLaunchKernelGGL(k_init_queue, dim3((unsigned)((nphotons + 255) / 256)), dim3(256), 0, ctx->stream, in_q,
-                       (uint64_t)nphotons, ncopies, (uint32_t)(nphotons / ncopies));
-    hipLaunchKernelGGL(k_set_word, dim3(1), dim3(1), 0, ctx->stream, out_q, 1u);
-    HIP_TRY(hipGetLastError());
-    const int max_steps = opt.max_steps;
-    int scatter_first = opt.scatter_first;
-    uint64_t n = nphotons;
-    int step = 0;
-    while (step < max_steps) {
-        const bool few = n < (uint64_t)PROP_BLOCK * 16 * 8;
-        int nsteps = (few || opt.use_weights) ? (max_steps - step) : 1;
-        if (opt.time_kernels) HIP_TRY(hipEventRecord(ctx->ev_start, ctx->stream));
-        int rc = launch_propagate(ctx, plan.counting, geom, pv, 0, (int)n, in_q + 1, out_q, rng, nsteps, opt.use_weights, scatter_first);
-        if (rc) return rc;
-        acc->launches++;
-        if (opt.time_kernels) {
-            HIP_TRY(hipEventRecord(ctx->ev_stop, ctx->stream));
-            HIP_TRY(hipEventSynchronize(ctx->ev_stop));
-            float ms = 0.f;
-            HIP_TRY(hipEventElapsedTime(&ms, ctx->ev_start, ctx->ev_stop));
-            acc->kernel_ms += ms;
-        }
-        step += nsteps;
-        scatter_first = 0;
-        if (step < max_steps) {
-            std::swap(in_q, out_q);
-            // survivors = tail - 1 (one 4-byte read per step, as photon.py:250)
-            HIP_TRY(hipMemcpyAsync(ctx->h_words + 1, in_q, 4, hipMemcpyDeviceToHost, ctx->stream));
-            hipLaunchKernelGGL(k_set_word, dim3(1), dim3(1), 0, ctx->stream, out_q, 1u);
-            HIP_TRY(hipStreamSynchronize(ctx->stream));
-            n = (uint64_t)ctx->h_words[1] - 1;
-            if (n == 0) break;
-        }
-    }
-    return CHROMA_OK;
-}
-
-// The call's last pass and its report.  `finalize` (a hits request, or final records): one pass takes the records to the
-// caller's arrays and writes the abort word, the hit count, the compacted hits and the per-channel arrays (k_finalize_hits),
-// unless it has run beside the tail kernel already (`finalized`, launch_tail).  Otherwise the abort word alone (photon.py:254-255).
-static int finish_call(chroma_ctx *ctx, chroma_geometry *geom, const chroma_photon_arrays *photons, uint64_t nphotons,
-                       const HitsOut *finalize, bool finalized, chroma_hits_request *hr, const chroma_propagate_stats &acc,
-                       chroma_propagate_stats *stats, int32_t *aborted)
-{
-    uint32_t word = 0;
-    if (finalize) {
-        if (!finalized) {
-            HIP_TRY(hipMemsetAsync(ctx->d_words, 0, 12, ctx->stream));
-            const unsigned blocks = (unsigned)((nphotons + COPY_ITEMS * 256 - 1) / (COPY_ITEMS * 256));
-            hipLaunchKernelGGL(k_finalize_hits, dim3(blocks), dim3(256), 0, ctx->stream, geom->view, to_view(photons), (const float4 *)ctx->final_use,
-                               ctx->final_epoch, (uint64_t)nphotons, *finalize, ctx->d_words, 0u);
-            HIP_TRY(hipGetLastError());
-        }
-        HIP_TRY(hipMemcpyAsync(ctx->h_words, ctx->d_words, 12, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        word = ctx->h_words[2];
-        if (hr) hr->nhits = ctx->h_words[0];
-    } else {
-        HIP_TRY(hipMemsetAsync(ctx->d_words + 2, 0, 4, ctx->stream));
-        const unsigned blocks = (unsigned)std::min<uint64_t>((nphotons + 255) / 256, 4096);
-        hipLaunchKernelGGL(k_flags_or, dim3(blocks), dim3(256), 0, ctx->stream, photons->flags, (uint64_t)nphotons, CHROMA_NAN_ABORT,
-                           ctx->d_words + 2);
-        HIP_TRY(hipGetLastError());
-        int rc = read_word(ctx, 2, &word); if (rc) return rc;
-    }
-    if (aborted) *aborted = (word & CHROMA_NAN_ABORT) ? 1 : 0;
-    chroma_propagate_stats tmp; memset(&tmp, 0, sizeof tmp);
-    chroma_propagate_stats *s = stats ? stats : &tmp;
-    int rc = chroma_propagate_stats_read(ctx, s); if (rc) return rc;
-    if (stats) {
-        stats->launches += acc.launches;
-        stats->kernel_ms += acc.kernel_ms;
-        stats->raycast_ms += acc.raycast_ms;
-        stats->raycast_launches += acc.raycast_launches;
-        stats->physics_ms += acc.physics_ms;
-        stats->physics_launches += acc.physics_launches;
-        stats->packet_ms += acc.packet_ms;
-        stats->packet_launches += acc.packet_launches;
-        stats->reordered += acc.reordered;
-    }
-    if (s->stack_overflows) return set_error(CHROMA_ERR_STACK, "traversal stack overflowed for %llu rays", (unsigned long long)s->stack_overflows);
     return CHROMA_OK;
 }
 
@@ -848,7 +842,6 @@ static int propagate_impl(chroma_ctx *ctx, chroma_geometry *geom, const chroma_p
     // (final records: with a hit request, or for every call under CHROMA_FINAL_RECORDS=1 -- an A/B switch)
     static const bool records_always = getenv("CHROMA_FINAL_RECORDS") && atoi(getenv("CHROMA_FINAL_RECORDS")) != 0;
     const bool use_records = (hr != nullptr || records_always) && plan.tail_mode != CHROMA_TAIL_FUSED;
-    ctx->final_use = nullptr;
     if (use_records) {
         rc = ensure_final_records(ctx, nphotons); if (rc) return rc;
         ctx->final_epoch++;
@@ -856,25 +849,20 @@ static int propagate_impl(chroma_ctx *ctx, chroma_geometry *geom, const chroma_p
             HIP_TRY(hipMemsetAsync(ctx->final_rec, 0, ctx->final_capacity * 4 * sizeof(float4), ctx->stream));
             ctx->final_epoch = 1u;
         }
-        ctx->final_use = ctx->final_rec;
     }
-    struct FinalGuard { chroma_ctx *c; ~FinalGuard() { c->final_use = nullptr; } } final_guard{ctx};
-    // where the call's last pass (k_finalize_hits) puts the hits, if it runs at all
-    HitsOut ho; memset(&ho, 0, sizeof ho);
+    PropagateCall call = {ctx, geom, plan, to_view(photons), rng, opt, nphotons, ncopies, ctx->queue_a, ctx->queue_b, ctx->work_a, ctx->work_b,
+                          ctx->rays, ctx->rays_b, use_records ? ctx->final_rec : nullptr, ctx->final_epoch};
     if (hr) {
-        ho.want = 1;
-        ho.detection_state = hr->detection_state;
-        if (hr->dst) { ho.dst = to_view(hr->dst); ho.channels = hr->d_channels; ho.capacity = hr->capacity; }
-        ho.hit_count = hr->d_hit_count; ho.earliest = hr->d_hit_count ? hr->d_earliest_time_bits : nullptr;
+        call.ho.want = 1;
+        call.ho.detection_state = hr->detection_state;
+        if (hr->dst) { call.ho.dst = to_view(hr->dst); call.ho.channels = hr->d_channels; call.ho.capacity = hr->capacity; }
+        call.ho.hit_count = hr->d_hit_count; call.ho.earliest = hr->d_hit_count ? hr->d_earliest_time_bits : nullptr;
     }
-    const HitsOut *finalize = (use_records || hr) ? &ho : nullptr;
-    const PhotonView pv = to_view(photons);
-    chroma_propagate_stats acc; memset(&acc, 0, sizeof acc);
-    bool finalized = false;
-    rc = plan.tail_mode == CHROMA_TAIL_FUSED ? run_fused(ctx, plan, geom, pv, nphotons, ncopies, rng, opt, &acc)
-                                             : run_device_steps(ctx, plan, geom, pv, nphotons, ncopies, rng, opt, finalize, &acc, &finalized);
+    call.finalize = use_records || hr;
+    call.n_upper = (long long)nphotons;
+    rc = plan.tail_mode == CHROMA_TAIL_FUSED ? call.run_fused() : call.run_device_steps();
     if (rc) return rc;
-    return finish_call(ctx, geom, photons, nphotons, finalize, finalized, hr, acc, stats, aborted);
+    return call.finish(hr, stats, aborted);
 }
 
 static chroma_propagate_options default_options(int32_t max_steps, int32_t use_weights, int32_t scatter_first, int32_t time_kernels)
@@ -924,9 +912,7 @@ static int hybrid_check(chroma_ctx *ctx, chroma_geometry *geom, int32_t nthreads
     if (max_steps < 0) return set_error(CHROMA_ERR_INVALID, "max_steps %d is negative", max_steps);
     if ((s_tri != nullptr) != (s_side != nullptr) || (s_tri != nullptr) != (s_history != nullptr))
         return set_error(CHROMA_ERR_INVALID, "sample outputs: give all or none");
-    if (geom->stack_need > STACK_LDS + STACK_SCRATCH)
-        return set_error(CHROMA_ERR_STACK, "BVH needs %u traversal stack entries, more than the %d supported", geom->stack_need, STACK_LDS + STACK_SCRATCH);
-    return CHROMA_OK;
+    return check_stack(geom);
 }
 
 int chroma_hybrid_lookup(chroma_ctx *ctx, chroma_geometry *geom, int32_t nthreads, int32_t total_threads, int32_t offset,

@@ -95,9 +95,9 @@ int chroma_init(int device, chroma_ctx **out)
     }
     HIP_TRY(hipMalloc((void **)&ctx->d_counters, sizeof(DeviceCounters)));
     HIP_TRY(hipMemset(ctx->d_counters, 0, sizeof(DeviceCounters)));
-    HIP_TRY(hipMalloc((void **)&ctx->d_words, 16 * sizeof(uint32_t)));
-    HIP_TRY(hipMemset(ctx->d_words, 0, 16 * sizeof(uint32_t)));
-    HIP_TRY(hipHostMalloc((void **)&ctx->h_words, 16 * sizeof(uint32_t), hipHostMallocDefault));
+    HIP_TRY(hipMalloc((void **)&ctx->d_words, SCRATCH_WORDS * sizeof(uint32_t)));
+    HIP_TRY(hipMemset(ctx->d_words, 0, SCRATCH_WORDS * sizeof(uint32_t)));
+    HIP_TRY(hipHostMalloc((void **)&ctx->h_words, SCRATCH_WORDS * sizeof(uint32_t), hipHostMallocDefault));
     HIP_TRY(hipMalloc((void **)&ctx->d_step, sizeof(StepState)));
     HIP_TRY(hipMemset(ctx->d_step, 0, sizeof(StepState)));
     HIP_TRY(hipHostMalloc((void **)&ctx->h_step, sizeof(StepState), hipHostMallocDefault));
@@ -123,20 +123,12 @@ int chroma_shutdown(chroma_ctx *ctx)
     if (ctx->aux_stream) { hipStreamSynchronize(ctx->aux_stream); hipStreamDestroy(ctx->aux_stream); }
     if (ctx->ev_fork) hipEventDestroy(ctx->ev_fork);
     if (ctx->ev_join) hipEventDestroy(ctx->ev_join);
-    if (ctx->queue_a) hipFree(ctx->queue_a);
-    if (ctx->queue_b) hipFree(ctx->queue_b);
+    for (const QueueBuffer &b : queue_buffers(ctx)) if (*b.ptr) hipFree(*b.ptr);
     if (ctx->wide_spill) hipFree(ctx->wide_spill);
     if (ctx->coop_spill) hipFree(ctx->coop_spill);
     if (ctx->d_step) hipFree(ctx->d_step);
     if (ctx->h_step) hipHostFree(ctx->h_step);
     for (hipEvent_t e : ctx->step_events) hipEventDestroy(e);
-    if (ctx->hit_triangle) hipFree(ctx->hit_triangle);
-    if (ctx->hit_distance) hipFree(ctx->hit_distance);
-    if (ctx->retry_list) hipFree(ctx->retry_list);
-    if (ctx->rays) hipFree(ctx->rays);
-    if (ctx->rays_b) hipFree(ctx->rays_b);
-    if (ctx->work_a) hipFree(ctx->work_a);
-    if (ctx->work_b) hipFree(ctx->work_b);
     hipFree(ctx->d_counters);
     hipFree(ctx->d_words);
     hipHostFree(ctx->h_words);

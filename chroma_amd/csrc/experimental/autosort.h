@@ -43,17 +43,20 @@ __global__ void k_order_probe(PhotonView pv, uint64_t n, uint32_t nsamples, uint
 #define AUTOSORT_MIN (1u << 21)
 #endif
 // *d_order: nullptr (take the photons as they come) or a chroma_malloc'ed permutation the caller frees after k_load_working
-static int propagate_order(chroma_ctx *ctx, const CallPlan &plan, const PhotonView &pv, uint64_t nphotons, uint32_t ncopies, uint32_t **d_order)
+static int propagate_order(PropagateCall &call, uint32_t **d_order)
 {
+    chroma_ctx *ctx = call.ctx;
+    const uint64_t nphotons = call.nphotons;
     *d_order = nullptr;
-    const int mode = plan.autosort;
-    if (mode == 0 || ncopies != 1 || nphotons < AUTOSORT_MIN) return CHROMA_OK;
+    const int mode = call.plan.autosort;
+    if (mode == 0 || call.ncopies != 1 || nphotons < AUTOSORT_MIN) return CHROMA_OK;
     if (mode == 2) {
         const uint32_t nsamples = 1024;
-        HIP_TRY(hipMemsetAsync(ctx->d_words + 8, 0, 12, ctx->stream));
-        hipLaunchKernelGGL(k_order_probe, dim3(nsamples / 4), dim3(256), 0, ctx->stream, pv, nphotons, nsamples, ctx->d_words + 8);
-        uint32_t h[3];
-        HIP_TRY(hipMemcpyAsync(h, ctx->d_words + 8, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+        uint32_t *probe = ctx->d_words + W_ORDER_PROBE;
+        uint32_t h[W_ORDER_PROBE_END - W_ORDER_PROBE];
+        HIP_TRY(hipMemsetAsync(probe, 0, sizeof h, ctx->stream));
+        hipLaunchKernelGGL(k_order_probe, dim3(nsamples / 4), dim3(256), 0, ctx->stream, call.pv, nphotons, nsamples, probe);
+        HIP_TRY(hipMemcpyAsync(h, probe, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
         // one origin in nine sampled waves of ten, and fewer than half of them already coherent
         if (h[2] == 0 || 10ull * h[0] < 9ull * h[2] || 2ull * h[1] >= h[0]) return CHROMA_OK;
@@ -61,9 +64,8 @@ static int propagate_order(chroma_ctx *ctx, const CallPlan &plan, const PhotonVi
     void *p = nullptr;
     int rc = chroma_malloc(ctx, (size_t)nphotons * 4, &p);
     if (rc != CHROMA_OK) return rc;
-    rc = chroma_internal_direction_order(ctx, pv.dir, (uint32_t)nphotons, (uint32_t *)p);
+    rc = chroma_internal_direction_order(ctx, call.pv.dir, (uint32_t)nphotons, (uint32_t *)p);
     if (rc != CHROMA_OK) { chroma_free(ctx, p); return rc; }
     *d_order = (uint32_t *)p;
     return CHROMA_OK;
 }
-

@@ -33,13 +33,13 @@ int chroma_count_photons(chroma_ctx *ctx, int32_t first_photon, int32_t nthreads
                          const uint32_t *d_flags, uint32_t *count)
 {
     if (!ctx || !d_flags || !count) return set_error(CHROMA_ERR_INVALID, "bad argument");
-    HIP_TRY(hipMemsetAsync(ctx->d_words, 0, 4, ctx->stream));
+    HIP_TRY(hipMemsetAsync(ctx->d_words + W_HIT_COUNT, 0, 4, ctx->stream));
     if (nthreads > 0) {
         hipLaunchKernelGGL(k_count_photons, dim3((unsigned)std::min((nthreads + 255) / 256, 4096)), dim3(256), 0, ctx->stream, d_flags, first_photon,
-                           nthreads, target_flag, ctx->d_words);
+                           nthreads, target_flag, ctx->d_words + W_HIT_COUNT);
         HIP_TRY(hipGetLastError());
     }
-    return read_word(ctx, 0, count);
+    return read_word(ctx, W_HIT_COUNT, count);
 }
 
 int chroma_copy_photons(chroma_ctx *ctx, int32_t first_photon, int32_t nthreads, uint32_t target_flag,
@@ -48,14 +48,14 @@ int chroma_copy_photons(chroma_ctx *ctx, int32_t first_photon, int32_t nthreads,
     if (!ctx) return set_error(CHROMA_ERR_INVALID, "null ctx");
     int rc = check_photons(src, false); if (rc) return rc;
     rc = check_photons(dst, false); if (rc) return rc;
-    HIP_TRY(hipMemsetAsync(ctx->d_words, 0, 4, ctx->stream));
+    HIP_TRY(hipMemsetAsync(ctx->d_words + W_HIT_COUNT, 0, 4, ctx->stream));
     if (nthreads > 0) {
         hipLaunchKernelGGL(k_copy_photons, dim3((unsigned)(((long long)nthreads + 16 * 256 - 1) / (16 * 256))), dim3(256), 0, ctx->stream, to_view(src), to_view(dst),
-                           first_photon, nthreads, target_flag, ctx->d_words);
+                           first_photon, nthreads, target_flag, ctx->d_words + W_HIT_COUNT);
         HIP_TRY(hipGetLastError());
     }
     uint32_t n = 0;
-    rc = read_word(ctx, 0, &n);
+    rc = read_word(ctx, W_HIT_COUNT, &n);
     if (ncopied) *ncopied = n;
     return rc;
 }
@@ -79,13 +79,13 @@ int chroma_count_photon_hits(chroma_ctx *ctx, chroma_geometry *geom, int32_t fir
     if (!ctx || !geom || !count) return set_error(CHROMA_ERR_INVALID, "bad argument");
     if (!geom->view.nsolids) return set_error(CHROMA_ERR_INVALID, "geometry has no detector channel map");
     int rc = check_photons(photons, false); if (rc) return rc;
-    HIP_TRY(hipMemsetAsync(ctx->d_words, 0, 4, ctx->stream));
+    HIP_TRY(hipMemsetAsync(ctx->d_words + W_HIT_COUNT, 0, 4, ctx->stream));
     if (nphotons > 0) {
         hipLaunchKernelGGL(k_count_hits, dim3((unsigned)std::min((nphotons + 255) / 256, 4096)), dim3(256), 0, ctx->stream, geom->view, photons->flags,
-                           photons->last_hit_triangles, first_photon, nphotons, detection_state, ctx->d_words);
+                           photons->last_hit_triangles, first_photon, nphotons, detection_state, ctx->d_words + W_HIT_COUNT);
         HIP_TRY(hipGetLastError());
     }
-    return read_word(ctx, 0, count);
+    return read_word(ctx, W_HIT_COUNT, count);
 }
 
 int chroma_copy_photon_hits(chroma_ctx *ctx, chroma_geometry *geom, int32_t first_photon, int32_t nphotons,
@@ -96,14 +96,14 @@ int chroma_copy_photon_hits(chroma_ctx *ctx, chroma_geometry *geom, int32_t firs
     if (!geom->view.nsolids) return set_error(CHROMA_ERR_INVALID, "geometry has no detector channel map");
     int rc = check_photons(src, false); if (rc) return rc;
     rc = check_photons(dst, false); if (rc) return rc;
-    HIP_TRY(hipMemsetAsync(ctx->d_words, 0, 4, ctx->stream));
+    HIP_TRY(hipMemsetAsync(ctx->d_words + W_HIT_COUNT, 0, 4, ctx->stream));
     if (nphotons > 0) {
         hipLaunchKernelGGL(k_copy_hits, dim3((unsigned)(((long long)nphotons + COPY_ITEMS * 256 - 1) / (COPY_ITEMS * 256))), dim3(256), 0, ctx->stream, geom->view, to_view(src),
-                           to_view(dst), d_channels, first_photon, nphotons, detection_state, ctx->d_words);
+                           to_view(dst), d_channels, first_photon, nphotons, detection_state, ctx->d_words + W_HIT_COUNT);
         HIP_TRY(hipGetLastError());
     }
     uint32_t n = 0;
-    rc = read_word(ctx, 0, &n);
+    rc = read_word(ctx, W_HIT_COUNT, &n);
     if (ncopied) *ncopied = n;
     return rc;
 }
