@@ -8,7 +8,7 @@
 // The kernels of this path live in one header per family, included below in dependency order (each family is compiled in
 // this translation unit alone):
 //   kernel_propagate_fused.h      k_propagate -- lane-per-photon fused multi-step kernel
-//   kernel_step_control.h         hit codes, k_step_begin, ray records, k_ray_setup
+//   kernel_step_control.h         hit codes, k_step_begin, RayRecord and k_ray_setup, settle_ray / retire_ray, WorkClaim and RayFeed
 //   kernels_raycast_crosscheck.h  k_raycast_persistent / _wide / _coop -- cross-check walks (+ the eight-lane helpers)
 //   kernel_raycast_quad.h         k_raycast_quad -- the DEFAULT ray cast
 //   kernel_raycast_pair.h         k_raycast_pair -- cross-check walk

@@ -79,21 +79,20 @@ k_raycast_packet(GeoView g, const float4 *rays, StepState *st, int32_t *hit_tria
         int last_hit = -1;
         if (slot < nthreads) {
             const float4 *r = rays + 4 * (size_t)slot;
-            const float4 r0 = r[0], r1 = r[1];
-            const int status = __float_as_int(r1.w);
-            if (status == 0) {
-                const float4 r2 = r[2], r3 = r[3];
-                ox = r0.x; oy = r0.y; oz = r0.z; dx = r1.x; dy = r1.y; dz = r1.z;
-                last_hit = __float_as_int(r0.w);
-                rax = r2.x; ray_ = r2.y; raz = r2.z;
-                const float mx = r2.w * cm_fabsf(rax), my = r2.w * cm_fabsf(ray_), mz = r2.w * cm_fabsf(raz);
-                rbx = (f32x2){r3.x - mx, r3.x + mx}; rby = (f32x2){r3.y - my, r3.y + my}; rbz = (f32x2){r3.z - mz, r3.z + mz};
+            RayRecord rec;
+            rec.load_head(r);
+            if (rec.status() == 0) {
+                rec.load_slabs(r);
+                const v3 o = rec.origin(), d = rec.direction(), a = rec.slab_a(), b = rec.slab_b();
+                ox = o.x; oy = o.y; oz = o.z; dx = d.x; dy = d.y; dz = d.z;
+                last_hit = rec.last_hit();
+                rax = a.x; ray_ = a.y; raz = a.z;
+                const float mx = rec.growth() * cm_fabsf(rax), my = rec.growth() * cm_fabsf(ray_), mz = rec.growth() * cm_fabsf(raz);
+                rbx = (f32x2){b.x - mx, b.x + mx}; rby = (f32x2){b.y - my, b.y + my}; rbz = (f32x2){b.z - mz, b.z + mz};
                 rsx = rax < 0.f ? 16u : 0u; rsy = ray_ < 0.f ? 16u : 0u; rsz = raz < 0.f ? 16u : 0u;
                 on = true;
-            } else {                                         // HIT_NAN, or HIT_RETRY: 1/d not moderate (as k_raycast_quad settles them)
-                hit_triangle[slot] = status;
-                hit_distance[slot] = 0.0f;
-                if (status == HIT_RETRY) retry_list[atomicAdd(&st->retry, 1u)] = slot;
+            } else {                                         // (as k_raycast_quad settles them)
+                settle_ray(rec.status(), (int)slot, hit_triangle, hit_distance, retry_list, &st->retry);
             }
         }
         int triangle_index = -1;
@@ -164,12 +163,11 @@ k_raycast_packet(GeoView g, const float4 *rays, StepState *st, int32_t *hit_tria
             }
         }
         if (on) {
-            hit_triangle[slot] = triangle_index;
-            hit_distance[slot] = triangle_index == -1 ? -1.0f : prune_t;
+            retire_ray((int)slot, triangle_index, triangle_index == -1 ? -1.0f : prune_t, hit_triangle, hit_distance);     // (it hands nothing over)
             if (COUNT) cnt.steps++;
         }
     }
-    if (COUNT) {
+    if (COUNT) {                 // (flush_counters, propagate_device.h, written out: the same sums also go to this kernel's share, the packet_* counts)
         unsigned long long nd = wave_sum_u64(cnt.nodes), tr = wave_sum_u64(cnt.tris), ry = wave_sum_u64(cnt.steps);
         if (lane == 0) {
             atomicAdd(&counters->nodes_visited, nd);

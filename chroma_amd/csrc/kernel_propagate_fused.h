@@ -75,14 +75,5 @@ k_propagate(GeoView g, PhotonView pv, int first_photon, int nthreads, const uint
     }
     if (output_queue) wave_queue_append(output_queue, alive, photon_id);
 
-    unsigned long long ov = wave_sum_u64(cnt.overflows);
-    if (COUNT) {
-        unsigned long long st = wave_sum_u64(cnt.steps), nd = wave_sum_u64(cnt.nodes), tr = wave_sum_u64(cnt.tris);
-        if (lane_id() == 0) {
-            atomicAdd(&counters->photon_steps, st);
-            atomicAdd(&counters->nodes_visited, nd);
-            atomicAdd(&counters->triangles_tested, tr);
-        }
-    }
-    if (lane_id() == 0 && ov) atomicAdd(&counters->stack_overflows, ov);
+    flush_counters<COUNT, FLUSH_STEPS | FLUSH_OVERFLOWS>(cnt, counters, lane_id());
 }

@@ -93,6 +93,8 @@ k_raycast_literal(GeoView g, const float4 *rays, StepState *st, int32_t *hit_tri
     uint32_t *work_counter = &st->work;
     const int chunk = ((long long)nthreads > 4ll * big_chunk * (long long)gridDim.x) ? big_chunk : 16;
     WorkClaim wc(nthreads, chunk, static_eighths);          // (kernel_step_control.h: most chunks without the counter)
+    // (RayFeed's frame, RayRecord's decode, settle_ray, retire_ray and flush_counters are written out in this kernel: through
+    //  them it compiles to another schedule, profiles/r11/not_converted.txt)
     static_assert(PROP_BLOCK == WAVE, "one wave per workgroup");
     __shared__ uint32_t s_lds[16 * LIT_STRIDE];
     const unsigned lane = lane_id();

@@ -40,7 +40,7 @@ k_raycast_pair(GeoView g, const float4 *rays, int first_photon, StepState *st,
     const int nthreads = (int)st->n;
     if ((long long)blockIdx.x * 32 >= nthreads) return;
     uint32_t *work_counter = &st->work, *retry_counter = &st->retry;
-    const int chunk = ((long long)nthreads > 4ll * big_chunk * (long long)gridDim.x) ? big_chunk : 32;
+    RayFeed feed(nthreads, ray_chunk(nthreads, big_chunk, 32), 0);         // (a share of 0: every chunk through the counter)
     static_assert(PROP_BLOCK == WAVE, "one wave per workgroup");
     static_assert((PAIR_PENDING & (PAIR_PENDING - 1)) == 0 && PAIR_FLUSH - 1 + 8 <= PAIR_PENDING && (PAIR_STRIDE & 1) == 0, "LDS layout");
     __shared__ __attribute__((aligned(8))) uint32_t s_lds[32 * PAIR_STRIDE];
@@ -68,38 +68,26 @@ k_raycast_pair(GeoView g, const float4 *rays, int first_photon, StepState *st,
     uint32_t cur = WIDE_NONE;
     int sp = 0, npend = 0;
     uint32_t phead = 0;
-    uint32_t loc_next = 0, loc_end = 0;
-    bool exhausted = false;
 
     for (;;) {
         // ---- refill idle pairs
         unsigned long long idle_mask = __ballot(!has_ray && j == 0);
         int n_idle = __popcll(idle_mask);
-        bool more = !exhausted || loc_next < loc_end;
-        if (more && (n_idle >= PAIR_REFILL_MIN || n_idle == 32)) {
-            if (loc_next >= loc_end) {
-                uint32_t base = 0;
-                if (lane == 0) base = atomicAdd(work_counter, (uint32_t)chunk);
-                base = __shfl(base, 0);
-                if (base + (uint32_t)chunk >= (uint32_t)nthreads) exhausted = true;
-                loc_next = min(base, (uint32_t)nthreads);
-                loc_end = min(base + (uint32_t)chunk, (uint32_t)nthreads);
-            }
-            uint32_t idx = loc_next + (uint32_t)__popcll(idle_mask & ((1ull << pshift) - 1ull));
-            loc_next = min(loc_end, loc_next + (uint32_t)n_idle);
-            if (!has_ray && idx < loc_end) {
+        if (feed.more() && (n_idle >= PAIR_REFILL_MIN || n_idle == 32)) {
+            const uint32_t idx = feed.take(idle_mask, pshift, n_idle, work_counter, lane);
+            if (!has_ray && idx < feed.loc_end) {
                 slot = first_photon + (int)idx;
                 const float4 *r = rays + 4 * (size_t)slot;
-                const float4 r0 = r[0], r1 = r[1];
-                if (__float_as_int(r1.w) == 0) {                 // (other slots were settled by k_ray_setup)
-                    const float4 r2 = r[2], r3 = r[3];
-                    origin = mk3(r0.x, r0.y, r0.z);
-                    direction = mk3(r1.x, r1.y, r1.z);
-                    { const int lh = __float_as_int(r0.w); last_hit_w = lh >= 0 ? (0x80000000u | (uint32_t)lh) : WIDE_NONE; }
-                    rax = r2.x; ray_ = r2.y; raz = r2.z;
-                    rbx = (f32x2){r3.x - r2.w * rax, r3.x + r2.w * rax};
-                    rby = (f32x2){r3.y - r2.w * ray_, r3.y + r2.w * ray_};
-                    rbz = (f32x2){r3.z - r2.w * raz, r3.z + r2.w * raz};
+                RayRecord rec;
+                rec.load_head(r);
+                if (rec.status() == 0) {                         // (other slots were settled by k_ray_setup)
+                    rec.load_slabs(r);
+                    origin = rec.origin();
+                    direction = rec.direction();
+                    last_hit_w = rec.leaf_word();
+                    const RayFast rf = rec.fast();
+                    rax = rf.a.x; ray_ = rf.a.y; raz = rf.a.z;
+                    rbx = (f32x2){rf.blo.x, rf.bhi.x}; rby = (f32x2){rf.blo.y, rf.bhi.y}; rbz = (f32x2){rf.blo.z, rf.bhi.z};
                     triangle_index = -1;
                     min_distance = -1.0f;
                     prune_t = cm_inff();
@@ -113,13 +101,12 @@ k_raycast_pair(GeoView g, const float4 *rays, int first_photon, StepState *st,
             }
         }
         if (!__any(has_ray)) {
-            if (exhausted && loc_next >= loc_end) break;
+            if (!feed.more()) break;
             continue;
         }
 
         // ---- node phase: every active pair visits one node per iteration
-        more = !exhausted || loc_next < loc_end;
-        const int stop_at = more ? max(0, (int)__popcll(__ballot(active && j == 0)) - (int)PAIR_REFILL_MIN) : 0;
+        const int stop_at = feed.stop_at((int)__popcll(__ballot(active && j == 0)), PAIR_REFILL_MIN);
         do {
             __builtin_amdgcn_s_setprio(3);       // a wave about to fetch its next node goes before waves that compute
             if (!__any(sp > PAIR_STACK)) {
@@ -258,20 +245,10 @@ k_raycast_pair(GeoView g, const float4 *rays, int first_photon, StepState *st,
 
         // ---- retire finished rays
         if (has_ray && !active) {
-            if (j == 0) {
-                hit_triangle[slot] = triangle_index;                 // record index, or a HIT_* code
-                hit_distance[slot] = min_distance;
-                if (triangle_index == HIT_RETRY) retry_list[atomicAdd(retry_counter, 1u)] = (uint32_t)slot;
-            }
+            if (j == 0) retire_ray(slot, triangle_index, min_distance, hit_triangle, hit_distance, retry_list, retry_counter);
             has_ray = false;
         }
     }
 
-    if (COUNT) {
-        unsigned long long nd = wave_sum_u64(cnt.nodes), tr = wave_sum_u64(cnt.tris);
-        if (lane == 0) {
-            atomicAdd(&counters->nodes_visited, nd);
-            atomicAdd(&counters->triangles_tested, tr);
-        }
-    }
+    flush_counters<COUNT>(cnt, counters, lane);
 }

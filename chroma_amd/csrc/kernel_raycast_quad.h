@@ -101,6 +101,8 @@ k_raycast_quad(GeoView g, const float4 *rays, int first_photon, StepState *st,
     uint32_t *work_counter = &st->work, *retry_counter = &st->retry;
     const int chunk = ((long long)nthreads > 4ll * big_chunk * (long long)gridDim.x) ? big_chunk : 16;
     WorkClaim wc(nthreads, chunk, static_eighths);
+    // (RayFeed's frame, RayRecord's decode, settle_ray and retire_ray of kernel_step_control.h are written out in this kernel:
+    //  through them it compiles to other registers, to scratch or to another schedule, profiles/r11/not_converted.txt)
     static_assert(PROP_BLOCK == WAVE, "one wave per workgroup");
     static_assert((QUAD_PENDING & (QUAD_PENDING - 1)) == 0 && QUAD_FLUSH - 1 + 8 <= QUAD_PENDING && QUAD_KEEP < QUAD_FLUSH, "ring of postponed triangles");
     __shared__ uint32_t s_lds[16 * QUAD_STRIDE];
@@ -357,11 +359,5 @@ k_raycast_quad(GeoView g, const float4 *rays, int first_photon, StepState *st,
                nthreads, blockIdx.x, total, tq_refill, tq_pop, tq_wait, tq_node, tq_leaf, tq_outer, tq_iters, tq_active, tq_rounds, tq_tests);
     }
 #endif
-    if (COUNT) {
-        unsigned long long nd = wave_sum_u64(cnt.nodes), tr = wave_sum_u64(cnt.tris);
-        if (lane == 0) {
-            atomicAdd(&counters->nodes_visited, nd);
-            atomicAdd(&counters->triangles_tested, tr);
-        }
-    }
+    flush_counters<COUNT>(cnt, counters, lane);
 }

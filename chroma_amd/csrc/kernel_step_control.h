@@ -1,4 +1,5 @@
-// kernel_step_control.h -- one step as separate launches: hit codes, the device-side step block (k_step_begin), ray records (k_ray_setup).
+// kernel_step_control.h -- one step as separate launches: hit codes, the device-side step block (k_step_begin), the ray record
+// (RayRecord, make_ray_record, k_ray_setup), what settles and retires a slot (settle_ray, retire_ray), how a wave takes rays (WorkClaim, RayFeed).
 // One of the kernel families of libchroma_hip.so; included by chroma_hip.hip (one translation unit: the families share
 // device helpers and launch-time constants, and are included in dependency order).
 #pragma once
@@ -41,13 +42,76 @@ __global__ void k_step_begin(const uint32_t *in_queue, uint32_t *out_queue, Step
 // persistent ray-cast kernels: there the set-up of a new ray (two dependent gathers, a normalisation,
 // six IEEE divisions for the slab constants, the NaN and "moderate" checks) was ~300 instructions
 // executed by the whole wave for the few rays being refilled -- a quarter of the kernel's VALU work.
-// A record is 64 bytes at the queue slot: {origin, last hit record}, {direction, status},
-// {a = scale/d}, {b = (world_origin - o)/d} (RayFast: blo = b - a, bhi = b + a).  Status 0 = cast; the
-// other slots (NaN, 1/d not moderate) get their hit entry -- and their place in the retry list -- right
-// here.  The photon comes from the dense working set (see k_load_working).
+// Status 0 = cast; the other slots (NaN, 1/d not moderate) get their hit entry -- and their place in the retry list -- from
+// whoever meets them first (settle_ray).  The photon comes from the dense working set (see k_load_working).
+#define WIDE_NONE 0xFFFFFFFFu      // no wide node / an empty entry of one / the leaf word of "no last hit"
+
+// ---- the ray record -----------------------------------------------------------------------------------------------
+// 64 bytes at the queue slot, four float4 rows ("ray records"):
+//   {origin, last hit} {direction, status} {a, growth} {b, 0}
+// LAST HIT is the index of a triangle RECORD (-1: none), STATUS 0 or the hit code the slot is settled with.  Rows 2-3 are
+//   - the fused slab constants a = scale/d and b = (world_origin - o)/d with the growth G of the boxes (ray_growth), for every
+//     walk but the exact one: RayFast's blo = b - G a and bhi = b + G a are rebuilt by the reader (fast());
+//   - the reference's own two per-ray constants 1/d and -o/d (mesh.h:52-53) for the exact walk (inv_dir(), noid()).
+// Written by make_ray_record (k_load_working, k_physics, k_ray_setup) and k_rays_from_arrays; read by every ray-cast kernel in
+// two halves -- rows 0-1, the status test, then rows 2-3 -- and by k_raycast_retry, k_physics and the distance kernels (rows 0-1).
+struct RayRecord {
+    float4 row[4];
+
+    RayRecord() = default;
+    __device__ inline RayRecord(v3 origin, int last_hit, v3 direction, int status, v3 a, float growth, v3 b)
+    {
+        row[0] = make_float4(origin.x, origin.y, origin.z, __int_as_float(last_hit));
+        row[1] = make_float4(direction.x, direction.y, direction.z, __int_as_float(status));
+        row[2] = make_float4(a.x, a.y, a.z, growth);
+        row[3] = make_float4(b.x, b.y, b.z, 0.0f);
+    }
+    __device__ inline void store(float4 *r) const { r[0] = row[0]; r[1] = row[1]; r[2] = row[2]; r[3] = row[3]; }
+    __device__ inline void load_head(const float4 *r) { row[0] = r[0]; row[1] = r[1]; }
+    __device__ inline void load_slabs(const float4 *r) { row[2] = r[2]; row[3] = r[3]; }      // (only of a record whose status is 0)
+
+    __device__ inline v3 origin() const { return mk3(row[0].x, row[0].y, row[0].z); }
+    __device__ inline v3 direction() const { return mk3(row[1].x, row[1].y, row[1].z); }
+    __device__ inline int last_hit() const { return __float_as_int(row[0].w); }
+    __device__ inline int status() const { return __float_as_int(row[1].w); }
+    // the last hit as the wide tree's leaf entries hold it (never entered: WIDE_NONE)
+    __device__ inline uint32_t leaf_word() const { const int lh = last_hit(); return lh >= 0 ? (0x80000000u | (uint32_t)lh) : WIDE_NONE; }
+    __device__ inline v3 slab_a() const { return mk3(row[2].x, row[2].y, row[2].z); }
+    __device__ inline float growth() const { return row[2].w; }
+    __device__ inline v3 slab_b() const { return mk3(row[3].x, row[3].y, row[3].z); }
+    __device__ inline RayFast fast() const
+    {
+        RayFast rf;
+        rf.a = slab_a();
+        rf.blo = slab_b() - growth() * rf.a;
+        rf.bhi = slab_b() + growth() * rf.a;
+        return rf;
+    }
+    __device__ inline v3 inv_dir() const { return slab_a(); }
+    __device__ inline v3 noid() const { return slab_b(); }
+};
+
+// a finished ray's hit entry: the record index of its triangle, -1, or a HIT_* code -- HIT_RETRY also lists the slot for
+// k_raycast_retry (the short form: k_raycast_packet, which hands nothing over)
+__device__ inline void retire_ray(int slot, int triangle_index, float distance, int32_t *hit_triangle, float *hit_distance)
+{
+    hit_triangle[slot] = triangle_index;
+    hit_distance[slot] = distance;
+}
+__device__ inline void retire_ray(int slot, int triangle_index, float distance, int32_t *hit_triangle, float *hit_distance,
+                                  uint32_t *retry_list, uint32_t *retry_counter)
+{
+    retire_ray(slot, triangle_index, distance, hit_triangle, hit_distance);
+    if (triangle_index == HIT_RETRY) retry_list[atomicAdd(retry_counter, 1u)] = (uint32_t)slot;
+}
+// a slot that is not to be cast (status HIT_NAN, or HIT_RETRY: 1/d not moderate) gets its hit entry and its place in the retry list
+__device__ inline void settle_ray(int status, int slot, int32_t *hit_triangle, float *hit_distance, uint32_t *retry_list, uint32_t *retry_counter)
+{
+    retire_ray(slot, status, 0.0f, hit_triangle, hit_distance, retry_list, retry_counter);
+}
+
 // the record of one ray at `r`; returns its status (0 = cast, HIT_NAN, HIT_RETRY)
-// `literal`: the record of the exact walk (k_raycast_literal) carries the reference's own two per-ray constants, 1/d and
-// -o/d (mesh.h:52-53), in place of the fused slab constants a and b.
+// `literal`: the record of the exact walk (k_raycast_literal), rows 2-3 in their second meaning
 __device__ inline int make_ray_record(const GeoView &g, float4 *r, v3 origin, v3 direction, int renorm, int last_hit, bool literal = false)
 {
     int status;
@@ -74,6 +138,8 @@ __device__ inline int make_ray_record(const GeoView &g, float4 *r, v3 origin, v3
             status = 0;
         }
     }
+    // (RayRecord's rows written out, growth computed between them: through the struct k_load_working and k_physics compile to another
+    //  schedule, profiles/r11/not_converted.txt)
     r[0] = make_float4(origin.x, origin.y, origin.z, __int_as_float(last_hit));
     r[1] = make_float4(direction.x, direction.y, direction.z, __int_as_float(status));
     r[2] = make_float4(a.x, a.y, a.z, ray_growth(g, origin));
@@ -93,22 +159,18 @@ k_ray_setup(GeoView g, const float4 *work, const StepState *st, float4 *rays,
     for (int slot = blockIdx.x * blockDim.x + threadIdx.x; slot < nthreads; slot += gridDim.x * blockDim.x) {
         const PhotonRecord rec = PhotonRecord::load(work + 4 * (size_t)slot);
         const int status = make_ray_record(g, rays + 4 * (size_t)slot, rec.position(), rec.direction(), renorm, rec.last_hit(), literal != 0);
-        if (status != 0) {
-            hit_triangle[slot] = status;
-            hit_distance[slot] = 0.0f;
-            if (status == HIT_RETRY) retry_list[atomicAdd(retry_counter, 1u)] = (uint32_t)slot;
-        }
+        if (status != 0) settle_ray(status, slot, hit_triangle, hit_distance, retry_list, retry_counter);
     }
 }
 
-// ---- how a persistent ray-cast wave takes its rays (k_raycast_quad, k_raycast_literal) ---------------------------------------
+// ---- how a persistent ray-cast wave takes its rays: WorkClaim claims chunks, RayFeed deals a chunk's rays to idle groups ------
 // Most of a launch's rays are dealt out WITHOUT the work counter: the atomics of all waves on one word run at ~1e8 per second
 // (every XCD's L2 hands them on to the memory side), and at 16-64 short rays per claim that rate IS the launch -- C5's 6-node
 // tree: 0.19 ns per ray at any size; a small launch: two atomics per wave, 0.1 ms (profiles/r04/ab_static_claims.txt).
 // Wave b of the W that take part owns the chunks b, b + W, b + 2W, ... of the first `eighths` / 8 of its share -- at least
 // one -- and only the rest, what evens the waves out, goes through the counter; a launch of at most W chunks touches no counter
 // at all.  `eighths` holds two shares: bits 0-3 for launches of big chunks (5: with 7 C3's big launches wait for their slowest
-// waves, +5 %), bits 4-7 for the small ones (8).  0: every chunk through the counter (rounds 1-3).
+// waves, +5 %), bits 4-7 for the small ones (8).  0: every chunk through the counter (rounds 1-3, and the cross-check walks).
 struct WorkClaim {
     uint32_t n, chunk, left, stride, next_static, dyn_base;
     bool no_dynamic;
@@ -140,3 +202,35 @@ struct WorkClaim {
         return base;
     }
 };
+
+// A wave's share of the launch: the rays [loc_next, loc_end) of the chunk it holds, and the claim that gets it the next one.
+// Every pass of a persistent kernel ballots its idle groups (one lane each), takes a ray for each while there are `more()`, and
+// ends its node phase early enough to refill (`stop_at`).  Used by k_raycast_pair and k_raycast_wide; k_raycast_quad,
+// k_raycast_literal and k_raycast_coop hold the same frame written out (profiles/r11/not_converted.txt: through the struct they
+// compile to other registers or to scratch), and k_raycast_persistent claims exactly n_idle rays per atomic and so holds no chunk.
+struct RayFeed {
+    WorkClaim claim;
+    uint32_t loc_next = 0, loc_end = 0;
+    bool exhausted = false;        // wave-uniform: no chunk after the one held
+    __device__ RayFeed(int nthreads, int chunk, int eighths) : claim(nthreads, chunk, eighths) {}
+    __device__ bool more() const { return !exhausted || loc_next < loc_end; }
+    // the ray of this lane's group, the k-th idle one taking the k-th ray (a ray only if < loc_end); `group_shift`: the group's first lane
+    __device__ uint32_t take(unsigned long long idle_mask, unsigned group_shift, int n_idle, uint32_t *counter, unsigned lane)
+    {
+        if (loc_next >= loc_end) {
+            const uint32_t base = claim.next(counter, lane, exhausted);        // (wave-uniform: scalar registers)
+            loc_next = min(base, claim.n);
+            loc_end = min(base + claim.chunk, claim.n);
+        }
+        const uint32_t idx = loc_next + (uint32_t)__popcll(idle_mask & ((1ull << group_shift) - 1ull));
+        loc_next = min(loc_end, loc_next + (uint32_t)n_idle);
+        return idx;
+    }
+    // the node phase runs until only this many groups are active: `refill_min` fewer than now while rays are left to take
+    __device__ int stop_at(int n_active, int refill_min) const { return more() ? max(0, n_active - refill_min) : 0; }
+};
+// rays per claim: `big_chunk` when every wave gets several rounds of them anyway (a hot word serves only ~88 atomics/us), else one wave-load
+__device__ inline int ray_chunk(int nthreads, int big_chunk, int rays_per_wave)
+{
+    return ((long long)nthreads > 4ll * big_chunk * (long long)gridDim.x) ? big_chunk : rays_per_wave;
+}

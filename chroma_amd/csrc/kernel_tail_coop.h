@@ -248,16 +248,7 @@ k_tail_coop(GeoView g, PhotonView pv, const StepState *st, const float4 *work_in
         }
     }
 
-    if (COUNT) {
-        unsigned long long sts = wave_sum_u64(cnt.steps), nd = wave_sum_u64(cnt.nodes), tr = wave_sum_u64(cnt.tris);
-        unsigned long long sx = wave_sum_u64(cnt.spills);
-        if (lane == 0) {
-            atomicAdd(&counters->photon_steps, sts);
-            atomicAdd(&counters->nodes_visited, nd);
-            atomicAdd(&counters->triangles_tested, tr);
-            if (sx) atomicAdd(&counters->stack_spills, sx);
-        }
-    }
+    flush_counters<COUNT, FLUSH_STEPS | FLUSH_SPILLS>(cnt, counters, lane);
 }
 
 // the photons the tail kernel is about to finish: their final-record slots are stamped, so that the k_finalize_hits that runs

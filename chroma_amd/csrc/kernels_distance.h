@@ -26,12 +26,7 @@ k_distance_to_mesh(GeoView g, int nthreads, const float *origin, const float *di
         if (tri != -1) distance_out[id] = dist;
         if (triangle_out) triangle_out[id] = tri;
     }
-    unsigned long long ov = wave_sum_u64(cnt.overflows);
-    if (COUNT) {
-        unsigned long long nd = wave_sum_u64(cnt.nodes), tr = wave_sum_u64(cnt.tris);
-        if (lane_id() == 0) { atomicAdd(&counters->nodes_visited, nd); atomicAdd(&counters->triangles_tested, tr); }
-    }
-    if (lane_id() == 0 && ov) atomicAdd(&counters->stack_overflows, ov);
+    flush_counters<COUNT, FLUSH_OVERFLOWS>(cnt, counters, lane_id());
 }
 
 // ---- distance_to_mesh through the fast ray cast --------------------------------------------------------
@@ -58,16 +53,8 @@ __global__ void k_rays_from_arrays(GeoView g, int n, const float *origin_in, con
         b = mk3(cm_fmaf(g.world_origin[0], inv_dir.x, noid.x), cm_fmaf(g.world_origin[1], inv_dir.y, noid.y),
                 cm_fmaf(g.world_origin[2], inv_dir.z, noid.z));
     }
-    float4 *r = rays + 4 * (size_t)slot;
-    r[0] = make_float4(origin.x, origin.y, origin.z, __int_as_float(last_hit));
-    r[1] = make_float4(direction.x, direction.y, direction.z, __int_as_float(status));
-    r[2] = make_float4(a.x, a.y, a.z, ray_growth(g, origin));
-    r[3] = make_float4(b.x, b.y, b.z, 0.0f);
-    if (status != 0) {
-        hit_triangle[slot] = status;
-        hit_distance[slot] = 0.0f;
-        retry_list[atomicAdd(&st->retry, 1u)] = (uint32_t)slot;
-    }
+    RayRecord(origin, last_hit, direction, status, a, ray_growth(g, origin), b).store(rays + 4 * (size_t)slot);
+    if (status != 0) settle_ray(status, slot, hit_triangle, hit_distance, retry_list, &st->retry);
 }
 __global__ void k_step_set(StepState *st, uint32_t n) { st->n = n; st->renorm = 0u; st->in_tail = 0u; st->launches = 0u; st->work = 0u; st->retry = 0u; }
 
@@ -113,10 +100,5 @@ k_distance_retry(GeoView g, const float4 *rays, const StepState *st, const uint3
         if (rec >= 0) distance_out[slot] = dist;
         if (triangle_out) triangle_out[slot] = rec >= 0 ? (int32_t)g.dev_to_tri[rec] : -1;
     }
-    unsigned long long ov = wave_sum_u64(cnt.overflows);
-    if (COUNT) {
-        unsigned long long nd = wave_sum_u64(cnt.nodes), tr = wave_sum_u64(cnt.tris);
-        if (lane_id() == 0) { atomicAdd(&counters->nodes_visited, nd); atomicAdd(&counters->triangles_tested, tr); }
-    }
-    if (lane_id() == 0 && ov) atomicAdd(&counters->stack_overflows, ov);
+    flush_counters<COUNT, FLUSH_OVERFLOWS>(cnt, counters, lane_id());
 }

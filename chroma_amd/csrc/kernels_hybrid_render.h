@@ -134,8 +134,7 @@ k_hybrid_lookup(GeoView g, int nthreads, int offset, float px, float py, float p
             s_cos[k] = cos_theta;
         }
     }
-    unsigned long long ov = wave_sum_u64(cnt.overflows);
-    if (lane_id() == 0 && ov) atomicAdd(&counters->stack_overflows, ov);
+    flush_counters<false, FLUSH_OVERFLOWS>(cnt, counters, lane_id());
 }
 
 // The lookup records of one k_hybrid_lookup launch, stably sorted by key (sample order within a key): the first record
@@ -203,8 +202,7 @@ k_hybrid_image(GeoView g, int nthreads, uint64_t seed, uint64_t id_base, uint32_
             s_history[k] = p.history;
         }
     }
-    unsigned long long ov = wave_sum_u64(cnt.overflows);
-    if (lane_id() == 0 && ov) atomicAdd(&counters->stack_overflows, ov);
+    flush_counters<false, FLUSH_OVERFLOWS>(cnt, counters, lane_id());
 }
 
 // process_image (hybrid_render.cu:170-201): image / nimages, clamped to [0, 1] (NaN to 0), floorf(x * 255), packed

@@ -49,6 +49,7 @@ k_raycast_persistent(GeoView g, const float4 *rays, int first_photon, StepState 
         unsigned long long idle_mask = __ballot(!has_ray);
         int n_idle = __popcll(idle_mask);
         if (!exhausted && (n_idle >= RAY_REFILL_MIN || n_idle == WAVE)) {
+            // (no RayFeed: this walk claims exactly the n_idle rays it is about to deal, one atomic per refill, and holds no chunk)
             uint32_t base = 0;
             if (lane == 0) base = atomicAdd(work_counter, (uint32_t)n_idle);
             base = __shfl(base, 0);
@@ -58,16 +59,14 @@ k_raycast_persistent(GeoView g, const float4 *rays, int first_photon, StepState 
                 if (idx < (uint32_t)nthreads) {
                     slot = first_photon + (int)idx;
                     const float4 *r = rays + 4 * (size_t)slot;
-                    const float4 r0 = r[0], r1 = r[1];
-                    if (__float_as_int(r1.w) == 0) {             // (other slots were settled by k_ray_setup)
-                        const float4 r2 = r[2], r3 = r[3];
-                        origin = mk3(r0.x, r0.y, r0.z);
-                        direction = mk3(r1.x, r1.y, r1.z);
-                        last_hit = __float_as_int(r0.w);
-                        rf.a = mk3(r2.x, r2.y, r2.z);
-                        const v3 bb = mk3(r3.x, r3.y, r3.z);
-                        rf.blo = bb - r2.w * rf.a;
-                        rf.bhi = bb + r2.w * rf.a;
+                    RayRecord rec;
+                    rec.load_head(r);
+                    if (rec.status() == 0) {                     // (other slots were settled by k_ray_setup)
+                        rec.load_slabs(r);
+                        origin = rec.origin();
+                        direction = rec.direction();
+                        last_hit = rec.last_hit();
+                        rf = rec.fast();
                         triangle_index = -1;
                         min_distance = -1.0f;
                         sp = 0;
@@ -151,21 +150,12 @@ k_raycast_persistent(GeoView g, const float4 *rays, int first_photon, StepState 
 
         // ---- retire finished rays
         if (has_ray && !active) {
-            hit_triangle[slot] = triangle_index;                 // record index, or a HIT_* code
-            hit_distance[slot] = min_distance;
-            if (triangle_index == HIT_RETRY) retry_list[atomicAdd(retry_counter, 1u)] = (uint32_t)slot;
+            retire_ray(slot, triangle_index, min_distance, hit_triangle, hit_distance, retry_list, retry_counter);
             has_ray = false;
         }
     }
 
-    if (COUNT) {
-        unsigned long long st = wave_sum_u64(cnt.steps), nd = wave_sum_u64(cnt.nodes), tr = wave_sum_u64(cnt.tris);
-        if (lane == 0) {
-            atomicAdd(&counters->photon_steps, st);
-            atomicAdd(&counters->nodes_visited, nd);
-            atomicAdd(&counters->triangles_tested, tr);
-        }
-    }
+    flush_counters<COUNT, FLUSH_STEPS>(cnt, counters, lane);
 }
 
 // ---- persistent ray cast over the derived 8-wide tree ---------------------------------------------
@@ -189,7 +179,6 @@ k_raycast_persistent(GeoView g, const float4 *rays, int first_photon, StepState 
 #ifndef WIDE_SPILL
 #define WIDE_SPILL 112       // further entries per lane in global memory (rarely touched)
 #endif
-#define WIDE_NONE 0xFFFFFFFFu
 
 template <bool COUNT>
 __global__ __launch_bounds__(PROP_BLOCK, RAY_WAVES) void
@@ -200,9 +189,7 @@ k_raycast_wide(GeoView g, const float4 *rays, int first_photon, StepState *st,
     const int nthreads = (int)st->n;
     if ((long long)blockIdx.x * PROP_BLOCK >= nthreads) return;
     uint32_t *work_counter = &st->work, *retry_counter = &st->retry;
-    // rays taken from the queue per atomic: many for big batches (a hot word serves only ~88 atomics/us),
-    // one wave-load when every wave gets only a few rounds anyway
-    const int chunk = ((long long)nthreads > 4ll * big_chunk * (long long)gridDim.x) ? big_chunk : PROP_BLOCK;
+    RayFeed feed(nthreads, ray_chunk(nthreads, big_chunk, PROP_BLOCK), 0);       // (a share of 0: every chunk through the counter)
     static_assert(WIDE_FLUSH - 1 + 8 <= WIDE_PENDING, "a node visit must fit the FIFO");
     static_assert(PROP_BLOCK == WAVE, "one wave per workgroup: blockIdx.x names the wave's spill area");
     // stack entries beyond the LDS part live in this wave's slice of a global buffer, [entry][lane]
@@ -224,41 +211,25 @@ k_raycast_wide(GeoView g, const float4 *rays, int first_photon, StepState *st,
     float min_distance = -1.0f;
     uint32_t cur = WIDE_NONE;
     int sp = 0, npend = 0;
-    // the wave's share of the queue, [loc_next, loc_end), taken `chunk` rays per atomic: a hot word
-    // serves only ~88 atomics/us, far fewer than the refills 1e8 rays need
-    uint32_t loc_next = 0, loc_end = 0;
-    bool exhausted = false;
 
     for (;;) {
         // ---- refill idle lanes
         unsigned long long idle_mask = __ballot(!has_ray);
         int n_idle = __popcll(idle_mask);
-        bool more = !exhausted || loc_next < loc_end;
-        if (more && (n_idle >= RAY_REFILL_MIN || n_idle == WAVE)) {
-            if (loc_next >= loc_end) {
-                uint32_t base = 0;
-                if (lane == 0) base = atomicAdd(work_counter, (uint32_t)chunk);
-                base = __shfl(base, 0);
-                if (base + (uint32_t)chunk >= (uint32_t)nthreads) exhausted = true;
-                loc_next = min(base, (uint32_t)nthreads);
-                loc_end = min(base + (uint32_t)chunk, (uint32_t)nthreads);
-            }
-            uint32_t idx = loc_next + (uint32_t)__popcll(idle_mask & ((1ull << lane) - 1ull));
-            loc_next = min(loc_end, loc_next + (uint32_t)n_idle);
+        if (feed.more() && (n_idle >= RAY_REFILL_MIN || n_idle == WAVE)) {
+            const uint32_t idx = feed.take(idle_mask, lane, n_idle, work_counter, lane);
             if (!has_ray) {
-                if (idx < loc_end) {
+                if (idx < feed.loc_end) {
                     slot = first_photon + (int)idx;
                     const float4 *r = rays + 4 * (size_t)slot;
-                    const float4 r0 = r[0], r1 = r[1];
-                    if (__float_as_int(r1.w) == 0) {             // (other slots were settled by k_ray_setup)
-                        const float4 r2 = r[2], r3 = r[3];
-                        origin = mk3(r0.x, r0.y, r0.z);
-                        direction = mk3(r1.x, r1.y, r1.z);
-                        last_hit = __float_as_int(r0.w);
-                        rf.a = mk3(r2.x, r2.y, r2.z);
-                        const v3 bb = mk3(r3.x, r3.y, r3.z);
-                        rf.blo = bb - r2.w * rf.a;
-                        rf.bhi = bb + r2.w * rf.a;
+                    RayRecord rec;
+                    rec.load_head(r);
+                    if (rec.status() == 0) {                     // (other slots were settled by k_ray_setup)
+                        rec.load_slabs(r);
+                        origin = rec.origin();
+                        direction = rec.direction();
+                        last_hit = rec.last_hit();
+                        rf = rec.fast();
                         triangle_index = -1;
                         min_distance = -1.0f;
                         sp = 0;
@@ -271,13 +242,12 @@ k_raycast_wide(GeoView g, const float4 *rays, int first_photon, StepState *st,
             }
         }
         if (!__any(has_ray)) {
-            if (exhausted && loc_next >= loc_end) break;
+            if (!feed.more()) break;
             continue;
         }
 
         // ---- node phase: one wide node per active lane per iteration
-        more = !exhausted || loc_next < loc_end;
-        const int stop_at = more ? max(0, __popcll(__ballot(active)) - RAY_REFILL_MIN) : 0;
+        const int stop_at = feed.stop_at(__popcll(__ballot(active)), RAY_REFILL_MIN);
         do {
             if (active && cur == WIDE_NONE) {
                 // next entry that can still hold a nearer hit
@@ -354,21 +324,12 @@ k_raycast_wide(GeoView g, const float4 *rays, int first_photon, StepState *st,
 
         // ---- retire finished rays
         if (has_ray && !active) {
-            hit_triangle[slot] = triangle_index;                 // record index, or a HIT_* code
-            hit_distance[slot] = min_distance;
-            if (triangle_index == HIT_RETRY) retry_list[atomicAdd(retry_counter, 1u)] = (uint32_t)slot;
+            retire_ray(slot, triangle_index, min_distance, hit_triangle, hit_distance, retry_list, retry_counter);
             has_ray = false;
         }
     }
 
-    if (COUNT) {
-        unsigned long long st = wave_sum_u64(cnt.steps), nd = wave_sum_u64(cnt.nodes), tr = wave_sum_u64(cnt.tris);
-        if (lane == 0) {
-            atomicAdd(&counters->photon_steps, st);
-            atomicAdd(&counters->nodes_visited, nd);
-            atomicAdd(&counters->triangles_tested, tr);
-        }
-    }
+    flush_counters<COUNT, FLUSH_STEPS>(cnt, counters, lane);
 }
 
 // ---- cooperative ray cast over the 8-wide tree: eight lanes per ray ---------------------------------
@@ -426,6 +387,9 @@ k_raycast_coop(GeoView g, const float4 *rays, int first_photon, StepState *st,
     if ((long long)blockIdx.x * 8 >= nthreads) return;
     uint32_t *work_counter = &st->work, *retry_counter = &st->retry;
     const int chunk = ((long long)nthreads > 4ll * big_chunk * (long long)gridDim.x) ? big_chunk : 8;
+    // (RayFeed's frame with a share of 0, RayRecord's decode and retire_ray, kernel_step_control.h, written out: this kernel sits at
+    //  the 72 registers of its 7 waves, and through them -- or with its walk shared with coop_cast, kernel_tail_coop.h, the same
+    //  text but for the triangle test -- it takes a 73rd and spills, profiles/r11/not_converted.txt)
     static_assert(PROP_BLOCK == WAVE, "one wave per workgroup");
     __shared__ uint32_t s_lds[8 * COOP_STRIDE];
     const unsigned lane = lane_id();
@@ -594,14 +558,5 @@ k_raycast_coop(GeoView g, const float4 *rays, int first_photon, StepState *st,
         }
     }
 
-    if (COUNT) {
-        unsigned long long st = wave_sum_u64(cnt.steps), nd = wave_sum_u64(cnt.nodes), tr = wave_sum_u64(cnt.tris);
-        unsigned long long sx = wave_sum_u64(cnt.spills);
-        if (lane == 0) {
-            atomicAdd(&counters->photon_steps, st);
-            atomicAdd(&counters->nodes_visited, nd);
-            atomicAdd(&counters->triangles_tested, tr);
-            if (sx) atomicAdd(&counters->stack_spills, sx);
-        }
-    }
+    flush_counters<COUNT, FLUSH_STEPS | FLUSH_SPILLS>(cnt, counters, lane);
 }

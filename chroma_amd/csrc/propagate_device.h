@@ -1,4 +1,4 @@
-// propagate_device.h -- ray cast and per-step photon physics, device side.
+// propagate_device.h -- ray cast and per-step photon physics, device side; a wave's counters and their flush (LaneCounters, flush_counters).
 //
 // Behavioural specification: chroma/cuda/{mesh.h,intersect.h,geometry.h,photon.h,random.h,
 // interpolate.h,rotate.h,cx.h} of the reference (cited per function).  The code is written for
@@ -25,6 +25,26 @@ struct State {
 };
 
 struct LaneCounters { uint32_t steps, nodes, tris, overflows, spills; };
+// A wave's LaneCounters go to the context's DeviceCounters at the end of a kernel, one atomic per wave and counter: nodes and
+// triangles in a counting build (COUNT), and what ALSO names -- steps and spills in a counting build, stack overflows in every build.
+enum { FLUSH_STEPS = 1, FLUSH_SPILLS = 2, FLUSH_OVERFLOWS = 4 };
+template <bool COUNT, int ALSO = 0>
+__device__ inline void flush_counters(const LaneCounters &cnt, DeviceCounters *counters, unsigned lane)
+{
+    unsigned long long ov = 0;
+    if (ALSO & FLUSH_OVERFLOWS) ov = wave_sum_u64(cnt.overflows);
+    if (COUNT) {
+        const unsigned long long nd = wave_sum_u64(cnt.nodes), tr = wave_sum_u64(cnt.tris);
+        const unsigned long long st = (ALSO & FLUSH_STEPS) ? wave_sum_u64(cnt.steps) : 0ull, sx = (ALSO & FLUSH_SPILLS) ? wave_sum_u64(cnt.spills) : 0ull;
+        if (lane == 0) {
+            if (ALSO & FLUSH_STEPS) atomicAdd(&counters->photon_steps, st);
+            atomicAdd(&counters->nodes_visited, nd);
+            atomicAdd(&counters->triangles_tested, tr);
+            if (sx) atomicAdd(&counters->stack_spills, sx);
+        }
+    }
+    if (lane == 0 && ov) atomicAdd(&counters->stack_overflows, ov);
+}
 
 // ---- geometry.h -------------------------------------------------------------------------
 // interp_property (geometry.h:64-75); index clamped where the reference reads one past the

@@ -771,3 +771,89 @@ def test_every_ray_of_a_launch_is_cast_once_at_the_sizes_where_the_work_claims_c
             ends.append(gp.get())
         assert_bit_exact(ends[0], ends[1], 'one step of %d photons, exact walk against default' % n)
         assert (ends[1].last_hit_triangles >= 0).mean() > 0.5
+
+
+def _host_walk(walk, ncus):
+    """(rays per wave R, grid cap W in waves, big chunk B) of a walk as the host resolves them: its row of WALKS
+    (csrc/chroma_hip.hip) with the macros of the kernel headers, the context's ray_chunk / coop_chunk (csrc/chroma_internal.h),
+    and the environment variables propagate_settings() honours for both."""
+    import glob
+    import os
+    import re
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'chroma_amd', 'csrc')
+    macros = {}
+    for header in sorted(glob.glob(os.path.join(csrc, '*.h'))):
+        for name, value in re.findall(r'^#define (\w+) (\d+)\b', open(header).read(), re.M):
+            macros.setdefault(name, value)
+
+    def number(expr):
+        expr = re.sub(r'[A-Za-z_]\w*', lambda m: macros[m.group(0)], expr)
+        assert re.fullmatch(r'[\d\s*+()]+', expr), expr
+        return int(eval(expr))
+    src = open(os.path.join(csrc, 'chroma_hip.hip')).read()
+    row = re.search(r'^\s*\{"%s", [^,]+, Cast::\w+, ([^,]+), ([^,]+), "(\w+)", [^,]+, (SPILL_\w+),' % walk, src, re.M)
+    assert row, 'the row of %s in WALKS not found' % walk
+    per_wave, per_cu, waves_env, spill = row.groups()
+    chunks = re.search(r'int ray_chunk = (\d+), coop_chunk = (\d+);', open(os.path.join(csrc, 'chroma_internal.h')).read())
+    assert chunks, 'the chunk sizes of the context not found'
+    per_cu = max(1, int(os.environ[waves_env])) if waves_env in os.environ else number(per_cu)
+    if spill == 'SPILL_WIDE':
+        big = max(64, int(os.environ['CHROMA_RAY_CHUNK'])) if 'CHROMA_RAY_CHUNK' in os.environ else int(chunks.group(1))
+    else:
+        big = max(8, int(os.environ['CHROMA_COOP_CHUNK'])) if 'CHROMA_COOP_CHUNK' in os.environ else int(chunks.group(2))
+    return number(per_wave), per_cu * ncus, big
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('walk', ['reference', 'wide', 'coop', 'pair'])
+def test_every_ray_of_a_launch_is_cast_once_by_the_cross_check_walks(gpu, oracle_mod, tiny_geometry, walk):
+    """The neighbour of the test above for the walks whose claim goes through RayFeed with a share of 0 (wide, coop, pair) and
+    for k_raycast_persistent's own claim: one step of n bomb photons around the sizes where a launch fills its grid (R rays
+    per wave, W waves) and where it starts to claim big chunks (4 B W), with a NaN direction, an axis-parallel one and one
+    whose 1/d is not moderate in every batch (the settle and retry paths).  Every field must equal the default walk's bit for
+    bit; the default walk's largest batch is checked against the oracle once.  The hit entries of a step are the context's
+    own, so a slot no wave took keeps what the launch before left there: before every launch under test the default walk
+    runs the same number of OTHER photons (the pool reversed), which poisons them."""
+    import re
+    from chroma_amd import _lib
+    from chroma_amd.gpu.photon import _structure
+    ctx = gpu.get_context()
+    R, W, B = _host_walk(walk, int(re.search(r'(\d+) CUs\)', ctx.device_name()).group(1)))      # (W: waves per CU x the device's CUs)
+    sizes = [1, R - 1, R, R + 1, 1000, R * W - 1, R * W + 1, 2 * R * W + 5]
+    if walk != 'reference':
+        sizes.append(4 * B * W + 1)                  # (k_raycast_persistent claims n_idle rays at a time: no chunks)
+    sizes = sorted(set(s for s in sizes if s > 0))
+    nmax = max(sizes)
+    pool = oracle_mod.generate_bomb(nmax, seed=97)
+    fields = ('pos', 'dir', 'pol', 'wavelengths', 't', 'last_hit_triangles', 'flags', 'weights', 'evidx')
+
+    def batch(n, reverse=False):
+        cut = {f: (getattr(pool, f)[::-1][:n] if reverse else getattr(pool, f)[:n]).copy() for f in fields}
+        ph = Photons(**cut)
+        if not reverse:                              # the awkward photons, wherever the batch has room for them
+            for k, d in ((n // 2, (0.0, 0.0, 1.0)), (n - 1, (1e-38, 0.6, 0.8)), (0, (np.nan, 0.0, 1.0))):
+                if k == 0 or n > 2 or (n == 2 and k == 1):          # (one slot each; a batch of one holds the NaN)
+                    ph.dir[k] = d
+        return ph
+
+    gg = gpu.GPUDetector(tiny_geometry)
+
+    def one_step(ph, name):
+        gp = gpu.GPUPhotons(ph)
+        opt = _lib.PropagateOptions(1, False, 0, False, walk=ctx.WALKS[name])
+        st, aborted, s = _lib.PropagateStats(), ctypes.c_int32(0), _structure(gp)
+        _lib.check(ctx._lib.chroma_propagate_opt(ctx.handle, gg.handle, ctypes.byref(s), gp.pos.size, gp.ncopies,
+                                                  gp._rng(gpu.get_rng_states(64, seed=3)), ctypes.byref(opt), ctypes.byref(st),
+                                                  ctypes.byref(aborted), None))
+        return gp.get()
+
+    for n in sorted(sizes, reverse=True):
+        ph = batch(n)
+        want = one_step(ph, 'quad')
+        if n == nmax:
+            ref, _, _ = oracle_mod.propagate(pack_geometry_cached(tiny_geometry), ph, seed=3, max_steps=1, nthreads=16)
+            assert_bit_exact(want, ref, 'one step of %d photons, default walk against the oracle' % n)
+            assert (want.flags & event.NAN_ABORT).any()
+        one_step(batch(n, reverse=True), 'quad')
+        got = one_step(ph, walk)
+        assert_bit_exact(got, want, 'one step of %d photons, walk %s against default' % (n, walk))
