@@ -834,14 +834,19 @@ static int propagate_impl(chroma_ctx *ctx, chroma_geometry *geom, const chroma_p
     if (nphotons >= 0x7fffffffull) return set_error(CHROMA_ERR_INVALID, "at most 2^31-2 photons per call");
     if (ncopies == 0 || nphotons % ncopies) return set_error(CHROMA_ERR_INVALID, "nphotons must be a multiple of ncopies");
     if (aborted) *aborted = 0;
-    if (nphotons == 0 || opt.max_steps <= 0) return CHROMA_OK;
-    if ((rc = check_stack(geom))) return rc;
+    // (no step to take: a hits request is honoured all the same -- the photons detected before the call are its hits, read from
+    //  the arrays as they are, so that the call means propagate + get_flat_hits for every max_steps)
+    const bool stepping = opt.max_steps > 0;
+    if (nphotons == 0 || (!stepping && !hr)) return CHROMA_OK;
+    if (stepping && (rc = check_stack(geom))) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
-    rc = ensure_queues(ctx, nphotons); if (rc) return rc;
-    rc = ensure_spill(ctx, plan.spill); if (rc) return rc;
+    if (stepping) {
+        rc = ensure_queues(ctx, nphotons); if (rc) return rc;
+        rc = ensure_spill(ctx, plan.spill); if (rc) return rc;
+    }
     // (final records: with a hit request, or for every call under CHROMA_FINAL_RECORDS=1 -- an A/B switch)
     static const bool records_always = getenv("CHROMA_FINAL_RECORDS") && atoi(getenv("CHROMA_FINAL_RECORDS")) != 0;
-    const bool use_records = (hr != nullptr || records_always) && plan.tail_mode != CHROMA_TAIL_FUSED;
+    const bool use_records = stepping && (hr != nullptr || records_always) && plan.tail_mode != CHROMA_TAIL_FUSED;
     if (use_records) {
         rc = ensure_final_records(ctx, nphotons); if (rc) return rc;
         ctx->final_epoch++;
@@ -860,8 +865,10 @@ static int propagate_impl(chroma_ctx *ctx, chroma_geometry *geom, const chroma_p
     }
     call.finalize = use_records || hr;
     call.n_upper = (long long)nphotons;
-    rc = plan.tail_mode == CHROMA_TAIL_FUSED ? call.run_fused() : call.run_device_steps();
-    if (rc) return rc;
+    if (stepping) {
+        rc = plan.tail_mode == CHROMA_TAIL_FUSED ? call.run_fused() : call.run_device_steps();
+        if (rc) return rc;
+    }
     return call.finish(hr, stats, aborted);
 }
 

@@ -238,6 +238,7 @@ k_tail_coop(GeoView g, PhotonView pv, const StepState *st, const float4 *work_in
                     h.dst.last_hit_triangles[off] = p.last_hit_triangle;
                     h.dst.weights[off] = p.weight;
                     h.dst.evidx[off] = pv.evidx[photon_id];
+                    if (h.dst.rng_counters) h.dst.rng_counters[off] = rng.counter;
                     h.channels[off] = ch;
                 }
                 if (h.hit_count) {

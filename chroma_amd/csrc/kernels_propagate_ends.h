@@ -158,6 +158,7 @@ k_finalize_hits(GeoView g, PhotonView pv, const float4 *final_rec, uint32_t epoc
                     h.dst.last_hit_triangles[off] = __float_as_int(f3.z);
                     h.dst.weights[off] = f2.w;
                     h.dst.evidx[off] = pv.evidx[id];
+                    if (h.dst.rng_counters) h.dst.rng_counters[off] = __float_as_uint(f3.y);
                 } else {
                     copy_photon(pv, id, h.dst, off);
                 }

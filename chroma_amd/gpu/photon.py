@@ -188,13 +188,14 @@ class GPUPhotons(object):
     @profile_if_possible
     def propagate_hits(self, gpu_detector, rng_states, max_steps=10, use_weights=False, scatter_first=0, target_flag=(0x1 << 2),
                        capacity=None, channel_arrays=None, stats=None, time_kernels=False, exact=False,
-                       nthreads_per_block=64, max_blocks=1024, sort=False):
+                       nthreads_per_block=64, max_blocks=1024, sort=False, device=False):
         """``propagate`` followed by ``get_flat_hits`` as ONE library call (chroma_propagate_hits): the pass that finishes
         the propagation also counts and compacts the detected photons with their channels (chroma/gpu/photon.py:96-175) and,
         when ``channel_arrays=(counts, earliest)`` (device arrays of nchannels uint32) is given, accumulates the per-channel
         hit count and earliest time into them.  Returns what ``get_flat_hits`` would return after ``propagate`` (the same set of photons;
         their order is unspecified, as in the reference).  ``capacity``: room for that many flat hits (default: a quarter of the photons, at least
-        65 536); should more be detected, the full set is fetched with ``get_flat_hits`` afterwards."""
+        65 536); should more be detected, the full set is fetched with ``get_flat_hits`` afterwards.  ``max_steps <= 0``: no step is
+        taken and the photons detected before the call are its hits.  ``device=True``: as ``get_flat_hits``."""
         nphotons = self.pos.size
         lib, ctx = self.ctx._lib, self.ctx
         if capacity is None:
@@ -225,14 +226,17 @@ class GPUPhotons(object):
             print("WARNING: ABORTED PHOTONS", file=sys.stderr)
         n = int(req.nhits)
         if n > capacity:
-            return self.get_flat_hits(gpu_detector, target_flag=target_flag, sort=sort)
+            return self.get_flat_hits(gpu_detector, target_flag=target_flag, sort=sort, device=device)
         if sort and n > 1:
             # (event, channel) order on the device (chroma_hits_sort): the caller's split by event and channel is slicing
             _lib.check(lib.chroma_hits_sort(ctx.handle, ctypes.byref(dst), channels.ptr, n))
         w = slice(0, n)
-        p = GPUPhotonsSlice(pos=out.pos[w], dir=out.dir[w], pol=out.pol[w], wavelengths=out.wavelengths[w], t=out.t[w],
-                            last_hit_triangles=out.last_hit_triangles[w], flags=out.flags[w], weights=out.weights[w],
-                            evidx=out.evidx[w], rng_counters=out.rng_counters[w]).get()
+        found = GPUPhotonsSlice(pos=out.pos[w], dir=out.dir[w], pol=out.pol[w], wavelengths=out.wavelengths[w], t=out.t[w],
+                                last_hit_triangles=out.last_hit_triangles[w], flags=out.flags[w], weights=out.weights[w],
+                                evidx=out.evidx[w], rng_counters=out.rng_counters[w])
+        if device:
+            return found, channels[w]
+        p = found.get()
         p.channel = channels[w].get().astype(np.uint32) if n else np.zeros(0, dtype=np.uint32)
         return p
 
@@ -281,10 +285,11 @@ class GPUPhotons(object):
         return {c: flat[a:b] for c, a, b in zip(ch[first].tolist(), first.tolist(), last.tolist())}
 
     def get_flat_hits(self, gpu_detector, target_flag=(0x1 << 2), nthreads_per_block=64, max_blocks=1024,
-                      start_photon=None, nphotons=None, no_map=False, sort=False):
+                      start_photon=None, nphotons=None, no_map=False, sort=False, device=False):
         """Photons with ``target_flag`` set whose last hit triangle belongs to a channel, plus
         that channel (chroma/gpu/photon.py:107-175).  Order is unspecified, as in the reference; ``sort=True``: in
-        (evidx, channel) order, made on the device (chroma_hits_sort)."""
+        (evidx, channel) order, made on the device (chroma_hits_sort).  ``device=True``: the hits stay on the device -- returns
+        (GPUPhotonsSlice, channels as an int32 GPUArray), the slice with the draw counters (``rng_counters``) of its photons."""
         if start_photon is None:
             start_photon = 0
         if nphotons is None:
@@ -305,6 +310,8 @@ class GPUPhotons(object):
             assert ncopied.value == n
             if sort and n > 1:
                 _lib.check(lib.chroma_hits_sort(ctx.handle, ctypes.byref(dst), channels.ptr, n))
+        if device:
+            return out, channels
         p = out.get()
         p.channel = channels.get().astype(np.uint32) if n else np.zeros(0, dtype=np.uint32)
         return p

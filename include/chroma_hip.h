@@ -290,7 +290,10 @@ int chroma_propagate(chroma_ctx *ctx, chroma_geometry *geom, const chroma_photon
  *   d_hit_count, d_earliest_time_bits   per-channel arrays (device, nchannels), ACCUMULATED into as by chroma_channel_hits;
  *                      d_hit_count may be NULL (then neither is touched), d_earliest_time_bits may be NULL
  *   nhits (out)        detected photons that belong to a channel; if it exceeds `capacity` only `capacity` of them were
- *                      written -- the photon arrays are final, chroma_copy_photon_hits with larger buffers gets all */
+ *                      written -- the photon arrays are final, chroma_copy_photon_hits with larger buffers gets all
+ * A hits request is honoured for max_steps <= 0 too: no step is taken, the photon arrays stay as they are, and the photons detected
+ * before the call are its hits (chroma_propagate followed by chroma_copy_photon_hits, for every max_steps).  Every flat hit carries
+ * its photon's draw counter in dst->rng_counters when that array is given -- tests/test_gpu_hits_oracle.py. */
 typedef struct chroma_hits_request {
     uint32_t detection_state;
     uint32_t capacity;

@@ -23,10 +23,22 @@ def gpu():
     ctx.pop()
 
 
-def canonical(hits):
+def canonical(hits, counters=None):
+    """``hits`` in an order of their own fields; with their draw counters (one per hit, as the device slice of the hits holds
+    them: event.Photons does not carry them), the counters are one more key and come back in the same order."""
     keys = [hits.dir[:, 0].view(np.uint32), hits.dir[:, 1].view(np.uint32), hits.pol[:, 0].view(np.uint32), hits.pos[:, 0].view(np.uint32),
             hits.pos[:, 1].view(np.uint32), hits.wavelengths.view(np.uint32), hits.t.view(np.uint32), hits.last_hit_triangles, hits.evidx, hits.channel]
-    return hits[np.lexsort(keys)]
+    if counters is None:
+        return hits[np.lexsort(keys)]
+    order = np.lexsort([counters] + keys)
+    return hits[order], counters[order]
+
+
+def fetch(found, channels):
+    """Host copies of the hits a call left on the device (device=True): (Photons with channel, draw counters)."""
+    hits = found.get()
+    hits.channel = channels.get().astype(np.uint32)
+    return hits, found.rng_counters.get()
 
 
 def both_ways(g, gg, photons, max_steps, ncopies=1, seed=7, capacity=None, **kw):
@@ -37,24 +49,25 @@ def both_ways(g, gg, photons, max_steps, ncopies=1, seed=7, capacity=None, **kw)
     a.propagate(gg, g.get_rng_states(64, seed=seed), max_steps=max_steps, **kw)
     want = a.get()
     want_counters = a.rng_counters.get()
-    want_hits = a.get_flat_hits(gg)
+    want_hits, want_hit_counters = fetch(*a.get_flat_hits(gg, device=True))
     wc, we = a.channel_hits(gg)
     # the fused call
     b = g.GPUPhotons(photons, ncopies=ncopies)
     counts = zeros(gg.nchannels, np.uint32, ctx)
     earliest = GPUArray(gg.nchannels, np.uint32, ctx).fill(np.uint32(0x7f800000))
     stats = {}
-    got_hits = b.propagate_hits(gg, g.get_rng_states(64, seed=seed), max_steps=max_steps, capacity=capacity,
-                                channel_arrays=(counts, earliest), stats=stats, **kw)
+    got_hits, got_hit_counters = fetch(*b.propagate_hits(gg, g.get_rng_states(64, seed=seed), max_steps=max_steps, capacity=capacity,
+                                                         channel_arrays=(counts, earliest), stats=stats, device=True, **kw))
     got = b.get()
     assert_bit_exact(got, want, 'photon arrays after the fused call')
     assert np.array_equal(b.rng_counters.get(), want_counters)
     assert len(got_hits) == len(want_hits) == stats['nhits']
     # (the order of the flat hits is unspecified, in the reference -- one atomic per hit -- and here -- one per block of 4096
     #  photons, blocks landing in the order their atomics do: compare as sets, in a canonical order)
-    got_hits, want_hits = canonical(got_hits), canonical(want_hits)
+    (got_hits, got_hit_counters), (want_hits, want_hit_counters) = canonical(got_hits, got_hit_counters), canonical(want_hits, want_hit_counters)
     assert_bit_exact(got_hits, want_hits, 'flat hits')
     assert np.array_equal(got_hits.channel, want_hits.channel)
+    assert np.array_equal(got_hit_counters, want_hit_counters), 'draw counters of the flat hits'
     assert np.array_equal(counts.get(), wc.get()) and np.array_equal(earliest.get(), we.get())
     assert int(counts.get().sum()) == len(want_hits)
     return want, want_hits
