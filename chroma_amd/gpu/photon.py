@@ -242,14 +242,20 @@ class GPUPhotons(object):
 
     @profile_if_possible
     def copy_queue(self, queue_gpu, nphotons, nthreads_per_block=64, max_blocks=1024, start_photon=0):
-        """Gather the photons listed in ``queue_gpu`` (tracking mode, photon.py:261-285)."""
-        f = _alloc_fields(nphotons, self.ctx)
+        """Gather the ``nphotons`` photons listed in ``queue_gpu`` from entry ``start_photon`` on (tracking mode,
+        photon.py:261-285): row i of the result is photon ``queue_gpu[start_photon + i]``."""
+        # the kernel writes row start_photon + i of its destination (propagate.cu:116-144): room for the rows below, too
+        start_photon, nphotons = int(start_photon), int(nphotons)
+        f = _alloc_fields(start_photon + nphotons, self.ctx)
+        f['rng_counters'] = zeros(start_photon + nphotons, np.uint32, self.ctx)
         out = GPUPhotonsSlice(**f)
         if nphotons > 0:
             src, dst = _structure(self), _structure(out)
             _lib.check(self.ctx._lib.chroma_copy_photon_queue(self.ctx.handle, start_photon, nphotons, queue_gpu.ptr,
                                                               ctypes.byref(src), ctypes.byref(dst)))
-        return out
+        if start_photon == 0:
+            return out
+        return GPUPhotonsSlice(**{name: a[start_photon:] for name, a in f.items()})
 
     @profile_if_possible
     def select(self, target_flag, nthreads_per_block=64, max_blocks=1024, start_photon=None, nphotons=None):

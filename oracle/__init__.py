@@ -156,18 +156,25 @@ def generate_bomb(n, seed, id_base=0, pos=(0, 0, 0), wavelength_lo=400.0, wavele
     return hp.photons()
 
 
+def daq_state(nwords):
+    """The three channel arrays of a DAQ as begin_acquire leaves them: (earliest time bits = 1e9, charge counts 0, histories 0)."""
+    return (np.full(nwords, np.float32(1e9).view(np.uint32), dtype=np.uint32), np.zeros(nwords, dtype=np.uint32),
+            np.zeros(nwords, dtype=np.uint32))
+
+
 def run_daq(packed, photons, tables_host, charge_unit, seed, photon_id_base=0, acquisition=0, weight=1.0,
-            start_photon=0, nphotons=None, variant='contract'):
+            start_photon=0, nphotons=None, variant='contract', state=None):
     """run_daq on HOST arrays.  ``tables_host`` = (time_cdf_x, time_cdf_y, charge_cdf_x, charge_cdf_y) float32
-    arrays of equal pairwise length.  Returns (earliest_time float32, charge float32, histories uint32, hit mask)."""
+    arrays of equal pairwise length.  Returns (earliest_time float32, charge float32, histories uint32, hit mask).
+    ``state``: the three arrays of ``daq_state`` to acquire ONTO, in place (a second acquire without a reset);
+    None: fresh ones."""
     lib = load(variant)
     hp = HostPhotons(photons)
     tx, ty, qx, qy = [np.ascontiguousarray(a, dtype=np.float32) for a in tables_host]
     tab = _abi.DaqTables(tx.ctypes.data, ty.ctypes.data, len(tx), qx.ctypes.data, qy.ctypes.data, len(qx), float(charge_unit))
     nch = packed.desc.nchannels
-    t_int = np.full(nch, np.float32(1e9).view(np.uint32), dtype=np.uint32)
-    q_int = np.zeros(nch, dtype=np.uint32)
-    hist = np.zeros(nch, dtype=np.uint32)
+    t_int, q_int, hist = daq_state(nch) if state is None else state
+    assert all(a.dtype == np.uint32 and a.flags['C_CONTIGUOUS'] and len(a) >= nch for a in (t_int, q_int, hist))
     if nphotons is None:
         nphotons = hp.n - start_photon
     lib.oracle_run_daq(ctypes.byref(packed.desc), ctypes.byref(tab), int(start_photon), int(nphotons), event.SURFACE_DETECT,
@@ -178,17 +185,18 @@ def run_daq(packed, photons, tables_host, charge_unit, seed, photon_id_base=0, a
 
 
 def run_daq_many(packed, photons, tables_host, charge_unit, seed, ndaq, photon_id_base=0, acquisition=0, weight=1.0,
-                 start_photon=0, nphotons=None, variant='contract'):
-    """run_daq_many on HOST arrays: ``ndaq`` acquisitions side by side (copy i = entries [i*nch, (i+1)*nch)).
-    Returns (earliest_time float32, charge float32, histories uint32, hit mask), each of ndaq * nchannels entries."""
+                 start_photon=0, nphotons=None, variant='contract', state=None, channel_stride=None):
+    """run_daq_many on HOST arrays: ``ndaq`` acquisitions side by side (copy i = entries [i*stride, (i+1)*stride),
+    ``channel_stride`` = nchannels unless given).  Returns (earliest_time float32, charge float32, histories uint32,
+    hit mask), each of ndaq * stride entries.  ``state``: as in ``run_daq``, arrays of at least ndaq * stride words."""
     lib = load(variant)
     hp = HostPhotons(photons)
     tx, ty, qx, qy = [np.ascontiguousarray(a, dtype=np.float32) for a in tables_host]
     tab = _abi.DaqTables(tx.ctypes.data, ty.ctypes.data, len(tx), qx.ctypes.data, qy.ctypes.data, len(qx), float(charge_unit))
-    nch = packed.desc.nchannels
-    t_int = np.full(nch * ndaq, np.float32(1e9).view(np.uint32), dtype=np.uint32)
-    q_int = np.zeros(nch * ndaq, dtype=np.uint32)
-    hist = np.zeros(nch * ndaq, dtype=np.uint32)
+    nch = packed.desc.nchannels if channel_stride is None else int(channel_stride)
+    assert nch >= packed.desc.nchannels
+    t_int, q_int, hist = daq_state(nch * ndaq) if state is None else state
+    assert all(a.dtype == np.uint32 and a.flags['C_CONTIGUOUS'] and len(a) >= nch * ndaq for a in (t_int, q_int, hist))
     if nphotons is None:
         nphotons = hp.n - start_photon
     lib.oracle_run_daq_many(ctypes.byref(packed.desc), ctypes.byref(tab), int(start_photon), int(nphotons), event.SURFACE_DETECT,

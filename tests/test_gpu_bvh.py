@@ -74,8 +74,11 @@ def test_device_builder_is_the_default_with_a_gpu_and_refuses_bad_input(gpu):
 def test_direction_sort_is_argsort_direction_on_the_device(gpu, oracle_mod):
     """GPUPhotons.sort_by_direction == chroma_amd.tools.argsort_direction (chroma/tools.py:175-193) applied to every
     array of the set: codes non-decreasing, the same multiset of photons; equal to the NumPy order wherever the two
-    arc functions give the same 16-bit angles (they differ in the last ulp for a few per million)."""
+    arc functions give the same 16-bit angles (they differ in the last ulp for a few per million).  And exactly, row by
+    row and with nothing left out: the stable order of the codes derived on the CPU from the contract's own acos and
+    atan2 (test_gpu_photon_arrays.direction_codes)."""
     from chroma_amd.tools import argsort_direction
+    from test_gpu_photon_arrays import direction_codes
     ph = oracle_mod.generate_bomb(200000, seed=3, id_base=0, wavelength_lo=300.0, wavelength_hi=700.0)
     gp = gpu.GPUPhotons(ph)
     gp.sort_by_direction()
@@ -100,3 +103,8 @@ def test_direction_sort_is_argsort_direction_on_the_device(gpu, oracle_mod):
     key_got = np.sort(np.ascontiguousarray(np.column_stack([got.wavelengths, got.dir, got.pol]).astype(np.float32)).view('V28').ravel())
     key_in = np.sort(np.ascontiguousarray(np.column_stack([ph.wavelengths, ph.dir, ph.pol]).astype(np.float32)).view('V28').ravel())
     assert np.array_equal(key_got, key_in)
+    exact = ph[np.argsort(direction_codes(oracle_mod, ph.dir)[0], kind='stable')]
+    for name in ('pos', 'dir', 'pol', 'wavelengths', 't', 'flags', 'last_hit_triangles', 'weights', 'evidx'):
+        a, b = getattr(got, name), getattr(exact, name)
+        differ = np.flatnonzero((a.view(np.uint32) != b.view(np.uint32)).reshape(len(a), -1).any(axis=1))
+        assert len(differ) == 0, '%s: %d rows are not where the contract codes put them (first: row %d)' % (name, len(differ), differ[0])
