@@ -150,14 +150,14 @@ struct CallPlan {
 };
 
 // `walk`, `tail`, `counting`: the call's choice, or -1 for the context's
-static int make_plan(const chroma_ctx *ctx, const chroma_geometry *geom, int walk, int tail, int counting, CallPlan *plan)
+static int make_plan(const CallState &cs, const chroma_geometry *geom, int walk, int tail, int counting, CallPlan *plan)
 {
     if (walk >= NWALKS) return set_error(CHROMA_ERR_INVALID, "unknown walk mode %d", walk);
     if (tail > CHROMA_TAIL_FUSED) return set_error(CHROMA_ERR_INVALID, "unknown tail mode %d", tail);
-    const int w = walk >= 0 ? walk : ctx->walk;
+    const int w = walk >= 0 ? walk : cs.walk;
     CallPlan p = {};
-    p.tail_mode = tail >= 0 ? tail : ctx->tail_mode;
-    p.counting = counting >= 0 ? counting != 0 : ctx->counting != 0;
+    p.tail_mode = tail >= 0 ? tail : cs.tail_mode;
+    p.counting = counting >= 0 ? counting != 0 : cs.counting != 0;
     // a fast walk whose stack is too shallow for the tree falls back to the next one (PAIR never to COOP)
     int r = w;
     while (!walk_fits(WALKS[r], geom)) {
@@ -174,9 +174,9 @@ static int make_plan(const chroma_ctx *ctx, const chroma_geometry *geom, int wal
     p.isect_quad = fits_coop && WALKS[w].stack != 0;
     if (p.tail_mode != CHROMA_TAIL_FUSED) p.spill = WALKS[r].spill | (p.tail ? SPILL_COOP : SPILL_NONE);
     if (p.chain && p.cast == Cast::QUAD) {
-        p.autosort = ctx->autosort_mode;
+        p.autosort = cs.autosort_mode;
 #if CHROMA_EXPERIMENTAL
-        if (geom->wide_stack_need <= PACKET_STACK) p.packet = ctx->packet_mode;
+        if (geom->wide_stack_need <= PACKET_STACK) p.packet = cs.packet_mode;
 #endif
     }
     *plan = p;
@@ -185,10 +185,11 @@ static int make_plan(const chroma_ctx *ctx, const chroma_geometry *geom, int wal
 
 // the global-memory parts of the fast walks' stacks, allocated at first use.  Every cooperative walk indexes the coop one
 // with (wave * rays-per-wave + ray) * COOP_SPILL, so it is sized for the largest grid of any of them.
-static int ensure_spill(chroma_ctx *ctx, unsigned kinds)
+static int ensure_spill(const CallScope &scope, unsigned kinds)
 {
-    const struct { SpillKind kind; uint2 **buf; size_t depth; } bufs[] = {{SPILL_COOP, &ctx->coop_spill, COOP_SPILL},
-                                                                          {SPILL_WIDE, &ctx->wide_spill, WIDE_SPILL}};
+    chroma_ctx *ctx = scope.ctx; CallState &cs = scope.state();
+    const struct { SpillKind kind; uint2 **buf; size_t depth; } bufs[] = {{SPILL_COOP, &cs.coop_spill, COOP_SPILL},
+                                                                          {SPILL_WIDE, &cs.wide_spill, WIDE_SPILL}};
     for (const auto &b : bufs) {
         if (!(kinds & b.kind) || *b.buf) continue;
         size_t rays = 0;
@@ -209,14 +210,34 @@ static unsigned cast_waves(const chroma_ctx *ctx, Cast cast, long long n)
 
 // the lane-per-photon kernel with the reference's launch shape (CHROMA_TAIL=fused, chroma_propagate_step)
 struct FusedLaunch { int first, nthreads; const uint32_t *in_q; uint32_t *out_q; int max_steps, use_weights, scatter_first; };
-static int launch_propagate(chroma_ctx *ctx, bool counting, chroma_geometry *geom, const PhotonView &pv, chroma_rng rng, const FusedLaunch &a)
+static int launch_propagate(const CallScope &scope, bool counting, chroma_geometry *geom, const PhotonView &pv, chroma_rng rng, const FusedLaunch &a)
 {
+    chroma_ctx *ctx = scope.ctx;
     const dim3 grid((unsigned)((a.nthreads + PROP_BLOCK - 1) / PROP_BLOCK)), block(PROP_BLOCK);
     with_bool(counting, [&](auto C) {
         hipLaunchKernelGGL((k_propagate<STACK_LDS, C>), grid, block, 0, ctx->stream, geom->view, pv, a.first, a.nthreads, a.in_q, a.out_q,
-                           rng.seed, rng.photon_id_base, a.max_steps, a.use_weights, a.scatter_first, ctx->d_counters);
+                           rng.seed, rng.photon_id_base, a.max_steps, a.use_weights, a.scatter_first, scope.state().d_counters);
     });
     HIP_TRY(hipGetLastError());
+    return CHROMA_OK;
+}
+
+// the kernels' counters since the last read, added to *stats; the counters start again at zero
+static int stats_read(const CallScope &scope, chroma_propagate_stats *stats)
+{
+    chroma_ctx *ctx = scope.ctx; CallState &cs = scope.state();
+    DeviceCounters c;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipMemcpy(&c, cs.d_counters, sizeof c, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemset(cs.d_counters, 0, sizeof c));
+    stats->photon_steps += c.photon_steps;
+    stats->nodes_visited += c.nodes_visited;
+    stats->triangles_tested += c.triangles_tested;
+    stats->stack_overflows += c.stack_overflows;
+    stats->stack_spills += c.stack_spills;
+    stats->packet_rays += c.packet_rays;
+    stats->packet_nodes_visited += c.packet_nodes;
+    stats->packet_triangles_tested += c.packet_tris;
     return CHROMA_OK;
 }
 
@@ -227,12 +248,13 @@ namespace { struct PropagateCall; }
 // *d_order: nullptr (the call takes its photons as they come) or a chroma_malloc'ed permutation to free after k_load_working
 static int propagate_order(PropagateCall &call, uint32_t **d_order);
 
-// One chroma_propagate* call: what it was asked, what it runs (CallPlan), the context's buffers in the roles they have at the
-// moment, and what it has found out so far.  Built once by propagate_impl after its checks; the functions of the path are its
+// One chroma_propagate* call: its entry point's scope and the CallState behind it, what it was asked, what it runs (CallPlan),
+// the context's buffers in the roles they have at the moment, and what it has found out so far.  Built once by propagate_impl after its checks; the functions of the path are its
 // members and take only what varies from one invocation to the next.  The context's own pointers and settings are not changed
 // by a call: the pairs below swap HERE.  (Unnamed namespace: its members are not the library's symbols.)
 namespace {
 struct PropagateCall {
+    const CallScope &scope; CallState &cs;
     chroma_ctx *ctx; chroma_geometry *geom;
     CallPlan plan;
     PhotonView pv; chroma_rng rng; chroma_propagate_options opt;
@@ -248,22 +270,22 @@ struct PropagateCall {
     long long n_upper;                 // bounds the live photons: sizes the grids
     bool finalized;                    // k_finalize_hits has run already, beside the tail kernel (launch_tail)
 
-    hipEvent_t *events(int step) const { return opt.time_kernels ? ctx->step_events.data() + EV_PER_STEP * step : nullptr; }
+    hipEvent_t *events(int step) const { return opt.time_kernels ? cs.step_events.data() + EV_PER_STEP * step : nullptr; }
 
     // the live photons into the dense working set (k_load_working), with the first step's ray records when the rays chain
     int load_working()
     {
         const unsigned blocks = (unsigned)std::min<uint64_t>((nphotons + PHYS_BLOCK - 1) / PHYS_BLOCK, (uint64_t)ctx->physics_blocks);
-        HIP_TRY(hipMemsetAsync(ctx->d_words + W_PACKET_USE, 0, (W_PACKET_END - W_PACKET_USE) * sizeof(uint32_t), ctx->stream));
+        int rc = scope.clear_words(W_PACKET_USE, W_PACKET_END - W_PACKET_USE); if (rc) return rc;
         uint32_t *d_order = nullptr;
-        int rc = propagate_order(*this, &d_order); if (rc) return rc;
+        rc = propagate_order(*this, &d_order); if (rc) return rc;
         hipLaunchKernelGGL(k_load_working, dim3(blocks), dim3(PHYS_BLOCK), 0, ctx->stream, geom->view, pv, in_q, work_in,
                            (uint64_t)nphotons, ncopies, (uint32_t)(nphotons / ncopies), plan.chain ? rays : nullptr,
-                           plan.packet == 2 ? ctx->d_words + W_PACKET_COHERENT : nullptr, (const uint32_t *)d_order, plan.cast == Cast::LITERAL ? 1 : 0);
+                           plan.packet == 2 ? cs.d_words + W_PACKET_COHERENT : nullptr, (const uint32_t *)d_order, plan.cast == Cast::LITERAL ? 1 : 0);
         if (d_order) { chroma_free(ctx, d_order); acc.reordered += nphotons; }      // (parked until the stream has passed this point)
 #if CHROMA_EXPERIMENTAL
         if (plan.packet)
-            hipLaunchKernelGGL(k_packet_decide, dim3(1), dim3(1), 0, ctx->stream, ctx->d_words + W_PACKET_COHERENT, ctx->d_words + W_PACKET_USE,
+            hipLaunchKernelGGL(k_packet_decide, dim3(1), dim3(1), 0, ctx->stream, cs.d_words + W_PACKET_COHERENT, cs.d_words + W_PACKET_USE,
                                (uint64_t)nphotons, plan.packet);
 #endif
         HIP_TRY(hipGetLastError());
@@ -273,7 +295,7 @@ struct PropagateCall {
     // (with weights the reference runs ALL steps in one launch: every count is "few")
     void launch_step_begin(uint32_t first_n)
     {
-        hipLaunchKernelGGL(k_step_begin, dim3(1), dim3(1), 0, ctx->stream, in_q, out_q, ctx->d_step,
+        hipLaunchKernelGGL(k_step_begin, dim3(1), dim3(1), 0, ctx->stream, in_q, out_q, cs.d_step,
                            opt.use_weights ? 0xFFFFFFFFu : (uint32_t)(PROP_BLOCK * 16 * 8), first_n);
     }
 
@@ -281,7 +303,7 @@ struct PropagateCall {
     // (a short list: a small grid), 2 every slot with the ray cast's results taken as they are (the exact walks).
     void launch_physics(int scatter_first, int fixup)
     {
-        StepState *st = ctx->d_step;
+        StepState *st = cs.d_step;
         float4 *chained = plan.chain ? rays_next : nullptr;
         const bool plain = geom->view.plain_optics != 0;      // (no re-emitting component, default surface model only)
         bool deal = false;
@@ -294,25 +316,25 @@ struct PropagateCall {
         //  launch of 2048 blocks that find nothing to do costs 0.07 ms, 29 times per batch; a plain geometry with faces on the
         //  world box lists a good part of its hits for the exact check, so not less than that)
         if (fixup == 1 && plain) blocks = std::max(std::min(blocks, 64u), blocks / 8);
-        DeviceCounters *pc = plan.counting ? ctx->d_counters : nullptr;
+        DeviceCounters *pc = plan.counting ? cs.d_counters : nullptr;
 #if PHYS_DEAL
         if (deal) {
             hipLaunchKernelGGL(k_physics_deal, dim3(blocks), dim3(PHYS_DEAL_BLOCK), 0, ctx->stream, geom->view, pv, st, work_in, out_q, work_out,
-                               ctx->hit_triangle, ctx->hit_distance, rng.seed, rng.photon_id_base, opt.use_weights, scatter_first,
-                               ctx->retry_list, fixup, pc, chained);
+                               cs.hit_triangle, cs.hit_distance, rng.seed, rng.photon_id_base, opt.use_weights, scatter_first,
+                               cs.retry_list, fixup, pc, chained);
             return;
         }
 #endif
         const int literal_rays = fixup == 2 ? 1 : 0;          // (the exact walks' ray records)
         with_bool(!plain, [&](auto FULL) {
             hipLaunchKernelGGL((k_physics<FULL>), dim3(blocks), dim3(PHYS_BLOCK_OF(FULL)), 0, ctx->stream, geom->view, pv, st, work_in, out_q,
-                               work_out, ctx->hit_triangle, ctx->hit_distance, rng.seed, rng.photon_id_base, opt.use_weights, scatter_first,
-                               ctx->retry_list, fixup, pc, chained, final_rec, final_epoch, literal_rays);
+                               work_out, cs.hit_triangle, cs.hit_distance, rng.seed, rng.photon_id_base, opt.use_weights, scatter_first,
+                               cs.retry_list, fixup, pc, chained, final_rec, final_epoch, literal_rays);
         });
     }
 
     // One step as ray set-up + ray cast + physics (+ the strict walk and the physics of the few rays that need it), all reading the
-    // photon count and the launch policy from ctx->d_step (k_step_begin).  `ev`: the step's EV_PER_STEP events, or NULL.  When the
+    // photon count and the launch policy from the step block (k_step_begin).  `ev`: the step's EV_PER_STEP events, or NULL.  When the
     // rays chain, this step's records are in `rays` already (written by k_load_working or by the k_physics of the step before),
     // k_physics writes the next step's to `rays_next`, and the two swap.
     // `packet` (experimental): the first step of a call whose k_load_working looked at the photons' coherence -- k_raycast_packet
@@ -320,7 +342,7 @@ struct PropagateCall {
     int launch_split_step(int scatter_first, hipEvent_t *ev, uint32_t first_n, bool packet)
     {
         if (n_upper <= 0) return CHROMA_OK;
-        StepState *st = ctx->d_step;
+        StepState *st = cs.d_step;
         const Cast cast = plan.cast;
         const bool exact = cast == Cast::LITERAL || cast == Cast::LITERAL_LANE;
         const dim3 block(PROP_BLOCK);
@@ -329,25 +351,25 @@ struct PropagateCall {
         //  geometry with faces on the world box lists a good part of its hits for the exact check: grids for that)
         const unsigned rblocks = (unsigned)std::min<long long>((n_upper + PROP_BLOCK - 1) / PROP_BLOCK, 8 * 256);
         auto retry = [&](auto C) {
-            hipLaunchKernelGGL((k_raycast_retry<C>), dim3(rblocks), block, 0, ctx->stream, geom->view, rays, st, ctx->hit_triangle,
-                               ctx->hit_distance, ctx->retry_list, ctx->d_counters);
+            hipLaunchKernelGGL((k_raycast_retry<C>), dim3(rblocks), block, 0, ctx->stream, geom->view, rays, st, cs.hit_triangle,
+                               cs.hit_distance, cs.retry_list, cs.d_counters);
         };
         launch_step_begin(first_n);
         HIP_TRY(record(EV_STEP_BEGIN));
         if (!plan.chain) {
             unsigned sblocks = (unsigned)std::min<long long>((n_upper + 255) / 256, (long long)ctx->physics_blocks * 4);
             hipLaunchKernelGGL(k_ray_setup, dim3(sblocks), dim3(256), 0, ctx->stream, geom->view, work_in, st, rays,
-                               ctx->hit_triangle, ctx->hit_distance, ctx->retry_list, &st->retry, cast == Cast::LITERAL ? 1 : 0);
+                               cs.hit_triangle, cs.hit_distance, cs.retry_list, &st->retry, cast == Cast::LITERAL ? 1 : 0);
         }
         HIP_TRY(record(EV_PACKET_BEGIN));                             // the ray-cast kernels proper are timed from here
         const uint32_t *skip_quad = nullptr;
 #if CHROMA_EXPERIMENTAL
         if (packet) {
-            skip_quad = ctx->d_words + W_PACKET_USE;
+            skip_quad = cs.d_words + W_PACKET_USE;
             const unsigned pwaves = (unsigned)std::min<long long>((n_upper + WAVE - 1) / WAVE, (long long)ctx->waves[(int)Cast::QUAD]);
             with_bool(plan.counting, [&](auto C) {
-                hipLaunchKernelGGL((k_raycast_packet<C>), dim3(pwaves), block, 0, ctx->stream, geom->view, rays, st, ctx->hit_triangle,
-                                   ctx->hit_distance, ctx->retry_list, ctx->d_counters, ctx->d_words + W_PACKET_USE);
+                hipLaunchKernelGGL((k_raycast_packet<C>), dim3(pwaves), block, 0, ctx->stream, geom->view, rays, st, cs.hit_triangle,
+                                   cs.hit_distance, cs.retry_list, cs.d_counters, cs.d_words + W_PACKET_USE);
             });
         }
 #else
@@ -359,35 +381,35 @@ struct PropagateCall {
         with_bool(plan.counting, [&](auto C) {
             switch (cast) {
             case Cast::PAIR:
-                hipLaunchKernelGGL((k_raycast_pair<C>), grid, block, 0, ctx->stream, geom->view, rays, 0, st, ctx->hit_triangle,
-                                   ctx->hit_distance, ctx->retry_list, ctx->coop_spill, ctx->d_counters, ctx->coop_chunk);
+                hipLaunchKernelGGL((k_raycast_pair<C>), grid, block, 0, ctx->stream, geom->view, rays, 0, st, cs.hit_triangle,
+                                   cs.hit_distance, cs.retry_list, cs.coop_spill, cs.d_counters, ctx->coop_chunk);
                 break;
             case Cast::QUAD:
-                hipLaunchKernelGGL((k_raycast_quad<C>), grid, block, 0, ctx->stream, geom->view, rays, 0, st, ctx->hit_triangle,
-                                   ctx->hit_distance, ctx->retry_list, ctx->coop_spill, ctx->d_counters, ctx->coop_chunk, chained, skip_quad,
+                hipLaunchKernelGGL((k_raycast_quad<C>), grid, block, 0, ctx->stream, geom->view, rays, 0, st, cs.hit_triangle,
+                                   cs.hit_distance, cs.retry_list, cs.coop_spill, cs.d_counters, ctx->coop_chunk, chained, skip_quad,
                                    ctx->claim_static);
                 break;
             case Cast::COOP:
-                hipLaunchKernelGGL((k_raycast_coop<C>), grid, block, 0, ctx->stream, geom->view, rays, 0, st, ctx->hit_triangle,
-                                   ctx->hit_distance, ctx->retry_list, ctx->coop_spill, ctx->d_counters, ctx->coop_chunk);
+                hipLaunchKernelGGL((k_raycast_coop<C>), grid, block, 0, ctx->stream, geom->view, rays, 0, st, cs.hit_triangle,
+                                   cs.hit_distance, cs.retry_list, cs.coop_spill, cs.d_counters, ctx->coop_chunk);
                 break;
             case Cast::WIDE:
-                hipLaunchKernelGGL((k_raycast_wide<C>), grid, block, 0, ctx->stream, geom->view, rays, 0, st, ctx->hit_triangle,
-                                   ctx->hit_distance, ctx->retry_list, ctx->wide_spill, ctx->d_counters, ctx->ray_chunk);
+                hipLaunchKernelGGL((k_raycast_wide<C>), grid, block, 0, ctx->stream, geom->view, rays, 0, st, cs.hit_triangle,
+                                   cs.hit_distance, cs.retry_list, cs.wide_spill, cs.d_counters, ctx->ray_chunk);
                 break;
             case Cast::PERSISTENT:
-                hipLaunchKernelGGL((k_raycast_persistent<C>), grid, block, 0, ctx->stream, geom->view, rays, 0, st, ctx->hit_triangle,
-                                   ctx->hit_distance, ctx->retry_list, ctx->d_counters);
+                hipLaunchKernelGGL((k_raycast_persistent<C>), grid, block, 0, ctx->stream, geom->view, rays, 0, st, cs.hit_triangle,
+                                   cs.hit_distance, cs.retry_list, cs.d_counters);
                 break;
             case Cast::LITERAL:
-                hipLaunchKernelGGL((k_raycast_literal<C>), grid, block, 0, ctx->stream, geom->view, rays, st, ctx->hit_triangle,
-                                   ctx->hit_distance, ctx->coop_spill, ctx->d_counters, ctx->coop_chunk, chained, ctx->retry_list,
+                hipLaunchKernelGGL((k_raycast_literal<C>), grid, block, 0, ctx->stream, geom->view, rays, st, cs.hit_triangle,
+                                   cs.hit_distance, cs.coop_spill, cs.d_counters, ctx->coop_chunk, chained, cs.retry_list,
                                    ctx->claim_static);
                 retry(C);
                 break;
             case Cast::LITERAL_LANE:
-                hipLaunchKernelGGL((k_raycast_retry<C, true>), grid, block, 0, ctx->stream, geom->view, rays, st, ctx->hit_triangle,
-                                   ctx->hit_distance, ctx->retry_list, ctx->d_counters);
+                hipLaunchKernelGGL((k_raycast_retry<C, true>), grid, block, 0, ctx->stream, geom->view, rays, st, cs.hit_triangle,
+                                   cs.hit_distance, cs.retry_list, cs.d_counters);
                 break;
             }
         });
@@ -421,25 +443,25 @@ struct PropagateCall {
         uint32_t *words = nullptr;
         if (finalize) {
             beside = ho;
-            words = ctx->d_words;
-            HIP_TRY(hipMemsetAsync(ctx->d_words, 0, W_RESULT_END * sizeof(uint32_t), ctx->stream));
+            words = cs.d_words;
+            int rc = scope.clear_results(); if (rc) return rc;
             if (final_rec)
                 hipLaunchKernelGGL(k_mark_tail, dim3(32), dim3(256), 0, ctx->stream, in_q, final_rec, photon_tail_stamp(final_epoch));
-            HIP_TRY(hipEventRecord(ctx->ev_fork, ctx->stream));          // (the words are cleared and the tail's photons stamped: the pass may start)
+            HIP_TRY(hipEventRecord(cs.ev_fork, ctx->stream));          // (the words are cleared and the tail's photons stamped: the pass may start)
         }
         if (ev) HIP_TRY(hipEventRecord(ev[EV_STEP_BEGIN], ctx->stream));
         with_bool(plan.cast == Cast::LITERAL, [&](auto L) {
             with_bool(plan.counting, [&](auto C) {
-                hipLaunchKernelGGL((k_tail_coop<C, L>), dim3(waves), dim3(PROP_BLOCK), 0, ctx->stream, geom->view, pv, ctx->d_step, work_in,
-                                   rng.seed, rng.photon_id_base, nsteps, opt.use_weights, scatter_first, ctx->coop_spill, ctx->d_counters, beside, words);
+                hipLaunchKernelGGL((k_tail_coop<C, L>), dim3(waves), dim3(PROP_BLOCK), 0, ctx->stream, geom->view, pv, cs.d_step, work_in,
+                                   rng.seed, rng.photon_id_base, nsteps, opt.use_weights, scatter_first, cs.coop_spill, cs.d_counters, beside, words);
             });
         });
         if (ev) HIP_TRY(hipEventRecord(ev[EV_STEP_END], ctx->stream));
         if (finalize) {
-            HIP_TRY(hipStreamWaitEvent(ctx->aux_stream, ctx->ev_fork, 0));
-            launch_finalize(ctx->aux_stream, photon_tail_stamp(final_epoch));
-            HIP_TRY(hipEventRecord(ctx->ev_join, ctx->aux_stream));
-            HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
+            HIP_TRY(hipStreamWaitEvent(cs.aux_stream, cs.ev_fork, 0));
+            launch_finalize(cs.aux_stream, photon_tail_stamp(final_epoch));
+            HIP_TRY(hipEventRecord(cs.ev_join, cs.aux_stream));
+            HIP_TRY(hipStreamWaitEvent(ctx->stream, cs.ev_join, 0));
             finalized = true;              // (the tail kernel writes every photon it held back)
         }
         HIP_TRY(hipGetLastError());
@@ -452,7 +474,7 @@ struct PropagateCall {
     {
         const unsigned blocks = (unsigned)((nphotons + COPY_ITEMS * 256 - 1) / (COPY_ITEMS * 256));
         hipLaunchKernelGGL(k_finalize_hits, dim3(blocks), dim3(256), 0, stream, geom->view, pv, (const float4 *)final_rec, final_epoch,
-                           (uint64_t)nphotons, ho, ctx->d_words, tail_mark);
+                           (uint64_t)nphotons, ho, cs.d_words, tail_mark);
     }
 
     // kernel, ray-cast, packet and physics times of a call's first `steps` steps from their events (time_kernels)
@@ -491,12 +513,12 @@ struct PropagateCall {
     int run_device_steps()
     {
         const int max_steps = opt.max_steps;
-        HIP_TRY(hipMemsetAsync(ctx->d_step, 0, sizeof(StepState), ctx->stream));
+        HIP_TRY(hipMemsetAsync(cs.d_step, 0, sizeof(StepState), ctx->stream));
         hipLaunchKernelGGL(k_set_word, dim3(1), dim3(1), 0, ctx->stream, in_q, 1u);
         hipLaunchKernelGGL(k_set_word, dim3(1), dim3(1), 0, ctx->stream, out_q, 1u);
         int rc = load_working(); if (rc) return rc;
         const int nev = opt.time_kernels ? EV_PER_STEP * max_steps : 0;
-        while ((int)ctx->step_events.size() < nev) { hipEvent_t e; HIP_TRY(hipEventCreate(&e)); ctx->step_events.push_back(e); }
+        while ((int)cs.step_events.size() < nev) { hipEvent_t e; HIP_TRY(hipEventCreate(&e)); cs.step_events.push_back(e); }
         const long long few = (long long)PROP_BLOCK * 16 * 8;
         int step = 0, next_check = 1, tail_step = -1;          // (tail_step: the step at which the fused tail was launched)
         bool done = false;
@@ -514,9 +536,7 @@ struct PropagateCall {
             std::swap(work_in, work_out);
             if (step == next_check && step < max_steps) {
                 // survivors = tail - 1 of what is now the input queue
-                HIP_TRY(hipMemcpyAsync(ctx->h_words + W_SURVIVORS, in_q, 4, hipMemcpyDeviceToHost, ctx->stream));
-                HIP_TRY(hipStreamSynchronize(ctx->stream));
-                n_upper = (long long)ctx->h_words[W_SURVIVORS] - 1;
+                rc = scope.read_survivors(in_q, &n_upper); if (rc) return rc;
                 if (n_upper <= 0) done = true;
                 // look every step once the tail is near, so that it starts when the reference's does
                 next_check = (plan.tail_watch && n_upper < 16 * few) ? step + 1 : (step < 8) ? step * 2 : step + 8;
@@ -527,9 +547,9 @@ struct PropagateCall {
             unsigned blocks = (unsigned)std::min<long long>((n_upper + 255) / 256, 4096);
             hipLaunchKernelGGL(k_store_working, dim3(std::max(blocks, 1u)), dim3(256), 0, ctx->stream, geom->view, pv, in_q, work_in);
         }
-        HIP_TRY(hipMemcpyAsync(ctx->h_step, ctx->d_step, sizeof(StepState), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(cs.h_step, cs.d_step, sizeof(StepState), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
-        acc.launches += ((const StepState *)ctx->h_step)->launches;
+        acc.launches += ((const StepState *)cs.h_step)->launches;
         return opt.time_kernels ? read_step_times(step, tail_step) : CHROMA_OK;
     }
 
@@ -542,20 +562,20 @@ struct PropagateCall {
         HIP_TRY(hipGetLastError());
         const int max_steps = opt.max_steps;
         int scatter_first = opt.scatter_first;
-        uint64_t n = nphotons;
+        long long n = (long long)nphotons;
         int step = 0;
         while (step < max_steps) {
-            const bool few = n < (uint64_t)PROP_BLOCK * 16 * 8;
+            const bool few = n < (long long)PROP_BLOCK * 16 * 8;
             int nsteps = (few || opt.use_weights) ? (max_steps - step) : 1;
-            if (opt.time_kernels) HIP_TRY(hipEventRecord(ctx->ev_start, ctx->stream));
-            int rc = launch_propagate(ctx, plan.counting, geom, pv, rng, {0, (int)n, in_q + 1, out_q, nsteps, opt.use_weights, scatter_first});
+            if (opt.time_kernels) HIP_TRY(hipEventRecord(cs.ev_start, ctx->stream));
+            int rc = launch_propagate(scope, plan.counting, geom, pv, rng, {0, (int)n, in_q + 1, out_q, nsteps, opt.use_weights, scatter_first});
             if (rc) return rc;
             acc.launches++;
             if (opt.time_kernels) {
-                HIP_TRY(hipEventRecord(ctx->ev_stop, ctx->stream));
-                HIP_TRY(hipEventSynchronize(ctx->ev_stop));
+                HIP_TRY(hipEventRecord(cs.ev_stop, ctx->stream));
+                HIP_TRY(hipEventSynchronize(cs.ev_stop));
                 float ms = 0.f;
-                HIP_TRY(hipEventElapsedTime(&ms, ctx->ev_start, ctx->ev_stop));
+                HIP_TRY(hipEventElapsedTime(&ms, cs.ev_start, cs.ev_stop));
                 acc.kernel_ms += ms;
             }
             step += nsteps;
@@ -563,10 +583,8 @@ struct PropagateCall {
             if (step < max_steps) {
                 std::swap(in_q, out_q);
                 // survivors = tail - 1 (one 4-byte read per step, as photon.py:250)
-                HIP_TRY(hipMemcpyAsync(ctx->h_words + W_SURVIVORS, in_q, 4, hipMemcpyDeviceToHost, ctx->stream));
                 hipLaunchKernelGGL(k_set_word, dim3(1), dim3(1), 0, ctx->stream, out_q, 1u);
-                HIP_TRY(hipStreamSynchronize(ctx->stream));
-                n = (uint64_t)ctx->h_words[W_SURVIVORS] - 1;
+                rc = scope.read_survivors(in_q, &n); if (rc) return rc;
                 if (n == 0) break;
             }
         }
@@ -578,29 +596,23 @@ struct PropagateCall {
     // tail kernel already (`finalized`, launch_tail).  Otherwise the abort word alone (photon.py:254-255).
     int finish(chroma_hits_request *hr, chroma_propagate_stats *stats, int32_t *aborted)
     {
-        uint32_t word = 0;
-        if (finalize) {
-            if (!finalized) {
-                HIP_TRY(hipMemsetAsync(ctx->d_words, 0, W_RESULT_END * sizeof(uint32_t), ctx->stream));
-                launch_finalize(ctx->stream, 0u);
-                HIP_TRY(hipGetLastError());
-            }
-            HIP_TRY(hipMemcpyAsync(ctx->h_words, ctx->d_words, W_RESULT_END * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-            HIP_TRY(hipStreamSynchronize(ctx->stream));
-            word = ctx->h_words[W_ABORT];
-            if (hr) hr->nhits = ctx->h_words[W_HIT_COUNT];
-        } else {
-            HIP_TRY(hipMemsetAsync(ctx->d_words + W_ABORT, 0, 4, ctx->stream));
+        int rc = CHROMA_OK;
+        if (!finalize) {
+            rc = scope.clear_words(W_ABORT); if (rc) return rc;
             const unsigned blocks = (unsigned)std::min<uint64_t>((nphotons + 255) / 256, 4096);
             hipLaunchKernelGGL(k_flags_or, dim3(blocks), dim3(256), 0, ctx->stream, pv.flags, (uint64_t)nphotons, CHROMA_NAN_ABORT,
-                               ctx->d_words + W_ABORT);
-            HIP_TRY(hipGetLastError());
-            int rc = read_word(ctx, W_ABORT, &word); if (rc) return rc;
+                               cs.d_words + W_ABORT);
+        } else if (!finalized) {
+            rc = scope.clear_results(); if (rc) return rc;
+            launch_finalize(ctx->stream, 0u);
         }
-        if (aborted) *aborted = (word & CHROMA_NAN_ABORT) ? 1 : 0;
+        HIP_TRY(hipGetLastError());
+        rc = scope.read_results(); if (rc) return rc;
+        if (hr) hr->nhits = scope.word(W_HIT_COUNT);          // (a call with a hits request finalizes)
+        if (aborted) *aborted = (scope.word(W_ABORT) & CHROMA_NAN_ABORT) ? 1 : 0;
         chroma_propagate_stats tmp; memset(&tmp, 0, sizeof tmp);
         chroma_propagate_stats *s = stats ? stats : &tmp;
-        int rc = chroma_propagate_stats_read(ctx, s); if (rc) return rc;
+        rc = stats_read(scope, s); if (rc) return rc;
         if (stats) {
             stats->launches += acc.launches;
             stats->kernel_ms += acc.kernel_ms;
@@ -620,29 +632,30 @@ struct PropagateCall {
 
 // chroma_init's share of this file: the grids of the ray-cast kernels from their residency, the walk and the launch policy
 // from the CHROMA_* environment
-int propagate_settings(chroma_ctx *ctx)
+int propagate_settings(const CallScope &scope)
 {
+    chroma_ctx *ctx = scope.ctx; CallState &cs = scope.state();
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, ctx->device));
     ctx->physics_blocks = prop.multiProcessorCount * 8;          // (for blocks of PHYS_BLOCK threads)
     const char *walk = getenv("CHROMA_WALK");
-    if (walk) ctx->walk = CHROMA_WALK_QUAD;                      // (what is no walk's name means the default)
+    if (walk) cs.walk = CHROMA_WALK_QUAD;                      // (what is no walk's name means the default)
     for (int w = 0; w < NWALKS; w++) {
         const Walk &row = WALKS[w];
         int per_cu = row.waves_per_cu;
         if (const char *e = getenv(row.waves_env)) per_cu = std::max(1, atoi(e));
         ctx->waves[(int)row.cast] = prop.multiProcessorCount * per_cu;
-        if (walk && (!strcmp(walk, row.name) || (row.alias && !strcmp(walk, row.alias)))) ctx->walk = w;
+        if (walk && (!strcmp(walk, row.name) || (row.alias && !strcmp(walk, row.alias)))) cs.walk = w;
     }
 #if CHROMA_EXPERIMENTAL
-    if (const char *e = getenv("CHROMA_PACKET")) ctx->packet_mode = !strcmp(e, "on") ? 1 : !strcmp(e, "auto") ? 2 : 0;
-    if (const char *e = getenv("CHROMA_AUTOSORT")) ctx->autosort_mode = !strcmp(e, "on") || !strcmp(e, "1") ? 1 : !strcmp(e, "off") || !strcmp(e, "0") ? 0 : 2;
+    if (const char *e = getenv("CHROMA_PACKET")) cs.packet_mode = !strcmp(e, "on") ? 1 : !strcmp(e, "auto") ? 2 : 0;
+    if (const char *e = getenv("CHROMA_AUTOSORT")) cs.autosort_mode = !strcmp(e, "on") || !strcmp(e, "1") ? 1 : !strcmp(e, "off") || !strcmp(e, "0") ? 0 : 2;
 #endif
     if (const char *e = getenv("CHROMA_RAY_CHUNK")) ctx->ray_chunk = std::max(64, atoi(e));
     if (const char *e = getenv("CHROMA_COOP_CHUNK")) ctx->coop_chunk = std::max(8, atoi(e));
     if (const char *e = getenv("CHROMA_CLAIM_STATIC")) { int big = 0, small = 0; if (sscanf(e, "%d:%d", &big, &small) < 2) small = big; ctx->claim_static = std::min(8, std::max(0, big)) | std::min(8, std::max(0, small)) << 4; }
     if (const char *e = getenv("CHROMA_TAIL"))        // coop (default) | split | fused (the lane-per-photon k_propagate)
-        ctx->tail_mode = !strcmp(e, "fused") ? CHROMA_TAIL_FUSED : !strcmp(e, "split") ? CHROMA_TAIL_SPLIT : CHROMA_TAIL_COOP;
+        cs.tail_mode = !strcmp(e, "fused") ? CHROMA_TAIL_FUSED : !strcmp(e, "split") ? CHROMA_TAIL_SPLIT : CHROMA_TAIL_COOP;
     return CHROMA_OK;
 }
 
@@ -663,19 +676,21 @@ int chroma_propagate_step(chroma_ctx *ctx, chroma_geometry *geom, int32_t first_
     if (first_photon < 0 || nthreads < 0) return set_error(CHROMA_ERR_INVALID, "negative photon range");
     if (nthreads == 0) return CHROMA_OK;
     if ((rc = check_stack(geom))) return rc;
-    return launch_propagate(ctx, ctx->counting != 0, geom, to_view(photons), rng,
+    const CallScope scope(ctx);
+    return launch_propagate(scope, scope.state().counting != 0, geom, to_view(photons), rng,
                             {first_photon, nthreads, d_input_queue, d_output_queue, max_steps, use_weights, scatter_first});
 }
 
-static int ensure_queues(chroma_ctx *ctx, size_t n)
+static int ensure_queues(const CallScope &scope, size_t n)
 {
-    if (ctx->queue_capacity >= n + 1) return CHROMA_OK;
+    chroma_ctx *ctx = scope.ctx; CallState &cs = scope.state();
+    if (cs.queue_capacity >= n + 1) return CHROMA_OK;
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    const auto buffers = queue_buffers(ctx);
+    const auto buffers = queue_buffers(cs);
     for (const QueueBuffer &b : buffers) { if (*b.ptr) hipFree(*b.ptr); *b.ptr = nullptr; }
-    ctx->queue_capacity = 0;
+    cs.queue_capacity = 0;
     for (const QueueBuffer &b : buffers) HIP_TRY(ctx_malloc(ctx, b.ptr, (n + 1) * b.bytes));
-    ctx->queue_capacity = n + 1;
+    cs.queue_capacity = n + 1;
     return CHROMA_OK;
 }
 
@@ -690,38 +705,39 @@ int chroma_intersect_mesh(chroma_ctx *ctx, chroma_geometry *geom, int32_t nthrea
 {
     if (!ctx || !geom || !d_origin || !d_direction || !d_distance) return set_error(CHROMA_ERR_INVALID, "bad argument");
     if (nthreads <= 0) return CHROMA_OK;
+    int rc = check_stack(geom); if (rc) return rc;
+    const CallScope scope(ctx);          // (the fast path uses the context's queues and ray records, as a propagate call does)
+    CallState &cs = scope.state();
     CallPlan plan;
-    int rc = make_plan(ctx, geom, -1, -1, -1, &plan); if (rc) return rc;
-    if ((rc = check_stack(geom))) return rc;
-    std::lock_guard<std::mutex> call_lock(ctx->call_mu);          // (the fast path uses the context's queues and ray records, as a propagate call does)
+    rc = make_plan(cs, geom, -1, -1, -1, &plan); if (rc) return rc;
     if (!plan.isect_quad) {
         const dim3 grid((unsigned)((nthreads + PROP_BLOCK - 1) / PROP_BLOCK)), block(PROP_BLOCK);
         with_bool(plan.counting, [&](auto C) {
             hipLaunchKernelGGL((k_distance_to_mesh<STACK_LDS, C>), grid, block, 0, ctx->stream, geom->view, nthreads, d_origin, d_direction,
-                               d_last_hit, d_distance, d_triangle, ctx->d_counters);
+                               d_last_hit, d_distance, d_triangle, cs.d_counters);
         });
         HIP_TRY(hipGetLastError());
         return CHROMA_OK;
     }
     // the quad walk of the default propagate step over the caller's rays: k_raycast_quad, then the strict loop for the rays it hands over
     HIP_TRY(hipSetDevice(ctx->device));
-    rc = ensure_queues(ctx, (size_t)nthreads); if (rc) return rc;
-    rc = ensure_spill(ctx, SPILL_COOP); if (rc) return rc;
-    StepState *st = ctx->d_step;
+    rc = ensure_queues(scope, (size_t)nthreads); if (rc) return rc;
+    rc = ensure_spill(scope, SPILL_COOP); if (rc) return rc;
+    StepState *st = cs.d_step;
     const unsigned blocks = (unsigned)((nthreads + 255) / 256);
     hipLaunchKernelGGL(k_step_set, dim3(1), dim3(1), 0, ctx->stream, st, (uint32_t)nthreads);
     hipLaunchKernelGGL(k_rays_from_arrays, dim3(blocks), dim3(256), 0, ctx->stream, geom->view, (int)nthreads, d_origin, d_direction,
-                       d_last_hit, ctx->rays, ctx->hit_triangle, ctx->hit_distance, ctx->retry_list, st);
+                       d_last_hit, cs.rays, cs.hit_triangle, cs.hit_distance, cs.retry_list, st);
     const unsigned waves = cast_waves(ctx, Cast::QUAD, nthreads);
     with_bool(plan.counting, [&](auto C) {
-        hipLaunchKernelGGL((k_raycast_quad<C>), dim3(waves), dim3(PROP_BLOCK), 0, ctx->stream, geom->view, ctx->rays, 0, st,
-                           ctx->hit_triangle, ctx->hit_distance, ctx->retry_list, ctx->coop_spill, ctx->d_counters, ctx->coop_chunk, 0, nullptr, ctx->claim_static);
+        hipLaunchKernelGGL((k_raycast_quad<C>), dim3(waves), dim3(PROP_BLOCK), 0, ctx->stream, geom->view, cs.rays, 0, st,
+                           cs.hit_triangle, cs.hit_distance, cs.retry_list, cs.coop_spill, cs.d_counters, ctx->coop_chunk, 0, nullptr, ctx->claim_static);
     });
-    hipLaunchKernelGGL(k_distance_finish, dim3(blocks), dim3(256), 0, ctx->stream, geom->view, (int)nthreads, ctx->rays, ctx->hit_triangle,
-                       ctx->hit_distance, d_distance, d_triangle, ctx->retry_list, st);
+    hipLaunchKernelGGL(k_distance_finish, dim3(blocks), dim3(256), 0, ctx->stream, geom->view, (int)nthreads, cs.rays, cs.hit_triangle,
+                       cs.hit_distance, d_distance, d_triangle, cs.retry_list, st);
     with_bool(plan.counting, [&](auto C) {
-        hipLaunchKernelGGL((k_distance_retry<C>), dim3(256), dim3(PROP_BLOCK), 0, ctx->stream, geom->view, ctx->rays, st,
-                           ctx->retry_list, d_distance, d_triangle, ctx->d_counters);
+        hipLaunchKernelGGL((k_distance_retry<C>), dim3(256), dim3(PROP_BLOCK), 0, ctx->stream, geom->view, cs.rays, st,
+                           cs.retry_list, d_distance, d_triangle, cs.d_counters);
     });
     HIP_TRY(hipGetLastError());
     return CHROMA_OK;
@@ -731,25 +747,14 @@ int chroma_intersect_mesh(chroma_ctx *ctx, chroma_geometry *geom, int32_t nthrea
 int chroma_propagate_stats_read(chroma_ctx *ctx, chroma_propagate_stats *stats)
 {
     if (!ctx || !stats) return set_error(CHROMA_ERR_INVALID, "bad argument");
-    DeviceCounters c;
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    HIP_TRY(hipMemcpy(&c, ctx->d_counters, sizeof c, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemset(ctx->d_counters, 0, sizeof c));
-    stats->photon_steps += c.photon_steps;
-    stats->nodes_visited += c.nodes_visited;
-    stats->triangles_tested += c.triangles_tested;
-    stats->stack_overflows += c.stack_overflows;
-    stats->stack_spills += c.stack_spills;
-    stats->packet_rays += c.packet_rays;
-    stats->packet_nodes_visited += c.packet_nodes;
-    stats->packet_triangles_tested += c.packet_tris;
-    return CHROMA_OK;
+    const CallScope scope(ctx);
+    return stats_read(scope, stats);
 }
 
 int chroma_set_counting(chroma_ctx *ctx, int32_t enabled)
 {
     if (!ctx) return set_error(CHROMA_ERR_INVALID, "null ctx");
-    ctx->counting = enabled ? 1 : 0;
+    CallScope(ctx).state().counting = enabled ? 1 : 0;
     return CHROMA_OK;
 }
 
@@ -757,7 +762,7 @@ int chroma_set_walk(chroma_ctx *ctx, int32_t mode)
 {
     if (!ctx) return set_error(CHROMA_ERR_INVALID, "null ctx");
     if (mode < 0 || mode >= NWALKS) return set_error(CHROMA_ERR_INVALID, "unknown walk mode %d", mode);
-    ctx->walk = mode;
+    CallScope(ctx).state().walk = mode;
     return CHROMA_OK;
 }
 
@@ -768,7 +773,7 @@ int chroma_set_packet(chroma_ctx *ctx, int32_t mode)
 #if !CHROMA_EXPERIMENTAL
     if (mode != 0) return set_error(CHROMA_ERR_INVALID, "the packet ray cast is an experiment that is not part of this build (csrc/experimental/: build_variants/libchroma_hip_experimental.so)");
 #endif
-    ctx->packet_mode = mode;
+    CallScope(ctx).state().packet_mode = mode;
     return CHROMA_OK;
 }
 
@@ -779,7 +784,7 @@ int chroma_set_autosort(chroma_ctx *ctx, int32_t mode)
 #if !CHROMA_EXPERIMENTAL
     if (mode != 0) return set_error(CHROMA_ERR_INVALID, "the engine-side direction sort is an experiment that is not part of this build (csrc/experimental/: build_variants/libchroma_hip_experimental.so)");
 #endif
-    ctx->autosort_mode = mode;
+    CallScope(ctx).state().autosort_mode = mode;
     return CHROMA_OK;
 }
 
@@ -788,7 +793,7 @@ int chroma_set_tail(chroma_ctx *ctx, int32_t mode)
     if (!ctx) return set_error(CHROMA_ERR_INVALID, "null ctx");
     if (mode != CHROMA_TAIL_COOP && mode != CHROMA_TAIL_SPLIT && mode != CHROMA_TAIL_FUSED)
         return set_error(CHROMA_ERR_INVALID, "unknown tail mode %d", mode);
-    ctx->tail_mode = mode;
+    CallScope(ctx).state().tail_mode = mode;
     return CHROMA_OK;
 }
 
@@ -801,16 +806,17 @@ static int propagate_order(PropagateCall &, uint32_t **d_order) { *d_order = nul
 
 // the photons' final records (chroma_propagate_hits): 64 bytes per photon of the largest batch seen, zeroed once -- a record
 // belongs to a call when it carries that call's epoch, and epochs start at 1
-static int ensure_final_records(chroma_ctx *ctx, size_t n)
+static int ensure_final_records(const CallScope &scope, size_t n)
 {
-    if (ctx->final_capacity >= n) return CHROMA_OK;
+    chroma_ctx *ctx = scope.ctx; CallState &cs = scope.state();
+    if (cs.final_capacity >= n) return CHROMA_OK;
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (ctx->final_rec) hipFree(ctx->final_rec);
-    ctx->final_rec = nullptr; ctx->final_capacity = 0;
-    HIP_TRY(ctx_malloc(ctx, (void **)&ctx->final_rec, n * 4 * sizeof(float4)));
-    HIP_TRY(hipMemsetAsync(ctx->final_rec, 0, n * 4 * sizeof(float4), ctx->stream));
-    ctx->final_capacity = n;
-    ctx->final_epoch = 0;
+    if (cs.final_rec) hipFree(cs.final_rec);
+    cs.final_rec = nullptr; cs.final_capacity = 0;
+    HIP_TRY(ctx_malloc(ctx, (void **)&cs.final_rec, n * 4 * sizeof(float4)));
+    HIP_TRY(hipMemsetAsync(cs.final_rec, 0, n * 4 * sizeof(float4), ctx->stream));
+    cs.final_capacity = n;
+    cs.final_epoch = 0;
     return CHROMA_OK;
 }
 
@@ -820,11 +826,12 @@ static int propagate_impl(chroma_ctx *ctx, chroma_geometry *geom, const chroma_p
 {
     if (!ctx || !geom) return set_error(CHROMA_ERR_INVALID, "bad argument");
     int rc = check_photons(photons, true); if (rc) return rc;
+    // one call at a time per context: the queues, working sets, step block and final records are the context's own
+    const CallScope scope(ctx);
+    CallState &cs = scope.state();
     // what this call does: the context's settings as they are NOW, overridden by the call's own options
     CallPlan plan;
-    rc = make_plan(ctx, geom, opt.walk, opt.tail, opt.counting, &plan); if (rc) return rc;
-    // one call at a time per context: the queues, working sets, step block and final records are the context's own
-    std::lock_guard<std::mutex> call_lock(ctx->call_mu);
+    rc = make_plan(cs, geom, opt.walk, opt.tail, opt.counting, &plan); if (rc) return rc;
     if (hr) {
         hr->nhits = 0;
         if (!geom->view.nsolids) return set_error(CHROMA_ERR_INVALID, "geometry has no detector channel map");
@@ -841,22 +848,22 @@ static int propagate_impl(chroma_ctx *ctx, chroma_geometry *geom, const chroma_p
     if (stepping && (rc = check_stack(geom))) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     if (stepping) {
-        rc = ensure_queues(ctx, nphotons); if (rc) return rc;
-        rc = ensure_spill(ctx, plan.spill); if (rc) return rc;
+        rc = ensure_queues(scope, nphotons); if (rc) return rc;
+        rc = ensure_spill(scope, plan.spill); if (rc) return rc;
     }
     // (final records: with a hit request, or for every call under CHROMA_FINAL_RECORDS=1 -- an A/B switch)
     static const bool records_always = getenv("CHROMA_FINAL_RECORDS") && atoi(getenv("CHROMA_FINAL_RECORDS")) != 0;
     const bool use_records = stepping && (hr != nullptr || records_always) && plan.tail_mode != CHROMA_TAIL_FUSED;
     if (use_records) {
-        rc = ensure_final_records(ctx, nphotons); if (rc) return rc;
-        ctx->final_epoch++;
-        if (ctx->final_epoch == 0u || ctx->final_epoch >= 0x7FFFFFFFu) {            // (wrapped -- the top bit marks the tail kernel's photons --: no stale record may look current)
-            HIP_TRY(hipMemsetAsync(ctx->final_rec, 0, ctx->final_capacity * 4 * sizeof(float4), ctx->stream));
-            ctx->final_epoch = 1u;
+        rc = ensure_final_records(scope, nphotons); if (rc) return rc;
+        cs.final_epoch++;
+        if (cs.final_epoch == 0u || cs.final_epoch >= 0x7FFFFFFFu) {            // (wrapped -- the top bit marks the tail kernel's photons --: no stale record may look current)
+            HIP_TRY(hipMemsetAsync(cs.final_rec, 0, cs.final_capacity * 4 * sizeof(float4), ctx->stream));
+            cs.final_epoch = 1u;
         }
     }
-    PropagateCall call = {ctx, geom, plan, to_view(photons), rng, opt, nphotons, ncopies, ctx->queue_a, ctx->queue_b, ctx->work_a, ctx->work_b,
-                          ctx->rays, ctx->rays_b, use_records ? ctx->final_rec : nullptr, ctx->final_epoch};
+    PropagateCall call = {scope, cs, ctx, geom, plan, to_view(photons), rng, opt, nphotons, ncopies, cs.queue_a, cs.queue_b, cs.work_a, cs.work_b,
+                          cs.rays, cs.rays_b, use_records ? cs.final_rec : nullptr, cs.final_epoch};
     if (hr) {
         call.ho.want = 1;
         call.ho.detection_state = hr->detection_state;
@@ -905,7 +912,7 @@ int chroma_propagate_opt(chroma_ctx *ctx, chroma_geometry *geom, const chroma_ph
 
 #if CHROMA_HYBRID_RENDER
 // ---- the hybrid render (chroma/cuda/hybrid_render.cu as chroma/camera.py:188-249 drives it; kernels_hybrid_render.h) ----
-// Everything is checked before the first launch.  The two sample passes take the context's call lock: they run the step
+// Everything is checked before the first launch.  The two sample passes hold a CallScope: they run the step
 // functions and count stack overflows into the context's counters, as the propagate calls do.
 static int hybrid_check(chroma_ctx *ctx, chroma_geometry *geom, int32_t nthreads, const uint32_t *d_rng_counters, uint32_t ncounters,
                         uint32_t nlookup, int32_t max_steps, const void *s_tri, const void *s_side, const void *s_history)
@@ -938,7 +945,7 @@ int chroma_hybrid_lookup(chroma_ctx *ctx, chroma_geometry *geom, int32_t nthread
     if (n <= 0) return CHROMA_OK;
     const uint32_t key_none = 2u * (uint32_t)geom->ntriangles;            // past every (2 * triangle + side)
     const int end_bit = 32 - __builtin_clz(key_none);
-    std::lock_guard<std::mutex> call_lock(ctx->call_mu);
+    const CallScope scope(ctx);
     void *buf[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};          // keys, ids, sorted keys, order, values
     const size_t bytes[5] = {(size_t)n * 4, (size_t)n * 4, (size_t)n * 4, (size_t)n * 4, (size_t)n * 12};
     for (int i = 0; i < 5 && rc == CHROMA_OK; i++) rc = chroma_malloc(ctx, bytes[i], &buf[i]);
@@ -948,7 +955,7 @@ int chroma_hybrid_lookup(chroma_ctx *ctx, chroma_geometry *geom, int32_t nthread
         hipLaunchKernelGGL((k_hybrid_lookup<STACK_LDS>), dim3((unsigned)((n + PROP_BLOCK - 1) / PROP_BLOCK)), dim3(PROP_BLOCK), 0,
                            ctx->stream, geom->view, (int)n, (int)offset, position[0], position[1], position[2], rng.seed,
                            rng.photon_id_base, d_rng_counters, wavelength, xyz[0], xyz[1], xyz[2], max_steps, key_none, keys, ids,
-                           values, d_sample_triangle, d_sample_side, d_sample_history, d_sample_cos, ctx->d_counters);
+                           values, d_sample_triangle, d_sample_side, d_sample_history, d_sample_cos, scope.state().d_counters);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) rc = set_error((int)e, "k_hybrid_lookup: %s", hipGetErrorString(e));
     }
@@ -976,11 +983,11 @@ int chroma_hybrid_image(chroma_ctx *ctx, chroma_geometry *geom, int32_t nthreads
     if ((uint32_t)nthreads > nimage) return set_error(CHROMA_ERR_INVALID, "%d rays but an image of %u pixels", nthreads, nimage);
     if (nlookup_calls < 1) return set_error(CHROMA_ERR_INVALID, "nlookup_calls must be at least 1");
     if (nthreads == 0) return CHROMA_OK;
-    std::lock_guard<std::mutex> call_lock(ctx->call_mu);
+    const CallScope scope(ctx);
     hipLaunchKernelGGL((k_hybrid_image<STACK_LDS>), dim3((unsigned)((nthreads + PROP_BLOCK - 1) / PROP_BLOCK)), dim3(PROP_BLOCK), 0,
                        ctx->stream, geom->view, (int)nthreads, rng.seed, rng.photon_id_base, d_rng_counters, d_positions, d_directions,
                        wavelength, xyz[0], xyz[1], xyz[2], d_lookup1, d_lookup2, d_image, (int)nlookup_calls, max_steps,
-                       d_sample_triangle, d_sample_side, d_sample_history, ctx->d_counters);
+                       d_sample_triangle, d_sample_side, d_sample_history, scope.state().d_counters);
     HIP_TRY(hipGetLastError());
     return CHROMA_OK;
 }

@@ -30,9 +30,9 @@ CHROMA_LOCAL int set_error(int code, const char *fmt, ...);
             return set_error((int)e_, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
 
-struct chroma_ctx {
-    int device;
-    hipStream_t stream;
+// What only one call at a time may touch: the context's scratch buffers, the events and the second stream that go with them,
+// and the settings a call reads when it starts.  A member of chroma_ctx that nothing but a CallScope hands out.
+struct CallState {
     // queue ping-pong buffers for chroma_propagate (n+1 words each)
     uint32_t *queue_a = nullptr, *queue_b = nullptr;
     size_t queue_capacity = 0;
@@ -49,21 +49,30 @@ struct chroma_ctx {
     DeviceCounters *d_counters = nullptr;
     uint32_t *d_words = nullptr;        // small device scratch: SCRATCH_WORDS words, the slots named by ScratchWord
     uint32_t *h_words = nullptr;        // pinned mirror
-    int counting = 0;
     StepState *d_step = nullptr;           // device-side step control block (k_step_begin)
     uint32_t *h_step = nullptr;            // pinned copy for the occasional read-back
-    int physics_blocks = 256 * 8;          // grid cap of k_physics (blocks stride over the queue)
     std::vector<hipEvent_t> step_events;   // 4 per step when kernels are timed
-    int waves[CHROMA_WALK_LITERAL_LANE + 1] = {};    // largest grid of each ray cast, by Cast: CUs x the waves per CU of its row in WALKS (chroma_hip.hip), set at init
     uint2 *wide_spill = nullptr;           // [waves of the wide cast][WIDE_SPILL][64] stack entries beyond the LDS part
     uint2 *coop_spill = nullptr;           // [rays in flight of the largest cooperative cast][COOP_SPILL]
-    int ray_chunk = 256, coop_chunk = 64;  // rays a persistent wave takes from the queue per atomic (big batches)
-    int claim_static = 5 | 8 << 4;                  // eighths of a wave's share of a launch's rays that it takes without the counter (k_raycast_quad; CHROMA_CLAIM_STATIC)
+    hipEvent_t ev_start = nullptr, ev_stop = nullptr, ev_mid = nullptr;
+    hipStream_t aux_stream = nullptr;          // k_finalize_hits beside the tail kernel (launch_tail)
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    // ---- the settings: chroma_set_* and the CHROMA_* environment write them, a call reads them when it starts (CallPlan) ----
+    int counting = 0;
     int tail_mode = CHROMA_TAIL_COOP;      // CHROMA_TAIL_*: the last photons in k_tail_coop | one launch set per step to the end | k_propagate only
     int autosort_mode = 0;                 // the order a large call takes its photons up in: 0 as they come (default: the index sort + gather cost more than they gain, profiles/r03/ab_autosort.txt), 1 by direction cell, 2 decided by a probe (propagate_order)
     int packet_mode = 0;                   // k_raycast_packet for the first step: 0 never (default: it is not faster, profiles/r03/ab_packet_first_step.txt), 1 always, 2 when the photons are coherent (CHROMA_PACKET=off|on|auto)
     int walk = CHROMA_WALK_QUAD;           // CHROMA_WALK_*: reference tree | wide tree with 1, 8 or 4 (default) lanes per ray
-    hipEvent_t ev_start = nullptr, ev_stop = nullptr, ev_mid = nullptr;
+};
+
+// Outside CallState: what is fixed once chroma_init returns, and what has a lock of its own.
+struct chroma_ctx {
+    int device;
+    hipStream_t stream;
+    int physics_blocks = 256 * 8;          // grid cap of k_physics (blocks stride over the queue)
+    int waves[CHROMA_WALK_LITERAL_LANE + 1] = {};    // largest grid of each ray cast, by Cast: CUs x the waves per CU of its row in WALKS (chroma_hip.hip), set at init
+    int ray_chunk = 256, coop_chunk = 64;  // rays a persistent wave takes from the queue per atomic (big batches)
+    int claim_static = 5 | 8 << 4;                  // eighths of a wave's share of a launch's rays that it takes without the counter (k_raycast_quad; CHROMA_CLAIM_STATIC)
     // the one exchange of the path (per-channel hit arrays): an RCCL communicator over the node's GPUs
     ncclComm_t comm = nullptr;
     int comm_nranks = 1, comm_rank = 0;
@@ -71,7 +80,6 @@ struct chroma_ctx {
     size_t gather_capacity = 0;
     // ---- device-memory pool behind chroma_malloc / chroma_free (see there) ----
     struct PoolBlock { void *ptr; hipEvent_t ev; };
-    std::mutex call_mu;                                    // one chroma_propagate* call at a time per context (see propagate_impl)
     std::mutex pool_mu;
     std::multimap<size_t, PoolBlock> pool;                 // free blocks by size
     std::unordered_map<void *, size_t> live;               // size of every block handed out
@@ -80,8 +88,6 @@ struct chroma_ctx {
     uint64_t pool_hits = 0, pool_misses = 0;
     // ---- host -> device uploads: a second stream and a ring of pinned staging buffers (chroma_upload) ----
     hipStream_t copy_stream = nullptr;
-    hipStream_t aux_stream = nullptr;          // k_finalize_hits beside the tail kernel (launch_tail)
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     std::mutex stage_mu;
     static constexpr int STAGE_N = 3;
     static constexpr size_t STAGE_BYTES = 64u << 20;
@@ -91,6 +97,14 @@ struct chroma_ctx {
     std::mutex stage_down_mu;
     void *stage_down[STAGE_N] = {nullptr, nullptr, nullptr};
     hipEvent_t stage_down_ev[STAGE_N] = {nullptr, nullptr, nullptr};
+private:
+    // THE RULE: calls on one context that use its scratch run one at a time, and two threads may share a handle.  call_state
+    // is reached through a CallScope and in no other way; a CallScope holds the mutex below for as long as it lives.  Only the
+    // extern "C" entry points construct one; what they call takes the scope (or its CallState) as a parameter and never
+    // locks, so no path takes the mutex twice.
+    friend class CallScope;
+    std::mutex call_mu;
+    CallState call_state;
 };
 
 struct chroma_geometry {
@@ -104,18 +118,7 @@ struct chroma_geometry {
     size_t device_bytes = 0;
 };
 
-// The buffers ensure_queues (chroma_hip.hip) sizes for the largest call seen and chroma_shutdown frees, in allocation order,
-// each of queue_capacity slots of `bytes` bytes
-struct QueueBuffer { void **ptr; size_t bytes; };
-static inline std::array<QueueBuffer, 9> queue_buffers(chroma_ctx *c)
-{
-    return {{{(void **)&c->queue_a, sizeof(uint32_t)}, {(void **)&c->queue_b, sizeof(uint32_t)},
-             {(void **)&c->hit_triangle, sizeof(int32_t)}, {(void **)&c->hit_distance, sizeof(float)},
-             {(void **)&c->retry_list, sizeof(uint32_t)}, {(void **)&c->rays, 4 * sizeof(float4)}, {(void **)&c->rays_b, 4 * sizeof(float4)},
-             {(void **)&c->work_a, 4 * sizeof(float4)}, {(void **)&c->work_b, 4 * sizeof(float4)}}};
-}
-
-// The slots of chroma_ctx::d_words and its pinned mirror h_words.  k_finalize_hits and k_tail_coop address the first three
+// The slots of CallState::d_words and its pinned mirror h_words.  k_finalize_hits and k_tail_coop address the first three
 // from one pointer (words[0] the count, words[2] the abort bits): the numbers are fixed.
 enum ScratchWord {
     W_HIT_COUNT = 0,        // hits counted or written (k_finalize_hits, k_tail_coop, the hit calls of kernel_calls.hip)
@@ -128,13 +131,68 @@ enum ScratchWord {
     SCRATCH_WORDS = 16
 };
 
+// One entry point's hold on the context's CallState, from its argument checks to its return.
+class CallScope {
+public:
+    explicit CallScope(chroma_ctx *c) : ctx(c), lock_(c->call_mu) {}
+    CallScope(const CallScope &) = delete;
+    CallScope &operator=(const CallScope &) = delete;
+    CallState &state() const { return ctx->call_state; }
+
+    // `count` scratch words from `first` on, zeroed on the context's stream
+    int clear_words(ScratchWord first, int count = 1) const
+    {
+        HIP_TRY(hipMemsetAsync(state().d_words + first, 0, count * sizeof(uint32_t), ctx->stream));
+        return CHROMA_OK;
+    }
+    int clear_results() const { return clear_words(W_HIT_COUNT, W_RESULT_END - W_HIT_COUNT); }
+    // ... and read back into the pinned mirror, once the stream has drained: word() has them
+    int read_words(ScratchWord first, int count = 1) const { return read_back(first, state().d_words + first, count); }
+    int read_results() const { return read_words(W_HIT_COUNT, W_RESULT_END - W_HIT_COUNT); }
+    uint32_t word(ScratchWord slot) const { return state().h_words[slot]; }
+    int read_word(ScratchWord slot, uint32_t *out) const
+    {
+        const int rc = read_words(slot);
+        *out = word(slot);
+        return rc;
+    }
+    // the photons a queue holds (its tail is survivors + 1), through W_SURVIVORS of the mirror
+    int read_survivors(const uint32_t *d_queue, long long *n) const
+    {
+        const int rc = read_back(W_SURVIVORS, d_queue, 1);
+        *n = (long long)word(W_SURVIVORS) - 1;
+        return rc;
+    }
+
+    chroma_ctx *const ctx;
+private:
+    int read_back(ScratchWord slot, const uint32_t *d_src, int count) const
+    {
+        HIP_TRY(hipMemcpyAsync(state().h_words + slot, d_src, count * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        return CHROMA_OK;
+    }
+    std::lock_guard<std::mutex> lock_;
+};
+
+// The buffers ensure_queues (chroma_hip.hip) sizes for the largest call seen and chroma_shutdown frees, in allocation order,
+// each of queue_capacity slots of `bytes` bytes
+struct QueueBuffer { void **ptr; size_t bytes; };
+static inline std::array<QueueBuffer, 9> queue_buffers(CallState &c)
+{
+    return {{{(void **)&c.queue_a, sizeof(uint32_t)}, {(void **)&c.queue_b, sizeof(uint32_t)},
+             {(void **)&c.hit_triangle, sizeof(int32_t)}, {(void **)&c.hit_distance, sizeof(float)},
+             {(void **)&c.retry_list, sizeof(uint32_t)}, {(void **)&c.rays, 4 * sizeof(float4)}, {(void **)&c.rays_b, 4 * sizeof(float4)},
+             {(void **)&c.work_a, 4 * sizeof(float4)}, {(void **)&c.work_b, 4 * sizeof(float4)}}};
+}
+
 // hipMalloc for the library's own working buffers: when the device is out of memory, everything parked in the pool
 // behind chroma_malloc / chroma_free is given back first (defined next to the pool)
 CHROMA_LOCAL hipError_t ctx_malloc(chroma_ctx *ctx, void **ptr, size_t bytes);
 
 // chroma_init's share of the propagate path: the ray-cast grids and the launch policy, from the device and the CHROMA_*
 // environment (chroma_hip.hip: it knows the kernels' residency)
-CHROMA_LOCAL int propagate_settings(chroma_ctx *ctx);
+CHROMA_LOCAL int propagate_settings(const CallScope &scope);
 
 extern "C" {
 // (bvh_device.hip) d_order[n] = the photons 0..n-1 ordered by a 16-bit cell of their direction; queued on the context's stream
@@ -170,13 +228,4 @@ template <class F>
 static void with_bool(bool b, F &&f)
 {
     if (b) f(std::true_type{}); else f(std::false_type{});
-}
-
-// one of the context's scratch words, read back
-static int read_word(chroma_ctx *ctx, ScratchWord slot, uint32_t *out)
-{
-    HIP_TRY(hipMemcpyAsync(ctx->h_words + slot, ctx->d_words + slot, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    *out = ctx->h_words[slot];
-    return CHROMA_OK;
 }

@@ -84,27 +84,29 @@ int chroma_init(int device, chroma_ctx **out)
     ctx->device = device;
     HIP_TRY(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
     HIP_TRY(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
-    HIP_TRY(hipStreamCreateWithFlags(&ctx->aux_stream, hipStreamNonBlocking));
-    HIP_TRY(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
     {
         size_t free_b = 0, total_b = 0;
         HIP_TRY(hipMemGetInfo(&free_b, &total_b));
         ctx->pool_limit = (size_t)(0.4 * (double)total_b);
         if (const char *e = getenv("CHROMA_POOL_MB")) ctx->pool_limit = (size_t)std::max(0ll, atoll(e)) << 20;
     }
-    HIP_TRY(hipMalloc((void **)&ctx->d_counters, sizeof(DeviceCounters)));
-    HIP_TRY(hipMemset(ctx->d_counters, 0, sizeof(DeviceCounters)));
-    HIP_TRY(hipMalloc((void **)&ctx->d_words, SCRATCH_WORDS * sizeof(uint32_t)));
-    HIP_TRY(hipMemset(ctx->d_words, 0, SCRATCH_WORDS * sizeof(uint32_t)));
-    HIP_TRY(hipHostMalloc((void **)&ctx->h_words, SCRATCH_WORDS * sizeof(uint32_t), hipHostMallocDefault));
-    HIP_TRY(hipMalloc((void **)&ctx->d_step, sizeof(StepState)));
-    HIP_TRY(hipMemset(ctx->d_step, 0, sizeof(StepState)));
-    HIP_TRY(hipHostMalloc((void **)&ctx->h_step, sizeof(StepState), hipHostMallocDefault));
-    { const int rc = propagate_settings(ctx); if (rc) return rc; }
-    HIP_TRY(hipEventCreate(&ctx->ev_start));
-    HIP_TRY(hipEventCreate(&ctx->ev_stop));
-    HIP_TRY(hipEventCreate(&ctx->ev_mid));
+    const CallScope scope(ctx);
+    CallState &cs = scope.state();
+    HIP_TRY(hipStreamCreateWithFlags(&cs.aux_stream, hipStreamNonBlocking));
+    HIP_TRY(hipEventCreateWithFlags(&cs.ev_fork, hipEventDisableTiming));
+    HIP_TRY(hipEventCreateWithFlags(&cs.ev_join, hipEventDisableTiming));
+    HIP_TRY(hipMalloc((void **)&cs.d_counters, sizeof(DeviceCounters)));
+    HIP_TRY(hipMemset(cs.d_counters, 0, sizeof(DeviceCounters)));
+    HIP_TRY(hipMalloc((void **)&cs.d_words, SCRATCH_WORDS * sizeof(uint32_t)));
+    HIP_TRY(hipMemset(cs.d_words, 0, SCRATCH_WORDS * sizeof(uint32_t)));
+    HIP_TRY(hipHostMalloc((void **)&cs.h_words, SCRATCH_WORDS * sizeof(uint32_t), hipHostMallocDefault));
+    HIP_TRY(hipMalloc((void **)&cs.d_step, sizeof(StepState)));
+    HIP_TRY(hipMemset(cs.d_step, 0, sizeof(StepState)));
+    HIP_TRY(hipHostMalloc((void **)&cs.h_step, sizeof(StepState), hipHostMallocDefault));
+    { const int rc = propagate_settings(scope); if (rc) return rc; }
+    HIP_TRY(hipEventCreate(&cs.ev_start));
+    HIP_TRY(hipEventCreate(&cs.ev_stop));
+    HIP_TRY(hipEventCreate(&cs.ev_mid));
     *out = ctx;
     return CHROMA_OK;
 }
@@ -120,21 +122,25 @@ int chroma_shutdown(chroma_ctx *ctx)
     for (int i = 0; i < chroma_ctx::STAGE_N; i++) { if (ctx->stage[i]) hipHostFree(ctx->stage[i]); if (ctx->stage_ev[i]) hipEventDestroy(ctx->stage_ev[i]); }
     for (int i = 0; i < chroma_ctx::STAGE_N; i++) { if (ctx->stage_down[i]) hipHostFree(ctx->stage_down[i]); if (ctx->stage_down_ev[i]) hipEventDestroy(ctx->stage_down_ev[i]); }
     hipStreamDestroy(ctx->copy_stream);
-    if (ctx->aux_stream) { hipStreamSynchronize(ctx->aux_stream); hipStreamDestroy(ctx->aux_stream); }
-    if (ctx->ev_fork) hipEventDestroy(ctx->ev_fork);
-    if (ctx->ev_join) hipEventDestroy(ctx->ev_join);
-    for (const QueueBuffer &b : queue_buffers(ctx)) if (*b.ptr) hipFree(*b.ptr);
-    if (ctx->wide_spill) hipFree(ctx->wide_spill);
-    if (ctx->coop_spill) hipFree(ctx->coop_spill);
-    if (ctx->d_step) hipFree(ctx->d_step);
-    if (ctx->h_step) hipHostFree(ctx->h_step);
-    for (hipEvent_t e : ctx->step_events) hipEventDestroy(e);
-    hipFree(ctx->d_counters);
-    hipFree(ctx->d_words);
-    hipHostFree(ctx->h_words);
-    hipEventDestroy(ctx->ev_start);
-    hipEventDestroy(ctx->ev_stop);
-    hipEventDestroy(ctx->ev_mid);
+    {
+        const CallScope scope(ctx);          // (gone before the context and its mutex are)
+        CallState &cs = scope.state();
+        if (cs.aux_stream) { hipStreamSynchronize(cs.aux_stream); hipStreamDestroy(cs.aux_stream); }
+        if (cs.ev_fork) hipEventDestroy(cs.ev_fork);
+        if (cs.ev_join) hipEventDestroy(cs.ev_join);
+        for (const QueueBuffer &b : queue_buffers(cs)) if (*b.ptr) hipFree(*b.ptr);
+        if (cs.wide_spill) hipFree(cs.wide_spill);
+        if (cs.coop_spill) hipFree(cs.coop_spill);
+        if (cs.d_step) hipFree(cs.d_step);
+        if (cs.h_step) hipHostFree(cs.h_step);
+        for (hipEvent_t e : cs.step_events) hipEventDestroy(e);
+        hipFree(cs.d_counters);
+        hipFree(cs.d_words);
+        hipHostFree(cs.h_words);
+        hipEventDestroy(cs.ev_start);
+        hipEventDestroy(cs.ev_stop);
+        hipEventDestroy(cs.ev_mid);
+    }
     hipStreamDestroy(ctx->stream);
     delete ctx;
     return CHROMA_OK;

@@ -52,7 +52,7 @@ static int propagate_order(PropagateCall &call, uint32_t **d_order)
     if (mode == 0 || call.ncopies != 1 || nphotons < AUTOSORT_MIN) return CHROMA_OK;
     if (mode == 2) {
         const uint32_t nsamples = 1024;
-        uint32_t *probe = ctx->d_words + W_ORDER_PROBE;
+        uint32_t *probe = call.cs.d_words + W_ORDER_PROBE;
         uint32_t h[W_ORDER_PROBE_END - W_ORDER_PROBE];
         HIP_TRY(hipMemsetAsync(probe, 0, sizeof h, ctx->stream));
         hipLaunchKernelGGL(k_order_probe, dim3(nsamples / 4), dim3(256), 0, ctx->stream, call.pv, nphotons, nsamples, probe);

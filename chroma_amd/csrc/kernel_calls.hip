@@ -14,6 +14,18 @@
 
 #include "kernels_pdf.h"
 
+// The count and copy calls: the hit word cleared, the launch it is given run on it (none for an empty range), the word read back
+template <class Launch>
+static int counted_launch(const CallScope &scope, bool any, uint32_t *count, Launch &&launch)
+{
+    uint32_t n = 0;
+    int rc = scope.clear_words(W_HIT_COUNT); if (rc) return rc;
+    if (any) { launch(scope.state().d_words + W_HIT_COUNT); HIP_TRY(hipGetLastError()); }
+    rc = scope.read_word(W_HIT_COUNT, &n);
+    if (count) *count = n;
+    return rc;
+}
+
 extern "C" {
 
 int chroma_photon_duplicate(chroma_ctx *ctx, int32_t first_photon, int32_t nthreads,
@@ -33,13 +45,11 @@ int chroma_count_photons(chroma_ctx *ctx, int32_t first_photon, int32_t nthreads
                          const uint32_t *d_flags, uint32_t *count)
 {
     if (!ctx || !d_flags || !count) return set_error(CHROMA_ERR_INVALID, "bad argument");
-    HIP_TRY(hipMemsetAsync(ctx->d_words + W_HIT_COUNT, 0, 4, ctx->stream));
-    if (nthreads > 0) {
+    const CallScope scope(ctx);
+    return counted_launch(scope, nthreads > 0, count, [&](uint32_t *word) {
         hipLaunchKernelGGL(k_count_photons, dim3((unsigned)std::min((nthreads + 255) / 256, 4096)), dim3(256), 0, ctx->stream, d_flags, first_photon,
-                           nthreads, target_flag, ctx->d_words + W_HIT_COUNT);
-        HIP_TRY(hipGetLastError());
-    }
-    return read_word(ctx, W_HIT_COUNT, count);
+                           nthreads, target_flag, word);
+    });
 }
 
 int chroma_copy_photons(chroma_ctx *ctx, int32_t first_photon, int32_t nthreads, uint32_t target_flag,
@@ -48,16 +58,11 @@ int chroma_copy_photons(chroma_ctx *ctx, int32_t first_photon, int32_t nthreads,
     if (!ctx) return set_error(CHROMA_ERR_INVALID, "null ctx");
     int rc = check_photons(src, false); if (rc) return rc;
     rc = check_photons(dst, false); if (rc) return rc;
-    HIP_TRY(hipMemsetAsync(ctx->d_words + W_HIT_COUNT, 0, 4, ctx->stream));
-    if (nthreads > 0) {
+    const CallScope scope(ctx);
+    return counted_launch(scope, nthreads > 0, ncopied, [&](uint32_t *word) {
         hipLaunchKernelGGL(k_copy_photons, dim3((unsigned)(((long long)nthreads + 16 * 256 - 1) / (16 * 256))), dim3(256), 0, ctx->stream, to_view(src), to_view(dst),
-                           first_photon, nthreads, target_flag, ctx->d_words + W_HIT_COUNT);
-        HIP_TRY(hipGetLastError());
-    }
-    uint32_t n = 0;
-    rc = read_word(ctx, W_HIT_COUNT, &n);
-    if (ncopied) *ncopied = n;
-    return rc;
+                           first_photon, nthreads, target_flag, word);
+    });
 }
 
 int chroma_copy_photon_queue(chroma_ctx *ctx, int32_t first_photon, int32_t nthreads, const uint32_t *d_queue,
@@ -79,13 +84,11 @@ int chroma_count_photon_hits(chroma_ctx *ctx, chroma_geometry *geom, int32_t fir
     if (!ctx || !geom || !count) return set_error(CHROMA_ERR_INVALID, "bad argument");
     if (!geom->view.nsolids) return set_error(CHROMA_ERR_INVALID, "geometry has no detector channel map");
     int rc = check_photons(photons, false); if (rc) return rc;
-    HIP_TRY(hipMemsetAsync(ctx->d_words + W_HIT_COUNT, 0, 4, ctx->stream));
-    if (nphotons > 0) {
+    const CallScope scope(ctx);
+    return counted_launch(scope, nphotons > 0, count, [&](uint32_t *word) {
         hipLaunchKernelGGL(k_count_hits, dim3((unsigned)std::min((nphotons + 255) / 256, 4096)), dim3(256), 0, ctx->stream, geom->view, photons->flags,
-                           photons->last_hit_triangles, first_photon, nphotons, detection_state, ctx->d_words + W_HIT_COUNT);
-        HIP_TRY(hipGetLastError());
-    }
-    return read_word(ctx, W_HIT_COUNT, count);
+                           photons->last_hit_triangles, first_photon, nphotons, detection_state, word);
+    });
 }
 
 int chroma_copy_photon_hits(chroma_ctx *ctx, chroma_geometry *geom, int32_t first_photon, int32_t nphotons,
@@ -96,16 +99,11 @@ int chroma_copy_photon_hits(chroma_ctx *ctx, chroma_geometry *geom, int32_t firs
     if (!geom->view.nsolids) return set_error(CHROMA_ERR_INVALID, "geometry has no detector channel map");
     int rc = check_photons(src, false); if (rc) return rc;
     rc = check_photons(dst, false); if (rc) return rc;
-    HIP_TRY(hipMemsetAsync(ctx->d_words + W_HIT_COUNT, 0, 4, ctx->stream));
-    if (nphotons > 0) {
+    const CallScope scope(ctx);
+    return counted_launch(scope, nphotons > 0, ncopied, [&](uint32_t *word) {
         hipLaunchKernelGGL(k_copy_hits, dim3((unsigned)(((long long)nphotons + COPY_ITEMS * 256 - 1) / (COPY_ITEMS * 256))), dim3(256), 0, ctx->stream, geom->view, to_view(src),
-                           to_view(dst), d_channels, first_photon, nphotons, detection_state, ctx->d_words + W_HIT_COUNT);
-        HIP_TRY(hipGetLastError());
-    }
-    uint32_t n = 0;
-    rc = read_word(ctx, W_HIT_COUNT, &n);
-    if (ncopied) *ncopied = n;
-    return rc;
+                           to_view(dst), d_channels, first_photon, nphotons, detection_state, word);
+    });
 }
 
 int chroma_channel_hits(chroma_ctx *ctx, chroma_geometry *geom, uint64_t nphotons, uint32_t detection_state,
@@ -208,7 +206,7 @@ int chroma_pdf_bin_hits(chroma_ctx *ctx, uint32_t nchannels, int32_t ndaq, uint3
         return set_error(CHROMA_ERR_INVALID, "need at least one time and one charge bin (and fewer than 2^31 per channel)");
     if (!(tmin < tmax) || !(qmin < qmax)) return set_error(CHROMA_ERR_INVALID, "empty or inverted time or charge range");
     if (nchannels == 0) return CHROMA_OK;
-    std::lock_guard<std::mutex> call_lock(ctx->call_mu);
+    const CallScope scope(ctx);          // (one at a time with the context's other calls; it uses none of their scratch)
     hipLaunchKernelGGL(k_pdf_bin_hits, dim3((nchannels + 255) / 256), dim3(256), 0, ctx->stream, nchannels, (int)ndaq, stride,
                        d_channel_q, d_channel_t, d_hitcount, (int)tbins, tmin, tmax, (int)qbins, qmin, qmax, d_pdf);
     HIP_TRY(hipGetLastError());
@@ -227,7 +225,7 @@ int chroma_pdf_eval_accumulate(chroma_ctx *ctx, uint32_t nchannels, int32_t ndaq
     if (!(tmin < tmax)) return set_error(CHROMA_ERR_INVALID, "empty or inverted time range");
     if (nhit > nchannels) return set_error(CHROMA_ERR_INVALID, "more hit channels than channels");
     if (nchannels == 0) return CHROMA_OK;
-    std::lock_guard<std::mutex> call_lock(ctx->call_mu);
+    const CallScope scope(ctx);          // (one at a time with the context's other calls; it uses none of their scratch)
     hipLaunchKernelGGL(k_pdf_eval_hitcount, dim3((nchannels + 255) / 256), dim3(256), 0, ctx->stream, nchannels, (int)ndaq, stride,
                        d_event_hit, d_mc_time, tmin, tmax, d_hitcount);
     HIP_TRY(hipGetLastError());
@@ -248,7 +246,7 @@ int chroma_pdf_moments(chroma_ctx *ctx, int32_t time_only, uint32_t nchannels, i
     int rc = check_pdf_layout(nchannels, ndaq, stride); if (rc) return rc;
     if (!(tmin < tmax) || (!time_only && !(qmin < qmax))) return set_error(CHROMA_ERR_INVALID, "empty or inverted time or charge range");
     if (nchannels == 0) return CHROMA_OK;
-    std::lock_guard<std::mutex> call_lock(ctx->call_mu);
+    const CallScope scope(ctx);          // (one at a time with the context's other calls; it uses none of their scratch)
     hipLaunchKernelGGL(k_pdf_moments, dim3((nchannels + 255) / 256), dim3(256), 0, ctx->stream, (int)(time_only != 0), nchannels,
                        (int)ndaq, stride, d_mc_time, d_mc_charge, tmin, tmax, qmin, qmax, d_mom0, d_t_mom1, d_t_mom2, d_q_mom1, d_q_mom2);
     HIP_TRY(hipGetLastError());
@@ -267,7 +265,7 @@ int chroma_pdf_kernel_eval(chroma_ctx *ctx, int32_t time_only, uint32_t nchannel
     int rc = check_pdf_layout(nchannels, ndaq, stride); if (rc) return rc;
     if (!(tmin < tmax) || (!time_only && !(qmin < qmax))) return set_error(CHROMA_ERR_INVALID, "empty or inverted time or charge range");
     if (nchannels == 0) return CHROMA_OK;
-    std::lock_guard<std::mutex> call_lock(ctx->call_mu);
+    const CallScope scope(ctx);          // (one at a time with the context's other calls; it uses none of their scratch)
     hipLaunchKernelGGL(k_pdf_kernel_eval, dim3((nchannels + 255) / 256), dim3(256), 0, ctx->stream, (int)(time_only != 0), nchannels,
                        (int)ndaq, stride, d_event_hit, d_event_time, d_event_charge, d_mc_time, d_mc_charge, tmin, tmax, qmin, qmax,
                        d_inv_time_bandwidths, d_inv_charge_bandwidths, d_hitcount, d_time_pdf_values, d_charge_pdf_values);
@@ -284,9 +282,10 @@ int chroma_render(chroma_ctx *ctx, chroma_geometry *geom, int32_t nthreads, cons
     if (nthreads <= 0) return CHROMA_OK;
     if (geom->stack_need > STACK_LDS + STACK_SCRATCH)
         return set_error(CHROMA_ERR_STACK, "BVH needs %u traversal stack entries, more than the %d supported", geom->stack_need, STACK_LDS + STACK_SCRATCH);
+    const CallScope scope(ctx);          // (the render counts stack overflows into the context's counters)
     hipLaunchKernelGGL((k_render<STACK_LDS>), dim3((unsigned)((nthreads + PROP_BLOCK - 1) / PROP_BLOCK)), dim3(PROP_BLOCK), 0, ctx->stream,
                        geom->view, (const uint32_t *)geom->d_colors, (int)nthreads, d_origin, d_direction, alpha_depth, d_pixels, d_dx,
-                       d_dxlen, (float4 *)d_color, bg_color, ctx->d_counters);
+                       d_dxlen, (float4 *)d_color, bg_color, scope.state().d_counters);
     HIP_TRY(hipGetLastError());
     return CHROMA_OK;
 }

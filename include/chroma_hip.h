@@ -312,8 +312,9 @@ int chroma_propagate_hits(chroma_ctx *ctx, chroma_geometry *geom, const chroma_p
 /* The general form of the two calls above: what a call does is an ARGUMENT, not a setting of the context -- which walk the ray
  * cast takes (GPUPhotons.propagate(exact=True) passes CHROMA_WALK_LITERAL here), how the tail runs, whether the kernels count
  * their work.  A field of -1 takes the context's setting (chroma_set_walk / chroma_set_tail / chroma_set_counting or the CHROMA_*
- * environment) as it is when the call starts; nothing a concurrent call or setter does changes a call under way.  Calls on one
- * context run one at a time (the context's queues and working sets are its own): two threads may share a handle.
+ * environment) as it is when the call starts; nothing a concurrent call or setter does changes a call under way.  Every call
+ * that uses the context's scratch (queues, working sets, result words, counters, settings) runs one at a time per context: two
+ * threads may share a handle.
  * `hits` may be NULL (then this is chroma_propagate).  Zero the structure, then set what you need: reserved fields must be 0. */
 typedef struct chroma_propagate_options {
     int32_t max_steps, use_weights, scatter_first, time_kernels;      /* as the arguments of chroma_propagate */
