@@ -101,6 +101,20 @@ class DaqTables(Structure):
                 ('charge_unit', c_float)]
 
 
+class LightSource(Structure):
+    """chroma_light_source (host pointers)"""
+    _fields_ = [('refractive_index', c_void_p), ('scintillation_cdf', c_void_p), ('time_cdf', c_void_p),
+                ('wavelength_n', c_uint32), ('wavelength_start', c_float), ('wavelength_step', c_float),
+                ('time_n', c_uint32), ('time_start', c_float), ('time_step', c_float),
+                ('light_yield', c_float), ('cherenkov_lo', c_uint32), ('cherenkov_hi', c_uint32)]
+
+
+class StepSegments(Structure):
+    """chroma_step_segments (device or host pointers, depending on the callee)"""
+    _fields_ = [('a', c_void_p), ('b', c_void_p), ('t_a', c_void_p), ('t_b', c_void_p), ('beta', c_void_p), ('z', c_void_p),
+                ('qedep', c_void_p), ('evidx', c_void_p), ('n', c_uint64), ('segment_base', c_uint64)]
+
+
 # name -> (restype, argtypes); every symbol include/chroma_hip.h declares
 SIGNATURES = {
     'chroma_last_error': (c_char_p, []),
@@ -163,6 +177,12 @@ SIGNATURES = {
                                          c_void_p, c_void_p, c_void_p]),
     'chroma_generate_bomb': (c_int32, [c_void_p, POINTER(PhotonArrays), c_uint64, c_uint64, c_uint64,
                                        POINTER(c_float), c_float, c_float]),
+    'chroma_steps_count': (c_int32, [c_void_p, POINTER(LightSource), POINTER(StepSegments), c_uint64, c_void_p, POINTER(c_uint64)]),
+    'chroma_steps_generate': (c_int32, [c_void_p, POINTER(LightSource), POINTER(StepSegments), c_uint64, c_void_p,
+                                        POINTER(PhotonArrays), c_uint64]),
+    'chroma_steps_count_host': (c_int32, [POINTER(LightSource), POINTER(StepSegments), c_uint64, c_void_p, POINTER(c_uint64)]),
+    'chroma_steps_generate_host': (c_int32, [POINTER(LightSource), POINTER(StepSegments), c_uint64, c_void_p,
+                                             POINTER(PhotonArrays), c_uint64]),
     'chroma_render': (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32]),
     'chroma_hybrid_lookup': (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, POINTER(c_float), Rng, c_void_p, c_uint32,
                                        c_float, POINTER(c_float), c_void_p, c_void_p, c_uint32, c_int32, c_void_p, c_void_p,

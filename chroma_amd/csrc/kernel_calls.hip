@@ -1,9 +1,11 @@
 // kernel_calls.hip -- the entry points that are the checks of their arguments around one kernel launch on the context's
 // stream, as the reference's kernels are called from Python: the photon-array calls, DAQ, PDFs, chroma_render, point
-// transforms, the probe, the bomb generator.
+// transforms, the probe, the bomb generator, the photons from particle steps.
 #include <stdint.h>
 #include <string.h>
 #include <algorithm>
+
+#include <hipcub/hipcub.hpp>
 
 #include "chroma_internal.h"
 #include "propagate_device.h"
@@ -13,6 +15,8 @@
 #include "kernels_daq_render.h"
 
 #include "kernels_pdf.h"
+
+#include "kernels_steps.h"
 
 // The count and copy calls: the hit word cleared, the launch it is given run on it (none for an empty range), the word read back
 template <class Launch>
@@ -26,7 +30,95 @@ static int counted_launch(const CallScope &scope, bool any, uint32_t *count, Lau
     return rc;
 }
 
+// ---- photons from particle steps (kernels_steps.h) ----
+// The context's scratch block of the two calls, in this order: the 64-bit total, the source's three tables, the 2 n + 1 counts,
+// the scan's workspace.  A call grows the block when it has to and copies the tables up (they are host arrays of the caller's).
+struct StepsScratch {
+    unsigned long long *total; float *refractive_index, *scintillation_cdf, *time_cdf; uint32_t *counts; void *scan; size_t scan_bytes;
+};
+static size_t round256(size_t b) { return (b + 255) & ~(size_t)255; }
+static int steps_scratch(const CallScope &scope, const chroma_light_source *src, uint64_t nsegments, StepsScratch *out)
+{
+    hipStream_t stream = scope.ctx->stream;
+    const size_t ncounts = 2 * (size_t)nsegments + 1;
+    size_t scan_bytes = 0;
+    { uint32_t *nul = nullptr; HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, nul, nul, (int)ncounts, stream)); }
+    const size_t wl_bytes = round256(src->wavelength_n * sizeof(float)), t_bytes = src->time_cdf ? round256(src->time_n * sizeof(float)) : 0;
+    const size_t need = 256 + 2 * wl_bytes + t_bytes + round256(ncounts * sizeof(uint32_t)) + round256(scan_bytes);
+    CallState &cs = scope.state();
+    if (cs.steps_scratch_bytes < need) {
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (cs.steps_scratch) { HIP_TRY(hipFree(cs.steps_scratch)); cs.steps_scratch = nullptr; cs.steps_scratch_bytes = 0; }
+        HIP_TRY(ctx_malloc(scope.ctx, &cs.steps_scratch, need));
+        cs.steps_scratch_bytes = need;
+    }
+    char *p = (char *)cs.steps_scratch;
+    out->total = (unsigned long long *)p; p += 256;
+    out->refractive_index = (float *)p; p += wl_bytes;
+    out->scintillation_cdf = src->scintillation_cdf ? (float *)p : nullptr; p += wl_bytes;
+    out->time_cdf = src->time_cdf ? (float *)p : nullptr; p += t_bytes;
+    out->counts = (uint32_t *)p; p += round256(ncounts * sizeof(uint32_t));
+    out->scan = p; out->scan_bytes = scan_bytes;
+    HIP_TRY(hipMemcpyAsync(out->refractive_index, src->refractive_index, src->wavelength_n * sizeof(float), hipMemcpyHostToDevice, stream));
+    if (src->scintillation_cdf)
+        HIP_TRY(hipMemcpyAsync(out->scintillation_cdf, src->scintillation_cdf, src->wavelength_n * sizeof(float), hipMemcpyHostToDevice, stream));
+    if (src->time_cdf) HIP_TRY(hipMemcpyAsync(out->time_cdf, src->time_cdf, src->time_n * sizeof(float), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipStreamSynchronize(stream));          // (the caller's tables are his again when the call returns)
+    return CHROMA_OK;
+}
+
 extern "C" {
+
+int chroma_steps_count(chroma_ctx *ctx, const chroma_light_source *src, const chroma_step_segments *segs, uint64_t seed,
+                       uint32_t *d_offsets, uint64_t *total)
+{
+    if (!ctx || !d_offsets || !total) return set_error(CHROMA_ERR_INVALID, "bad argument");
+    if (const char *why = steps::check_source(src)) return set_error(CHROMA_ERR_INVALID, "%s", why);
+    if (const char *why = steps::check_segments(segs)) return set_error(CHROMA_ERR_INVALID, "%s", why);
+    const CallScope scope(ctx);
+    *total = 0;
+    if (segs->n == 0) {
+        HIP_TRY(hipMemsetAsync(d_offsets, 0, sizeof(uint32_t), ctx->stream));
+        return CHROMA_OK;
+    }
+    StepsScratch sc;
+    int rc = steps_scratch(scope, src, segs->n, &sc); if (rc) return rc;
+    const steps::Source s = steps::make_source(*src, sc.refractive_index, sc.scintillation_cdf, sc.time_cdf);
+    HIP_TRY(hipMemsetAsync(sc.total, 0, sizeof(unsigned long long), ctx->stream));
+    hipLaunchKernelGGL(k_steps_count, dim3((unsigned)((segs->n + STEPS_BLOCK - 1) / STEPS_BLOCK)), dim3(STEPS_BLOCK), 0, ctx->stream, s, *segs, seed,
+                       sc.counts, sc.total);
+    HIP_TRY(hipGetLastError());
+    { size_t b = sc.scan_bytes; HIP_TRY(hipcub::DeviceScan::ExclusiveSum(sc.scan, b, sc.counts, d_offsets, (int)(2 * segs->n + 1), ctx->stream)); }
+    unsigned long long sum = 0;
+    HIP_TRY(hipMemcpyAsync(&sum, sc.total, sizeof(sum), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    *total = sum;
+    if (sum > 0xffffffffull) return set_error(CHROMA_ERR_INVALID, "%llu photons in one call: more than 32-bit offsets hold, pass fewer segments", sum);
+    return CHROMA_OK;
+}
+
+int chroma_steps_generate(chroma_ctx *ctx, const chroma_light_source *src, const chroma_step_segments *segs, uint64_t seed,
+                          const uint32_t *d_offsets, const chroma_photon_arrays *photons, uint64_t capacity)
+{
+    if (!ctx || !d_offsets) return set_error(CHROMA_ERR_INVALID, "bad argument");
+    if (const char *why = steps::check_source(src)) return set_error(CHROMA_ERR_INVALID, "%s", why);
+    if (const char *why = steps::check_segments(segs)) return set_error(CHROMA_ERR_INVALID, "%s", why);
+    if (segs->n == 0) return CHROMA_OK;
+    const CallScope scope(ctx);
+    uint32_t total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, d_offsets + 2 * segs->n, sizeof(total), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (capacity < total) return set_error(CHROMA_ERR_INVALID, "room for %llu photons, the segments emit %u", (unsigned long long)capacity, total);
+    if (total == 0) return CHROMA_OK;
+    int rc = check_photons(photons, true); if (rc) return rc;
+    StepsScratch sc;
+    rc = steps_scratch(scope, src, segs->n, &sc); if (rc) return rc;
+    const steps::Source s = steps::make_source(*src, sc.refractive_index, sc.scintillation_cdf, sc.time_cdf);
+    hipLaunchKernelGGL(k_steps_generate, dim3((total + STEPS_BLOCK - 1) / STEPS_BLOCK), dim3(STEPS_BLOCK), 0, ctx->stream, s, *segs, seed, d_offsets,
+                       to_view(photons), total);
+    HIP_TRY(hipGetLastError());
+    return CHROMA_OK;
+}
 
 int chroma_photon_duplicate(chroma_ctx *ctx, int32_t first_photon, int32_t nthreads,
                             const chroma_photon_arrays *photons, int32_t copies, int32_t stride)

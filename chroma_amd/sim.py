@@ -3,7 +3,8 @@
 Reference: chroma/sim.py:21-343 (``Simulation.__init__``, ``_simulate_batch``, ``simulate``, and the PDF entry
 points ``create_pdf``, ``eval_pdf``, ``setup_kernel``, ``eval_kernel``).
 Out of scope here, as in SURVEY.md section 8: GEANT4 photon generation (``geant4_processes``
-is accepted; Event/Vertex inputs need a generator that this package does not provide).  The PDF entry points take
+is accepted; bare Vertex input and Events without photons or steps need a generator that this package does not provide).
+Events whose vertices carry ``steps`` get their photons made on the device (chroma_amd.gpu.steps).  The PDF entry points take
 Photons (or Events that carry ``photons_beg``) and run their DAQ acquisitions as GPUDaq(ndaq=K) chunks of at most 64.
 """
 import os
@@ -22,7 +23,13 @@ def pick_seed():
 
 class Simulation(object):
     def __init__(self, detector, seed=None, cuda_device=None, particle_tracking=False, photon_tracking=False,
-                 geant4_processes=0, nthreads_per_block=64, max_blocks=1024, exact=False, prefetch=True, lanes=1):
+                 geant4_processes=0, nthreads_per_block=64, max_blocks=1024, exact=False, prefetch=True, lanes=1,
+                 light_medium=None):
+        # ``light_medium``: the Material whose Cherenkov and scintillation light the steps of Events without photons emit
+        # (simulate(); chroma_amd.gpu.steps.LightSource); None: the detector's ``detector_material``
+        self.light_medium = light_medium
+        self._light_source = None
+        self._segment_base = 0               # segments generated so far: a segment's random streams are keyed by its global index
         # ``exact``: propagate with the reference's own traversal loop for every ray (GPUPhotons.propagate(exact=True)):
         # the reference's hit triangle on every ray, several times slower than the default walk
         self.exact = bool(exact)
@@ -182,13 +189,16 @@ class Simulation(object):
         if isinstance(first, event.Photons):
             iterable = (event.Event(photons_beg=x) for x in iterable)
         elif isinstance(first, event.Event):
-            if first.photons_beg is None:
+            if first.photons_beg is None and not self._has_steps(first):
                 raise NotImplementedError('events without photons need the GEANT4 generator, which is out of scope')
         else:
             raise NotImplementedError('Vertex input needs the GEANT4 generator, which is out of scope')
 
         kwargs = dict(keep_photons_beg=keep_photons_beg, keep_photons_end=keep_photons_end, keep_hits=keep_hits,
                       keep_flat_hits=keep_flat_hits, run_daq=run_daq, max_steps=max_steps)
+        if isinstance(first, event.Event) and first.photons_beg is None:
+            yield from self._simulate_stepped(iterable, photons_per_batch, evid_start, kwargs)
+            return
         def batches():
             nphotons = 0
             batch = []
@@ -231,6 +241,59 @@ class Simulation(object):
                 yield from self._simulate_batch(cur, uploaded=uploaded, **kwargs)
                 uploaded = None
                 cur = nxt
+
+    # ---- events that carry steps instead of photons ------------------------------------------------------------------
+    @staticmethod
+    def _has_steps(ev):
+        return any(getattr(v, 'steps', None) is not None for v in ev.vertices)
+
+    @property
+    def light_source(self):
+        """The LightSource of ``light_medium`` (or of the detector's ``detector_material``), made on first use."""
+        if self._light_source is None:
+            medium = self.light_medium if self.light_medium is not None else getattr(self.detector, 'detector_material', None)
+            if medium is None:
+                raise ValueError('events with steps need a medium: Simulation(light_medium=...) or the detector\'s detector_material')
+            self._light_source = gpu.steps.LightSource(medium)
+        return self._light_source
+
+    def _simulate_stepped(self, iterable, photons_per_batch, evid_start, kwargs):
+        """Events without ``photons_beg`` whose vertices carry ``steps``: the photons of a batch are generated on the device
+        (chroma_amd.gpu.steps.generate_photons, seed ``self.seed``) and propagated where they are.  Events are batched by the
+        photons their steps are EXPECTED to emit; the segments of the events are numbered on in iterable order from one
+        simulate() call to the next, so the photons do not depend on the batching.  ``photons_beg`` is fetched only with
+        ``keep_photons_beg``."""
+        source = self.light_source
+
+        def batches():
+            expected, batch, evid = 0.0, [], evid_start
+            for ev in iterable:
+                if ev.photons_beg is not None or not self._has_steps(ev):
+                    raise NotImplementedError('events with steps and events with photons (or with neither) in one simulate() call')
+                ev.id = evid
+                evid += 1
+                segments = gpu.steps.segments_from_vertices(ev.vertices, evidx=len(batch))
+                expected += source.expected_photons(segments)
+                batch.append((ev, segments))
+                if expected >= photons_per_batch:
+                    yield batch
+                    expected, batch = 0.0, []
+            if batch:
+                yield batch
+
+        for batch in batches():
+            segments = gpu.steps.Segments.join([s for _, s in batch], segment_base=self._segment_base)
+            self._segment_base += len(segments)
+            gpu_photons, offsets = gpu.steps.generate_photons(segments, source, self.seed, ctx=self.context, return_offsets=True)
+            cuts = 2 * np.cumsum([0] + [len(s) for _, s in batch])
+            bounds = offsets[cuts].astype(np.int64)
+            events = [ev for ev, _ in batch]
+            photons_beg = gpu_photons.get() if kwargs['keep_photons_beg'] else None
+            for ev, lo, hi in zip(events, bounds[:-1], bounds[1:]):
+                ev.nphotons = int(hi - lo)
+                if photons_beg is not None:
+                    ev.photons_beg = photons_beg[int(lo):int(hi)]
+            yield from self._simulate_batch(events, uploaded=(gpu_photons, bounds), **kwargs)
 
     def _simulate_lanes(self, batches, kwargs):
         """``lanes`` batches in flight at once, each on its own context from its own host thread (the library calls

@@ -421,6 +421,55 @@ int chroma_generate_bomb(chroma_ctx *ctx, const chroma_photon_arrays *photons, u
                          uint64_t seed, uint64_t id_base, const float pos[3],
                          float wavelength_lo, float wavelength_hi);
 
+/* ---- photons from charged-particle steps (csrc/steps_common.h: the per-segment and per-photon functions, compiled for
+ * the device and for the host alike) ----
+ * A SEGMENT is two consecutive step points A -> B of one track.  It emits Cherenkov light (Frank-Tamm: mean
+ * 2 pi alpha z^2 L sum_trapezoid max(0, 1 - 1/(beta^2 n_j^2)) / lambda_j^2 d_lambda over the grid nodes cherenkov_lo ..
+ * cherenkov_hi, L and lambda in one unit) and scintillation light (mean light_yield * qedep).  Counts: Poisson by Knuth's
+ * product of uniforms for a mean <= 16, max(0, round(mean + sqrt(mean) * normal)) above.  Random streams: segment g =
+ * segment_base + its index draws its two counts (Cherenkov first) from Philox stream word 0 of id 0x57E9000000000000 + g,
+ * photon j of the segment (Cherenkov photons first) everything it needs from stream word 1 + j of the same id -- so a
+ * photon does not depend on how the segments were split into calls.  The propagation stream (keyed by photon id) is not
+ * touched: rng_counters of a generated photon is 0. */
+
+/* One medium's tables, HOST pointers (the calls copy what they need), on the geometry's wavelength and time grids. */
+typedef struct chroma_light_source {
+    const float *refractive_index;    /* [wavelength_n] n at the grid nodes                                       */
+    const float *scintillation_cdf;   /* [wavelength_n] CDF of the emission spectrum, 0 .. 1; NULL: no such light */
+    const float *time_cdf;            /* [time_n] CDF of the emission delay, 0 .. 1; NULL: prompt                 */
+    uint32_t wavelength_n; float wavelength_start, wavelength_step;
+    uint32_t time_n;       float time_start, time_step;
+    float light_yield;                /* scintillation photons per unit of (quenched) deposit                    */
+    uint32_t cherenkov_lo, cherenkov_hi;   /* first and last grid node of the Cherenkov range, lo < hi            */
+} chroma_light_source;
+
+/* The segments of one call as arrays (DEVICE pointers for the device calls, host pointers for the _host calls). */
+typedef struct chroma_step_segments {
+    const float *a, *b;               /* [n][3] the two step points, mm                                           */
+    const float *t_a, *t_b;           /* [n] their times, ns                                                      */
+    const float *beta;                /* [n] mean of the two points' beta                                         */
+    const float *z;                   /* [n] charge in units of e; 0: no Cherenkov light                          */
+    const float *qedep;               /* [n] quenched deposit of the step                                         */
+    const uint32_t *evidx;            /* [n] event index given to the photons; NULL: 0                            */
+    uint64_t n;
+    uint64_t segment_base;            /* global index of segment 0                                                */
+} chroma_step_segments;
+
+/* Counts: d_offsets[2 n + 1] (uint32) gets the exclusive sum of (Cherenkov_0, scintillation_0, Cherenkov_1, ...), so the
+ * photons of segment s are [d_offsets[2 s], d_offsets[2 s + 2]) of the output, Cherenkov before scintillation, and
+ * d_offsets[2 n] == *total.  CHROMA_ERR_INVALID when the total does not fit 32 bits. */
+int chroma_steps_count(chroma_ctx *ctx, const chroma_light_source *src, const chroma_step_segments *segs, uint64_t seed,
+                       uint32_t *d_offsets, uint64_t *total);
+/* The photons themselves, into the first d_offsets[2 n] slots of `photons` (all ten arrays; last_hit_triangles -1, weights 1,
+ * rng_counters 0).  `capacity` < that total: CHROMA_ERR_INVALID and nothing is written.  Queued on the context's stream. */
+int chroma_steps_generate(chroma_ctx *ctx, const chroma_light_source *src, const chroma_step_segments *segs, uint64_t seed,
+                          const uint32_t *d_offsets, const chroma_photon_arrays *photons, uint64_t capacity);
+/* The same two calls as loops on the host (every pointer a host pointer): the same photons bit for bit. */
+int chroma_steps_count_host(const chroma_light_source *src, const chroma_step_segments *segs, uint64_t seed,
+                            uint32_t *offsets, uint64_t *total);
+int chroma_steps_generate_host(const chroma_light_source *src, const chroma_step_segments *segs, uint64_t seed,
+                               const uint32_t *offsets, const chroma_photon_arrays *photons, uint64_t capacity);
+
 /* tools.argsort_direction (chroma/tools.py:175-193) and the reordering it serves, for a photon set on the device: the
  * photons are put in the order of a 32-bit Morton code of (theta, phi) of their directions (stable), every array of
  * the set gathered accordingly.  The reference's own benchmark does this to its photons before it starts the clock
