@@ -109,6 +109,15 @@ class LightSource(Structure):
                 ('light_yield', c_float), ('cherenkov_lo', c_uint32), ('cherenkov_hi', c_uint32)]
 
 
+class LightMediaDesc(Structure):
+    """chroma_light_media_desc (host pointers)"""
+    _fields_ = [('nmedia', c_uint32), ('refractive_index', c_void_p), ('scintillation_cdf', c_void_p), ('time_cdf', c_void_p),
+                ('light_yield', c_void_p), ('prompt', c_void_p),
+                ('wavelength_n', c_uint32), ('wavelength_start', c_float), ('wavelength_step', c_float),
+                ('time_n', c_uint32), ('time_start', c_float), ('time_step', c_float),
+                ('cherenkov_lo', c_uint32), ('cherenkov_hi', c_uint32)]
+
+
 class StepSegments(Structure):
     """chroma_step_segments (device or host pointers, depending on the callee)"""
     _fields_ = [('a', c_void_p), ('b', c_void_p), ('t_a', c_void_p), ('t_b', c_void_p), ('beta', c_void_p), ('z', c_void_p),
@@ -152,6 +161,7 @@ SIGNATURES = {
                                           POINTER(PhotonArrays), c_void_p, POINTER(c_uint32)]),
     'chroma_distance_to_mesh': (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     'chroma_intersect_mesh': (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'chroma_locate_materials': (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, POINTER(c_float), c_int32, c_void_p, c_void_p]),
     'chroma_propagate': (c_int32, [c_void_p, c_void_p, POINTER(PhotonArrays), c_uint64, c_uint32, Rng, c_int32,
                                    c_int32, c_int32, c_int32, POINTER(PropagateStats), POINTER(c_int32)]),
     'chroma_propagate_hits': (c_int32, [c_void_p, c_void_p, POINTER(PhotonArrays), c_uint64, c_uint32, Rng, c_int32,
@@ -183,6 +193,15 @@ SIGNATURES = {
     'chroma_steps_count_host': (c_int32, [POINTER(LightSource), POINTER(StepSegments), c_uint64, c_void_p, POINTER(c_uint64)]),
     'chroma_steps_generate_host': (c_int32, [POINTER(LightSource), POINTER(StepSegments), c_uint64, c_void_p,
                                              POINTER(PhotonArrays), c_uint64]),
+    'chroma_light_media_create': (c_int32, [c_void_p, POINTER(LightMediaDesc), POINTER(c_void_p)]),
+    'chroma_light_media_destroy': (c_int32, [c_void_p]),
+    'chroma_steps_count_media': (c_int32, [c_void_p, c_void_p, POINTER(StepSegments), c_void_p, c_uint64, c_void_p, POINTER(c_uint64)]),
+    'chroma_steps_generate_media': (c_int32, [c_void_p, c_void_p, POINTER(StepSegments), c_void_p, c_uint64, c_void_p,
+                                              POINTER(PhotonArrays), c_uint64]),
+    'chroma_steps_count_media_host': (c_int32, [POINTER(LightMediaDesc), POINTER(StepSegments), c_void_p, c_uint64, c_void_p,
+                                                POINTER(c_uint64)]),
+    'chroma_steps_generate_media_host': (c_int32, [POINTER(LightMediaDesc), POINTER(StepSegments), c_void_p, c_uint64, c_void_p,
+                                                   POINTER(PhotonArrays), c_uint64]),
     'chroma_render': (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32]),
     'chroma_hybrid_lookup': (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, POINTER(c_float), Rng, c_void_p, c_uint32,
                                        c_float, POINTER(c_float), c_void_p, c_void_p, c_uint32, c_int32, c_void_p, c_void_p,

@@ -19,9 +19,11 @@
 //   kernels_working_set.h         k_load_working, k_store_working
 //   kernels_propagate_ends.h      the initial queue, the abort-flag reduction, k_finalize_hits
 //   kernels_distance.h            k_distance_to_mesh, and the fast path of chroma_intersect_mesh around k_raycast_quad
+//   kernels_locate.h              chroma_locate_materials: rays of one probe direction, the material from a ray's hit
 //   kernels_hybrid_render.h       the hybrid render: k_propagate's step functions, one lane per sample
 //   experimental/*.h              measured-and-not-faster kernels: ONLY in build_variants/libchroma_hip_experimental.so
 // See DESIGN.md for the data layout and what bounds each kernel.
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -73,6 +75,8 @@
 #include "kernels_propagate_ends.h"
 
 #include "kernels_distance.h"
+
+#include "kernels_locate.h"
 
 #if CHROMA_HYBRID_RENDER
 #include "kernels_hybrid_render.h"
@@ -739,6 +743,55 @@ int chroma_intersect_mesh(chroma_ctx *ctx, chroma_geometry *geom, int32_t nthrea
         hipLaunchKernelGGL((k_distance_retry<C>), dim3(256), dim3(PROP_BLOCK), 0, ctx->stream, geom->view, cs.rays, st,
                            cs.retry_list, d_distance, d_triangle, cs.d_counters);
     });
+    HIP_TRY(hipGetLastError());
+    return CHROMA_OK;
+}
+
+// The ray cast of chroma_intersect_mesh over rays that share one direction, then the material from each ray's triangle.  The
+// cast's own per-slot results are its scratch: the distances go back where they came from, and the triangle ids take the
+// place of the hit records when the caller does not ask for them.
+int chroma_locate_materials(chroma_ctx *ctx, chroma_geometry *geom, int32_t n, const float *d_points, const float direction[3],
+                            int32_t outside, int32_t *d_material, int32_t *d_triangle)
+{
+    if (!ctx || !geom || !d_points || !d_material) return set_error(CHROMA_ERR_INVALID, "bad argument");
+    if (n < 0) return set_error(CHROMA_ERR_INVALID, "negative number of points");
+    const float dx = direction ? direction[0] : 0.0f, dy = direction ? direction[1] : 0.0f, dz = direction ? direction[2] : 1.0f;
+    const float len = sqrtf(dx * dx + dy * dy + dz * dz);
+    if (!(len > 0.0f) || !isfinite(len)) return set_error(CHROMA_ERR_INVALID, "probe direction of no length");
+    if (n == 0) return CHROMA_OK;
+    int rc = check_stack(geom); if (rc) return rc;
+    const CallScope scope(ctx);
+    CallState &cs = scope.state();
+    CallPlan plan;
+    rc = make_plan(cs, geom, -1, -1, -1, &plan); if (rc) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    rc = ensure_queues(scope, (size_t)n); if (rc) return rc;
+    int32_t *triangle = d_triangle ? d_triangle : cs.hit_triangle;
+    const unsigned blocks = (unsigned)((n + 255) / 256);
+    if (!plan.isect_quad) {
+        with_bool(plan.counting, [&](auto C) {
+            hipLaunchKernelGGL((k_locate_walk<STACK_LDS, C>), dim3((unsigned)((n + PROP_BLOCK - 1) / PROP_BLOCK)), dim3(PROP_BLOCK), 0, ctx->stream,
+                               geom->view, (int)n, d_points, dx, dy, dz, triangle, cs.d_counters);
+        });
+    } else {
+        rc = ensure_spill(scope, SPILL_COOP); if (rc) return rc;
+        StepState *st = cs.d_step;
+        hipLaunchKernelGGL(k_step_set, dim3(1), dim3(1), 0, ctx->stream, st, (uint32_t)n);
+        hipLaunchKernelGGL(k_locate_rays, dim3(blocks), dim3(256), 0, ctx->stream, geom->view, (int)n, d_points, dx, dy, dz, cs.rays,
+                           cs.hit_triangle, cs.hit_distance, cs.retry_list, st);
+        const unsigned waves = cast_waves(ctx, Cast::QUAD, n);
+        with_bool(plan.counting, [&](auto C) {
+            hipLaunchKernelGGL((k_raycast_quad<C>), dim3(waves), dim3(PROP_BLOCK), 0, ctx->stream, geom->view, cs.rays, 0, st,
+                               cs.hit_triangle, cs.hit_distance, cs.retry_list, cs.coop_spill, cs.d_counters, ctx->coop_chunk, 0, nullptr, ctx->claim_static);
+        });
+        hipLaunchKernelGGL(k_distance_finish, dim3(blocks), dim3(256), 0, ctx->stream, geom->view, (int)n, cs.rays, cs.hit_triangle,
+                           cs.hit_distance, cs.hit_distance, triangle, cs.retry_list, st);
+        with_bool(plan.counting, [&](auto C) {
+            hipLaunchKernelGGL((k_distance_retry<C>), dim3(256), dim3(PROP_BLOCK), 0, ctx->stream, geom->view, cs.rays, st,
+                               cs.retry_list, cs.hit_distance, triangle, cs.d_counters);
+        });
+    }
+    hipLaunchKernelGGL(k_locate_material, dim3(blocks), dim3(256), 0, ctx->stream, geom->view, (int)n, triangle, dx, dy, dz, outside, d_material);
     HIP_TRY(hipGetLastError());
     return CHROMA_OK;
 }

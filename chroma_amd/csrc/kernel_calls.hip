@@ -37,6 +37,16 @@ struct StepsScratch {
     unsigned long long *total; float *refractive_index, *scintillation_cdf, *time_cdf; uint32_t *counts; void *scan; size_t scan_bytes;
 };
 static size_t round256(size_t b) { return (b + 255) & ~(size_t)255; }
+static int steps_block(const CallScope &scope, size_t need)
+{
+    CallState &cs = scope.state();
+    if (cs.steps_scratch_bytes >= need) return CHROMA_OK;
+    HIP_TRY(hipStreamSynchronize(scope.ctx->stream));
+    if (cs.steps_scratch) { HIP_TRY(hipFree(cs.steps_scratch)); cs.steps_scratch = nullptr; cs.steps_scratch_bytes = 0; }
+    HIP_TRY(ctx_malloc(scope.ctx, &cs.steps_scratch, need));
+    cs.steps_scratch_bytes = need;
+    return CHROMA_OK;
+}
 static int steps_scratch(const CallScope &scope, const chroma_light_source *src, uint64_t nsegments, StepsScratch *out)
 {
     hipStream_t stream = scope.ctx->stream;
@@ -45,14 +55,8 @@ static int steps_scratch(const CallScope &scope, const chroma_light_source *src,
     { uint32_t *nul = nullptr; HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, nul, nul, (int)ncounts, stream)); }
     const size_t wl_bytes = round256(src->wavelength_n * sizeof(float)), t_bytes = src->time_cdf ? round256(src->time_n * sizeof(float)) : 0;
     const size_t need = 256 + 2 * wl_bytes + t_bytes + round256(ncounts * sizeof(uint32_t)) + round256(scan_bytes);
-    CallState &cs = scope.state();
-    if (cs.steps_scratch_bytes < need) {
-        HIP_TRY(hipStreamSynchronize(stream));
-        if (cs.steps_scratch) { HIP_TRY(hipFree(cs.steps_scratch)); cs.steps_scratch = nullptr; cs.steps_scratch_bytes = 0; }
-        HIP_TRY(ctx_malloc(scope.ctx, &cs.steps_scratch, need));
-        cs.steps_scratch_bytes = need;
-    }
-    char *p = (char *)cs.steps_scratch;
+    int rc = steps_block(scope, need); if (rc) return rc;
+    char *p = (char *)scope.state().steps_scratch;
     out->total = (unsigned long long *)p; p += 256;
     out->refractive_index = (float *)p; p += wl_bytes;
     out->scintillation_cdf = src->scintillation_cdf ? (float *)p : nullptr; p += wl_bytes;
@@ -67,7 +71,132 @@ static int steps_scratch(const CallScope &scope, const chroma_light_source *src,
     return CHROMA_OK;
 }
 
+// ---- a medium per segment ----
+// The device-resident table of chroma_light_media_create: ONE block of the context's pool, the three tables first (a row per
+// medium), then the per-medium yields and n_max, then the prompt bytes.  Never written after it is made.
+struct chroma_light_media {
+    chroma_ctx *ctx;
+    void *block;
+    steps::Media view;
+};
+// the media calls' share of the context's scratch block: the 64-bit total, the 2 n + 1 counts, the scan's workspace (no tables)
+static int media_scratch(const CallScope &scope, uint64_t nsegments, StepsScratch *out)
+{
+    const size_t ncounts = 2 * (size_t)nsegments + 1;
+    size_t scan_bytes = 0;
+    { uint32_t *nul = nullptr; HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, nul, nul, (int)ncounts, scope.ctx->stream)); }
+    int rc = steps_block(scope, 256 + round256(ncounts * sizeof(uint32_t)) + round256(scan_bytes)); if (rc) return rc;
+    char *p = (char *)scope.state().steps_scratch;
+    *out = StepsScratch();
+    out->total = (unsigned long long *)p; p += 256;
+    out->counts = (uint32_t *)p; p += round256(ncounts * sizeof(uint32_t));
+    out->scan = p; out->scan_bytes = scan_bytes;
+    return CHROMA_OK;
+}
+static int check_media_call(chroma_ctx *ctx, const chroma_light_media *media, const chroma_step_segments *segs, const int32_t *d_medium)
+{
+    if (!ctx || !media) return set_error(CHROMA_ERR_INVALID, "bad argument");
+    if (media->ctx != ctx) return set_error(CHROMA_ERR_INVALID, "light media: made on another context");
+    if (const char *why = steps::check_segments(segs)) return set_error(CHROMA_ERR_INVALID, "%s", why);
+    if (segs->n && !d_medium) return set_error(CHROMA_ERR_INVALID, "segments: no medium array");
+    return CHROMA_OK;
+}
+
 extern "C" {
+
+int chroma_light_media_create(chroma_ctx *ctx, const chroma_light_media_desc *desc, chroma_light_media **media)
+{
+    if (!ctx || !media) return set_error(CHROMA_ERR_INVALID, "bad argument");
+    *media = nullptr;
+    if (const char *why = steps::check_media(desc)) return set_error(CHROMA_ERR_INVALID, "%s", why);
+    const size_t nm = desc->nmedia, wl_bytes = round256(nm * desc->wavelength_n * sizeof(float));
+    const size_t t_bytes = round256(nm * std::max<size_t>(desc->time_n, 1) * sizeof(float)), m_bytes = round256(nm * sizeof(float));
+    void *block = nullptr;
+    int rc = chroma_malloc(ctx, 2 * wl_bytes + t_bytes + 3 * m_bytes, &block); if (rc) return rc;
+    char *p = (char *)block;
+    float *ri = (float *)p; p += wl_bytes;
+    float *scint = (float *)p; p += wl_bytes;
+    float *tcdf = (float *)p; p += t_bytes;
+    float *yield = (float *)p; p += m_bytes;
+    float *n_max = (float *)p; p += m_bytes;
+    uint8_t *prompt = (uint8_t *)p;
+    // one row at a time for the CDFs: a row that is ignored need not be readable, and is left as zeros
+    std::vector<float> h_n_max(nm);
+    steps::media_n_max(*desc, h_n_max.data());
+    hipStream_t stream = ctx->stream;
+    hipError_t e = hipMemsetAsync(scint, 0, wl_bytes + t_bytes, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(ri, desc->refractive_index, nm * desc->wavelength_n * sizeof(float), hipMemcpyHostToDevice, stream);
+    for (size_t m = 0; m < nm && e == hipSuccess; m++) {
+        if (desc->light_yield[m] == 0.0f) continue;
+        e = hipMemcpyAsync(scint + m * desc->wavelength_n, desc->scintillation_cdf + m * desc->wavelength_n, desc->wavelength_n * sizeof(float),
+                           hipMemcpyHostToDevice, stream);
+        if (e == hipSuccess && !desc->prompt[m])
+            e = hipMemcpyAsync(tcdf + m * desc->time_n, desc->time_cdf + m * desc->time_n, desc->time_n * sizeof(float), hipMemcpyHostToDevice, stream);
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(yield, desc->light_yield, nm * sizeof(float), hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(n_max, h_n_max.data(), nm * sizeof(float), hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(prompt, desc->prompt, nm, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);          // (the caller's tables are his again when the call returns)
+    if (e != hipSuccess) {
+        chroma_free(ctx, block);
+        return set_error((int)e, "light media: upload failed: %s", hipGetErrorString(e));
+    }
+    *media = new chroma_light_media{ctx, block, steps::make_media(*desc, ri, scint, tcdf, yield, prompt, n_max)};
+    return CHROMA_OK;
+}
+
+int chroma_light_media_destroy(chroma_light_media *media)
+{
+    if (!media) return CHROMA_OK;
+    const int rc = chroma_free(media->ctx, media->block);
+    delete media;
+    return rc;
+}
+
+int chroma_steps_count_media(chroma_ctx *ctx, const chroma_light_media *media, const chroma_step_segments *segs, const int32_t *d_medium,
+                             uint64_t seed, uint32_t *d_offsets, uint64_t *total)
+{
+    if (!d_offsets || !total) return set_error(CHROMA_ERR_INVALID, "bad argument");
+    int rc = check_media_call(ctx, media, segs, d_medium); if (rc) return rc;
+    const CallScope scope(ctx);
+    *total = 0;
+    if (segs->n == 0) {
+        HIP_TRY(hipMemsetAsync(d_offsets, 0, sizeof(uint32_t), ctx->stream));
+        return CHROMA_OK;
+    }
+    StepsScratch sc;
+    rc = media_scratch(scope, segs->n, &sc); if (rc) return rc;
+    HIP_TRY(hipMemsetAsync(sc.total, 0, sizeof(unsigned long long), ctx->stream));
+    hipLaunchKernelGGL(k_steps_count_media, dim3((unsigned)((segs->n + STEPS_BLOCK - 1) / STEPS_BLOCK)), dim3(STEPS_BLOCK), 0, ctx->stream,
+                       media->view, *segs, d_medium, seed, sc.counts, sc.total);
+    HIP_TRY(hipGetLastError());
+    { size_t b = sc.scan_bytes; HIP_TRY(hipcub::DeviceScan::ExclusiveSum(sc.scan, b, sc.counts, d_offsets, (int)(2 * segs->n + 1), ctx->stream)); }
+    unsigned long long sum = 0;
+    HIP_TRY(hipMemcpyAsync(&sum, sc.total, sizeof(sum), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    *total = sum;
+    if (sum > 0xffffffffull) return set_error(CHROMA_ERR_INVALID, "%llu photons in one call: more than 32-bit offsets hold, pass fewer segments", sum);
+    return CHROMA_OK;
+}
+
+int chroma_steps_generate_media(chroma_ctx *ctx, const chroma_light_media *media, const chroma_step_segments *segs, const int32_t *d_medium,
+                                uint64_t seed, const uint32_t *d_offsets, const chroma_photon_arrays *photons, uint64_t capacity)
+{
+    if (!d_offsets) return set_error(CHROMA_ERR_INVALID, "bad argument");
+    int rc = check_media_call(ctx, media, segs, d_medium); if (rc) return rc;
+    if (segs->n == 0) return CHROMA_OK;
+    const CallScope scope(ctx);
+    uint32_t total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, d_offsets + 2 * segs->n, sizeof(total), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (capacity < total) return set_error(CHROMA_ERR_INVALID, "room for %llu photons, the segments emit %u", (unsigned long long)capacity, total);
+    if (total == 0) return CHROMA_OK;
+    rc = check_photons(photons, true); if (rc) return rc;
+    hipLaunchKernelGGL(k_steps_generate_media, dim3((total + STEPS_BLOCK - 1) / STEPS_BLOCK), dim3(STEPS_BLOCK), 0, ctx->stream, media->view, *segs,
+                       d_medium, seed, d_offsets, to_view(photons), total);
+    HIP_TRY(hipGetLastError());
+    return CHROMA_OK;
+}
 
 int chroma_steps_count(chroma_ctx *ctx, const chroma_light_source *src, const chroma_step_segments *segs, uint64_t seed,
                        uint32_t *d_offsets, uint64_t *total)

@@ -124,6 +124,90 @@ static inline Source make_source(const chroma_light_source &s, const float *ri, 
     return o;
 }
 
+// A chroma_light_media as the callee reads it: the three tables one row per medium, and per medium what make_source works out
+// for one source -- the yield (0: no scintillation light), whether the emission is prompt, the largest n of the Cherenkov
+// range.  What is the same for every row is here once.
+struct Media {
+    const float *refractive_index, *scintillation_cdf, *time_cdf;      // [nmedia][wavelength_n], ditto, [nmedia][time_n]
+    const float *light_yield, *n_max;                                  // [nmedia]
+    const uint8_t *prompt;                                             // [nmedia]
+    uint32_t nmedia;
+    uint32_t wavelength_n; float wavelength_start, wavelength_step;
+    uint32_t time_n;       float time_start, time_step;
+    uint32_t node_lo, node_hi;
+    float wl_lo, wl_hi;
+};
+
+// the Source of row m (m < nmedia): what make_source gives for that medium's chroma_light_source, field for field
+CM_FN Source media_source(const Media &t, uint32_t m)
+{
+    Source o;
+    o.refractive_index = t.refractive_index + (size_t)m * t.wavelength_n;
+    o.scintillation_cdf = t.scintillation_cdf + (size_t)m * t.wavelength_n;
+    o.time_cdf = t.prompt[m] ? nullptr : t.time_cdf + (size_t)m * t.time_n;
+    o.wavelength_n = t.wavelength_n; o.wavelength_start = t.wavelength_start; o.wavelength_step = t.wavelength_step;
+    o.time_n = t.time_n; o.time_start = t.time_start; o.time_step = t.time_step;
+    o.light_yield = t.light_yield[m];
+    o.node_lo = t.node_lo; o.node_hi = t.node_hi;
+    o.wl_lo = t.wl_lo; o.wl_hi = t.wl_hi;
+    o.n_max = t.n_max[m];
+    return o;
+}
+// the row of a segment: a medium outside the table emits nothing
+CM_FN bool medium_ok(const Media &t, int32_t m) { return m >= 0 && (uint32_t)m < t.nmedia; }
+
+// what chroma_light_media_desc must satisfy (host side; NULL: fine): check_source's conditions for every row, and CDF rows
+// that rise from their first node to their last, which sample_cdf's bisection takes for granted
+static inline const char *check_cdf_row(const float *row, uint32_t n)
+{
+    for (uint32_t j = 0; j < n; j++) {
+        if (!cm_isfinite(row[j])) return "not finite";
+        if (j && row[j] < row[j - 1]) return "falls";
+    }
+    return nullptr;
+}
+static inline const char *check_media(const chroma_light_media_desc *d)
+{
+    if (!d || !d->refractive_index || !d->light_yield || !d->prompt) return "light media: null pointer";
+    if (d->nmedia < 1 || d->nmedia > 256) return "light media: need 1 to 256 media";
+    if (d->wavelength_n < 2 || !(d->wavelength_step > 0.0f) || !(d->wavelength_start > 0.0f)) return "light media: need a rising wavelength grid of at least 2 nodes above 0";
+    if (!(d->cherenkov_lo < d->cherenkov_hi) || d->cherenkov_hi >= d->wavelength_n) return "light media: Cherenkov range must be two different grid nodes, lo < hi";
+    for (uint32_t m = 0; m < d->nmedia; m++) {
+        if (!(d->light_yield[m] >= 0.0f) || !cm_isfinite(d->light_yield[m])) return "light media: light_yield must be finite and not negative";
+        if (d->light_yield[m] == 0.0f) continue;
+        if (!d->scintillation_cdf) return "light media: a medium with a light yield needs a scintillation CDF";
+        if (check_cdf_row(d->scintillation_cdf + (size_t)m * d->wavelength_n, d->wavelength_n)) return "light media: a scintillation CDF row is not finite or does not rise";
+        if (d->prompt[m]) continue;
+        if (!d->time_cdf || d->time_n < 2 || !(d->time_step > 0.0f)) return "light media: a time CDF needs a rising grid of at least 2 nodes";
+        if (check_cdf_row(d->time_cdf + (size_t)m * d->time_n, d->time_n)) return "light media: a time CDF row is not finite or does not rise";
+    }
+    return nullptr;
+}
+// n_max[m], the largest n of row m over the Cherenkov range, as make_source finds it (host side)
+static inline void media_n_max(const chroma_light_media_desc &d, float *n_max)
+{
+    for (uint32_t m = 0; m < d.nmedia; m++) {
+        const float *row = d.refractive_index + (size_t)m * d.wavelength_n;
+        n_max[m] = row[d.cherenkov_lo];
+        for (uint32_t j = d.cherenkov_lo; j <= d.cherenkov_hi; j++) if (row[j] > n_max[m]) n_max[m] = row[j];
+    }
+}
+// (host side: the seven pointers where the callee can read them)
+static inline Media make_media(const chroma_light_media_desc &d, const float *ri, const float *scint_cdf, const float *time_cdf,
+                               const float *light_yield, const uint8_t *prompt, const float *n_max)
+{
+    Media o;
+    o.refractive_index = ri; o.scintillation_cdf = scint_cdf; o.time_cdf = time_cdf;
+    o.light_yield = light_yield; o.n_max = n_max; o.prompt = prompt;
+    o.nmedia = d.nmedia;
+    o.wavelength_n = d.wavelength_n; o.wavelength_start = d.wavelength_start; o.wavelength_step = d.wavelength_step;
+    o.time_n = d.time_n; o.time_start = d.time_start; o.time_step = d.time_step;
+    o.node_lo = d.cherenkov_lo; o.node_hi = d.cherenkov_hi;
+    o.wl_lo = o.wavelength_start + (float)o.node_lo * o.wavelength_step;          // (node_wavelength's expression)
+    o.wl_hi = o.wavelength_start + (float)o.node_hi * o.wavelength_step;
+    return o;
+}
+
 struct Segment { v3 a, b; float t_a, t_b, beta, z, qedep; uint32_t evidx; };
 CM_FN Segment load_segment(const chroma_step_segments &g, uint64_t s)
 {

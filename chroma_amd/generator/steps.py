@@ -3,14 +3,16 @@
 A track's ``event.Steps`` (as a stepping action records them: point 0 the pre-step point with zero deposit, point k + 1
 the post-step point of step k with that step's deposits) is cut into SEGMENTS, two consecutive points A -> B of one vertex.
 A segment emits Cherenkov light (Frank-Tamm over the wavelength grid) and scintillation light (``light_yield * qedep``) in ONE
-medium, described by a :class:`LightSource`.  ``generate_photons`` here runs the library's host loops
-(``chroma_steps_count_host`` / ``chroma_steps_generate_host``): no GPU is needed, and the photons are bit for bit those
+medium -- a stepping action limits every step at a volume boundary -- described by a :class:`LightSource`: the same one for
+every segment of a call, or, with a :class:`LightMedia` and a ``medium`` array, row ``medium[s]`` of a table of them for
+segment s.  ``generate_photons`` here runs the library's host loops (``chroma_steps_count_host`` /
+``chroma_steps_generate_host`` and their ``_media_host`` twins): no GPU is needed, and the photons are bit for bit those
 ``chroma_amd.gpu.steps.generate_photons`` makes on the device from the same segments, seed and ``segment_base``.
 
 Of a Material's scintillation properties ``scintillation_spectrum``, ``scintillation_light_yield`` and
 ``scintillation_waveform`` are read.  ``scintillation_rise_time`` and ``scintillation_mod`` are NOT: the delay comes from the
-waveform alone, and ``qedep`` is taken as it is -- it is already quenched.  No table of a per-step material is looked up and
-no secondary particle is made: one medium per call.
+waveform alone, and ``qedep`` is taken as it is -- it is already quenched.  No secondary particle is made.  Which medium a
+segment lies in is the caller's to say here (``medium``); ``chroma_amd.gpu.steps`` can find it in the geometry itself.
 """
 import ctypes
 
@@ -92,6 +94,10 @@ class LightSource(object):
         sizes batches by before anything is drawn."""
         if len(segments) == 0:
             return 0.0
+        return float(self.expected_per_segment(segments).sum())
+
+    def expected_per_segment(self, segments):
+        """... and segment by segment: float64 (n,)."""
         lo, hi = self.cherenkov_nodes
         wl, n = self.wavelengths[lo:hi + 1], self.refractive_index[lo:hi + 1].astype(np.float64)
         beta2 = np.maximum(segments.beta.astype(np.float64), 1e-30)[:, None] ** 2
@@ -99,7 +105,76 @@ class LightSource(object):
         integral = (0.5 * (f[:, 1:] + f[:, :-1]) * np.diff(wl)).sum(axis=1)
         length = np.linalg.norm(segments.b.astype(np.float64) - segments.a, axis=1)
         cherenkov = 2 * np.pi * 7.2973525693e-3 * 1e6 * segments.z.astype(np.float64) ** 2 * length * integral
-        return float(cherenkov.sum() + self.light_yield * np.maximum(segments.qedep, 0).sum(dtype=np.float64))
+        return cherenkov + self.light_yield * np.maximum(segments.qedep, 0).astype(np.float64)
+
+
+class LightMedia(object):
+    """Several media as ONE table of light sources, a row per material: ``sources[m]`` is the :class:`LightSource` of
+    ``materials[m]``, and ``desc`` the chroma_light_media_desc over their stacked tables (all on the same grids, with the same
+    Cherenkov range).  A segment in row m emits exactly what ``sources[m]`` emits for it."""
+
+    def __init__(self, materials, wavelengths=None, cherenkov_range=(200, 800), times=None):
+        self.materials = list(materials)
+        if not self.materials:
+            raise ValueError('light media: no material')
+        self.sources = [LightSource(m, wavelengths, cherenkov_range, times) for m in self.materials]
+        first = self.sources[0].struct
+        nwl, nt = first.wavelength_n, first.time_n
+        self.refractive_index = np.ascontiguousarray([s.refractive_index for s in self.sources], dtype=np.float32)
+        self.light_yield = np.array([s.light_yield for s in self.sources], dtype=np.float32)
+        self.prompt = np.array([s.time_cdf is None for s in self.sources], dtype=np.uint8)
+        self.scintillation_cdf = self.time_cdf = None
+        if self.light_yield.any():
+            self.scintillation_cdf = np.zeros((len(self.sources), nwl), dtype=np.float32)
+            for row, s in zip(self.scintillation_cdf, self.sources):
+                if s.scintillation_cdf is not None:
+                    row[:] = s.scintillation_cdf
+        if not self.prompt.all():
+            self.time_cdf = np.zeros((len(self.sources), nt), dtype=np.float32)
+            for row, s in zip(self.time_cdf, self.sources):
+                if s.time_cdf is not None:
+                    row[:] = s.time_cdf
+        d = self.desc = _lib.LightMediaDesc()
+        d.nmedia = len(self.sources)
+        for name in ('refractive_index', 'scintillation_cdf', 'time_cdf', 'light_yield', 'prompt'):
+            setattr(d, name, _lib.ptr(getattr(self, name)))
+        for name in ('wavelength_n', 'wavelength_start', 'wavelength_step', 'time_n', 'time_start', 'time_step', 'cherenkov_lo', 'cherenkov_hi'):
+            setattr(d, name, getattr(first, name))
+
+    @classmethod
+    def from_geometry(cls, geometry, **kwargs):
+        """A row per material of ``geometry.unique_materials``, in that order: row m is the geometry's material index m,
+        which is what ``chroma_amd.gpu.steps.locate_materials`` answers with."""
+        return cls(geometry.unique_materials, **kwargs)
+
+    def __len__(self):
+        return len(self.sources)
+
+    def index(self, material):
+        """The row of ``material`` (by identity), or -1."""
+        for m, have in enumerate(self.materials):
+            if have is material:
+                return m
+        return -1
+
+    def expected_per_segment(self, segments):
+        """(nmedia, n) float64: what each segment is expected to emit in each medium."""
+        return np.array([s.expected_per_segment(segments) for s in self.sources]).reshape(len(self.sources), len(segments))
+
+    def expected_photons(self, segments, medium):
+        """About how many photons ``segments`` emit in all with segment s in row ``medium[s]`` (rows outside the table: none)."""
+        medium = np.asarray(medium, dtype=np.int64)
+        if len(segments) == 0:
+            return 0.0
+        ok = (medium >= 0) & (medium < len(self.sources))
+        per = self.expected_per_segment(segments)
+        return float(per[np.where(ok, medium, 0), np.arange(len(segments))][ok].sum())
+
+    def expected_at_most(self, segments):
+        """An upper bound of ``expected_photons`` that needs no medium array: every segment in the medium it would emit most in."""
+        if len(segments) == 0:
+            return 0.0
+        return float(self.expected_per_segment(segments).max(axis=0).sum())
 
 
 _SEGMENT_FIELDS = ('a', 'b', 't_a', 't_b', 'beta', 'z', 'qedep', 'evidx')
@@ -180,22 +255,42 @@ def _as_segments(vertices_or_segments, evidx, segment_base):
     return segments_from_vertices(vertices_or_segments, evidx=evidx, segment_base=segment_base)
 
 
-def count_photons(segments, source, seed):
+def _medium_array(segments, source, medium):
+    """The int32 row per segment for a LightMedia ``source``; None for a LightSource (which takes no ``medium``)."""
+    if not isinstance(source, LightMedia):
+        if medium is not None:
+            raise ValueError('medium= goes with a LightMedia, not with one LightSource')
+        return None
+    if medium is None:
+        raise ValueError('a LightMedia needs medium=: the row of every segment')
+    medium = np.ascontiguousarray(np.broadcast_to(np.asarray(medium, dtype=np.int32), (len(segments),)))
+    return medium
+
+
+def count_photons(segments, source, seed, medium=None):
     """(offsets, total) of the host count: ``offsets`` uint32 (2 n + 1,), the photons of segment s are
-    ``offsets[2 s] .. offsets[2 s + 2]``, Cherenkov before scintillation."""
+    ``offsets[2 s] .. offsets[2 s + 2]``, Cherenkov before scintillation.  ``source``: a LightSource, or a LightMedia with
+    ``medium`` (int array, the row of each segment; a row outside the table emits nothing)."""
     offsets = np.zeros(2 * len(segments) + 1, dtype=np.uint32)
     total = ctypes.c_uint64()
     seg = segments.struct()
-    _lib.check(_lib.load().chroma_steps_count_host(ctypes.byref(source.struct), ctypes.byref(seg), int(seed) & (2 ** 64 - 1),
-                                                   _lib.ptr(offsets), ctypes.byref(total)))
+    seed = int(seed) & (2 ** 64 - 1)
+    medium = _medium_array(segments, source, medium)
+    if medium is None:
+        _lib.check(_lib.load().chroma_steps_count_host(ctypes.byref(source.struct), ctypes.byref(seg), seed, _lib.ptr(offsets), ctypes.byref(total)))
+    else:
+        _lib.check(_lib.load().chroma_steps_count_media_host(ctypes.byref(source.desc), ctypes.byref(seg), _lib.ptr(medium), seed,
+                                                             _lib.ptr(offsets), ctypes.byref(total)))
     return offsets, total.value
 
 
-def generate_photons(vertices_or_segments, source, seed, evidx=0, segment_base=0):
+def generate_photons(vertices_or_segments, source, seed, evidx=0, segment_base=0, medium=None):
     """The photons ``source`` emits along the segments (or the steps of the vertices), made on the HOST: an
-    ``event.Photons`` in segment order, a segment's Cherenkov photons before its scintillation photons."""
+    ``event.Photons`` in segment order, a segment's Cherenkov photons before its scintillation photons.  ``source`` and
+    ``medium`` as for ``count_photons``."""
     segments = _as_segments(vertices_or_segments, evidx, segment_base)
-    offsets, n = count_photons(segments, source, seed)
+    medium = _medium_array(segments, source, medium)
+    offsets, n = count_photons(segments, source, seed, medium)
     out = event.Photons(np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32), np.zeros(n, np.float32))
     counters = np.zeros(n, dtype=np.uint32)
     arrays = _lib.PhotonArrays()
@@ -203,6 +298,11 @@ def generate_photons(vertices_or_segments, source, seed, evidx=0, segment_base=0
         setattr(arrays, name, _lib.ptr(getattr(out, name)))
     arrays.rng_counters = _lib.ptr(counters)
     seg = segments.struct()
-    _lib.check(_lib.load().chroma_steps_generate_host(ctypes.byref(source.struct), ctypes.byref(seg), int(seed) & (2 ** 64 - 1),
-                                                      _lib.ptr(offsets), ctypes.byref(arrays), n))
+    seed = int(seed) & (2 ** 64 - 1)
+    if medium is None:
+        _lib.check(_lib.load().chroma_steps_generate_host(ctypes.byref(source.struct), ctypes.byref(seg), seed, _lib.ptr(offsets),
+                                                          ctypes.byref(arrays), n))
+    else:
+        _lib.check(_lib.load().chroma_steps_generate_media_host(ctypes.byref(source.desc), ctypes.byref(seg), _lib.ptr(medium), seed,
+                                                                _lib.ptr(offsets), ctypes.byref(arrays), n))
     return out

@@ -86,6 +86,8 @@ class Context(object):
         context cannot be used afterwards; device arrays made on it must be gone by then."""
         if self.handle is not None and self.handle.value:
             self.pop()
+            for table in self.__dict__.pop('_light_media', {}).values():      # (chroma_amd.gpu.steps.device_media)
+                table.destroy()
             _lib.check(self._lib.chroma_shutdown(self.handle))
             self.handle = ctypes.c_void_p()
 

@@ -26,9 +26,13 @@ class Simulation(object):
                  geant4_processes=0, nthreads_per_block=64, max_blocks=1024, exact=False, prefetch=True, lanes=1,
                  light_medium=None):
         # ``light_medium``: the Material whose Cherenkov and scintillation light the steps of Events without photons emit
-        # (simulate(); chroma_amd.gpu.steps.LightSource); None: the detector's ``detector_material``
+        # (simulate(); chroma_amd.gpu.steps.LightSource); None: the detector's ``detector_material``; 'located': every segment
+        # emits the light of the material it lies in, found on the device in this geometry (chroma_amd.gpu.steps.locate_materials:
+        # a LightMedia with a row per material of the detector; a segment outside every solid is in ``detector_material``, or
+        # emits nothing when the detector has none)
         self.light_medium = light_medium
         self._light_source = None
+        self._outside_row = -1
         self._segment_base = 0               # segments generated so far: a segment's random streams are keyed by its global index
         # ``exact``: propagate with the reference's own traversal loop for every ray (GPUPhotons.propagate(exact=True)):
         # the reference's hit triangle on every ray, several times slower than the default walk
@@ -249,7 +253,19 @@ class Simulation(object):
 
     @property
     def light_source(self):
-        """The LightSource of ``light_medium`` (or of the detector's ``detector_material``), made on first use."""
+        """The LightSource of ``light_medium`` (or of the detector's ``detector_material``), made on first use; with
+        ``light_medium='located'`` the LightMedia of the detector's materials."""
+        if self._light_source is None and isinstance(self.light_medium, str):
+            if self.light_medium != 'located':
+                raise ValueError("light_medium: a Material, None or 'located'")
+            materials = list(self.detector.unique_materials)
+            outside = getattr(self.detector, 'detector_material', None)
+            if outside is not None:
+                rows = [m for m, have in enumerate(materials) if have is outside]
+                if not rows:
+                    materials.append(outside)          # (a row of its own behind the geometry's: no triangle names it)
+                self._outside_row = rows[0] if rows else len(materials) - 1
+            self._light_source = gpu.steps.LightMedia(materials)
         if self._light_source is None:
             medium = self.light_medium if self.light_medium is not None else getattr(self.detector, 'detector_material', None)
             if medium is None:
@@ -262,8 +278,16 @@ class Simulation(object):
         (chroma_amd.gpu.steps.generate_photons, seed ``self.seed``) and propagated where they are.  Events are batched by the
         photons their steps are EXPECTED to emit; the segments of the events are numbered on in iterable order from one
         simulate() call to the next, so the photons do not depend on the batching.  ``photons_beg`` is fetched only with
-        ``keep_photons_beg``."""
+        ``keep_photons_beg``.
+
+        With ``light_medium='located'`` the medium of a segment is not known before its batch is on the device, and the
+        batches have to be cut before anything is drawn; so an event counts with what its segments would emit each in the
+        medium it emits MOST in (LightMedia.expected_at_most).  That is an upper bound of what it is expected to emit: a
+        batch is closed no later than the true media would close it, so it never grows beyond what ``photons_per_batch``
+        allows for a single medium, and may hold fewer photons."""
         source = self.light_source
+        located = isinstance(source, gpu.steps.LightMedia)
+        expected_photons = source.expected_at_most if located else source.expected_photons
 
         def batches():
             expected, batch, evid = 0.0, [], evid_start
@@ -273,7 +297,7 @@ class Simulation(object):
                 ev.id = evid
                 evid += 1
                 segments = gpu.steps.segments_from_vertices(ev.vertices, evidx=len(batch))
-                expected += source.expected_photons(segments)
+                expected += expected_photons(segments)
                 batch.append((ev, segments))
                 if expected >= photons_per_batch:
                     yield batch
@@ -284,7 +308,8 @@ class Simulation(object):
         for batch in batches():
             segments = gpu.steps.Segments.join([s for _, s in batch], segment_base=self._segment_base)
             self._segment_base += len(segments)
-            gpu_photons, offsets = gpu.steps.generate_photons(segments, source, self.seed, ctx=self.context, return_offsets=True)
+            where = dict(gpu_geometry=self.gpu_geometry, outside=self._outside_row) if located else {}
+            gpu_photons, offsets = gpu.steps.generate_photons(segments, source, self.seed, ctx=self.context, return_offsets=True, **where)
             cuts = 2 * np.cumsum([0] + [len(s) for _, s in batch])
             bounds = offsets[cuts].astype(np.int64)
             events = [ev for ev, _ in batch]

@@ -267,6 +267,17 @@ int chroma_intersect_mesh(chroma_ctx *ctx, chroma_geometry *geom, int32_t nthrea
                           const float *d_origin, const float *d_direction, const int32_t *d_last_hit,
                           float *d_distance, int32_t *d_triangle);
 
+/* Which material each point lies in, by the rule of the reference's `fill_state` (chroma/cuda/photon.h:99-120) for a photon
+ * that would start at the point along `direction` (one probe direction for all points; NULL: (0, 0, 1)): the nearest
+ * triangle along the ray, no last-hit exclusion; with normal = normalize(cross(v1 - v0, v2 - v1)), the point is in the
+ * triangle's OUTER material ((code >> 16) & 0xFF) when dot(normal, -d) > 0 and in its INNER material ((code >> 24) & 0xFF)
+ * otherwise -- the engine's own float arithmetic and strict comparison.  A point whose ray hits nothing gets `outside`.
+ * d_triangle (may be NULL) receives the deciding triangle, -1 for none: exactly what chroma_intersect_mesh returns for the
+ * same rays (the same ray-cast pipeline).  n == 0 does nothing; n < 0, a null pointer or a direction of no length is
+ * CHROMA_ERR_INVALID.  Queued on the context's stream. */
+int chroma_locate_materials(chroma_ctx *ctx, chroma_geometry *geom, int32_t n, const float *d_points,
+                            const float direction[3], int32_t outside, int32_t *d_material, int32_t *d_triangle);
+
 /* ---- fused host loops ---- */
 
 /* GPUPhotons.propagate (chroma/gpu/photon.py:193-259) for n photons, whole loop on the
@@ -469,6 +480,45 @@ int chroma_steps_count_host(const chroma_light_source *src, const chroma_step_se
                             uint32_t *offsets, uint64_t *total);
 int chroma_steps_generate_host(const chroma_light_source *src, const chroma_step_segments *segs, uint64_t seed,
                                const uint32_t *offsets, const chroma_photon_arrays *photons, uint64_t capacity);
+
+/* ---- a medium per segment ----
+ * The media of a detector as ONE device-resident table, a row per medium (for chroma_locate_materials' answers: a row per
+ * material of the geometry), made once: the single-medium calls above copy their tables up on every call.  Row m is the
+ * chroma_light_source with row m of each table, light_yield[m] (0: no scintillation light, the two CDF rows are ignored) and
+ * time_cdf = prompt[m] ? NULL : row m; the grids and the Cherenkov range are the same for all rows.  Checked row by row as
+ * one source is, and every CDF row that is read has to be finite and must not fall. */
+typedef struct chroma_light_media_desc {
+    uint32_t nmedia;
+    const float *refractive_index;    /* [nmedia][wavelength_n]                                                   */
+    const float *scintillation_cdf;   /* [nmedia][wavelength_n]; rows of media without such light are ignored     */
+    const float *time_cdf;            /* [nmedia][time_n]; ditto                                                  */
+    const float *light_yield;         /* [nmedia]; 0: no scintillation                                            */
+    const uint8_t *prompt;            /* [nmedia]; 1: no time_cdf row, emission is prompt                         */
+    uint32_t wavelength_n; float wavelength_start, wavelength_step;
+    uint32_t time_n;       float time_start, time_step;
+    uint32_t cherenkov_lo, cherenkov_hi;
+} chroma_light_media_desc;            /* HOST pointers */
+typedef struct chroma_light_media chroma_light_media;
+
+/* The table on the device of `ctx` (blocks of chroma_malloc's pool); the desc's arrays are the caller's again on return. */
+int chroma_light_media_create(chroma_ctx *ctx, const chroma_light_media_desc *desc, chroma_light_media **media);
+/* Before chroma_shutdown of its context.  NULL: nothing. */
+int chroma_light_media_destroy(chroma_light_media *media);
+
+/* chroma_steps_count / chroma_steps_generate with segment s in row d_medium[s] (int32 [n], a DEVICE array; host for the
+ * _host calls).  A segment whose row is negative or >= nmedia emits nothing: both its counts are 0.  Segment s in medium m
+ * emits, bit for bit, what the single-medium call emits for it with medium m's chroma_light_source, seed and global segment
+ * index being the same.  Layout, offsets, the 32-bit refusal and the capacity rule are those of the calls above. */
+int chroma_steps_count_media(chroma_ctx *ctx, const chroma_light_media *media, const chroma_step_segments *segs,
+                             const int32_t *d_medium, uint64_t seed, uint32_t *d_offsets, uint64_t *total);
+int chroma_steps_generate_media(chroma_ctx *ctx, const chroma_light_media *media, const chroma_step_segments *segs,
+                                const int32_t *d_medium, uint64_t seed, const uint32_t *d_offsets,
+                                const chroma_photon_arrays *photons, uint64_t capacity);
+int chroma_steps_count_media_host(const chroma_light_media_desc *desc, const chroma_step_segments *segs, const int32_t *medium,
+                                  uint64_t seed, uint32_t *offsets, uint64_t *total);
+int chroma_steps_generate_media_host(const chroma_light_media_desc *desc, const chroma_step_segments *segs, const int32_t *medium,
+                                     uint64_t seed, const uint32_t *offsets, const chroma_photon_arrays *photons,
+                                     uint64_t capacity);
 
 /* tools.argsort_direction (chroma/tools.py:175-193) and the reordering it serves, for a photon set on the device: the
  * photons are put in the order of a 32-bit Morton code of (theta, phi) of their directions (stable), every array of
