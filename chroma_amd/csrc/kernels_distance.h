@@ -20,7 +20,8 @@ k_distance_to_mesh(GeoView g, int nthreads, const float *origin, const float *di
         d = d / norm(d);
     }
     float dist;
-    const int last_hit = (on && last_hit_in) ? last_hit_in[id] : -1;
+    int last_hit = (on && last_hit_in) ? last_hit_in[id] : -1;
+    if ((uint32_t)last_hit >= g.ntriangles) last_hit = -1;   // an id outside the mesh excludes nothing (as k_rays_from_arrays)
     int tri = intersect_mesh<LDS_N, PROP_BLOCK, COUNT>(g, o, d, dist, last_hit, s_lds + threadIdx.x, cnt, on);
     if (on) {
         if (tri != -1) distance_out[id] = dist;

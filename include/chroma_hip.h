@@ -261,7 +261,8 @@ int chroma_distance_to_mesh(chroma_ctx *ctx, chroma_geometry *geom, int32_t nthr
                             float *d_distance, int32_t *d_triangle);
 /* The device function `intersect_mesh` (chroma/cuda/mesh.h:42-118) over a ray bundle, with its
  * `last_hit_triangle` argument: ray i never hits triangle d_last_hit[i] (mesh.h:82; NULL or -1: no
- * exclusion).  chroma_distance_to_mesh is this call with d_last_hit = NULL.  Same fast walk, check and
+ * exclusion).  An id outside the mesh -- negative, or >= the number of triangles -- names no triangle and excludes
+ * nothing, under every walk.  chroma_distance_to_mesh is this call with d_last_hit = NULL.  Same fast walk, check and
  * literal-walk fallback as a propagation step. */
 int chroma_intersect_mesh(chroma_ctx *ctx, chroma_geometry *geom, int32_t nthreads,
                           const float *d_origin, const float *d_direction, const int32_t *d_last_hit,
