@@ -23,12 +23,37 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _libs = {}
 
 
+REF_PHYSICS_LIBS = {'contract': 'libchroma_ref_physics_contract.so', 'libm': 'libchroma_ref_physics_libm.so'}
+
+
+def ref_physics_path(variant='contract'):
+    return os.path.join(_HERE, '_ref', REF_PHYSICS_LIBS[variant])
+
+
+def have_ref_physics():
+    return all(os.path.exists(ref_physics_path(v)) for v in REF_PHYSICS_LIBS)
+
+
 def build(force=False):
-    """Compile liboracle.so / liboracle_libm.so (and oracle/_ref when the reference is present)."""
+    """Compile liboracle.so / liboracle_libm.so (and oracle/_ref when the reference is present).  The host builds of
+    the reference's physics (oracle/_ref/libchroma_ref_physics_*.so) are made on their own when only they are missing:
+    the Makefile's `ref-physics` target compiles them if the reference tree is there and says so if it is not."""
     have = all(os.path.exists(os.path.join(_HERE, n)) for n in ('liboracle.so', 'liboracle_libm.so'))
     if have and not force:
+        if not have_ref_physics():
+            subprocess.check_call(['make', '-C', _HERE, 'ref-physics'], stdout=subprocess.DEVNULL)
         return
     subprocess.check_call(['make', '-C', _HERE, 'all'], stdout=subprocess.DEVNULL)
+
+
+_SINGLE_ARGTYPES = [POINTER(_abi.GeometryDesc), POINTER(_abi.PhotonArrays), _abi.Rng, c_int32,
+                    POINTER(c_float), c_float, c_float, c_float, c_float, c_int32, c_int32, c_float,
+                    c_int32, c_int32]
+_RUN_DAQ_ARGTYPES = [POINTER(_abi.GeometryDesc), POINTER(_abi.DaqTables), c_int32, c_int32, c_uint32,
+                     POINTER(_abi.PhotonArrays), _abi.Rng, c_uint32, c_float, c_void_p, c_void_p, c_void_p]
+_RUN_DAQ_MANY_ARGTYPES = [POINTER(_abi.GeometryDesc), POINTER(_abi.DaqTables), c_int32, c_int32, c_uint32,
+                          POINTER(_abi.PhotonArrays), _abi.Rng, c_uint32, c_float, c_int32, c_int32,
+                          c_void_p, c_void_p, c_void_p]
 
 
 def load(variant='contract'):
@@ -53,12 +78,9 @@ def load(variant='contract'):
     lib.oracle_generate_bomb.argtypes = [POINTER(_abi.PhotonArrays), c_uint64, c_uint64, c_uint64, POINTER(c_float),
                                          c_float, c_float]
     lib.oracle_run_daq.restype = c_int32
-    lib.oracle_run_daq.argtypes = [POINTER(_abi.GeometryDesc), POINTER(_abi.DaqTables), c_int32, c_int32, c_uint32,
-                                   POINTER(_abi.PhotonArrays), _abi.Rng, c_uint32, c_float, c_void_p, c_void_p, c_void_p]
+    lib.oracle_run_daq.argtypes = _RUN_DAQ_ARGTYPES
     lib.oracle_run_daq_many.restype = c_int32
-    lib.oracle_run_daq_many.argtypes = [POINTER(_abi.GeometryDesc), POINTER(_abi.DaqTables), c_int32, c_int32, c_uint32,
-                                        POINTER(_abi.PhotonArrays), _abi.Rng, c_uint32, c_float, c_int32, c_int32,
-                                        c_void_p, c_void_p, c_void_p]
+    lib.oracle_run_daq_many.argtypes = _RUN_DAQ_MANY_ARGTYPES
     lib.oracle_math.restype = c_int32
     lib.oracle_math.argtypes = [c_int32, c_uint64, c_void_p, c_void_p, c_void_p]
     lib.oracle_philox.restype = None
@@ -66,10 +88,35 @@ def load(variant='contract'):
     lib.oracle_uniform_stream.restype = None
     lib.oracle_uniform_stream.argtypes = [c_uint64, c_uint64, c_uint32, c_uint32, c_void_p]
     lib.oracle_single.restype = c_int32
-    lib.oracle_single.argtypes = [POINTER(_abi.GeometryDesc), POINTER(_abi.PhotonArrays), _abi.Rng, c_int32,
-                                  POINTER(c_float), c_float, c_float, c_float, c_float, c_int32, c_int32, c_float,
-                                  c_int32, c_int32]
+    lib.oracle_single.argtypes = _SINGLE_ARGTYPES
     _libs[variant] = lib
+    return lib
+
+
+_ref_libs = {}
+
+
+def load_ref_physics(variant='contract'):
+    """The reference's OWN physics and DAQ sources compiled for the host (oracle/ref_physics_driver.cc) -- only what
+    oracle/_ref holds is loaded, the reference tree itself is never read here.  None when the library is not there."""
+    if variant in _ref_libs:
+        return _ref_libs[variant]
+    path = ref_physics_path(variant)
+    if not os.path.exists(path):
+        return None
+    lib = ctypes.CDLL(path)
+    lib.ref_phys_variant.restype = ctypes.c_char_p
+    assert lib.ref_phys_variant().decode() == variant
+    lib.ref_phys_propagate.restype = c_int32
+    lib.ref_phys_propagate.argtypes = [POINTER(_abi.GeometryDesc), POINTER(_abi.PhotonArrays), c_uint64, _abi.Rng,
+                                       c_int32, c_int32, c_int32, POINTER(c_uint64)]
+    lib.ref_phys_single.restype = c_int32
+    lib.ref_phys_single.argtypes = _SINGLE_ARGTYPES
+    lib.ref_phys_run_daq.restype = c_int32
+    lib.ref_phys_run_daq.argtypes = _RUN_DAQ_ARGTYPES
+    lib.ref_phys_run_daq_many.restype = c_int32
+    lib.ref_phys_run_daq_many.argtypes = _RUN_DAQ_MANY_ARGTYPES
+    _ref_libs[variant] = lib
     return lib
 
 
@@ -112,6 +159,55 @@ def propagate(packed, photons, seed, photon_id_base=0, max_steps=10, use_weights
     if rc != 0:
         raise RuntimeError('oracle_propagate failed (%d)' % rc)
     return hp.photons(), hp.rng_counters, stats.as_dict()
+
+
+def ref_propagate(packed, photons, seed, photon_id_base=0, max_steps=10, use_weights=False, scatter_first=0,
+                  rng_counters=None, variant='contract'):
+    """``propagate`` through the reference's own kernel and its host loop (ref_phys_propagate).  Returns
+    (Photons, rng_counters, {'launches': n})."""
+    lib = load_ref_physics(variant)
+    hp = HostPhotons(photons, rng_counters=rng_counters)
+    launches = c_uint64(0)
+    rc = lib.ref_phys_propagate(ctypes.byref(packed.desc), ctypes.byref(hp.struct), hp.n, _abi.Rng(int(seed), int(photon_id_base)),
+                                int(max_steps), int(bool(use_weights)), int(scatter_first), ctypes.byref(launches))
+    if rc != 0:
+        raise RuntimeError('ref_phys_propagate failed (%d)' % rc)
+    return hp.photons(), hp.rng_counters, {'launches': launches.value}
+
+
+SINGLE = {'rayleigh_scatter': 0, 'propagate_at_boundary': 1, 'specular_reflector': 2, 'diffuse_reflector': 3,
+          'propagate_at_surface': 4, 'propagate_to_boundary': 5}
+
+
+def _single(fn, packed, which, photon, seed, photon_id, counter, normal, n1, n2, absorption_length, scattering_length,
+            material1, surface_index, distance_to_boundary, use_weights, scatter_first):
+    hp = HostPhotons(photon, rng_counters=[counter])
+    assert hp.n == 1
+    nrm = (c_float * 3)(*[float(x) for x in normal])
+    command = fn(ctypes.byref(packed.desc), ctypes.byref(hp.struct), _abi.Rng(int(seed), int(photon_id)), SINGLE[which], nrm,
+                 float(n1), float(n2), float(absorption_length), float(scattering_length), int(material1), int(surface_index),
+                 float(distance_to_boundary), int(bool(use_weights)), int(scatter_first))
+    if command <= -100:
+        raise RuntimeError('single routine %s refused its arguments (%d)' % (which, command))
+    return hp.photons(), int(hp.rng_counters[0]), command
+
+
+def single(packed, which, photon, seed=0, photon_id=0, counter=0, normal=(0.0, 0.0, 1.0), n1=1.0, n2=1.0,
+           absorption_length=1.0, scattering_length=1.0, material1=0, surface_index=-1, distance_to_boundary=0.0,
+           use_weights=False, scatter_first=0, variant='contract'):
+    """ONE call of one physics routine (a name of ``SINGLE``) of the oracle on a one-photon ``photon`` with an explicit
+    State; the stream is (seed, photon_id) at ``counter``.  Returns (Photons, counter afterwards, command), command
+    being BREAK 0 / CONTINUE 1 / PASS 2, or -1 for the two routines that return nothing."""
+    return _single(load(variant).oracle_single, packed, which, photon, seed, photon_id, counter, normal, n1, n2, absorption_length,
+                   scattering_length, material1, surface_index, distance_to_boundary, use_weights, scatter_first)
+
+
+def ref_single(packed, which, photon, seed=0, photon_id=0, counter=0, normal=(0.0, 0.0, 1.0), n1=1.0, n2=1.0,
+               absorption_length=1.0, scattering_length=1.0, material1=0, surface_index=-1, distance_to_boundary=0.0,
+               use_weights=False, scatter_first=0, variant='contract'):
+    """``single`` through the reference's own routine (ref_phys_single)."""
+    return _single(load_ref_physics(variant).ref_phys_single, packed, which, photon, seed, photon_id, counter, normal, n1, n2,
+                   absorption_length, scattering_length, material1, surface_index, distance_to_boundary, use_weights, scatter_first)
 
 
 def distance_to_mesh(packed, origins, directions, variant='contract', last_hits=None):
@@ -163,12 +259,12 @@ def daq_state(nwords):
 
 
 def run_daq(packed, photons, tables_host, charge_unit, seed, photon_id_base=0, acquisition=0, weight=1.0,
-            start_photon=0, nphotons=None, variant='contract', state=None):
-    """run_daq on HOST arrays.  ``tables_host`` = (time_cdf_x, time_cdf_y, charge_cdf_x, charge_cdf_y) float32
+            start_photon=0, nphotons=None, variant='contract', state=None, reference=False):
+    """run_daq on HOST arrays (``reference``: through the reference's own kernel, ref_phys_run_daq).  ``tables_host`` = (time_cdf_x, time_cdf_y, charge_cdf_x, charge_cdf_y) float32
     arrays of equal pairwise length.  Returns (earliest_time float32, charge float32, histories uint32, hit mask).
     ``state``: the three arrays of ``daq_state`` to acquire ONTO, in place (a second acquire without a reset);
     None: fresh ones."""
-    lib = load(variant)
+    fn = load_ref_physics(variant).ref_phys_run_daq if reference else load(variant).oracle_run_daq
     hp = HostPhotons(photons)
     tx, ty, qx, qy = [np.ascontiguousarray(a, dtype=np.float32) for a in tables_host]
     tab = _abi.DaqTables(tx.ctypes.data, ty.ctypes.data, len(tx), qx.ctypes.data, qy.ctypes.data, len(qx), float(charge_unit))
@@ -177,19 +273,19 @@ def run_daq(packed, photons, tables_host, charge_unit, seed, photon_id_base=0, a
     assert all(a.dtype == np.uint32 and a.flags['C_CONTIGUOUS'] and len(a) >= nch for a in (t_int, q_int, hist))
     if nphotons is None:
         nphotons = hp.n - start_photon
-    lib.oracle_run_daq(ctypes.byref(packed.desc), ctypes.byref(tab), int(start_photon), int(nphotons), event.SURFACE_DETECT,
-                       ctypes.byref(hp.struct), _abi.Rng(int(seed), int(photon_id_base)), int(acquisition), float(weight),
-                       t_int.ctypes.data, q_int.ctypes.data, hist.ctypes.data)
+    fn(ctypes.byref(packed.desc), ctypes.byref(tab), int(start_photon), int(nphotons), event.SURFACE_DETECT,
+       ctypes.byref(hp.struct), _abi.Rng(int(seed), int(photon_id_base)), int(acquisition), float(weight),
+       t_int.ctypes.data, q_int.ctypes.data, hist.ctypes.data)
     t = t_int.view(np.float32)
     return t, (q_int.astype(np.float32) * np.float32(charge_unit)).astype(np.float32), hist, t < 1e8
 
 
 def run_daq_many(packed, photons, tables_host, charge_unit, seed, ndaq, photon_id_base=0, acquisition=0, weight=1.0,
-                 start_photon=0, nphotons=None, variant='contract', state=None, channel_stride=None):
-    """run_daq_many on HOST arrays: ``ndaq`` acquisitions side by side (copy i = entries [i*stride, (i+1)*stride),
+                 start_photon=0, nphotons=None, variant='contract', state=None, channel_stride=None, reference=False):
+    """run_daq_many on HOST arrays (``reference``: through the reference's own kernel, ref_phys_run_daq_many): ``ndaq`` acquisitions side by side (copy i = entries [i*stride, (i+1)*stride),
     ``channel_stride`` = nchannels unless given).  Returns (earliest_time float32, charge float32, histories uint32,
     hit mask), each of ndaq * stride entries.  ``state``: as in ``run_daq``, arrays of at least ndaq * stride words."""
-    lib = load(variant)
+    fn = load_ref_physics(variant).ref_phys_run_daq_many if reference else load(variant).oracle_run_daq_many
     hp = HostPhotons(photons)
     tx, ty, qx, qy = [np.ascontiguousarray(a, dtype=np.float32) for a in tables_host]
     tab = _abi.DaqTables(tx.ctypes.data, ty.ctypes.data, len(tx), qx.ctypes.data, qy.ctypes.data, len(qx), float(charge_unit))
@@ -199,9 +295,9 @@ def run_daq_many(packed, photons, tables_host, charge_unit, seed, ndaq, photon_i
     assert all(a.dtype == np.uint32 and a.flags['C_CONTIGUOUS'] and len(a) >= nch * ndaq for a in (t_int, q_int, hist))
     if nphotons is None:
         nphotons = hp.n - start_photon
-    lib.oracle_run_daq_many(ctypes.byref(packed.desc), ctypes.byref(tab), int(start_photon), int(nphotons), event.SURFACE_DETECT,
-                            ctypes.byref(hp.struct), _abi.Rng(int(seed), int(photon_id_base)), int(acquisition), float(weight),
-                            int(ndaq), int(nch), t_int.ctypes.data, q_int.ctypes.data, hist.ctypes.data)
+    fn(ctypes.byref(packed.desc), ctypes.byref(tab), int(start_photon), int(nphotons), event.SURFACE_DETECT,
+       ctypes.byref(hp.struct), _abi.Rng(int(seed), int(photon_id_base)), int(acquisition), float(weight),
+       int(ndaq), int(nch), t_int.ctypes.data, q_int.ctypes.data, hist.ctypes.data)
     t = t_int.view(np.float32)
     return t, (q_int.astype(np.float32) * np.float32(charge_unit)).astype(np.float32), hist, t < 1e8
 

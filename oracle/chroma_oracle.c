@@ -13,8 +13,8 @@
  * (0,1] the way curand_uniform does (include/chroma_math.h); draws are taken in
  * exactly the order the reference takes them.
  *
- * PARITY PIN STATUS (the reference's own sources compiled for gfx950 by oracle/Makefile into oracle/_ref,
- * from where they lie, nothing copied; the tests run on the GPU box)
+ * PARITY PIN STATUS (the reference's own sources compiled by oracle/Makefile into oracle/_ref -- for gfx950, the physics
+ * and the DAQ for the host -- from where they lie, nothing copied)
  *   - ray cast (intersect_mesh / intersect_box / intersect_triangle / get_node, with last_hit_triangle and
  *     with rays through vertices and edges, where the reference's test order decides): PINNED on
  *     chroma/cuda/mesh.h (tests/test_gpu_ref_mesh.py).
@@ -24,11 +24,17 @@
  *   - render: PINNED on chroma/cuda/render.cu (tests/test_gpu_render.py).
  *   - host tables, meshes, spiral, flatten: PINNED on vectors made by importing the reference's NumPy modules
  *     (tests/golden/ref_host_model.npz, tools/gen_golden.py).
- *   - physics (photon.h, random.h, cx.h) and daq.cu: the reference's device code needs curand_kernel.h and
- *     cuComplex.h, bvh.cu needs cuda.h; this image has none of them, so they are unbuildable here (no stand-in
- *     headers were written); the reference holds no golden vectors for them, only statistical tests
- *     (test/test_rayleigh.py, test/test_propagation.py, test/test_detector.py), which tests/ restate.  Bit-level
- *     parity of the physics with the CUDA reference is therefore UNPINNED ("parity unpinned").
+ *   - physics (photon.h:137-733, random.h, cx.h, the propagate kernel with the host loop of gpu/photon.py:225-252) and
+ *     daq.cu:35-150: PINNED on the reference's own propagate.cu and daq.cu, compiled for the HOST by g++ from where they
+ *     lie (oracle/ref_physics_driver.cc) over the project's stand-ins for the CUDA names (oracle/ref_shim: the language
+ *     words, curand_kernel.h, cuComplex.h), once against the host libm and once with the transcendental calls mapped onto
+ *     include/chroma_math.h.  tests/test_ref_physics_host.py: this file == the reference, libm against libm and contract
+ *     against contract, bit for bit in every photon field and draw counter -- full histories, the launch policy, entry
+ *     edges, each routine alone at its branch edges, run_daq and run_daq_many; no GPU needed.
+ *     tests/test_gpu_ref_physics.py: the HIP engine == the reference's contract build, this file not in the chain.
+ *     What stays the project's own contract on both sides, because the reference's has no counterpart here: the generator
+ *     (Philox for XORWOW), the mapping of a word to (0, 1], and the Box-Muller normal deviate of run_daq_many.
+ *   - bvh.cu needs cuda.h and a CUDA device: not built (the BVH builder is pinned on committed vectors).
  */
 #include <stdint.h>
 #include <stdlib.h>

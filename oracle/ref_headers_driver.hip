@@ -5,8 +5,9 @@
 // reference's own Material struct of geometry_types.h).  Each kernel below only loads arguments, calls
 // the reference function and stores what it returned.
 //
-// Still unbuildable here (no stand-ins are written): photon.h / random.h (curand_kernel.h), cx.h
-// (cuComplex.h), daq.cu (curand), bvh.cu (cuda.h) -- see DESIGN.md section 4.
+// The physics and the DAQ (propagate.cu + photon.h / random.h / cx.h, daq.cu) are pinned elsewhere: compiled for the
+// HOST over the stand-in headers of oracle/ref_shim by oracle/ref_physics_driver.cc.  bvh.cu (cuda.h) is not built --
+// see DESIGN.md section 4.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
