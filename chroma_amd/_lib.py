@@ -175,6 +175,10 @@ SIGNATURES = {
                                      Rng, c_uint32, c_float, c_void_p, c_void_p, c_void_p]),
     'chroma_daq_acquire_many': (c_int32, [c_void_p, c_void_p, POINTER(DaqTables), c_int32, c_int32, c_uint32, POINTER(PhotonArrays),
                                           Rng, c_uint32, c_float, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    'chroma_daq_acquire_events': (c_int32, [c_void_p, c_void_p, POINTER(DaqTables), c_uint32, c_void_p, c_uint32, POINTER(PhotonArrays),
+                                            c_uint32, Rng, c_uint32, c_float, c_uint32, c_void_p, c_void_p, c_void_p]),
+    'chroma_daq_compact_events': (c_int32, [c_void_p, c_uint32, c_uint32, c_uint32, c_float, c_void_p, c_void_p, c_void_p, c_uint64,
+                                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_uint64)]),
     'chroma_daq_convert': (c_int32, [c_void_p, c_uint32, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     'chroma_pdf_bin_hits': (c_int32, [c_void_p, c_uint32, c_int32, c_uint32, c_void_p, c_void_p, c_int32, c_float, c_float,
                                       c_int32, c_float, c_float, c_void_p, c_void_p]),

@@ -56,7 +56,7 @@ struct CallState {
     uint2 *coop_spill = nullptr;           // [rays in flight of the largest cooperative cast][COOP_SPILL]
     hipEvent_t ev_start = nullptr, ev_stop = nullptr, ev_mid = nullptr;
     hipStream_t aux_stream = nullptr;          // k_finalize_hits beside the tail kernel (launch_tail)
-    void *steps_scratch = nullptr; size_t steps_scratch_bytes = 0;     // chroma_steps_*: the source's tables, the counts, the scan's workspace
+    void *steps_scratch = nullptr; size_t steps_scratch_bytes = 0;     // chroma_steps_*: the source's tables, the counts, the scan's workspace; chroma_daq_*_events: the bounds, the flags and their scan
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     // ---- the settings: chroma_set_* and the CHROMA_* environment write them, a call reads them when it starts (CallPlan) ----
     int counting = 0;

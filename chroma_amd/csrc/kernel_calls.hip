@@ -397,6 +397,79 @@ int chroma_daq_acquire_many(chroma_ctx *ctx, chroma_geometry *geom, const chroma
     return CHROMA_OK;
 }
 
+int chroma_daq_acquire_events(chroma_ctx *ctx, chroma_geometry *geom, const chroma_daq_tables *tables, uint32_t nrows,
+                              const uint32_t *bounds, uint32_t detection_state, const chroma_photon_arrays *photons,
+                              uint32_t nphotons, chroma_rng rng, uint32_t acquisition, float global_weight,
+                              uint32_t channel_stride, uint32_t *d_earliest_time_int, uint32_t *d_channel_q_int,
+                              uint32_t *d_channel_histories)
+{
+    if (!ctx || !geom || !tables || !bounds || !d_earliest_time_int || !d_channel_q_int || !d_channel_histories)
+        return set_error(CHROMA_ERR_INVALID, "bad argument");
+    if (!geom->view.nsolids) return set_error(CHROMA_ERR_INVALID, "geometry has no detector channel map");
+    if (nrows < 1 || channel_stride < geom->view.nchannels)
+        return set_error(CHROMA_ERR_INVALID, "need at least one row and a channel stride of at least the number of channels");
+    if ((uint64_t)nrows * channel_stride > 0xffffffffull)
+        return set_error(CHROMA_ERR_INVALID, "%u rows of %u words: more than 32-bit word indices hold, pass fewer rows", nrows, channel_stride);
+    for (uint32_t r = 0; r < nrows; r++)
+        if (bounds[r] > bounds[r + 1]) return set_error(CHROMA_ERR_INVALID, "event bounds: bound %u is below bound %u", r + 1, r);
+    if (bounds[nrows] > nphotons || bounds[nrows] > 0x7fffffffu)
+        return set_error(CHROMA_ERR_INVALID, "event bounds: the last bound %u is beyond the %u photons of the set", bounds[nrows], nphotons);
+    if (tables->time_cdf_len < 2 || tables->charge_cdf_len < 2 || !tables->d_time_cdf_x || !tables->d_time_cdf_y ||
+        !tables->d_charge_cdf_x || !tables->d_charge_cdf_y || !(tables->charge_unit > 0.0f))
+        return set_error(CHROMA_ERR_INVALID, "DAQ tables: need two CDFs of at least 2 points and a positive charge unit");
+    int rc = check_photons(photons, false); if (rc) return rc;
+    const uint32_t window = bounds[nrows] - bounds[0];
+    if (window == 0) return CHROMA_OK;
+    const CallScope scope(ctx);
+    rc = steps_block(scope, round256(((size_t)nrows + 1) * sizeof(uint32_t))); if (rc) return rc;
+    uint32_t *d_bounds = (uint32_t *)scope.state().steps_scratch;
+    HIP_TRY(hipMemcpyAsync(d_bounds, bounds, ((size_t)nrows + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));          // (the caller's bounds are his again when the call returns)
+    hipLaunchKernelGGL(k_run_daq_events, dim3((window + DAQ_EVENTS_BLOCK - 1) / DAQ_EVENTS_BLOCK), dim3(DAQ_EVENTS_BLOCK), 0, ctx->stream,
+                       geom->view, *tables, nrows, d_bounds, detection_state, photons->t, photons->flags, photons->last_hit_triangles,
+                       photons->weights, rng.seed, rng.photon_id_base, acquisition, global_weight, channel_stride,
+                       d_earliest_time_int, d_channel_q_int, d_channel_histories);
+    HIP_TRY(hipGetLastError());
+    return CHROMA_OK;
+}
+
+int chroma_daq_compact_events(chroma_ctx *ctx, uint32_t nrows, uint32_t nchannels, uint32_t channel_stride, float charge_unit,
+                              const uint32_t *d_earliest_time_int, const uint32_t *d_channel_q_int,
+                              const uint32_t *d_channel_histories, uint64_t capacity, uint32_t *d_offsets, int32_t *d_channel,
+                              float *d_t, float *d_q, uint32_t *d_flags, uint64_t *ntouched)
+{
+    if (!ctx || !d_earliest_time_int || !d_channel_q_int || !d_channel_histories || !d_offsets || !ntouched ||
+        (capacity && (!d_channel || !d_t || !d_q || !d_flags)))
+        return set_error(CHROMA_ERR_INVALID, "bad argument");
+    *ntouched = 0;
+    if (nrows < 1 || nchannels < 1 || channel_stride < nchannels)
+        return set_error(CHROMA_ERR_INVALID, "need at least one row, one channel and a channel stride of at least the number of channels");
+    if ((uint64_t)nrows * channel_stride > 0xffffffffull || (uint64_t)nrows * nchannels >= 0x7fffffffull)
+        return set_error(CHROMA_ERR_INVALID, "%u rows of %u words: more than the scan's 31-bit count holds, pass fewer rows", nrows, channel_stride);
+    const CallScope scope(ctx);
+    const uint32_t nwords = nrows * nchannels, nflags = nwords + 1;
+    size_t scan_bytes = 0;
+    { uint32_t *nul = nullptr; HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, nul, nul, (int)nflags, ctx->stream)); }
+    const size_t flag_bytes = round256((size_t)nflags * sizeof(uint32_t));
+    int rc = steps_block(scope, flag_bytes + round256(scan_bytes)); if (rc) return rc;
+    uint32_t *d_positions = (uint32_t *)scope.state().steps_scratch;          // the flags, then (in place) their exclusive sum
+    void *d_scan = (char *)scope.state().steps_scratch + flag_bytes;
+    const dim3 grid((nflags + 255) / 256), block(256);
+    hipLaunchKernelGGL(k_daq_events_flag, grid, block, 0, ctx->stream, nwords, nchannels, channel_stride, d_channel_histories, d_positions);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_scan, scan_bytes, d_positions, d_positions, (int)nflags, ctx->stream));
+    hipLaunchKernelGGL(k_daq_events_scatter, grid, block, 0, ctx->stream, nwords, nchannels, channel_stride, charge_unit,
+                       d_earliest_time_int, d_channel_q_int, d_channel_histories, d_positions, capacity, d_offsets, d_channel,
+                       (uint32_t *)d_t, d_q, d_flags);
+    HIP_TRY(hipGetLastError());
+    uint32_t total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, d_positions + nwords, sizeof(total), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    *ntouched = total;
+    if (total > capacity) return set_error(CHROMA_ERR_INVALID, "room for %llu touched words, the state holds %u", (unsigned long long)capacity, total);
+    return CHROMA_OK;
+}
+
 int chroma_daq_convert(chroma_ctx *ctx, uint32_t nchannels, float charge_unit, const uint32_t *d_earliest_time_int,
                        const uint32_t *d_channel_q_int, float *d_earliest_time, float *d_channel_q)
 {

@@ -74,6 +74,7 @@ class Simulation(object):
         self.gpu_geometry = make(detector, packed=packed)
         if hasattr(detector, 'num_channels'):
             self.gpu_daq = gpu.GPUDaq(self.gpu_geometry)
+        self._gpu_event_daq = None           # the GPUEventDaq of simulate(run_daq=True), made on first use
         self._lanes = [(self.context, self.gpu_geometry)]
         for _ in range(1, self.nlanes):
             ctx = gpu.tools.Context(self.context.device_id)
@@ -141,6 +142,14 @@ class Simulation(object):
             else:
                 cuts = np.searchsorted(batch_hits.evidx, np.arange(len(batch_events) + 1))
                 per_event_hits = [batch_hits[a:b] for a, b in zip(cuts[:-1], cuts[1:])]
+        event_channels = None
+        if run_daq and hasattr(self, 'gpu_daq') and self.gpu_geometry.nchannels > 0:
+            # the events' acquisitions as ONE (GPUEventDaq: a row of channels per event, read back sparse), numbered as the
+            # reference's one acquisition per event (chroma/sim.py:128-137) numbers them: on from self.gpu_daq's counter
+            if self._gpu_event_daq is None:
+                self._gpu_event_daq = gpu.GPUEventDaq(self.gpu_geometry)
+            event_channels = self._gpu_event_daq.acquire(gpu_photons, self.rng_states, bounds, acquisition=self.gpu_daq.acquisition)
+            self.gpu_daq.acquisition += len(batch_events)
         for i, (ev, lo, hi) in enumerate(zip(batch_events, bounds[:-1], bounds[1:])):
             if not keep_photons_beg:
                 ev.photons_beg = None
@@ -169,8 +178,10 @@ class Simulation(object):
                     ev.hits = {c: ev_hits[a:b] for c, a, b in zip(ch[first].tolist(), first.tolist(), last.tolist())}
                 if keep_flat_hits:
                     ev.flat_hits = ev_hits
-            if hasattr(self, 'gpu_daq') and run_daq:
-                # one acquisition per event, as the reference (chroma/sim.py:128-137)
+            if event_channels is not None:
+                ev.channels = event_channels[i]
+            elif hasattr(self, 'gpu_daq') and run_daq:
+                # (a detector without channels: one acquisition per event, as the reference, chroma/sim.py:128-137)
                 self.gpu_daq.begin_acquire()
                 self.gpu_daq.acquire(gpu_photons, self.rng_states, start_photon=int(lo), nphotons=int(hi - lo),
                                      nthreads_per_block=self.nthreads_per_block, max_blocks=self.max_blocks)

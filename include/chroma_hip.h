@@ -381,6 +381,34 @@ int chroma_daq_acquire_many(chroma_ctx *ctx, chroma_geometry *geom, const chroma
                             const chroma_photon_arrays *photons, chroma_rng rng, uint32_t acquisition,
                             float global_weight, int32_t ndaq, int32_t channel_stride,
                             uint32_t *d_earliest_time_int, uint32_t *d_channel_q_int, uint32_t *d_channel_histories);
+/* The per-event acquisitions of a batch as ONE launch: `nrows` events given as nrows + 1 ascending photon
+ * bounds (a HOST array; row r is the photons [bounds[r], bounds[r + 1]), empty rows allowed, bounds[0]
+ * need not be 0 nor bounds[nrows] the end of the set of `nphotons` photons).  A photon of row r does what
+ * chroma_daq_acquire does for it in the acquisition numbered `acquisition + r` -- the same rejects, the
+ * same three draws from Philox stream 1 + acquisition + r, no jitter -- into word r * channel_stride +
+ * channel of the three arrays (nrows * channel_stride words each, accumulated into: reset them first).
+ * Word for word what nrows chroma_daq_acquire calls onto nrows separate states leave.  Bounds that
+ * descend or end beyond `nphotons`, nrows < 1 and channel_stride < nchannels are CHROMA_ERR_INVALID before
+ * anything is launched. */
+int chroma_daq_acquire_events(chroma_ctx *ctx, chroma_geometry *geom, const chroma_daq_tables *tables,
+                              uint32_t nrows, const uint32_t *bounds, uint32_t detection_state,
+                              const chroma_photon_arrays *photons, uint32_t nphotons, chroma_rng rng,
+                              uint32_t acquisition, float global_weight, uint32_t channel_stride,
+                              uint32_t *d_earliest_time_int, uint32_t *d_channel_q_int,
+                              uint32_t *d_channel_histories);
+/* The touched words of such a state -- history != 0: an accepted photon always carries the detection
+ * flag, so these are exactly the (row, channel) pairs any accepted photon reached, those whose time is
+ * still the reset value included -- in (row, channel) order: row r is the entries [d_offsets[r],
+ * d_offsets[r + 1]) (d_offsets: nrows + 1 words) of d_channel, d_t (the time bits as they are), d_q
+ * (charge count * charge_unit, as chroma_daq_convert) and d_flags, arrays of `capacity` entries.  The
+ * order comes from a scan, not from an atomic: the output is deterministic.  *ntouched: the number of
+ * touched words (never more than the photons acquired, nor than nrows * nchannels); beyond `capacity`
+ * nothing is written and the call is CHROMA_ERR_INVALID.  Returns when the arrays are written. */
+int chroma_daq_compact_events(chroma_ctx *ctx, uint32_t nrows, uint32_t nchannels, uint32_t channel_stride,
+                              float charge_unit, const uint32_t *d_earliest_time_int,
+                              const uint32_t *d_channel_q_int, const uint32_t *d_channel_histories,
+                              uint64_t capacity, uint32_t *d_offsets, int32_t *d_channel, float *d_t,
+                              float *d_q, uint32_t *d_flags, uint64_t *ntouched);
 /* `convert_sortable_int_to_float` + `convert_charge_int_to_float` (daq.cu:152-173) */
 int chroma_daq_convert(chroma_ctx *ctx, uint32_t nchannels, float charge_unit, const uint32_t *d_earliest_time_int,
                        const uint32_t *d_channel_q_int, float *d_earliest_time, float *d_channel_q);
