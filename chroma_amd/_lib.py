@@ -168,6 +168,10 @@ SIGNATURES = {
                                         c_int32, c_int32, c_int32, POINTER(PropagateStats), POINTER(c_int32), POINTER(HitsRequest)]),
     'chroma_propagate_opt': (c_int32, [c_void_p, c_void_p, POINTER(PhotonArrays), c_uint64, c_uint32, Rng, POINTER(PropagateOptions),
                                        POINTER(PropagateStats), POINTER(c_int32), POINTER(HitsRequest)]),
+    'chroma_propagate_tracks': (c_int32, [c_void_p, c_void_p, POINTER(PhotonArrays), c_uint64, c_uint32, Rng, POINTER(PropagateOptions),
+                                          POINTER(PropagateStats), POINTER(c_int32), POINTER(c_void_p), POINTER(c_uint64)]),
+    'chroma_tracks_gather': (c_int32, [c_void_p, c_void_p, POINTER(PhotonArrays), c_void_p]),
+    'chroma_tracks_destroy': (c_int32, [c_void_p, c_void_p]),
     'chroma_channel_hits': (c_int32, [c_void_p, c_void_p, c_uint64, c_uint32, POINTER(PhotonArrays),
                                       c_void_p, c_void_p]),
     'chroma_daq_reset': (c_int32, [c_void_p, c_float, c_uint32, c_void_p, c_void_p, c_void_p]),

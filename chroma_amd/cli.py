@@ -5,8 +5,8 @@ GEANT4 and writes a ROOT file; neither GEANT4 nor ROOT is part of this engine, s
 keeps the command-line shape (detector string, -n/--nevents, -o/--output, -s/--seed, -j device)
 but the particle source is the isotropic photon bomb of chroma/benchmark.py:77-83 and the output is
 an ``.npz``: per event the flat hits (channel, t, wavelength, pos, flags), with --run-daq the channel
-times and charges, with --save-photons-beg/--save-photons-end the photons themselves and with --track
-every photon's state after each step.
+times and charges, with --save-photons-beg/--save-photons-end the photons themselves and with --track or
+--device-tracks every photon's state after each step.
 """
 import argparse
 import sys
@@ -49,6 +49,7 @@ def main(argv=None):
     ap.add_argument('--save-photons-beg', action='store_true', help='also write the initial photons of every event (bin/chroma-sim:51-53)')
     ap.add_argument('--save-photons-end', action='store_true', help='also write the final photons of every event (bin/chroma-sim:54-56)')
     ap.add_argument('--track', action='store_true', help='also write every photon\'s state after each step (Simulation(photon_tracking=True))')
+    ap.add_argument('--device-tracks', action='store_true', help='what --track writes, recorded on the device (Simulation(photon_tracking=\'device\'))')
     ap.add_argument('--exact', action='store_true', help='the reference\'s own traversal loop for every ray: its hit triangle on EVERY ray, several times slower (Simulation(exact=True))')
     ap.add_argument('--cache-dir', default=None, help='directory of the BVH cache (off by default)')
     args = ap.parse_args(argv)
@@ -61,7 +62,8 @@ def main(argv=None):
     t0 = time.time()
     detector = load_geometry_from_string(args.detector, cache_dir=args.cache_dir)
     print('geometry: %d triangles, BVH %d nodes (%.1f s)' % (len(detector.mesh.triangles), len(detector.bvh.nodes), time.time() - t0))
-    sim = Simulation(detector, seed=args.seed, cuda_device=args.device, geant4_processes=0, photon_tracking=args.track, exact=args.exact)
+    sim = Simulation(detector, seed=args.seed, cuda_device=args.device, geant4_processes=0,
+                     photon_tracking='device' if args.device_tracks else args.track, exact=args.exact)
     rng = np.random.default_rng(sim.seed)
     events = (bomb_event(args.nphotons, wl, pos, rng) for _ in range(args.nevents))
     out = {'nevents': np.array(args.nevents), 'nphotons': np.array(args.nphotons), 'seed': np.array(sim.seed)}
@@ -75,7 +77,13 @@ def main(argv=None):
             if ph is not None:
                 for name in ('pos', 'dir', 'pol', 'wavelengths', 't', 'flags', 'last_hit_triangles', 'weights'):
                     out['%s/%s/%s' % (key, tag, name)] = getattr(ph, name)
-        if args.track and getattr(ev, 'photon_tracks', None) is not None:
+        if args.device_tracks and getattr(ev, 'photon_tracks', None) is not None:
+            # the same keys straight from the flat rows (PhotonTracks)
+            tracks = ev.photon_tracks
+            out[key + '/track/photon'] = np.repeat(np.arange(len(tracks), dtype=np.uint32), tracks.steps_taken + 1)
+            for name in ('pos', 'dir', 't', 'flags'):
+                out['%s/track/%s' % (key, name)] = getattr(tracks.photons, name)
+        elif args.track and getattr(ev, 'photon_tracks', None) is not None:
             # one row per (photon, step): ragged tracks flattened, with the photon index beside them
             tracks = ev.photon_tracks
             out[key + '/track/photon'] = np.concatenate([np.full(len(tr), i, dtype=np.uint32) for i, tr in enumerate(tracks)]

@@ -18,6 +18,7 @@
 //   kernel_physics.h              k_physics
 //   kernels_working_set.h         k_load_working, k_store_working
 //   kernels_propagate_ends.h      the initial queue, the abort-flag reduction, k_finalize_hits
+//   kernels_tracks.h              k_track_row0, k_track_step, k_track_scatter*: the rows of chroma_propagate_tracks, between the steps
 //   kernels_distance.h            k_distance_to_mesh, and the fast path of chroma_intersect_mesh around k_raycast_quad
 //   kernels_locate.h              chroma_locate_materials: rays of one probe direction, the material from a ray's hit
 //   kernels_hybrid_render.h       the hybrid render: k_propagate's step functions, one lane per sample
@@ -73,6 +74,8 @@
 #include "kernels_working_set.h"
 
 #include "kernels_propagate_ends.h"
+
+#include "kernels_tracks.h"
 
 #include "kernels_distance.h"
 
@@ -248,6 +251,25 @@ static int stats_read(const CallScope &scope, chroma_propagate_stats *stats)
 // the timing events of one step, in the order they are recorded (EV_PER_STEP per step when a call times its kernels)
 enum { EV_STEP_BEGIN, EV_PACKET_BEGIN, EV_CAST_BEGIN, EV_CAST_END, EV_PHYSICS_END, EV_STEP_END, EV_PER_STEP };
 
+// The rows of one chroma_propagate_tracks call (kernels_tracks.h), all from the context's pool: row 0 of every photon, one slab
+// per step run, and the rows per photon that the call's last launch turns into offsets.
+struct chroma_tracks {
+    struct Slab { float4 *rows; uint32_t count; };
+    uint64_t nphotons = 0, nrows = 0;
+    float4 *rows0 = nullptr;               // [nphotons][4]
+    uint32_t *offsets = nullptr;           // [nphotons + 1] rows per photon while the call runs, their exclusive sum after it; [nphotons + 1] is k_track_step's cursor
+    std::vector<Slab> slabs;               // slab k: the rows of step k
+};
+
+static void tracks_release(chroma_ctx *ctx, chroma_tracks *tr)
+{
+    if (!tr) return;
+    for (const chroma_tracks::Slab &s : tr->slabs) chroma_free(ctx, s.rows);       // (parked until the stream has passed this point)
+    chroma_free(ctx, tr->rows0);
+    chroma_free(ctx, tr->offsets);
+    delete tr;
+}
+
 namespace { struct PropagateCall; }
 // *d_order: nullptr (the call takes its photons as they come) or a chroma_malloc'ed permutation to free after k_load_working
 static int propagate_order(PropagateCall &call, uint32_t **d_order);
@@ -273,6 +295,7 @@ struct PropagateCall {
     chroma_propagate_stats acc;        // launches and kernel times so far
     long long n_upper;                 // bounds the live photons: sizes the grids
     bool finalized;                    // k_finalize_hits has run already, beside the tail kernel (launch_tail)
+    chroma_tracks *tracks;             // chroma_propagate_tracks: where the call records its rows, else NULL
 
     hipEvent_t *events(int step) const { return opt.time_kernels ? cs.step_events.data() + EV_PER_STEP * step : nullptr; }
 
@@ -296,11 +319,12 @@ struct PropagateCall {
         return CHROMA_OK;
     }
 
-    // (with weights the reference runs ALL steps in one launch: every count is "few")
+    // (with weights the reference runs ALL steps in one launch: every count is "few"; when it tracks, one step per launch
+    //  to the end, also with weights -- chroma/gpu/photon.py:218-238 --: no count is)
     void launch_step_begin(uint32_t first_n)
     {
         hipLaunchKernelGGL(k_step_begin, dim3(1), dim3(1), 0, ctx->stream, in_q, out_q, cs.d_step,
-                           opt.use_weights ? 0xFFFFFFFFu : (uint32_t)(PROP_BLOCK * 16 * 8), first_n);
+                           tracks ? 0u : opt.use_weights ? 0xFFFFFFFFu : (uint32_t)(PROP_BLOCK * 16 * 8), first_n);
     }
 
     // k_physics for one pass of a step.  `fixup`: 0 the main pass over every slot, 1 the slots k_raycast_retry has walked again
@@ -555,6 +579,85 @@ struct PropagateCall {
         HIP_TRY(hipStreamSynchronize(ctx->stream));
         acc.launches += ((const StepState *)cs.h_step)->launches;
         return opt.time_kernels ? read_step_times(step, tail_step) : CHROMA_OK;
+    }
+
+    // The step loop of a call that records tracks: the reference's tracking loop (chroma/gpu/photon.py:218-238) -- one step per
+    // launch, every one re-normalising, the survivor count read after each -- with the rows taken on the device between the
+    // steps.  Row 0 before anything moves; then per step a slab the size of its input queue from the pool, the step, and
+    // k_track_step behind its last launch; at the end the rows per photon summed into offsets.
+    // the photons still alive (the input working set as it stands) back to the caller's arrays
+    void store_working()
+    {
+        const unsigned blocks = (unsigned)std::min<long long>((n_upper + 255) / 256, 4096);
+        hipLaunchKernelGGL(k_store_working, dim3(std::max(blocks, 1u)), dim3(256), 0, ctx->stream, geom->view, pv, in_q, work_in);
+    }
+
+    int run_tracked_steps(uint64_t max_rows)
+    {
+        chroma_tracks &tr = *tracks;
+        const int max_steps = std::max(opt.max_steps, 0);
+        const unsigned tblocks = (unsigned)std::min<uint64_t>((nphotons + TRACK_BLOCK - 1) / TRACK_BLOCK, 4096);
+        hipLaunchKernelGGL(k_track_row0, dim3(tblocks), dim3(TRACK_BLOCK), 0, ctx->stream, pv, (uint64_t)nphotons, tr.rows0, tr.offsets,
+                           (uint32_t)max_steps + 1u, max_steps >= 1 ? 2u : 1u);
+        HIP_TRY(hipGetLastError());
+        tr.nrows = nphotons;
+        int step = 0;
+        if (max_steps >= 1) {
+            HIP_TRY(hipMemsetAsync(cs.d_step, 0, sizeof(StepState), ctx->stream));
+            hipLaunchKernelGGL(k_set_word, dim3(1), dim3(1), 0, ctx->stream, in_q, 1u);
+            hipLaunchKernelGGL(k_set_word, dim3(1), dim3(1), 0, ctx->stream, out_q, 1u);
+            int rc = load_working(); if (rc) return rc;
+            const int nev = opt.time_kernels ? EV_PER_STEP * max_steps : 0;
+            while ((int)cs.step_events.size() < nev) { hipEvent_t e; HIP_TRY(hipEventCreate(&e)); cs.step_events.push_back(e); }
+            rc = scope.read_survivors(in_q, &n_upper); if (rc) return rc;
+            tr.nrows += nphotons - (uint64_t)n_upper;             // (the second row of the photons that were terminal already)
+            uint32_t *cursor = tr.offsets + nphotons + 1;
+            while (step < max_steps && n_upper > 0) {
+                const uint32_t n_in = (uint32_t)n_upper;
+                chroma_tracks::Slab slab = {nullptr, n_in};
+                // (the one thing that can stop a call between two steps: no room for the next step's rows, on the device or
+                //  under the caller's limit.  The live photons go back to the arrays first, so that the photons are what the
+                //  steps taken so far left them, draw counters included, and the caller can go on from there)
+                if (step == 0) {
+                    slab.rows = tr.slabs[0].rows;                 // (reserved before the first launch, for up to every photon)
+                    tr.slabs.clear();
+                    rc = CHROMA_OK;
+                } else if (tr.nrows + n_in > max_rows)
+                    rc = set_error(CHROMA_ERR_INVALID, "tracks: step %d would bring the call to %llu rows, more than the %llu of CHROMA_TRACKS_MAX_ROWS; %d steps were taken",
+                                   step, (unsigned long long)(tr.nrows + n_in), (unsigned long long)max_rows, step);
+                else
+                    rc = chroma_malloc(ctx, (size_t)n_in * 4 * sizeof(float4), (void **)&slab.rows);
+                if (rc) {
+                    store_working();
+                    hipStreamSynchronize(ctx->stream);
+                    return rc;
+                }
+                tr.slabs.push_back(slab);
+                HIP_TRY(hipMemsetAsync(cursor, 0, sizeof(uint32_t), ctx->stream));
+                rc = launch_split_step(step == 0 ? opt.scatter_first : 0, events(step), step == 0 ? (uint32_t)nphotons : 0u, false);
+                if (rc) return rc;
+                const unsigned blocks = (unsigned)std::min<uint64_t>(((uint64_t)n_in + TRACK_BLOCK - 1) / TRACK_BLOCK, 4096);
+                hipLaunchKernelGGL(k_track_step, dim3(blocks), dim3(TRACK_BLOCK), 0, ctx->stream, geom->view, pv, (const uint32_t *)in_q,
+                                   (const uint32_t *)out_q, (const float4 *)work_out, slab.rows, n_in, cursor, tr.offsets, (uint32_t)step);
+                HIP_TRY(hipGetLastError());
+                tr.nrows += n_in;
+                step++;
+                std::swap(in_q, out_q);
+                std::swap(work_in, work_out);
+                rc = scope.read_survivors(in_q, &n_upper); if (rc) return rc;
+            }
+            if (n_upper > 0) store_working();
+            HIP_TRY(hipMemcpyAsync(cs.h_step, cs.d_step, sizeof(StepState), hipMemcpyDeviceToHost, ctx->stream));
+        }
+        int rc = chroma_internal_exclusive_sum(ctx, tr.offsets, (uint32_t)nphotons + 1u); if (rc) return rc;
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        // (the caller sizes the arrays of chroma_tracks_gather by the host's count: the device's has to be the same)
+        uint32_t total = 0;
+        HIP_TRY(hipMemcpy(&total, tr.offsets + nphotons, sizeof total, hipMemcpyDeviceToHost));
+        if (total != tr.nrows)
+            return set_error(CHROMA_ERR_INTERNAL, "tracks: %u rows recorded where the step counts give %llu", total, (unsigned long long)tr.nrows);
+        if (max_steps >= 1) acc.launches += ((const StepState *)cs.h_step)->launches;
+        return opt.time_kernels ? read_step_times(step, -1) : CHROMA_OK;
     }
 
     // CHROMA_TAIL=fused: the lane-per-photon kernel with the reference's own launch shapes
@@ -961,6 +1064,102 @@ int chroma_propagate_opt(chroma_ctx *ctx, chroma_geometry *geom, const chroma_ph
 {
     if (!options) return set_error(CHROMA_ERR_INVALID, "bad argument");
     return propagate_impl(ctx, geom, photons, nphotons, ncopies, rng, *options, stats, aborted, hits);
+}
+
+// ---- photon tracks ------------------------------------------------------------------------------------------------------
+// A propagate call that also records every photon's track (kernels_tracks.h, PropagateCall::run_tracked_steps): the split step
+// loop with one re-normalising launch per step, no hits request and no final records.  Everything that can be refused is
+// refused before the first launch; what the call allocates as it goes (a slab per step) comes from the context's pool.
+int chroma_propagate_tracks(chroma_ctx *ctx, chroma_geometry *geom, const chroma_photon_arrays *photons, uint64_t nphotons,
+                            uint32_t ncopies, chroma_rng rng, const chroma_propagate_options *options,
+                            chroma_propagate_stats *stats, int32_t *aborted, chroma_tracks **tracks, uint64_t *nrows)
+{
+    if (!ctx || !geom || !options || !tracks || !nrows) return set_error(CHROMA_ERR_INVALID, "bad argument");
+    *tracks = nullptr; *nrows = 0;
+    int rc = check_photons(photons, true); if (rc) return rc;
+    const CallScope scope(ctx);
+    CallState &cs = scope.state();
+    const chroma_propagate_options &opt = *options;
+    if ((opt.tail >= 0 ? opt.tail : cs.tail_mode) == CHROMA_TAIL_FUSED)
+        return set_error(CHROMA_ERR_INVALID, "tracks are recorded between the steps of the split step loop: not with the fused tail");
+    CallPlan plan;
+    rc = make_plan(cs, geom, opt.walk, CHROMA_TAIL_SPLIT, opt.counting, &plan); if (rc) return rc;
+    plan.packet = plan.autosort = 0;
+    if (nphotons >= 0x7fffffffull) return set_error(CHROMA_ERR_INVALID, "at most 2^31-2 photons per call");
+    if (ncopies == 0 || nphotons % ncopies) return set_error(CHROMA_ERR_INVALID, "nphotons must be a multiple of ncopies");
+    const uint64_t max_steps = opt.max_steps > 0 ? (uint64_t)opt.max_steps : 0u;
+    if (nphotons * (max_steps + 1) > 0xFFFFFFFFull)
+        return set_error(CHROMA_ERR_INVALID, "%llu photons of up to %llu rows each: more than the 2^32-1 rows a call holds, pass fewer photons or steps",
+                         (unsigned long long)nphotons, (unsigned long long)(max_steps + 1));
+    // (CHROMA_TRACKS_MAX_ROWS: the rows a call may record -- 64 bytes of device memory each while it runs -- read at every call)
+    uint64_t max_rows = 0xFFFFFFFFull;
+    if (const char *e = getenv("CHROMA_TRACKS_MAX_ROWS")) max_rows = std::min<uint64_t>(max_rows, strtoull(e, nullptr, 10));
+    const uint64_t least_rows = nphotons * (max_steps > 0 ? 2u : 1u);          // (row 0, and one more for a photon alive or not)
+    if (least_rows > max_rows)
+        return set_error(CHROMA_ERR_INVALID, "%llu photons have at least %llu rows, more than the %llu of CHROMA_TRACKS_MAX_ROWS",
+                         (unsigned long long)nphotons, (unsigned long long)least_rows, (unsigned long long)max_rows);
+    if (aborted) *aborted = 0;
+    if (max_steps > 0 && nphotons > 0 && (rc = check_stack(geom))) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    chroma_tracks *tr = new chroma_tracks;
+    tr->nphotons = nphotons;
+    if (nphotons == 0) { *tracks = tr; return CHROMA_OK; }
+    rc = chroma_malloc(ctx, (size_t)nphotons * 4 * sizeof(float4), (void **)&tr->rows0);
+    if (rc == CHROMA_OK) rc = chroma_malloc(ctx, ((size_t)nphotons + 2) * sizeof(uint32_t), (void **)&tr->offsets);
+    if (rc == CHROMA_OK && max_steps > 0) {
+        // (the first step's slab too, for as many rows as there are photons: what fails for lack of memory before a step has
+        //  been taken fails here, before the first launch)
+        chroma_tracks::Slab first = {nullptr, 0u};
+        rc = chroma_malloc(ctx, (size_t)nphotons * 4 * sizeof(float4), (void **)&first.rows);
+        if (rc == CHROMA_OK) tr->slabs.push_back(first);
+    }
+    if (rc == CHROMA_OK && max_steps > 0) {
+        rc = ensure_queues(scope, nphotons);
+        if (rc == CHROMA_OK) rc = ensure_spill(scope, plan.spill);
+    }
+    if (rc == CHROMA_OK) {
+        PropagateCall call = {scope, cs, ctx, geom, plan, to_view(photons), rng, opt, nphotons, ncopies, cs.queue_a, cs.queue_b, cs.work_a, cs.work_b,
+                              cs.rays, cs.rays_b, nullptr, 0u};
+        call.n_upper = (long long)nphotons;
+        call.tracks = tr;
+        rc = call.run_tracked_steps(max_rows);
+        if (rc == CHROMA_OK) rc = call.finish(nullptr, stats, aborted);
+    }
+    if (rc != CHROMA_OK) { tracks_release(ctx, tr); return rc; }
+    *tracks = tr; *nrows = tr->nrows;
+    return CHROMA_OK;
+}
+
+int chroma_tracks_gather(chroma_ctx *ctx, chroma_tracks *tracks, const chroma_photon_arrays *dst, uint64_t *d_offsets)
+{
+    if (!ctx || !tracks || !d_offsets) return set_error(CHROMA_ERR_INVALID, "bad argument");
+    const CallScope scope(ctx);
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (tracks->nphotons == 0) {
+        HIP_TRY(hipMemsetAsync(d_offsets, 0, sizeof(uint64_t), ctx->stream));
+        return CHROMA_OK;
+    }
+    int rc = check_photons(dst, false); if (rc) return rc;
+    const PhotonView out = to_view(dst);
+    const uint64_t n = tracks->nphotons;
+    hipLaunchKernelGGL(k_track_scatter_row0, dim3((unsigned)std::min<uint64_t>((n + TRACK_BLOCK - 1) / TRACK_BLOCK, 4096)), dim3(TRACK_BLOCK), 0,
+                       ctx->stream, (const float4 *)tracks->rows0, n, (const uint32_t *)tracks->offsets, out, d_offsets);
+    for (size_t k = 0; k < tracks->slabs.size(); k++) {
+        const chroma_tracks::Slab &s = tracks->slabs[k];
+        if (!s.count) continue;
+        hipLaunchKernelGGL(k_track_scatter, dim3((unsigned)std::min<uint64_t>(((uint64_t)s.count + TRACK_BLOCK - 1) / TRACK_BLOCK, 4096)),
+                           dim3(TRACK_BLOCK), 0, ctx->stream, (const float4 *)s.rows, s.count, (uint32_t)k, n, (const uint32_t *)tracks->offsets, out);
+    }
+    HIP_TRY(hipGetLastError());
+    return CHROMA_OK;
+}
+
+int chroma_tracks_destroy(chroma_ctx *ctx, chroma_tracks *tracks)
+{
+    if (!ctx) return set_error(CHROMA_ERR_INVALID, "null ctx");
+    const CallScope scope(ctx);            // (not while another thread's chroma_tracks_gather reads the handle)
+    tracks_release(ctx, tracks);
+    return CHROMA_OK;
 }
 
 #if CHROMA_HYBRID_RENDER

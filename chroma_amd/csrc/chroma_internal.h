@@ -201,6 +201,8 @@ int chroma_internal_direction_order(chroma_ctx *ctx, const float *d_dir, uint32_
 // (bvh_device.hip) stable radix sort of n (key, value) pairs on bits [0, end_bit) of the keys; queued on the context's stream
 int chroma_internal_sort_pairs(chroma_ctx *ctx, const uint32_t *d_keys, uint32_t *d_keys_out, const uint32_t *d_values,
                                uint32_t *d_values_out, uint32_t n, int end_bit);
+// (kernel_calls.hip) exclusive sum of n counts, in place; queued on the context's stream
+int chroma_internal_exclusive_sum(chroma_ctx *ctx, uint32_t *d_counts, uint32_t n);
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -640,4 +640,21 @@ int chroma_generate_bomb(chroma_ctx *ctx, const chroma_photon_arrays *photons, u
     return CHROMA_OK;
 }
 
+// ---- an exclusive sum in place for the other translation units (chroma_propagate_tracks: rows per photon -> offsets) ----
+// Scratch from the context's pool, freed behind the stream's work.
+int chroma_internal_exclusive_sum(chroma_ctx *ctx, uint32_t *d_counts, uint32_t n)
+{
+    if (n == 0) return CHROMA_OK;
+    if (n >= 0x7fffffffu) return set_error(CHROMA_ERR_INVALID, "exclusive_sum: bad argument");
+    size_t tmp_bytes = 0;
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_counts, d_counts, (int)n, ctx->stream));
+    void *tmp = nullptr;
+    int rc = chroma_malloc(ctx, std::max<size_t>(tmp_bytes, 4), &tmp);
+    if (rc != CHROMA_OK) return rc;
+    const hipError_t e = hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, d_counts, d_counts, (int)n, ctx->stream);
+    chroma_free(ctx, tmp);                 // (parked behind the scan)
+    if (e != hipSuccess) return set_error((int)e, "exclusive_sum: %s", hipGetErrorString(e));
+    return CHROMA_OK;
+}
+
 }  // extern "C"

@@ -186,6 +186,51 @@ class GPUPhotons(object):
         return step_photon_ids, step_photons
 
     @profile_if_possible
+    def propagate_tracks(self, gpu_geometry, rng_states, max_steps=10, use_weights=False, scatter_first=0, exact=False, stats=None):
+        """``propagate`` that records every photon's track ON THE DEVICE (chroma_propagate_tracks) and returns the tracks as a
+        ``chroma_amd.tracks.PhotonTracks``: per photon -- the index in this set's arrays, copies included -- row 0, its state
+        before the first step, and one row for every step it entered, its state after that step (a photon that is terminal
+        already: two equal rows).  The rows are what ``PhotonTracks.from_steps(*self.propagate(track=True), len(self))`` gives,
+        bit for bit, and the photon set ends as ``propagate(track=True)`` leaves it.
+
+        As the reference's tracking mode (chroma/gpu/photon.py:218-238) this is one launch per step, also with
+        ``use_weights``: ``dir`` and ``pol`` are re-normalised at EVERY step.  That is not the untracked ``propagate``,
+        whose last < 8192 photons (and, with weights, all steps after the first) share one launch and skip it -- the
+        reference behaves the same way.  The steps run in the engine's step loop with the default ray cast (``exact=True``:
+        the reference's own traversal loop, as in ``propagate``); between them streaming kernels take the rows from the
+        working set, 64 bytes per row, so the cost follows the number of rows and no per-step array comes to the host."""
+        from chroma_amd.tracks import PhotonTracks
+        nphotons = self.pos.size
+        lib, ctx = self.ctx._lib, self.ctx
+        s = _structure(self)
+        st = _lib.PropagateStats()
+        aborted = ctypes.c_int32(0)
+        opt = _lib.PropagateOptions(max_steps, use_weights, scatter_first, False, walk=ctx.WALKS['literal'] if exact else -1)
+        handle, nrows = ctypes.c_void_p(), ctypes.c_uint64(0)
+        _lib.check(lib.chroma_propagate_tracks(ctx.handle, gpu_geometry.handle, ctypes.byref(s), nphotons, self.ncopies,
+                                               self._rng(rng_states), ctypes.byref(opt), ctypes.byref(st), ctypes.byref(aborted),
+                                               ctypes.byref(handle), ctypes.byref(nrows)))
+        try:
+            rows = _alloc_fields(int(nrows.value), ctx)
+            dst = _lib.PhotonArrays()
+            for name in _FIELDS:
+                setattr(dst, name, rows[name].ptr)
+            offsets = empty(nphotons + 1, np.uint64, ctx)
+            _lib.check(lib.chroma_tracks_gather(ctx.handle, handle, ctypes.byref(dst), offsets.ptr))
+            flat = event.Photons(_vec3_to_rows(rows['pos'].get()), _vec3_to_rows(rows['dir'].get()), _vec3_to_rows(rows['pol'].get()),
+                                 rows['wavelengths'].get(), rows['t'].get(), rows['last_hit_triangles'].get(), rows['flags'].get(),
+                                 rows['weights'].get(), rows['evidx'].get())
+            tracks = PhotonTracks(offsets.get(), flat)
+        finally:
+            _lib.check(lib.chroma_tracks_destroy(ctx.handle, handle))
+        if stats is not None:
+            for k, v in st.as_dict().items():
+                stats[k] = stats.get(k, 0) + v
+        if aborted.value:
+            print("WARNING: ABORTED PHOTONS", file=sys.stderr)
+        return tracks
+
+    @profile_if_possible
     def propagate_hits(self, gpu_detector, rng_states, max_steps=10, use_weights=False, scatter_first=0, target_flag=(0x1 << 2),
                        capacity=None, channel_arrays=None, stats=None, time_kernels=False, exact=False,
                        nthreads_per_block=64, max_blocks=1024, sort=False, device=False):

@@ -56,6 +56,12 @@ class Simulation(object):
         self.detector = detector
         self.nthreads_per_block = nthreads_per_block
         self.max_blocks = max_blocks
+        # ``photon_tracking``: True -- ev.photon_tracks is a list of Photons, one per photon, built on the host from the per-step
+        # copies of GPUPhotons.propagate(track=True) (the reference's way, chroma/sim.py:102-114); 'device' -- the tracks are
+        # recorded on the device (GPUPhotons.propagate_tracks) and ev.photon_tracks is a chroma_amd.tracks.PhotonTracks, the same
+        # sequence of Photons as slices of one flat array
+        if isinstance(photon_tracking, str) and photon_tracking != 'device':
+            raise ValueError("photon_tracking: False, True or 'device'")
         self.photon_tracking = photon_tracking
         self.seed = pick_seed() if seed is None else seed
         np.random.seed(self.seed % (2 ** 32))
@@ -115,7 +121,10 @@ class Simulation(object):
         is_detector = hasattr(self.detector, 'num_channels')
         want_hits = is_detector and (keep_hits or keep_flat_hits)
         batch_hits = tracking = None
-        if want_hits and not self.photon_tracking:
+        device_tracks = self.photon_tracking == 'device'
+        if device_tracks:
+            tracking = gpu_photons.propagate_tracks(geometry, self.rng_states, max_steps=max_steps, exact=self.exact)
+        elif want_hits and not self.photon_tracking:
             # propagate + get_flat_hits as one library call (chroma_propagate_hits): the same set of hits
             batch_hits = gpu_photons.propagate_hits(geometry, self.rng_states, max_steps=max_steps, exact=self.exact, sort=True)
         else:
@@ -153,7 +162,9 @@ class Simulation(object):
         for i, (ev, lo, hi) in enumerate(zip(batch_events, bounds[:-1], bounds[1:])):
             if not keep_photons_beg:
                 ev.photons_beg = None
-            if self.photon_tracking:
+            if device_tracks:
+                ev.photon_tracks = tracking.cut(int(lo), int(hi))
+            elif self.photon_tracking:
                 step_ids_list, step_photons_list = tracking
                 tracks = [[] for _ in range(hi - lo)]
                 for step_ids, step_photons in zip(step_ids_list, step_photons_list):

@@ -340,6 +340,38 @@ int chroma_propagate_opt(chroma_ctx *ctx, chroma_geometry *geom, const chroma_ph
                          const chroma_propagate_options *options,
                          chroma_propagate_stats *stats, int32_t *aborted, chroma_hits_request *hits);
 
+/* chroma_propagate_opt that also records every photon's TRACK, on the device (the reference's tracking mode,
+ * chroma/gpu/photon.py:218-238 and chroma/sim.py:102-114): row 0 of a photon is its state before the first step, and every step
+ * whose input queue holds it adds one row, its state after that step.  A photon that is terminal when the call starts is in the
+ * first step's queue and left untouched: two equal rows (one when max_steps <= 0).  Rows carry pos, dir, pol, wavelengths, t,
+ * flags, last_hit_triangles (a triangle id), weights and evidx.
+ * As in the reference's tracking mode every step is a launch of its own, also with use_weights, so dir and pol are
+ * re-normalised at every step (propagate.cu:248,250): the photons end as chroma_propagate_step driven with max_steps = 1 once
+ * per step leaves them -- which is NOT what chroma_propagate gives for the last < 8192 photons of a call, whose steps share
+ * one launch in the reference.  The call runs the split step loop (options->tail is taken as CHROMA_TAIL_SPLIT;
+ * CHROMA_TAIL_FUSED, in the options or as the context's setting, is CHROMA_ERR_INVALID), with any walk, without final records,
+ * and reads the survivor count after every step.
+ * Refused before anything is launched: nphotons * (max_steps + 1) above 2^32-1 rows, nphotons * 2 rows (the least a call
+ * with a step records) above $CHROMA_TRACKS_MAX_ROWS (CHROMA_ERR_INVALID), and no memory for rows 0, the row counts and the
+ * first step's rows (64 bytes per photon each, from the pool of chroma_malloc).  How many rows the LATER steps add is known
+ * only as they run: the rows of step k >= 1 are allocated when its photon count is known (64 bytes each), so a call can also
+ * fail BETWEEN two steps, for lack of memory or because the rows would exceed $CHROMA_TRACKS_MAX_ROWS (default: 2^32-1; read
+ * at every call).  It then stores the live photons back, returns the error and no tracks, and leaves the photon arrays
+ * and draw counters exactly as the steps taken so far left them (the message says how many): a caller may go on from there.
+ * *tracks: the rows, on the device, to hand to chroma_tracks_gather and chroma_tracks_destroy (NULL when the call fails);
+ * *nrows: how many there are.  Returns when the photon arrays and the rows are complete. */
+typedef struct chroma_tracks chroma_tracks;
+int chroma_propagate_tracks(chroma_ctx *ctx, chroma_geometry *geom, const chroma_photon_arrays *photons,
+                            uint64_t nphotons, uint32_t ncopies, chroma_rng rng,
+                            const chroma_propagate_options *options,
+                            chroma_propagate_stats *stats, int32_t *aborted, chroma_tracks **tracks, uint64_t *nrows);
+/* The rows per photon (CSR): d_offsets[0 .. nphotons] (device), and rows d_offsets[i] .. d_offsets[i + 1] of the arrays of `dst`
+ * (device, *nrows entries each; rng_counters is not written and may be NULL) are the track of photon i -- the index in the
+ * arrays of the call, copies included -- in step order.  Queued on the context's stream; may be called more than once. */
+int chroma_tracks_gather(chroma_ctx *ctx, chroma_tracks *tracks, const chroma_photon_arrays *dst, uint64_t *d_offsets);
+/* gives the rows back to the pool (behind the work queued on the context's stream); `tracks` may be NULL */
+int chroma_tracks_destroy(chroma_ctx *ctx, chroma_tracks *tracks);
+
 /* Per-channel reduction of detected photons: hit count and earliest hit time
  * (float bits, valid for t >= 0 as in chroma/cuda/daq.cu:5-20).  The arrays
  * (length nchannels, device) are ACCUMULATED into: zero / 0x7f800000-fill them first.
