@@ -101,6 +101,11 @@ class DaqTables(Structure):
                 ('charge_unit', c_float)]
 
 
+class DaqWindow(Structure):
+    """chroma_daq_window"""
+    _fields_ = [('t0', c_float), ('dt', c_float), ('nbins', c_uint32)]
+
+
 class LightSource(Structure):
     """chroma_light_source (host pointers)"""
     _fields_ = [('refractive_index', c_void_p), ('scintillation_cdf', c_void_p), ('time_cdf', c_void_p),
@@ -182,6 +187,11 @@ SIGNATURES = {
     'chroma_daq_acquire_events': (c_int32, [c_void_p, c_void_p, POINTER(DaqTables), c_uint32, c_void_p, c_uint32, POINTER(PhotonArrays),
                                             c_uint32, Rng, c_uint32, c_float, c_uint32, c_void_p, c_void_p, c_void_p]),
     'chroma_daq_compact_events': (c_int32, [c_void_p, c_uint32, c_uint32, c_uint32, c_float, c_void_p, c_void_p, c_void_p, c_uint64,
+                                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_uint64)]),
+    'chroma_daq_count_pulses': (c_int32, [c_void_p, c_void_p, POINTER(DaqTables), c_uint32, c_void_p, c_uint32, POINTER(PhotonArrays),
+                                          c_uint32, Rng, c_uint32, c_float, POINTER(DaqWindow), POINTER(c_uint64)]),
+    'chroma_daq_acquire_pulses': (c_int32, [c_void_p, c_void_p, POINTER(DaqTables), c_uint32, c_void_p, c_uint32, POINTER(PhotonArrays),
+                                            c_uint32, Rng, c_uint32, c_float, POINTER(DaqWindow), c_uint64, c_void_p, c_void_p, c_void_p,
                                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_uint64)]),
     'chroma_daq_convert': (c_int32, [c_void_p, c_uint32, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     'chroma_pdf_bin_hits': (c_int32, [c_void_p, c_uint32, c_int32, c_uint32, c_void_p, c_void_p, c_int32, c_float, c_float,

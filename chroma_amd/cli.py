@@ -5,7 +5,7 @@ GEANT4 and writes a ROOT file; neither GEANT4 nor ROOT is part of this engine, s
 keeps the command-line shape (detector string, -n/--nevents, -o/--output, -s/--seed, -j device)
 but the particle source is the isotropic photon bomb of chroma/benchmark.py:77-83 and the output is
 an ``.npz``: per event the flat hits (channel, t, wavelength, pos, flags), with --run-daq the channel
-times and charges, with --save-photons-beg/--save-photons-end the photons themselves and with --track or
+times and charges, with --daq-window T0,DT,NBINS also the pulses per (channel, time bin), with --save-photons-beg/--save-photons-end the photons themselves and with --track or
 --device-tracks every photon's state after each step.
 """
 import argparse
@@ -46,6 +46,8 @@ def main(argv=None):
     ap.add_argument('--pos', default='0,0,0')
     ap.add_argument('--max-steps', type=int, default=100)
     ap.add_argument('--run-daq', action='store_true')
+    ap.add_argument('--daq-window', default=None, metavar='T0,DT,NBINS',
+                    help='also write the time-binned DAQ: the pulses per (channel, bin) of NBINS bins of DT ns from T0 on (implies --run-daq)')
     ap.add_argument('--save-photons-beg', action='store_true', help='also write the initial photons of every event (bin/chroma-sim:51-53)')
     ap.add_argument('--save-photons-end', action='store_true', help='also write the final photons of every event (bin/chroma-sim:54-56)')
     ap.add_argument('--track', action='store_true', help='also write every photon\'s state after each step (Simulation(photon_tracking=True))')
@@ -59,6 +61,13 @@ def main(argv=None):
 
     wl = tuple(float(x) for x in args.wavelength.split(':')) if ':' in args.wavelength else float(args.wavelength)
     pos = [float(x) for x in args.pos.split(',')]
+    daq_window = None
+    if args.daq_window is not None:
+        parts = args.daq_window.split(',')
+        if len(parts) != 3:
+            ap.error('--daq-window takes T0,DT,NBINS')
+        daq_window = (float(parts[0]), float(parts[1]), int(parts[2]))
+        args.run_daq = True
     t0 = time.time()
     detector = load_geometry_from_string(args.detector, cache_dir=args.cache_dir)
     print('geometry: %d triangles, BVH %d nodes (%.1f s)' % (len(detector.mesh.triangles), len(detector.bvh.nodes), time.time() - t0))
@@ -71,7 +80,7 @@ def main(argv=None):
     nhits = 0
     for ev in sim.simulate(events, keep_photons_beg=args.save_photons_beg, keep_photons_end=args.save_photons_end,
                            keep_hits=False, keep_flat_hits=hasattr(detector, 'num_channels'),
-                           run_daq=args.run_daq, max_steps=args.max_steps):
+                           run_daq=args.run_daq, max_steps=args.max_steps, daq_window=daq_window):
         key = 'ev%d' % ev.id
         for tag, ph in (('photons_beg', ev.photons_beg), ('photons_end', ev.photons_end)):
             if ph is not None:
@@ -103,6 +112,13 @@ def main(argv=None):
             out[key + '/daq_hit'] = ev.channels.hit
             out[key + '/daq_t'] = ev.channels.t
             out[key + '/daq_q'] = ev.channels.q
+        if ev.pulses is not None:
+            out[key + '/pulse_channel'] = ev.pulses.channel
+            out[key + '/pulse_bin'] = ev.pulses.bin
+            out[key + '/pulse_npe'] = ev.pulses.npe
+            out[key + '/pulse_q'] = ev.pulses.q
+            out[key + '/pulse_t'] = ev.pulses.t_first
+            out[key + '/pulse_outside'] = np.array([ev.pulses.early, ev.pulses.late], dtype=np.uint32)
     dt = time.time() - t0
     np.savez_compressed(args.output, **out)
     print('%d events, %d photons, %d hits in %.2f s (%.1f events/s, %.3g photons/s) -> %s' % (

@@ -1,9 +1,10 @@
 // kernel_calls.hip -- the entry points that are the checks of their arguments around one kernel launch on the context's
 // stream, as the reference's kernels are called from Python: the photon-array calls, DAQ, PDFs, chroma_render, point
-// transforms, the probe, the bomb generator, the photons from particle steps.
+// transforms, the probe, the bomb generator, the photons from particle steps, the time-binned DAQ.
 #include <stdint.h>
 #include <string.h>
 #include <algorithm>
+#include <cmath>
 
 #include <hipcub/hipcub.hpp>
 
@@ -13,6 +14,8 @@
 #include "kernels_photons_hits.h"
 
 #include "kernels_daq_render.h"
+
+#include "kernels_daq_pulses.h"
 
 #include "kernels_pdf.h"
 
@@ -467,6 +470,166 @@ int chroma_daq_compact_events(chroma_ctx *ctx, uint32_t nrows, uint32_t nchannel
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     *ntouched = total;
     if (total > capacity) return set_error(CHROMA_ERR_INVALID, "room for %llu touched words, the state holds %u", (unsigned long long)capacity, total);
+    return CHROMA_OK;
+}
+
+// ---- the time-binned DAQ (kernels_daq_pulses.h) ----
+// what chroma_daq_acquire_events refuses, and the window's rules
+static int check_pulses_call(chroma_ctx *ctx, chroma_geometry *geom, const chroma_daq_tables *tables, uint32_t nrows, const uint32_t *bounds,
+                             const chroma_photon_arrays *photons, uint32_t nphotons, const chroma_daq_window *window)
+{
+    if (!ctx || !geom || !tables || !bounds || !window) return set_error(CHROMA_ERR_INVALID, "bad argument");
+    if (!geom->view.nsolids || !geom->view.nchannels) return set_error(CHROMA_ERR_INVALID, "geometry has no detector channel map");
+    if (nrows < 1) return set_error(CHROMA_ERR_INVALID, "need at least one row");
+    if (!(window->dt > 0.0f) || !std::isfinite(window->dt) || !std::isfinite(window->t0) || window->nbins < 1 || window->nbins > 65536)
+        return set_error(CHROMA_ERR_INVALID, "DAQ window: need a finite t0, a finite positive dt and 1 .. 65536 bins");
+    if ((uint64_t)nrows * geom->view.nchannels > 0x7fffffffffffffffull / window->nbins)
+        return set_error(CHROMA_ERR_INVALID, "%u rows of %u channels of %u bins: more than 63-bit keys hold, pass fewer rows", nrows,
+                         geom->view.nchannels, window->nbins);
+    for (uint32_t r = 0; r < nrows; r++)
+        if (bounds[r] > bounds[r + 1]) return set_error(CHROMA_ERR_INVALID, "event bounds: bound %u is below bound %u", r + 1, r);
+    if (bounds[nrows] > nphotons || bounds[nrows] > 0x7fffffffu)
+        return set_error(CHROMA_ERR_INVALID, "event bounds: the last bound %u is beyond the %u photons of the set", bounds[nrows], nphotons);
+    if (tables->time_cdf_len < 2 || tables->charge_cdf_len < 2 || !tables->d_time_cdf_x || !tables->d_time_cdf_y ||
+        !tables->d_charge_cdf_x || !tables->d_charge_cdf_y || !(tables->charge_unit > 0.0f))
+        return set_error(CHROMA_ERR_INVALID, "DAQ tables: need two CDFs of at least 2 points and a positive charge unit");
+    return check_photons(photons, false);
+}
+
+// The pooled block of a pulses call: the bounds first, then 256 bytes of counters, then what the caller lays out.  Grows the block to
+// `need` and puts the bounds there, unless this call has `placed` them already and the block need not grow.
+static int pulses_block(const CallScope &scope, size_t need, uint32_t nrows, const uint32_t *bounds, bool placed)
+{
+    const bool keep = placed && scope.state().steps_scratch_bytes >= need;
+    int rc = steps_block(scope, need); if (rc) return rc;
+    if (keep) return CHROMA_OK;
+    HIP_TRY(hipMemcpyAsync(scope.state().steps_scratch, bounds, ((size_t)nrows + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, scope.ctx->stream));
+    HIP_TRY(hipStreamSynchronize(scope.ctx->stream));          // (the caller's bounds are his again when the call returns)
+    return CHROMA_OK;
+}
+
+// the accepted in-window photons of the window (k_daq_pulses_count), with the bounds already in the block
+static int pulses_count(const CallScope &scope, chroma_geometry *geom, const chroma_daq_tables *tables, uint32_t nrows, uint32_t span,
+                        uint32_t detection_state, const chroma_photon_arrays *photons, chroma_rng rng, uint32_t acquisition,
+                        float global_weight, const chroma_daq_window *window, uint32_t *naccepted)
+{
+    hipStream_t stream = scope.ctx->stream;
+    const uint32_t *d_bounds = (const uint32_t *)scope.state().steps_scratch;
+    uint32_t *d_count = (uint32_t *)((char *)scope.state().steps_scratch + round256(((size_t)nrows + 1) * sizeof(uint32_t)));
+    HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(uint32_t), stream));
+    hipLaunchKernelGGL(k_daq_pulses_count, dim3((span + DAQ_PULSES_SPAN - 1) / DAQ_PULSES_SPAN), dim3(DAQ_PULSES_BLOCK), 0, stream, geom->view,
+                       *tables, *window, nrows, d_bounds, detection_state, photons->t, photons->flags, photons->last_hit_triangles,
+                       photons->weights, rng.seed, rng.photon_id_base, acquisition, global_weight, d_count);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(naccepted, d_count, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return CHROMA_OK;
+}
+
+int chroma_daq_count_pulses(chroma_ctx *ctx, chroma_geometry *geom, const chroma_daq_tables *tables, uint32_t nrows,
+                            const uint32_t *bounds, uint32_t detection_state, const chroma_photon_arrays *photons, uint32_t nphotons,
+                            chroma_rng rng, uint32_t acquisition, float global_weight, const chroma_daq_window *window,
+                            uint64_t *naccepted)
+{
+    if (!naccepted) return set_error(CHROMA_ERR_INVALID, "bad argument");
+    int rc = check_pulses_call(ctx, geom, tables, nrows, bounds, photons, nphotons, window); if (rc) return rc;
+    *naccepted = 0;
+    const uint32_t span = bounds[nrows] - bounds[0];
+    if (span == 0) return CHROMA_OK;
+    const CallScope scope(ctx);
+    rc = pulses_block(scope, round256(((size_t)nrows + 1) * sizeof(uint32_t)) + 256, nrows, bounds, false); if (rc) return rc;
+    uint32_t n = 0;
+    rc = pulses_count(scope, geom, tables, nrows, span, detection_state, photons, rng, acquisition, global_weight, window, &n);
+    *naccepted = n;
+    return rc;
+}
+
+int chroma_daq_acquire_pulses(chroma_ctx *ctx, chroma_geometry *geom, const chroma_daq_tables *tables, uint32_t nrows,
+                              const uint32_t *bounds, uint32_t detection_state, const chroma_photon_arrays *photons, uint32_t nphotons,
+                              chroma_rng rng, uint32_t acquisition, float global_weight, const chroma_daq_window *window,
+                              uint64_t capacity, uint32_t *d_offsets, int32_t *d_channel, uint32_t *d_bin, uint32_t *d_npe,
+                              uint32_t *d_q_int, float *d_t_first, uint32_t *d_flags, uint32_t *d_outside, uint64_t *npulses)
+{
+    if (!d_offsets || !d_outside || !npulses || (capacity && (!d_channel || !d_bin || !d_npe || !d_q_int || !d_t_first || !d_flags)))
+        return set_error(CHROMA_ERR_INVALID, "bad argument");
+    int rc = check_pulses_call(ctx, geom, tables, nrows, bounds, photons, nphotons, window); if (rc) return rc;
+    *npulses = 0;
+    hipStream_t stream = ctx->stream;
+    const size_t offsets_bytes = ((size_t)nrows + 1) * sizeof(uint32_t), outside_bytes = 2 * (size_t)nrows * sizeof(uint32_t);
+    const uint32_t span = bounds[nrows] - bounds[0];
+    if (span == 0) {
+        HIP_TRY(hipMemsetAsync(d_offsets, 0, offsets_bytes, stream));
+        HIP_TRY(hipMemsetAsync(d_outside, 0, outside_bytes, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        return CHROMA_OK;
+    }
+    const CallScope scope(ctx);
+    const size_t head_bytes = round256(offsets_bytes) + 256;          // the bounds and the counters (word 0: the count, then the emit's cursor)
+    rc = pulses_block(scope, head_bytes + round256(outside_bytes), nrows, bounds, false); if (rc) return rc;
+    uint32_t n = 0;
+    rc = pulses_count(scope, geom, tables, nrows, span, detection_state, photons, rng, acquisition, global_weight, window, &n); if (rc) return rc;
+    if (n >= 0x7fffffffu) return set_error(CHROMA_ERR_INVALID, "%u accepted photons: more than the scan's 31-bit count holds, pass fewer rows", n);
+    // the block: bounds, counters, the rows' early and late counts; then, per accepted photon, the keys and their positions before and
+    // behind the sort, charge count, time bits and history; the heads (n + 1); the workspaces of the sort and of the scan
+    const uint64_t nkeys = (uint64_t)nrows * geom->view.nchannels * window->nbins;
+    int end_bit = 1;
+    while (end_bit < 64 && ((nkeys - 1) >> end_bit)) end_bit++;
+    size_t sort_bytes = 0, scan_bytes = 0;
+    if (n) {
+        uint64_t *k = nullptr; uint32_t *v = nullptr;
+        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, k, k, v, v, (int)n, 0, end_bit, stream));
+        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, v, v, (int)(n + 1), stream));
+    }
+    const size_t key_bytes = round256((size_t)n * sizeof(uint64_t)), word_bytes = round256((size_t)n * sizeof(uint32_t));
+    const size_t need = head_bytes + round256(outside_bytes) + 2 * key_bytes + 5 * word_bytes + round256(((size_t)n + 1) * sizeof(uint32_t)) +
+                        round256(sort_bytes) + round256(scan_bytes);
+    rc = pulses_block(scope, need, nrows, bounds, true); if (rc) return rc;
+    char *p = (char *)scope.state().steps_scratch;
+    const uint32_t *d_bounds = (const uint32_t *)p; p += round256(offsets_bytes);
+    uint32_t *d_cursor = (uint32_t *)p + 1; p += 256;
+    uint32_t *d_rows_outside = (uint32_t *)p; p += round256(outside_bytes);
+    uint64_t *d_keys = (uint64_t *)p; p += key_bytes;
+    uint64_t *d_keys_sorted = (uint64_t *)p; p += key_bytes;
+    uint32_t *d_order = (uint32_t *)p; p += word_bytes;
+    uint32_t *d_order_sorted = (uint32_t *)p; p += word_bytes;
+    uint32_t *d_charge = (uint32_t *)p; p += word_bytes;
+    uint32_t *d_time = (uint32_t *)p; p += word_bytes;
+    uint32_t *d_history = (uint32_t *)p; p += word_bytes;
+    uint32_t *d_positions = (uint32_t *)p; p += round256(((size_t)n + 1) * sizeof(uint32_t));          // the heads, then (in place) their exclusive sum
+    void *d_sort = p; p += round256(sort_bytes);
+    void *d_scan = p;
+    HIP_TRY(hipMemsetAsync(d_cursor, 0, sizeof(uint32_t), stream));
+    HIP_TRY(hipMemsetAsync(d_rows_outside, 0, outside_bytes, stream));
+    hipLaunchKernelGGL(k_daq_pulses_emit, dim3((span + DAQ_PULSES_SPAN - 1) / DAQ_PULSES_SPAN), dim3(DAQ_PULSES_BLOCK), 0, stream, geom->view,
+                       *tables, *window, nrows, d_bounds, detection_state, photons->t, photons->flags, photons->last_hit_triangles,
+                       photons->weights, rng.seed, rng.photon_id_base, acquisition, global_weight, n, d_cursor, d_keys, d_order, d_charge,
+                       d_time, d_history, d_rows_outside);
+    HIP_TRY(hipGetLastError());
+    uint32_t total = 0;
+    if (n) {
+        const dim3 grid((n + 1 + DAQ_PULSES_BLOCK - 1) / DAQ_PULSES_BLOCK), block(DAQ_PULSES_BLOCK);
+        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(d_sort, sort_bytes, d_keys, d_keys_sorted, d_order, d_order_sorted, (int)n, 0, end_bit, stream));
+        hipLaunchKernelGGL(k_daq_pulses_heads, grid, block, 0, stream, n, d_keys_sorted, d_positions);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_scan, scan_bytes, d_positions, d_positions, (int)(n + 1), stream));
+        HIP_TRY(hipMemcpyAsync(&total, d_positions + n, sizeof(total), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        *npulses = total;
+        if (total > capacity) return set_error(CHROMA_ERR_INVALID, "room for %llu pulses, the rows hold %u", (unsigned long long)capacity, total);
+        hipLaunchKernelGGL(k_daq_pulses_open, grid, block, 0, stream, n, geom->view.nchannels, window->nbins, d_keys_sorted, d_positions, d_channel,
+                           d_bin, d_npe, d_q_int, (uint32_t *)d_t_first, d_flags);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_daq_pulses_reduce, dim3((n + DAQ_PULSES_BLOCK - 1) / DAQ_PULSES_BLOCK), dim3(DAQ_PULSES_BLOCK), 0, stream, n,
+                           d_keys_sorted, d_positions, d_order_sorted, d_charge, d_time, d_history, d_npe, d_q_int, (uint32_t *)d_t_first, d_flags);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_daq_pulses_finish, dim3((std::max(total, nrows + 1) + DAQ_PULSES_BLOCK - 1) / DAQ_PULSES_BLOCK), block, 0, stream, n, total, nrows,
+                           (uint64_t)geom->view.nchannels * window->nbins, d_keys_sorted, d_positions, (uint32_t *)d_t_first, d_offsets);
+        HIP_TRY(hipGetLastError());
+    } else {
+        HIP_TRY(hipMemsetAsync(d_offsets, 0, offsets_bytes, stream));
+    }
+    HIP_TRY(hipMemcpyAsync(d_outside, d_rows_outside, outside_bytes, hipMemcpyDeviceToDevice, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
     return CHROMA_OK;
 }
 

@@ -155,7 +155,7 @@ class Event(object):
 
     def __init__(self, id=0, vertices=None, photons_beg=None, photons_end=None,
                  photon_tracks=None, photon_parent_trackids=None, hits=None,
-                 flat_hits=None, channels=None):
+                 flat_hits=None, channels=None, pulses=None):
         self.id = id
         self.nphotons = None
         if vertices is None:
@@ -171,3 +171,4 @@ class Event(object):
         self.hits = hits
         self.flat_hits = flat_hits
         self.channels = channels
+        self.pulses = pulses          # the time-binned DAQ of simulate(daq_window=...): per (channel, bin) pulses, or None

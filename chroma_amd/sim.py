@@ -108,7 +108,8 @@ class Simulation(object):
         return gpu.GPUPhotons(batch_photons, copy_triangles=False, copy_weights=False, upload=upload), bounds
 
     def _simulate_batch(self, batch_events, keep_photons_beg=False, keep_photons_end=False, keep_hits=True,
-                        keep_flat_hits=True, run_daq=False, max_steps=100, verbose=False, uploaded=None, gpu_geometry=None):
+                        keep_flat_hits=True, run_daq=False, max_steps=100, verbose=False, uploaded=None, gpu_geometry=None,
+                        daq_window=None):
         """Propagate the photons of all ``batch_events`` in one go and split the results
         back per event (by evidx).  Yields the events.  ``uploaded``: what _upload_batch returned for them;
         ``gpu_geometry``: the geometry of the lane this batch runs on (default: the simulation's own)."""
@@ -151,13 +152,17 @@ class Simulation(object):
             else:
                 cuts = np.searchsorted(batch_hits.evidx, np.arange(len(batch_events) + 1))
                 per_event_hits = [batch_hits[a:b] for a, b in zip(cuts[:-1], cuts[1:])]
-        event_channels = None
+        event_channels = event_pulses = None
         if run_daq and hasattr(self, 'gpu_daq') and self.gpu_geometry.nchannels > 0:
             # the events' acquisitions as ONE (GPUEventDaq: a row of channels per event, read back sparse), numbered as the
             # reference's one acquisition per event (chroma/sim.py:128-137) numbers them: on from self.gpu_daq's counter
             if self._gpu_event_daq is None:
                 self._gpu_event_daq = gpu.GPUEventDaq(self.gpu_geometry)
             event_channels = self._gpu_event_daq.acquire(gpu_photons, self.rng_states, bounds, acquisition=self.gpu_daq.acquisition)
+            if daq_window is not None:
+                # (under the acquisition numbers of the events' channels: both describe the same photoelectrons)
+                event_pulses = self._gpu_event_daq.acquire_pulses(gpu_photons, self.rng_states, bounds, daq_window,
+                                                                  acquisition=self.gpu_daq.acquisition)
             self.gpu_daq.acquisition += len(batch_events)
         for i, (ev, lo, hi) in enumerate(zip(batch_events, bounds[:-1], bounds[1:])):
             if not keep_photons_beg:
@@ -191,6 +196,8 @@ class Simulation(object):
                     ev.flat_hits = ev_hits
             if event_channels is not None:
                 ev.channels = event_channels[i]
+                if event_pulses is not None:
+                    ev.pulses = event_pulses.event(i)
             elif hasattr(self, 'gpu_daq') and run_daq:
                 # (a detector without channels: one acquisition per event, as the reference, chroma/sim.py:128-137)
                 self.gpu_daq.begin_acquire()
@@ -200,9 +207,13 @@ class Simulation(object):
             yield ev
 
     def simulate(self, iterable, keep_photons_beg=False, keep_photons_end=False, keep_hits=True,
-                 keep_flat_hits=True, run_daq=False, max_steps=1000, photons_per_batch=1000000, evid_start=0):
+                 keep_flat_hits=True, run_daq=False, max_steps=1000, photons_per_batch=1000000, evid_start=0, daq_window=None):
         """Simulate Photons objects (or Events that already carry ``photons_beg``); events are
         batched until ``photons_per_batch`` photons are collected (chroma/sim.py:141-186).
+
+        ``daq_window=(t0, dt, nbins)`` (with ``run_daq=True``, on a detector with channels): besides ``ev.channels`` every event
+        gets ``ev.pulses``, the time-binned view of the same photoelectrons (gpu.Pulses: per (channel, bin) npe, charge, earliest
+        time and histories; GPUEventDaq.acquire_pulses).
 
         With ``Simulation(prefetch=True)`` (the default) the NEXT batch is taken from ``iterable`` and uploaded by a second
         thread while the current one propagates: the iterable is consumed one batch ahead of the events this generator
@@ -220,8 +231,14 @@ class Simulation(object):
         else:
             raise NotImplementedError('Vertex input needs the GEANT4 generator, which is out of scope')
 
+        if daq_window is not None:
+            if not run_daq:
+                raise ValueError('daq_window needs run_daq=True')
+            if not hasattr(self, 'gpu_daq') or self.gpu_geometry.nchannels < 1:
+                raise ValueError('daq_window needs a detector with channels')
+            daq_window = gpu.DaqWindow.of(daq_window)
         kwargs = dict(keep_photons_beg=keep_photons_beg, keep_photons_end=keep_photons_end, keep_hits=keep_hits,
-                      keep_flat_hits=keep_flat_hits, run_daq=run_daq, max_steps=max_steps)
+                      keep_flat_hits=keep_flat_hits, run_daq=run_daq, max_steps=max_steps, daq_window=daq_window)
         if isinstance(first, event.Event) and first.photons_beg is None:
             yield from self._simulate_stepped(iterable, photons_per_batch, evid_start, kwargs)
             return

@@ -441,6 +441,58 @@ int chroma_daq_compact_events(chroma_ctx *ctx, uint32_t nrows, uint32_t nchannel
                               const uint32_t *d_channel_q_int, const uint32_t *d_channel_histories,
                               uint64_t capacity, uint32_t *d_offsets, int32_t *d_channel, float *d_t,
                               float *d_q, uint32_t *d_flags, uint64_t *ntouched);
+/* ---- the time-binned DAQ: per-channel pulse histograms, kept sparse ---------------------------
+ * A second view of the very photoelectrons chroma_daq_acquire_events accumulates: per (row, channel,
+ * time bin) instead of per (row, channel), and only the bins that hold something.
+ *
+ * A photon of row r is treated exactly as chroma_daq_acquire_events treats it: the same rejects (no
+ * triangle, no channel, detection flag not set), the same three draws in the same order from Philox
+ * stream 1 + acquisition + r of photon photon_id_base + photon index -- the weight gate, the time smear
+ * through the time CDF, the charge through the charge CDF -- time = photon time + smear and charge_int =
+ * (uint32)cm_roundf(charge / charge_unit).  A pulse acquisition with the `acquisition` of a
+ * chroma_daq_acquire_events call therefore describes the same accepted photons.
+ *
+ * The window: dt > 0 and finite, t0 finite, 1 <= nbins <= 65536.  In float32, with IEEE subtract and
+ * divide: x = (time - t0) / dt; the photon is in the window iff x >= 0.0f && x < (float)nbins, and its bin
+ * is (uint32)cm_floorf(x).  An accepted photon outside the window is EARLY if time < t0 and LATE otherwise
+ * (a NaN time is late).  Times are compared as floats, so negative times bin like any other (the unsigned
+ * minimum of chroma_daq_acquire, which ranks them above the reset value, has no part here).
+ *
+ * A pulse is a (row, channel, bin) with at least one accepted in-window photon: npe, the number of them;
+ * q_int, the sum of their charge_int (wrapping, as the accumulator of chroma_daq_acquire does); t_first,
+ * the smallest of their times as floats (-0 ranks below +0); flags, the OR of their histories.  Pulses
+ * come in ascending (row, channel, bin) order, row r the entries [d_offsets[r], d_offsets[r + 1]).  The
+ * order comes from a sort and a scan and every reduction is of integers: the output is deterministic. */
+typedef struct chroma_daq_window {
+    float t0;           /* the lower edge of bin 0 */
+    float dt;           /* the width of a bin */
+    uint32_t nbins;
+} chroma_daq_window;
+/* *naccepted: the accepted in-window photons of the rows -- an upper bound on the number of pulses, by
+ * which a caller sizes the arrays of chroma_daq_acquire_pulses.  Writes nothing else.  Arguments and
+ * refusals as chroma_daq_acquire_events (there is no channel stride) and the window rules above; also
+ * refused: nrows * nchannels * nbins of 2^63 or more.  All CHROMA_ERR_INVALID before anything is
+ * launched. */
+int chroma_daq_count_pulses(chroma_ctx *ctx, chroma_geometry *geom, const chroma_daq_tables *tables,
+                            uint32_t nrows, const uint32_t *bounds, uint32_t detection_state,
+                            const chroma_photon_arrays *photons, uint32_t nphotons, chroma_rng rng,
+                            uint32_t acquisition, float global_weight, const chroma_daq_window *window,
+                            uint64_t *naccepted);
+/* The pulses: d_offsets (nrows + 1 words), and `capacity` entries each of d_channel, d_bin, d_npe,
+ * d_q_int, d_t_first and d_flags (these six may be NULL when capacity is 0); d_outside, 2 * nrows words:
+ * the early and the late photons of row r in words 2 r and 2 r + 1 -- written, not accumulated.
+ * *npulses: the number of pulses; beyond `capacity` NOTHING is written (d_offsets and d_outside
+ * neither), *npulses still holds the number needed and the call is CHROMA_ERR_INVALID.  An empty photon
+ * window is CHROMA_OK with no pulse and d_offsets and d_outside all zero.  Returns when the arrays are
+ * written.  Scratch is the context's pooled per-call block, grown to what the accepted photons need
+ * (some 50 bytes each), never to photons of the window or to rows x channels x bins. */
+int chroma_daq_acquire_pulses(chroma_ctx *ctx, chroma_geometry *geom, const chroma_daq_tables *tables,
+                              uint32_t nrows, const uint32_t *bounds, uint32_t detection_state,
+                              const chroma_photon_arrays *photons, uint32_t nphotons, chroma_rng rng,
+                              uint32_t acquisition, float global_weight, const chroma_daq_window *window,
+                              uint64_t capacity, uint32_t *d_offsets, int32_t *d_channel, uint32_t *d_bin,
+                              uint32_t *d_npe, uint32_t *d_q_int, float *d_t_first, uint32_t *d_flags,
+                              uint32_t *d_outside, uint64_t *npulses);
 /* `convert_sortable_int_to_float` + `convert_charge_int_to_float` (daq.cu:152-173) */
 int chroma_daq_convert(chroma_ctx *ctx, uint32_t nchannels, float charge_unit, const uint32_t *d_earliest_time_int,
                        const uint32_t *d_channel_q_int, float *d_earliest_time, float *d_channel_q);
