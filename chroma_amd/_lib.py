@@ -106,6 +106,12 @@ class DaqWindow(Structure):
     _fields_ = [('t0', c_float), ('dt', c_float), ('nbins', c_uint32)]
 
 
+class DaqTrigger(Structure):
+    """chroma_daq_trigger"""
+    _fields_ = [('kind', c_uint32), ('threshold', c_uint32), ('width', c_uint32), ('holdoff', c_uint32), ('pre', c_uint32),
+                ('post', c_uint32)]
+
+
 class LightSource(Structure):
     """chroma_light_source (host pointers)"""
     _fields_ = [('refractive_index', c_void_p), ('scintillation_cdf', c_void_p), ('time_cdf', c_void_p),
@@ -193,6 +199,10 @@ SIGNATURES = {
     'chroma_daq_acquire_pulses': (c_int32, [c_void_p, c_void_p, POINTER(DaqTables), c_uint32, c_void_p, c_uint32, POINTER(PhotonArrays),
                                             c_uint32, Rng, c_uint32, c_float, POINTER(DaqWindow), c_uint64, c_void_p, c_void_p, c_void_p,
                                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_uint64)]),
+    'chroma_daq_trigger_pulses': (c_int32, [c_void_p, c_uint32, c_uint32, POINTER(DaqWindow), POINTER(DaqTrigger), c_void_p, c_void_p, c_void_p,
+                                            c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                            c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_uint64),
+                                            POINTER(c_uint64)]),
     'chroma_daq_convert': (c_int32, [c_void_p, c_uint32, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     'chroma_pdf_bin_hits': (c_int32, [c_void_p, c_uint32, c_int32, c_uint32, c_void_p, c_void_p, c_int32, c_float, c_float,
                                       c_int32, c_float, c_float, c_void_p, c_void_p]),

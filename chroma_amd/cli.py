@@ -5,7 +5,7 @@ GEANT4 and writes a ROOT file; neither GEANT4 nor ROOT is part of this engine, s
 keeps the command-line shape (detector string, -n/--nevents, -o/--output, -s/--seed, -j device)
 but the particle source is the isotropic photon bomb of chroma/benchmark.py:77-83 and the output is
 an ``.npz``: per event the flat hits (channel, t, wavelength, pos, flags), with --run-daq the channel
-times and charges, with --daq-window T0,DT,NBINS also the pulses per (channel, time bin), with --save-photons-beg/--save-photons-end the photons themselves and with --track or
+times and charges, with --daq-window T0,DT,NBINS also the pulses per (channel, time bin), with --daq-trigger the triggers on them, with --save-photons-beg/--save-photons-end the photons themselves and with --track or
 --device-tracks every photon's state after each step.
 """
 import argparse
@@ -48,6 +48,10 @@ def main(argv=None):
     ap.add_argument('--run-daq', action='store_true')
     ap.add_argument('--daq-window', default=None, metavar='T0,DT,NBINS',
                     help='also write the time-binned DAQ: the pulses per (channel, bin) of NBINS bins of DT ns from T0 on (implies --run-daq)')
+    ap.add_argument('--daq-trigger', default=None, metavar='THRESHOLD,WIDTH[,HOLDOFF,PRE,POST]',
+                    help='with --daq-window, also write the triggers on the pulses: the firings of a sum over WIDTH bins that reaches THRESHOLD, '
+                         'HOLDOFF bins apart at the least, and the channels in each gate of PRE bins before to POST bins from the firing')
+    ap.add_argument('--daq-trigger-kind', default='nhit', choices=('nhit', 'npe'), help='what the trigger sums: distinct channels or photoelectrons')
     ap.add_argument('--save-photons-beg', action='store_true', help='also write the initial photons of every event (bin/chroma-sim:51-53)')
     ap.add_argument('--save-photons-end', action='store_true', help='also write the final photons of every event (bin/chroma-sim:54-56)')
     ap.add_argument('--track', action='store_true', help='also write every photon\'s state after each step (Simulation(photon_tracking=True))')
@@ -68,6 +72,18 @@ def main(argv=None):
             ap.error('--daq-window takes T0,DT,NBINS')
         daq_window = (float(parts[0]), float(parts[1]), int(parts[2]))
         args.run_daq = True
+    daq_trigger = None
+    if args.daq_trigger is not None:
+        if daq_window is None:
+            ap.error('--daq-trigger needs --daq-window')
+        parts = args.daq_trigger.split(',')
+        if len(parts) not in (2, 5):
+            ap.error('--daq-trigger takes THRESHOLD,WIDTH[,HOLDOFF,PRE,POST]')
+        from chroma_amd.gpu.daq import DaqTrigger
+        try:
+            daq_trigger = DaqTrigger(*[int(x) for x in parts], kind=args.daq_trigger_kind)
+        except ValueError as e:
+            ap.error('--daq-trigger: %s' % e)
     t0 = time.time()
     detector = load_geometry_from_string(args.detector, cache_dir=args.cache_dir)
     print('geometry: %d triangles, BVH %d nodes (%.1f s)' % (len(detector.mesh.triangles), len(detector.bvh.nodes), time.time() - t0))
@@ -80,7 +96,7 @@ def main(argv=None):
     nhits = 0
     for ev in sim.simulate(events, keep_photons_beg=args.save_photons_beg, keep_photons_end=args.save_photons_end,
                            keep_hits=False, keep_flat_hits=hasattr(detector, 'num_channels'),
-                           run_daq=args.run_daq, max_steps=args.max_steps, daq_window=daq_window):
+                           run_daq=args.run_daq, max_steps=args.max_steps, daq_window=daq_window, daq_trigger=daq_trigger):
         key = 'ev%d' % ev.id
         for tag, ph in (('photons_beg', ev.photons_beg), ('photons_end', ev.photons_end)):
             if ph is not None:
@@ -119,6 +135,16 @@ def main(argv=None):
             out[key + '/pulse_q'] = ev.pulses.q
             out[key + '/pulse_t'] = ev.pulses.t_first
             out[key + '/pulse_outside'] = np.array([ev.pulses.early, ev.pulses.late], dtype=np.uint32)
+        if ev.triggers is not None:
+            out[key + '/trigger_bin'] = ev.triggers.bin
+            out[key + '/trigger_time'] = ev.triggers.time
+            out[key + '/trigger_sum'] = ev.triggers.sum
+            out[key + '/trigger_hit_offsets'] = ev.triggers.hit_offsets
+            out[key + '/trigger_hit_channel'] = ev.triggers.hit_channel
+            out[key + '/trigger_hit_npe'] = ev.triggers.hit_npe
+            out[key + '/trigger_hit_q'] = ev.triggers.hit_q
+            out[key + '/trigger_hit_t'] = ev.triggers.hit_t_first
+            out[key + '/pulse_trigger'] = ev.triggers.pulse_trigger
     dt = time.time() - t0
     np.savez_compressed(args.output, **out)
     print('%d events, %d photons, %d hits in %.2f s (%.1f events/s, %.3g photons/s) -> %s' % (

@@ -1,6 +1,6 @@
 // kernel_calls.hip -- the entry points that are the checks of their arguments around one kernel launch on the context's
 // stream, as the reference's kernels are called from Python: the photon-array calls, DAQ, PDFs, chroma_render, point
-// transforms, the probe, the bomb generator, the photons from particle steps, the time-binned DAQ.
+// transforms, the probe, the bomb generator, the photons from particle steps, the time-binned DAQ and its trigger.
 #include <stdint.h>
 #include <string.h>
 #include <algorithm>
@@ -16,6 +16,8 @@
 #include "kernels_daq_render.h"
 
 #include "kernels_daq_pulses.h"
+
+#include "kernels_daq_trigger.h"
 
 #include "kernels_pdf.h"
 
@@ -629,6 +631,144 @@ int chroma_daq_acquire_pulses(chroma_ctx *ctx, chroma_geometry *geom, const chro
         HIP_TRY(hipMemsetAsync(d_offsets, 0, offsets_bytes, stream));
     }
     HIP_TRY(hipMemcpyAsync(d_outside, d_rows_outside, outside_bytes, hipMemcpyDeviceToDevice, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return CHROMA_OK;
+}
+
+// ---- the trigger of the time-binned DAQ (kernels_daq_trigger.h) ----
+int chroma_daq_trigger_pulses(chroma_ctx *ctx, uint32_t nrows, uint32_t nchannels, const chroma_daq_window *window,
+                              const chroma_daq_trigger *trigger, const uint32_t *d_offsets, const int32_t *d_channel, const uint32_t *d_bin,
+                              const uint32_t *d_npe, const uint32_t *d_q_int, const float *d_t_first, const uint32_t *d_flags, uint64_t npulses,
+                              uint64_t trigger_capacity, uint32_t *d_trig_offsets, uint32_t *d_trig_bin, uint32_t *d_trig_sum,
+                              uint32_t *d_hit_offsets, uint64_t hit_capacity, int32_t *d_hit_channel, uint32_t *d_hit_npe, uint32_t *d_hit_q_int,
+                              float *d_hit_t_first, uint32_t *d_hit_flags, uint32_t *d_pulse_trigger, uint64_t *ntriggers, uint64_t *nhits)
+{
+    if (!ctx || !window || !trigger || !d_offsets || !d_trig_offsets || !d_hit_offsets || !ntriggers || !nhits ||
+        (npulses && (!d_channel || !d_bin || !d_npe || !d_q_int || !d_t_first || !d_flags)) || (trigger_capacity && (!d_trig_bin || !d_trig_sum)) ||
+        (hit_capacity && (!d_hit_channel || !d_hit_npe || !d_hit_q_int || !d_hit_t_first || !d_hit_flags)))
+        return set_error(CHROMA_ERR_INVALID, "bad argument");
+    if (nrows < 1 || nchannels < 1 || nchannels > 0x7fffffffu) return set_error(CHROMA_ERR_INVALID, "need at least one row and 1 .. 2^31 - 1 channels");
+    if (!(window->dt > 0.0f) || !std::isfinite(window->dt) || !std::isfinite(window->t0) || window->nbins < 1 || window->nbins > 65536)
+        return set_error(CHROMA_ERR_INVALID, "DAQ window: need a finite t0, a finite positive dt and 1 .. 65536 bins");
+    const uint32_t nbins = window->nbins;
+    if (trigger->kind != CHROMA_TRIGGER_NHIT && trigger->kind != CHROMA_TRIGGER_NPE) return set_error(CHROMA_ERR_INVALID, "DAQ trigger: unknown kind %u", trigger->kind);
+    if (trigger->threshold < 1 || trigger->width < 1 || trigger->width > nbins || trigger->post < 1 ||
+        trigger->holdoff < std::max<uint64_t>(1, (uint64_t)trigger->pre + trigger->post))
+        return set_error(CHROMA_ERR_INVALID, "DAQ trigger: need a threshold of at least 1, a width of 1 .. %u bins, post >= 1 and holdoff >= max(1, pre + post)", nbins);
+    if (npulses >= 0x7fffffffull) return set_error(CHROMA_ERR_INVALID, "%llu pulses: more than the scan's 31-bit count holds, pass fewer rows", (unsigned long long)npulses);
+    if ((uint64_t)nrows * nbins >= 0x80000000ull)
+        return set_error(CHROMA_ERR_INVALID, "%u rows of %u bins: more than 31-bit (row, bin) indices hold, pass fewer rows", nrows, nbins);
+    hipStream_t stream = ctx->stream;
+    const size_t offsets_bytes = ((size_t)nrows + 1) * sizeof(uint32_t);
+    if (npulses == 0) {
+        *ntriggers = 0; *nhits = 0;
+        HIP_TRY(hipMemsetAsync(d_trig_offsets, 0, offsets_bytes, stream));
+        HIP_TRY(hipMemsetAsync(d_hit_offsets, 0, sizeof(uint32_t), stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        return CHROMA_OK;
+    }
+    // (what lies beyond the window changes nothing: a lockout, a gate or a reach of more than nbins bins is one of nbins)
+    const uint32_t n = (uint32_t)npulses, holdoff = std::min(trigger->holdoff, nbins), pre = std::min(trigger->pre, nbins), post = std::min(trigger->post, nbins);
+    const uint64_t per_row = (nbins + holdoff - 1) / holdoff, per_pulse = (trigger->width + holdoff - 1) / holdoff;
+    const uint32_t room = (uint32_t)std::min<uint64_t>((uint64_t)nrows * per_row, (uint64_t)n * per_pulse);          // (<= nrows * nbins < 2^31)
+    // The block, sized once from the bounds (growing it would lose what is in it): the sum per (row, bin); per pulse its row, its
+    // trigger, the gated flags and their scan (n + 1), the keys and indices before and behind the sort, the heads (n + 1), the bin
+    // that k_daq_pulses_open writes; per row the counts and their scan (nrows + 1); per trigger its bin and sum; the workspaces
+    const CallScope scope(ctx);
+    size_t sort_bytes = 0, scan_bytes = 0, scan_rows_bytes = 0;
+    {
+        uint64_t *k = nullptr; uint32_t *v = nullptr;
+        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, k, k, v, v, (int)n, 0, 64, stream));
+        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, v, v, (int)(n + 1), stream));
+        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_rows_bytes, v, v, (int)(nrows + 1), stream));
+    }
+    scan_bytes = std::max(scan_bytes, scan_rows_bytes);
+    const size_t sum_bytes = round256((size_t)nrows * nbins * sizeof(uint32_t)), word_bytes = round256((size_t)n * sizeof(uint32_t)),
+                 word1_bytes = round256(((size_t)n + 1) * sizeof(uint32_t)), key_bytes = round256((size_t)n * sizeof(uint64_t)),
+                 trig_bytes = round256((size_t)room * sizeof(uint32_t));
+    const size_t need = sum_bytes + 5 * word_bytes + 2 * word1_bytes + 2 * key_bytes + round256(offsets_bytes) + 2 * trig_bytes + round256(sort_bytes) +
+                        round256(scan_bytes);
+    int rc = steps_block(scope, need); if (rc) return rc;
+    char *p = (char *)scope.state().steps_scratch;
+    uint32_t *d_sum = (uint32_t *)p; p += sum_bytes;
+    uint32_t *d_rows = (uint32_t *)p; p += word_bytes;
+    uint32_t *d_of = (uint32_t *)p; p += word_bytes;          // the trigger of every pulse
+    uint32_t *d_order = (uint32_t *)p; p += word_bytes;
+    uint32_t *d_order_sorted = (uint32_t *)p; p += word_bytes;
+    uint32_t *d_hit_bin = (uint32_t *)p; p += word_bytes;
+    uint32_t *d_gated = (uint32_t *)p; p += word1_bytes;          // the flags, then (in place) their exclusive sum
+    uint32_t *d_positions = (uint32_t *)p; p += word1_bytes;          // the heads, then (in place) their exclusive sum
+    uint64_t *d_keys = (uint64_t *)p; p += key_bytes;
+    uint64_t *d_keys_sorted = (uint64_t *)p; p += key_bytes;
+    uint32_t *d_row_triggers = (uint32_t *)p; p += round256(offsets_bytes);          // the counts, then (in place) the rows' offsets
+    uint32_t *d_bins = (uint32_t *)p; p += trig_bytes;
+    uint32_t *d_sums = (uint32_t *)p; p += trig_bytes;
+    void *d_sort = p; p += round256(sort_bytes);
+    void *d_scan = p;
+    const dim3 block(DAQ_TRIGGER_BLOCK), per_pulse_grid((n + DAQ_TRIGGER_BLOCK - 1) / DAQ_TRIGGER_BLOCK), per_pulse1_grid(n / DAQ_TRIGGER_BLOCK + 1);
+    HIP_TRY(hipMemsetAsync(d_sum, 0, (size_t)nrows * nbins * sizeof(uint32_t), stream));
+    hipLaunchKernelGGL(k_daq_trigger_edges, per_pulse_grid, block, 0, stream, n, nrows, nchannels, nbins, trigger->kind, trigger->width, d_offsets, d_channel,
+                       d_bin, d_npe, d_rows, d_sum);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_daq_trigger_count, dim3(nrows / DAQ_TRIGGER_WAVES + 1), block, 0, stream, nrows, nbins, trigger->threshold, holdoff, d_sum, d_row_triggers);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_scan, scan_bytes, d_row_triggers, d_row_triggers, (int)(nrows + 1), stream));
+    uint32_t total = 0, ngated = 0, total_hits = 0;
+    HIP_TRY(hipMemcpyAsync(&total, d_row_triggers + nrows, sizeof(total), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (total > room) return set_error(CHROMA_ERR_INTERNAL, "DAQ trigger: %u firings, the bound is %u", total, room);
+    int end_bit = 1;
+    if (total) {
+        hipLaunchKernelGGL(k_daq_trigger_fire, dim3((nrows + DAQ_TRIGGER_WAVES - 1) / DAQ_TRIGGER_WAVES), block, 0, stream, nrows, nbins, trigger->threshold,
+                           holdoff, d_sum, d_row_triggers, room, d_bins, d_sums);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_daq_trigger_gates, per_pulse1_grid, block, 0, stream, n, pre, post, d_rows, d_bin, d_row_triggers, d_bins, d_of, d_gated);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_scan, scan_bytes, d_gated, d_gated, (int)(n + 1), stream));
+        hipLaunchKernelGGL(k_daq_trigger_compact, per_pulse_grid, block, 0, stream, n, nchannels, d_of, d_channel, d_gated, n, d_keys, d_order);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(&ngated, d_gated + n, sizeof(ngated), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+    }
+    if (ngated) {
+        const uint64_t nkeys = (uint64_t)total * nchannels;
+        while (end_bit < 64 && ((nkeys - 1) >> end_bit)) end_bit++;
+        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(d_sort, sort_bytes, d_keys, d_keys_sorted, d_order, d_order_sorted, (int)ngated, 0, end_bit, stream));
+        hipLaunchKernelGGL(k_daq_pulses_heads, dim3(ngated / DAQ_PULSES_BLOCK + 1), dim3(DAQ_PULSES_BLOCK), 0, stream, ngated, d_keys_sorted, d_positions);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_scan, scan_bytes, d_positions, d_positions, (int)(ngated + 1), stream));
+        HIP_TRY(hipMemcpyAsync(&total_hits, d_positions + ngated, sizeof(total_hits), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+    }
+    *ntriggers = total; *nhits = total_hits;
+    if (total > trigger_capacity || total_hits > hit_capacity)
+        return set_error(CHROMA_ERR_INVALID, "room for %llu triggers and %llu hits, the rows hold %u and %u", (unsigned long long)trigger_capacity,
+                         (unsigned long long)hit_capacity, total, total_hits);
+    // nothing of the caller's was written so far
+    HIP_TRY(hipMemcpyAsync(d_trig_offsets, d_row_triggers, offsets_bytes, hipMemcpyDeviceToDevice, stream));
+    if (total) {
+        HIP_TRY(hipMemcpyAsync(d_trig_bin, d_bins, (size_t)total * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(d_trig_sum, d_sums, (size_t)total * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
+    }
+    if (d_pulse_trigger) {
+        if (total) { HIP_TRY(hipMemcpyAsync(d_pulse_trigger, d_of, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream)); }
+        else { HIP_TRY(hipMemsetAsync(d_pulse_trigger, 0xff, (size_t)n * sizeof(uint32_t), stream)); }
+    }
+    if (ngated) {
+        const dim3 pulses_block(DAQ_PULSES_BLOCK);
+        hipLaunchKernelGGL(k_daq_pulses_open, dim3((ngated + DAQ_PULSES_BLOCK - 1) / DAQ_PULSES_BLOCK), pulses_block, 0, stream, ngated, nchannels, 1u,
+                           d_keys_sorted, d_positions, d_hit_channel, d_hit_bin, d_hit_npe, d_hit_q_int, (uint32_t *)d_hit_t_first, d_hit_flags);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_daq_trigger_reduce, dim3((ngated + DAQ_TRIGGER_BLOCK - 1) / DAQ_TRIGGER_BLOCK), block, 0, stream, ngated, d_keys_sorted,
+                           d_positions, d_order_sorted, d_npe, d_q_int, (const uint32_t *)d_t_first, d_flags, d_hit_npe, d_hit_q_int,
+                           (uint32_t *)d_hit_t_first, d_hit_flags);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_daq_pulses_finish, dim3(std::max(total_hits, total + 1) / DAQ_PULSES_BLOCK + 1), pulses_block, 0, stream, ngated, total_hits,
+                           total, (uint64_t)nchannels, d_keys_sorted, d_positions, (uint32_t *)d_hit_t_first, d_hit_offsets);
+        HIP_TRY(hipGetLastError());
+    } else {
+        HIP_TRY(hipMemsetAsync(d_hit_offsets, 0, ((size_t)total + 1) * sizeof(uint32_t), stream));
+    }
     HIP_TRY(hipStreamSynchronize(stream));
     return CHROMA_OK;
 }

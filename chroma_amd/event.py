@@ -155,7 +155,7 @@ class Event(object):
 
     def __init__(self, id=0, vertices=None, photons_beg=None, photons_end=None,
                  photon_tracks=None, photon_parent_trackids=None, hits=None,
-                 flat_hits=None, channels=None, pulses=None):
+                 flat_hits=None, channels=None, pulses=None, triggers=None):
         self.id = id
         self.nphotons = None
         if vertices is None:
@@ -172,3 +172,4 @@ class Event(object):
         self.flat_hits = flat_hits
         self.channels = channels
         self.pulses = pulses          # the time-binned DAQ of simulate(daq_window=...): per (channel, bin) pulses, or None
+        self.triggers = triggers      # the triggers on those pulses of simulate(daq_trigger=...): firings and their gated channels, or None

@@ -12,7 +12,10 @@ photons differ.
 acquisition over a row of channels per event and reads the touched words back sparse (``EventChannels``).  Its
 ``acquire_pulses`` is the time-binned view of the same photoelectrons (chroma_daq_count_pulses / chroma_daq_acquire_pulses): per
 (event, channel, time bin of a ``DaqWindow``) the number of photoelectrons, their charge, the earliest of their times and the OR
-of their histories, only the bins that hold something (``EventPulses``, per event ``Pulses``).
+of their histories, only the bins that hold something (``EventPulses``, per event ``Pulses``).  With a ``DaqTrigger`` the pulses are
+triggered where they lie on the device (chroma_daq_trigger_pulses): the firings of a multiplicity or photoelectron sum over a
+coincidence window, and per firing the channels of its readout gate (``EventTriggers``, per event ``Triggers``);
+``EventPulses.trigger`` is the same computed in NumPy on the host arrays.
 """
 import ctypes
 
@@ -247,6 +250,7 @@ class EventPulses(object):
         self.q = (q_int.astype(np.float32) * np.float32(charge_unit)).astype(np.float32)          # as k_daq_convert
         self._outside = outside
         self.nevents = len(offsets) - 1
+        self.triggers = None                 # the EventTriggers of acquire_pulses(trigger=...)
 
     def __len__(self):
         return self.nevents
@@ -287,6 +291,268 @@ class EventPulses(object):
         """(npe[nbins] uint32, q[nbins] float32) of one channel of event ``i``, dense."""
         return self.event(i).waveform(channel)
 
+    def trigger(self, trigger):
+        """The ``EventTriggers`` of these pulses under ``trigger`` (a DaqTrigger or its tuple), computed in NumPy on the host
+        arrays -- no GPU, no library: what ``GPUEventDaq.acquire_pulses(trigger=...)`` computes on the device, bit for bit."""
+        return trigger_pulses_host(self.window, trigger, self.nchannels, self.charge_unit, self.offsets, self.channel, self.bin, self.npe,
+                                   self.q_int, self.t_first, self.flags)
+
+
+NO_TRIGGER = 0xffffffff          # pulse_trigger of a pulse that lies in no gate
+
+
+class DaqTrigger(object):
+    """A trigger on the pulses of a ``DaqWindow`` (chroma_daq_trigger; everything in BINS of the window).  The sum S(b) of a bin
+    is over the pulses of the bins (b - width, b]: the number of distinct channels among them (``kind='nhit'``) or their
+    photoelectrons (``'npe'``).  Through the bins ascending the trigger fires at b if S(b) >= threshold and b is not within
+    ``holdoff`` bins behind the last firing; the gate of a firing is the bins [b - pre, b + post), clipped to the window.
+    Defaults: ``post = width`` and ``holdoff = pre + post`` (the smallest allowed: the gates of an event never overlap)."""
+
+    KINDS = {'nhit': 0, 'npe': 1}
+
+    def __init__(self, threshold, width, holdoff=None, pre=0, post=None, kind='nhit'):
+        if kind not in self.KINDS:
+            raise ValueError("a DAQ trigger's kind is 'nhit' or 'npe'")
+        self.kind = kind
+        values = {}
+        for name, value in (('threshold', threshold), ('width', width), ('pre', pre), ('post', width if post is None else post), ('holdoff', holdoff)):
+            if name == 'holdoff' and value is None:
+                value = values['pre'] + values['post']
+            try:
+                whole = int(value)
+            except (TypeError, ValueError):
+                raise ValueError('a DAQ trigger\'s %s is a whole number of bins' % name)
+            if whole != value or not 0 <= whole <= 0xffffffff:
+                raise ValueError('a DAQ trigger\'s %s is a whole number of 32 bits' % name)
+            values[name] = whole
+        values = [values[name] for name in ('threshold', 'width', 'holdoff', 'pre', 'post')]
+        self.threshold, self.width, self.holdoff, self.pre, self.post = values
+        if self.threshold < 1 or self.width < 1 or self.post < 1:
+            raise ValueError('a DAQ trigger needs a threshold, a width and a post of at least 1')
+        if self.holdoff < max(1, self.pre + self.post):
+            raise ValueError('a DAQ trigger needs holdoff >= max(1, pre + post): the gates of an event do not overlap')
+
+    @classmethod
+    def of(cls, trigger):
+        """``trigger`` itself if it is a DaqTrigger, or the DaqTrigger of a (threshold, width[, holdoff, pre, post[, kind]]) tuple."""
+        if isinstance(trigger, cls):
+            return trigger
+        try:
+            parts = tuple(trigger)
+        except TypeError:
+            raise ValueError('a DAQ trigger is (threshold, width[, holdoff, pre, post[, kind]])')
+        if not 2 <= len(parts) <= 6:
+            raise ValueError('a DAQ trigger is (threshold, width[, holdoff, pre, post[, kind]])')
+        return cls(*parts)
+
+    def check(self, window):
+        """Raises ValueError unless the trigger fits ``window`` (a coincidence window of at most its bins)."""
+        if self.width > window.nbins:
+            raise ValueError('a DAQ trigger of width %d on a window of %d bins' % (self.width, window.nbins))
+        return self
+
+    def struct(self):
+        return _lib.DaqTrigger(self.KINDS[self.kind], self.threshold, self.width, self.holdoff, self.pre, self.post)
+
+    def _key(self):
+        return (self.kind, self.threshold, self.width, self.holdoff, self.pre, self.post)
+
+    def __eq__(self, other):
+        return isinstance(other, DaqTrigger) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        return 'DaqTrigger(threshold=%d, width=%d, holdoff=%d, pre=%d, post=%d, kind=%r)' % (
+            self.threshold, self.width, self.holdoff, self.pre, self.post, self.kind)
+
+
+class Triggers(object):
+    """The triggers of ONE event (``EventTriggers.event(i)``, ``ev.triggers``): ``bin`` and ``sum`` of every firing, ascending;
+    ``sparse(k)`` the channels in the gate of firing k, ``channels(k)`` the same as a dense ``event.Channels``; ``pulse_trigger``:
+    per pulse of the event's ``Pulses`` the firing (numbered within the event) whose gate holds it, or ``NO_TRIGGER``."""
+
+    def __init__(self, window, trigger, nchannels, charge_unit, bin, sum, hit_offsets, hit_channel, hit_npe, hit_q_int, hit_t_first,
+                 hit_flags, pulse_trigger):
+        self.window, self.trigger, self.nchannels, self.charge_unit = window, trigger, nchannels, charge_unit
+        self.bin, self.sum = bin, sum
+        self.hit_offsets = hit_offsets          # (len + 1, into the hit arrays; the first is 0)
+        self.hit_channel, self.hit_npe, self.hit_q_int, self.hit_t_first, self.hit_flags = hit_channel, hit_npe, hit_q_int, hit_t_first, hit_flags
+        self.hit_q = (hit_q_int.astype(np.float32) * np.float32(charge_unit)).astype(np.float32)          # as k_daq_convert
+        self.pulse_trigger = pulse_trigger
+
+    def __len__(self):
+        return len(self.bin)
+
+    @property
+    def time(self):
+        """The nominal lower edge t0 + bin dt of every firing's bin (float64)."""
+        return self.window.t0 + self.window.dt * self.bin.astype(np.float64)
+
+    def _slice(self, k):
+        k = int(k)
+        if k < 0:
+            k += len(self)
+        if not 0 <= k < len(self):
+            raise IndexError('trigger %d of %d' % (k, len(self)))
+        return slice(int(self.hit_offsets[k]), int(self.hit_offsets[k + 1]))
+
+    def sparse(self, k):
+        """(channel, npe, q, t_first, flags) of the gate of firing ``k``, in channel order, as slices (no copy)."""
+        w = self._slice(k)
+        return self.hit_channel[w], self.hit_npe[w], self.hit_q[w], self.hit_t_first[w], self.hit_flags[w]
+
+    def channels(self, k):
+        """The dense ``event.Channels`` of the gate of firing ``k``: a channel's earliest time and charge in the gate, built as
+        ``EventChannels.__getitem__`` builds an event's (t = 1e9 and not hit where the gate holds nothing of the channel)."""
+        channel, npe, qs, ts, fs = self.sparse(k)
+        t = np.full(self.nchannels, 1e9, dtype=np.float32)
+        q = np.zeros(self.nchannels, dtype=np.float32)
+        flags = np.zeros(self.nchannels, dtype=np.uint32)
+        t[channel] = ts
+        q[channel] = qs
+        flags[channel] = fs
+        return event.Channels(t < 1e8, t, q, flags)
+
+
+class EventTriggers(object):
+    """The triggers of every event of a batch (``EventPulses.triggers`` after ``GPUEventDaq.acquire_pulses(trigger=...)``, or
+    ``EventPulses.trigger(...)``): firings in (event, bin) order -- ``bin``, ``sum`` (uint32), ``offsets`` (len + 1) the events'
+    places in them; gated hits in (firing, channel) order -- ``hit_channel`` (int32), ``hit_npe``, ``hit_q_int``, ``hit_flags``
+    (uint32), ``hit_t_first`` (float32), ``hit_offsets`` (firings + 1); ``pulse_trigger`` (uint32, per pulse of the batch): the
+    firing, numbered within the batch, whose gate holds the pulse, or ``NO_TRIGGER``."""
+
+    def __init__(self, window, trigger, nchannels, charge_unit, pulse_offsets, offsets, bin, sum, hit_offsets, hit_channel, hit_npe,
+                 hit_q_int, hit_t_first, hit_flags, pulse_trigger):
+        self.window, self.trigger, self.nchannels, self.charge_unit = window, trigger, nchannels, charge_unit
+        self.pulse_offsets, self.offsets, self.bin, self.sum, self.hit_offsets = pulse_offsets, offsets, bin, sum, hit_offsets
+        self.hit_channel, self.hit_npe, self.hit_q_int, self.hit_t_first, self.hit_flags = hit_channel, hit_npe, hit_q_int, hit_t_first, hit_flags
+        self.pulse_trigger = pulse_trigger
+        self.nevents = len(offsets) - 1
+
+    def __len__(self):
+        return self.nevents
+
+    def event(self, i):
+        """The ``Triggers`` of event ``i``."""
+        i = int(i)
+        if i < 0:
+            i += self.nevents
+        if not 0 <= i < self.nevents:
+            raise IndexError('event %d of %d' % (i, self.nevents))
+        a, b = int(self.offsets[i]), int(self.offsets[i + 1])
+        h = slice(int(self.hit_offsets[a]), int(self.hit_offsets[b]))
+        of = self.pulse_trigger[int(self.pulse_offsets[i]):int(self.pulse_offsets[i + 1])]
+        of = np.where(of == NO_TRIGGER, of, of - np.uint32(a)).astype(np.uint32)
+        return Triggers(self.window, self.trigger, self.nchannels, self.charge_unit, self.bin[a:b], self.sum[a:b],
+                        self.hit_offsets[a:b + 1] - self.hit_offsets[a], self.hit_channel[h], self.hit_npe[h], self.hit_q_int[h],
+                        self.hit_t_first[h], self.hit_flags[h], of)
+
+
+def _time_image(bits):
+    """The order-preserving image of float32 bits (daq_time_image: -0 below +0) ..."""
+    return np.where(bits & np.uint32(0x80000000), ~bits, bits | np.uint32(0x80000000)).astype(np.uint32)
+
+
+def _time_bits(image):
+    """... and back."""
+    return np.where(image & np.uint32(0x80000000), image & np.uint32(0x7fffffff), ~image).astype(np.uint32)
+
+
+def _follow(first, successor):
+    """The members of the chains that begin at ``first`` and go on by ``successor`` (an index, or len(successor) for none),
+    ascending: pointer doubling, so a chain of k members takes log2(k) rounds."""
+    m = len(successor)
+    jump = np.append(successor, m)
+    mark = np.zeros(m + 1, dtype=bool)
+    mark[first] = True
+    while True:
+        reached = jump[np.flatnonzero(mark[:m])]
+        reached = reached[~mark[reached] & (reached < m)]
+        if len(reached) == 0:
+            return np.flatnonzero(mark[:m])
+        mark[reached] = True
+        jump = jump[jump]
+
+
+def trigger_pulses_host(window, trigger, nchannels, charge_unit, offsets, channel, bin, npe, q_int, t_first, flags):
+    """chroma_daq_trigger_pulses in NumPy, on pulses in (event, channel, bin) order (``offsets`` from 0 to their number): the
+    differences of the sum per (event, bin) -- a channel's overlapping coincidence intervals united by a look at the entry before --
+    summed along the bins for some 2^22 (event, bin) words at a time; the firings followed from each event's first bin at or
+    above threshold to the next one ``holdoff`` or more behind; every pulse looked up among its event's firings; the gated
+    pulses reduced per (firing, channel) behind a stable sort.  Returns an ``EventTriggers``."""
+    nbins, nch = window.nbins, int(nchannels)
+    trigger = DaqTrigger.of(trigger).check(window)
+    offsets = np.asarray(offsets, dtype=np.int64)
+    nrows, n = len(offsets) - 1, len(channel)
+    width, holdoff, pre, post = trigger.width, min(trigger.holdoff, nbins), min(trigger.pre, nbins), min(trigger.post, nbins)
+    row = np.repeat(np.arange(nrows, dtype=np.int64), np.diff(offsets))
+    b, ch = bin.astype(np.int64), channel.astype(np.int64)
+    valid = (b < nbins) & (ch >= 0) & (ch < nch)
+    up = b.copy()
+    if trigger.kind == 'npe':
+        amount = npe.astype(np.float64)
+    else:
+        amount = np.ones(n, dtype=np.float64)
+        if n > 1:
+            same = valid[1:] & valid[:-1] & (row[1:] == row[:-1]) & (ch[1:] == ch[:-1])
+            up[1:] = np.where(same, np.maximum(b[1:], b[:-1] + width), b[1:])
+    down = b + width
+    counts = valid & (up < down)
+    # the bins at or above threshold, in (event, bin) order
+    at_row, at_bin, at_sum = [np.zeros(0, dtype=np.int64)], [np.zeros(0, dtype=np.int64)], [np.zeros(0, dtype=np.int64)]
+    rows_at_once = max(1, (1 << 22) // nbins)
+    for first in range(0, nrows, rows_at_once):
+        k = min(rows_at_once, nrows - first)
+        w = slice(int(offsets[first]), int(offsets[first + k]))
+        m = counts[w]
+        base = (row[w][m] - first) * nbins
+        u, d, a = up[w][m], down[w][m], amount[w][m]
+        total = np.bincount((base + u)[u < nbins], weights=a[u < nbins], minlength=k * nbins)
+        total -= np.bincount((base + d)[d < nbins], weights=a[d < nbins], minlength=k * nbins)
+        s = np.cumsum(np.rint(total).astype(np.int64).reshape(k, nbins), axis=1) & 0xffffffff
+        r, c = np.nonzero(s >= trigger.threshold)
+        at_row.append(r + first)
+        at_bin.append(c)
+        at_sum.append(s[r, c])
+    at_row, at_bin, at_sum = np.concatenate(at_row), np.concatenate(at_bin), np.concatenate(at_sum)
+    # the firings: the first such bin of an event, then from each the first one `holdoff` or more bins behind it
+    key = at_row * (2 * nbins) + at_bin
+    successor = np.searchsorted(key, key + holdoff)
+    inside = successor < len(key)
+    inside[inside] = at_row[successor[inside]] == at_row[inside]
+    successor = np.where(inside, successor, len(key))
+    starts = np.flatnonzero(np.concatenate(([True], at_row[1:] != at_row[:-1]))) if len(key) else np.zeros(0, dtype=np.int64)
+    fired = _follow(starts, successor)
+    t_row, t_bin, t_sum = at_row[fired], at_bin[fired], at_sum[fired]
+    ntriggers = len(fired)
+    trig_offsets = np.searchsorted(t_row, np.arange(nrows + 1))
+    # the gate of every pulse: the last firing of its event at or before bin + pre, if the pulse is before its bin + post
+    found = np.searchsorted(t_row * (4 * nbins) + t_bin, row * (4 * nbins) + b + pre, side='right') - 1
+    gated = valid & (found >= 0)
+    at = found[gated]
+    gated[gated] = (t_row[at] == row[gated]) & (b[gated] < t_bin[at] + post)
+    pulse_trigger = np.where(gated, found, NO_TRIGGER).astype(np.uint32)
+    # the hits: the gated pulses per (firing, channel)
+    source = np.flatnonzero(gated)
+    hit_key = found[source] * nch + ch[source]
+    order = np.argsort(hit_key, kind='stable')
+    hit_key, source = hit_key[order], source[order]
+    if len(source):
+        heads = np.flatnonzero(np.concatenate(([True], hit_key[1:] != hit_key[:-1])))
+        hit_npe = np.add.reduceat(npe[source].astype(np.uint32), heads)
+        hit_q = np.add.reduceat(q_int[source].astype(np.uint32), heads)          # (wrapping)
+        hit_t = _time_bits(np.minimum.reduceat(_time_image(np.ascontiguousarray(t_first[source], dtype=np.float32).view(np.uint32)), heads))
+        hit_flags = np.bitwise_or.reduceat(flags[source].astype(np.uint32), heads)
+        hit_key = hit_key[heads]
+    else:
+        hit_npe = hit_q = hit_t = hit_flags = np.zeros(0, dtype=np.uint32)
+    hit_offsets = np.searchsorted(hit_key // nch, np.arange(ntriggers + 1))
+    return EventTriggers(window, trigger, nch, charge_unit, offsets, trig_offsets.astype(np.int64), t_bin.astype(np.uint32),
+                         t_sum.astype(np.uint32), hit_offsets.astype(np.int64), (hit_key % nch).astype(np.int32), hit_npe.astype(np.uint32),
+                         hit_q.astype(np.uint32), hit_t.view(np.float32), hit_flags.astype(np.uint32), pulse_trigger)
+
 
 class GPUEventDaq(object):
     """The per-event acquisitions of a batch as one acquisition (chroma_daq_acquire_events), read back sparse
@@ -314,6 +580,9 @@ class GPUEventDaq(object):
         self._sparse_gpu = None
         self._pulse_rows_gpu = None          # acquire_pulses' outputs: per row (offsets, outside), per pulse the six arrays
         self._pulses_gpu = None
+        self._trigger_rows_gpu = None        # acquire_pulses(trigger=...): per row the offsets; per trigger (bin, sum, hit offsets) in one
+        self._triggers_gpu = None            # buffer; per hit the five arrays and per pulse its trigger in another
+        self._trigger_hits_gpu = None
 
     def _compaction_buffers(self, nrows, capacity):
         if self._offsets_gpu is None or len(self._offsets_gpu) < nrows + 1:
@@ -362,11 +631,50 @@ class GPUEventDaq(object):
                                 for dtype in (np.int32, np.uint32, np.uint32, np.uint32, np.float32, np.uint32)]
         return self._pulse_rows_gpu, self._pulses_gpu
 
-    def acquire_pulses(self, gpuphotons, rng_states, bounds, window, acquisition=0, weight=1.0):
+    def _trigger_chunk(self, win, trigger, nrows, d_offsets, arrays, npulses):
+        """chroma_daq_trigger_pulses on the pulses of one chunk where acquire_pulses left them; the host arrays (offsets, bin, sum,
+        hit offsets, the five hit arrays, pulse_trigger).  The per-trigger arrays share one device buffer and the per-hit and
+        per-pulse arrays another (all of 32-bit words), so a chunk comes back in three copies.  The hit arrays hold a hit per
+        pulse, which always suffices; the trigger arrays grow to what a call reports, and the call is made again."""
+        lib, handle = self.ctx._lib, self.ctx.handle
+        n = int(npulses)
+        if self._trigger_rows_gpu is None or len(self._trigger_rows_gpu) < nrows + 1:
+            self._trigger_rows_gpu = empty(nrows + 1, np.uint32, self.ctx)
+        if self._trigger_hits_gpu is None or len(self._trigger_hits_gpu) < 6 * n:
+            self._trigger_hits_gpu = empty(6 * n, np.uint32, self.ctx)
+        if self._triggers_gpu is None:
+            self._triggers_gpu = empty(3 * 1024 + 1, np.uint32, self.ctx)
+        per_pulse = [self._trigger_hits_gpu[k * n:(k + 1) * n] for k in range(6)]          # channel, npe, q_int, t_first, flags; pulse_trigger
+        trig = trigger.struct()
+        ntriggers, nhits = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        for attempt in range(2):
+            capacity = (len(self._triggers_gpu) - 1) // 3
+            per_trigger = [self._triggers_gpu[:capacity], self._triggers_gpu[capacity:2 * capacity], self._triggers_gpu[2 * capacity:3 * capacity + 1]]
+            rc = lib.chroma_daq_trigger_pulses(handle, nrows, self.nchannels, ctypes.byref(win), ctypes.byref(trig), d_offsets.ptr,
+                                               *([a.ptr for a in arrays] + [n, capacity, self._trigger_rows_gpu.ptr] + [a.ptr for a in per_trigger] +
+                                                 [n] + [a.ptr for a in per_pulse] + [ctypes.byref(ntriggers), ctypes.byref(nhits)]))
+            if rc == 0 or attempt or ntriggers.value <= capacity:
+                break
+            grown = int(ntriggers.value) + int(ntriggers.value) // 4
+            self._triggers_gpu = empty(3 * grown + 1, np.uint32, self.ctx)
+        _lib.check(rc)
+        nt, nh = int(ntriggers.value), int(nhits.value)
+        t = self._triggers_gpu[:3 * capacity + 1].get()
+        h = self._trigger_hits_gpu[:6 * n].get()
+        return [self._trigger_rows_gpu[:nrows + 1].get(), t[:nt], t[capacity:capacity + nt], t[2 * capacity:2 * capacity + nt + 1],
+                h[:nh].view(np.int32), h[n:n + nh], h[2 * n:2 * n + nh], h[3 * n:3 * n + nh].view(np.float32), h[4 * n:4 * n + nh], h[5 * n:6 * n]]
+
+    def acquire_pulses(self, gpuphotons, rng_states, bounds, window, acquisition=0, weight=1.0, trigger=None):
         """The time-binned view of ``acquire`` with the same arguments: the same accepted photons, per (event, channel, bin of
         ``window``: a DaqWindow or (t0, dt, nbins)).  Counts first (chroma_daq_count_pulses), then acquires into buffers grown to
-        the largest count seen, ``rows_per_chunk`` events at a time.  Returns an ``EventPulses``."""
+        the largest count seen, ``rows_per_chunk`` events at a time.  Returns an ``EventPulses``.
+
+        ``trigger`` (a DaqTrigger or its tuple): each chunk's pulses are also triggered where they lie on the device, before they
+        are read back (chroma_daq_trigger_pulses), and the result carries ``.triggers``, an ``EventTriggers``.  Events are
+        independent, so it does not depend on the chunking either; the pulses are what they are without it."""
         window = DaqWindow.of(window)
+        if trigger is not None:
+            trigger = DaqTrigger.of(trigger).check(window)
         bounds = np.asarray(bounds)
         if bounds.ndim != 1 or len(bounds) < 1 or not np.issubdtype(bounds.dtype, np.integer):
             raise ValueError('bounds: a 1-D array of at least one photon index')
@@ -381,6 +689,8 @@ class GPUEventDaq(object):
         offsets, outside = [np.zeros(1, dtype=np.int64)], []
         parts = [[] for _ in range(6)]
         total = 0
+        triggered = [[np.zeros(1, dtype=np.int64)] if k in (0, 3) else [] for k in range(10)]
+        ntriggers = nhits = 0
         for first in range(0, nevents, self.rows_per_chunk):
             nrows = min(self.rows_per_chunk, nevents - first)
             b = bounds[first:first + nrows + 1]
@@ -397,8 +707,22 @@ class GPUEventDaq(object):
             outside.append(d_outside[:2 * nrows].get().reshape(nrows, 2))
             for part, a in zip(parts, arrays):
                 part.append(a[:npulses.value].get())
+            if trigger is not None:
+                got = self._trigger_chunk(win, trigger, nrows, d_offsets, arrays, int(npulses.value))
+                triggered[0].append(got[0][1:].astype(np.int64) + ntriggers)
+                triggered[3].append(got[3][1:].astype(np.int64) + nhits)
+                triggered[9].append(np.where(got[9] == NO_TRIGGER, got[9], got[9] + np.uint32(ntriggers & 0xffffffff)).astype(np.uint32))
+                for k in (1, 2, 4, 5, 6, 7, 8):
+                    triggered[k].append(got[k])
+                ntriggers += len(got[1])
+                nhits += len(got[4])
             total += int(npulses.value)
         dtypes = (np.int32, np.uint32, np.uint32, np.uint32, np.float32, np.uint32)
         columns = [np.concatenate(part) if part else np.zeros(0, dtype=dtype) for part, dtype in zip(parts, dtypes)]
         outside = np.concatenate(outside) if outside else np.zeros((0, 2), dtype=np.uint32)
-        return EventPulses(window, self.nchannels, self.charge_unit, np.concatenate(offsets), *columns, outside=outside)
+        pulses = EventPulses(window, self.nchannels, self.charge_unit, np.concatenate(offsets), *columns, outside=outside)
+        if trigger is not None:
+            kinds = (np.int64, np.uint32, np.uint32, np.int64, np.int32, np.uint32, np.uint32, np.float32, np.uint32, np.uint32)
+            pulses.triggers = EventTriggers(window, trigger, self.nchannels, self.charge_unit, pulses.offsets,
+                                            *[np.concatenate(part) if part else np.zeros(0, dtype=dtype) for part, dtype in zip(triggered, kinds)])
+        return pulses

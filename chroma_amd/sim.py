@@ -109,7 +109,7 @@ class Simulation(object):
 
     def _simulate_batch(self, batch_events, keep_photons_beg=False, keep_photons_end=False, keep_hits=True,
                         keep_flat_hits=True, run_daq=False, max_steps=100, verbose=False, uploaded=None, gpu_geometry=None,
-                        daq_window=None):
+                        daq_window=None, daq_trigger=None):
         """Propagate the photons of all ``batch_events`` in one go and split the results
         back per event (by evidx).  Yields the events.  ``uploaded``: what _upload_batch returned for them;
         ``gpu_geometry``: the geometry of the lane this batch runs on (default: the simulation's own)."""
@@ -162,7 +162,7 @@ class Simulation(object):
             if daq_window is not None:
                 # (under the acquisition numbers of the events' channels: both describe the same photoelectrons)
                 event_pulses = self._gpu_event_daq.acquire_pulses(gpu_photons, self.rng_states, bounds, daq_window,
-                                                                  acquisition=self.gpu_daq.acquisition)
+                                                                  acquisition=self.gpu_daq.acquisition, trigger=daq_trigger)
             self.gpu_daq.acquisition += len(batch_events)
         for i, (ev, lo, hi) in enumerate(zip(batch_events, bounds[:-1], bounds[1:])):
             if not keep_photons_beg:
@@ -198,6 +198,8 @@ class Simulation(object):
                 ev.channels = event_channels[i]
                 if event_pulses is not None:
                     ev.pulses = event_pulses.event(i)
+                    if event_pulses.triggers is not None:
+                        ev.triggers = event_pulses.triggers.event(i)
             elif hasattr(self, 'gpu_daq') and run_daq:
                 # (a detector without channels: one acquisition per event, as the reference, chroma/sim.py:128-137)
                 self.gpu_daq.begin_acquire()
@@ -207,18 +209,23 @@ class Simulation(object):
             yield ev
 
     def simulate(self, iterable, keep_photons_beg=False, keep_photons_end=False, keep_hits=True,
-                 keep_flat_hits=True, run_daq=False, max_steps=1000, photons_per_batch=1000000, evid_start=0, daq_window=None):
+                 keep_flat_hits=True, run_daq=False, max_steps=1000, photons_per_batch=1000000, evid_start=0, daq_window=None,
+                 daq_trigger=None):
         """Simulate Photons objects (or Events that already carry ``photons_beg``); events are
         batched until ``photons_per_batch`` photons are collected (chroma/sim.py:141-186).
 
         ``daq_window=(t0, dt, nbins)`` (with ``run_daq=True``, on a detector with channels): besides ``ev.channels`` every event
         gets ``ev.pulses``, the time-binned view of the same photoelectrons (gpu.Pulses: per (channel, bin) npe, charge, earliest
-        time and histories; GPUEventDaq.acquire_pulses).
+        time and histories; GPUEventDaq.acquire_pulses).  ``daq_trigger`` (with ``daq_window``; a gpu.DaqTrigger or (threshold, width[,
+        holdoff, pre, post[, kind]]) in bins): every event also gets ``ev.triggers`` (gpu.Triggers): the firings of a multiplicity
+        or photoelectron trigger on those pulses and the channels in each firing's readout gate.
 
         With ``Simulation(prefetch=True)`` (the default) the NEXT batch is taken from ``iterable`` and uploaded by a second
         thread while the current one propagates: the iterable is consumed one batch ahead of the events this generator
         yields.  An iterable whose items share buffers, or depend on results already yielded, needs ``prefetch=False``;
         ``keep_photons_beg=True`` turns the read-ahead off by itself (the reference's loop is lazy, chroma/sim.py:141-186)."""
+        if daq_trigger is not None and daq_window is None:
+            raise ValueError('daq_trigger needs daq_window')          # (before anything is looked at)
         if isinstance(iterable, event.Photons):
             first, iterable = iterable, [iterable]
         else:
@@ -237,8 +244,10 @@ class Simulation(object):
             if not hasattr(self, 'gpu_daq') or self.gpu_geometry.nchannels < 1:
                 raise ValueError('daq_window needs a detector with channels')
             daq_window = gpu.DaqWindow.of(daq_window)
+            if daq_trigger is not None:
+                daq_trigger = gpu.DaqTrigger.of(daq_trigger).check(daq_window)
         kwargs = dict(keep_photons_beg=keep_photons_beg, keep_photons_end=keep_photons_end, keep_hits=keep_hits,
-                      keep_flat_hits=keep_flat_hits, run_daq=run_daq, max_steps=max_steps, daq_window=daq_window)
+                      keep_flat_hits=keep_flat_hits, run_daq=run_daq, max_steps=max_steps, daq_window=daq_window, daq_trigger=daq_trigger)
         if isinstance(first, event.Event) and first.photons_beg is None:
             yield from self._simulate_stepped(iterable, photons_per_batch, evid_start, kwargs)
             return

@@ -493,6 +493,75 @@ int chroma_daq_acquire_pulses(chroma_ctx *ctx, chroma_geometry *geom, const chro
                               uint64_t capacity, uint32_t *d_offsets, int32_t *d_channel, uint32_t *d_bin,
                               uint32_t *d_npe, uint32_t *d_q_int, float *d_t_first, uint32_t *d_flags,
                               uint32_t *d_outside, uint64_t *npulses);
+/* ---- the trigger of the time-binned DAQ: firings and their readout gates ------------------------
+ * A second, purely integer stage on the pulses of chroma_daq_acquire_pulses (no random draws): a
+ * multiplicity or photoelectron sum over a sliding coincidence window, a level trigger with lockout on
+ * it, and per firing the pulses of its readout gate, reduced per channel.
+ *
+ * The sum.  For row r and bin b, with W = width:
+ *   CHROMA_TRIGGER_NHIT  S(r, b) = the number of DISTINCT channels of row r that have a pulse in a bin p
+ *                        with b - W < p <= b;
+ *   CHROMA_TRIGGER_NPE   S(r, b) = the sum of npe over row r's pulses with b - W < p <= b (exact below
+ *                        2^32; it wraps beyond).
+ * The firing rule.  Per row, next = 0; through b = 0 .. nbins - 1 ascending the trigger fires at b iff
+ * S(r, b) >= threshold and b >= next, and then next = b + holdoff.  A level trigger with lockout: it
+ * fires again after the lockout while the sum is still at or above threshold.  The gate of a firing at
+ * bin b is the bins [b - pre, b + post), clipped to [0, nbins); holdoff >= pre + post, so the gates of
+ * one row never overlap and a pulse lies in one gate at the most. */
+#define CHROMA_TRIGGER_NHIT 0
+#define CHROMA_TRIGGER_NPE 1
+typedef struct chroma_daq_trigger {   /* 24 bytes, all in BINS of the window */
+    uint32_t kind;        /* CHROMA_TRIGGER_NHIT = 0: channels; CHROMA_TRIGGER_NPE = 1: photoelectrons */
+    uint32_t threshold;   /* >= 1 */
+    uint32_t width;       /* W, the coincidence window: 1 .. nbins */
+    uint32_t holdoff;     /* H, bins from one firing to the next possible one: >= max(1, pre + post) */
+    uint32_t pre, post;   /* the gate of a firing at bin b: bins [b - pre, b + post), clipped to [0, nbins); post >= 1 */
+} chroma_daq_trigger;
+/* Input: the pulses of `nrows` rows as chroma_daq_acquire_pulses writes them -- d_offsets (nrows + 1
+ * words) and, per pulse, d_channel, d_bin, d_npe, d_q_int, d_t_first and d_flags (npulses entries, in
+ * ascending (row, channel, bin) order) -- the window they were binned with and the number of channels.
+ *
+ * Output, its order from scans and a sort, never from the arrival order of atomics:
+ *   triggers, in (row, bin) order: row r the entries [d_trig_offsets[r], d_trig_offsets[r + 1])
+ *     (nrows + 1 words) of d_trig_bin and d_trig_sum (S at the firing bin), `trigger_capacity` entries
+ *     each; d_hit_offsets, trigger_capacity + 1 words of which *ntriggers + 1 are written;
+ *   gated hits, in (trigger, channel) order: trigger k the entries [d_hit_offsets[k],
+ *     d_hit_offsets[k + 1]) of d_hit_channel, d_hit_npe, d_hit_q_int, d_hit_t_first and d_hit_flags
+ *     (`hit_capacity` entries each) -- one entry per (trigger, channel) with at least one pulse of the
+ *     trigger's row in its gate: the sum of their npe, the wrapping sum of their q_int, the smallest of
+ *     their t_first as floats (-0 below +0) and the OR of their flags.  A trigger may have no hit (a
+ *     gate shorter than the coincidence window);
+ *   d_pulse_trigger (npulses words, or NULL): per pulse the index of the trigger whose gate holds it,
+ *     or 0xffffffff.
+ *
+ * Capacities.  nrows * ceil(nbins / holdoff) triggers always suffice, and so do npulses *
+ * ceil(width / holdoff) (a pulse holds the sum up for `width` bins); npulses hits always suffice.  If
+ * either capacity is too small NOTHING is written, *ntriggers and *nhits hold what is needed and the
+ * call is CHROMA_ERR_INVALID.
+ *
+ * Refused, CHROMA_ERR_INVALID before anything is launched: a window the pulse calls refuse; nrows or
+ * nchannels of 0; threshold == 0; width outside 1 .. nbins; post == 0; holdoff < max(1, pre + post); an
+ * unknown kind; npulses of 2^31 - 1 or more (so of 2^32 or more), nrows * nbins of 2^31 or more; a NULL
+ * array that is needed (the pulse arrays when npulses, the trigger arrays when trigger_capacity, the hit
+ * arrays when hit_capacity; d_offsets, d_trig_offsets, d_hit_offsets, ntriggers and nhits always).
+ *
+ * npulses == 0 is CHROMA_OK with all offsets zero.  A pulse whose bin is >= nbins, whose channel is
+ * outside [0, nchannels) or which the offsets put in no row contributes nothing, indexes nothing and
+ * has 0xffffffff in d_pulse_trigger.  Input that is not in (row, channel, bin) order gives unspecified
+ * values, but no access outside the caller's arrays and the call's scratch.
+ *
+ * Runs on the context's stream and returns when the arrays are written.  Scratch is the context's
+ * pooled per-call block: 4 bytes per (row, bin) for the sum, some 50 bytes per pulse, 8 bytes per
+ * trigger of the bound above. */
+int chroma_daq_trigger_pulses(chroma_ctx *ctx, uint32_t nrows, uint32_t nchannels, const chroma_daq_window *window,
+                              const chroma_daq_trigger *trigger, const uint32_t *d_offsets, const int32_t *d_channel,
+                              const uint32_t *d_bin, const uint32_t *d_npe, const uint32_t *d_q_int,
+                              const float *d_t_first, const uint32_t *d_flags, uint64_t npulses,
+                              uint64_t trigger_capacity, uint32_t *d_trig_offsets, uint32_t *d_trig_bin,
+                              uint32_t *d_trig_sum, uint32_t *d_hit_offsets, uint64_t hit_capacity,
+                              int32_t *d_hit_channel, uint32_t *d_hit_npe, uint32_t *d_hit_q_int,
+                              float *d_hit_t_first, uint32_t *d_hit_flags, uint32_t *d_pulse_trigger,
+                              uint64_t *ntriggers, uint64_t *nhits);
 /* `convert_sortable_int_to_float` + `convert_charge_int_to_float` (daq.cu:152-173) */
 int chroma_daq_convert(chroma_ctx *ctx, uint32_t nchannels, float charge_unit, const uint32_t *d_earliest_time_int,
                        const uint32_t *d_channel_q_int, float *d_earliest_time, float *d_channel_q);
