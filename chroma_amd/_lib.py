@@ -106,6 +106,11 @@ class DaqWindow(Structure):
     _fields_ = [('t0', c_float), ('dt', c_float), ('nbins', c_uint32)]
 
 
+class DaqNoise(Structure):
+    """chroma_daq_noise"""
+    _fields_ = [('count_cdf', c_void_p), ('ncount', c_uint32), ('d_accept', c_void_p), ('flag', c_uint32)]
+
+
 class DaqTrigger(Structure):
     """chroma_daq_trigger"""
     _fields_ = [('kind', c_uint32), ('threshold', c_uint32), ('width', c_uint32), ('holdoff', c_uint32), ('pre', c_uint32),
@@ -199,6 +204,14 @@ SIGNATURES = {
     'chroma_daq_acquire_pulses': (c_int32, [c_void_p, c_void_p, POINTER(DaqTables), c_uint32, c_void_p, c_uint32, POINTER(PhotonArrays),
                                             c_uint32, Rng, c_uint32, c_float, POINTER(DaqWindow), c_uint64, c_void_p, c_void_p, c_void_p,
                                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_uint64)]),
+    'chroma_daq_count_pulses_noise': (c_int32, [c_void_p, c_void_p, POINTER(DaqTables), c_uint32, c_void_p, c_uint32, POINTER(PhotonArrays),
+                                                c_uint32, Rng, c_uint32, c_float, POINTER(DaqWindow), POINTER(DaqNoise), POINTER(c_uint64)]),
+    'chroma_daq_acquire_pulses_noise': (c_int32, [c_void_p, c_void_p, POINTER(DaqTables), c_uint32, c_void_p, c_uint32, POINTER(PhotonArrays),
+                                                  c_uint32, Rng, c_uint32, c_float, POINTER(DaqWindow), POINTER(DaqNoise), c_uint64, c_void_p,
+                                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                  POINTER(c_uint64)]),
+    'chroma_daq_noise_host': (c_int32, [POINTER(DaqTables), POINTER(DaqWindow), POINTER(DaqNoise), c_uint32, c_uint32, c_uint64, c_uint32,
+                                        c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_uint64)]),
     'chroma_daq_trigger_pulses': (c_int32, [c_void_p, c_uint32, c_uint32, POINTER(DaqWindow), POINTER(DaqTrigger), c_void_p, c_void_p, c_void_p,
                                             c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p,
                                             c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_uint64),

@@ -5,7 +5,7 @@ GEANT4 and writes a ROOT file; neither GEANT4 nor ROOT is part of this engine, s
 keeps the command-line shape (detector string, -n/--nevents, -o/--output, -s/--seed, -j device)
 but the particle source is the isotropic photon bomb of chroma/benchmark.py:77-83 and the output is
 an ``.npz``: per event the flat hits (channel, t, wavelength, pos, flags), with --run-daq the channel
-times and charges, with --daq-window T0,DT,NBINS also the pulses per (channel, time bin), with --daq-trigger the triggers on them, with --save-photons-beg/--save-photons-end the photons themselves and with --track or
+times and charges, with --daq-window T0,DT,NBINS also the pulses per (channel, time bin), with --daq-trigger the triggers on them, with --daq-noise RATE_HZ dark noise among them, with --save-photons-beg/--save-photons-end the photons themselves and with --track or
 --device-tracks every photon's state after each step.
 """
 import argparse
@@ -52,6 +52,8 @@ def main(argv=None):
                     help='with --daq-window, also write the triggers on the pulses: the firings of a sum over WIDTH bins that reaches THRESHOLD, '
                          'HOLDOFF bins apart at the least, and the channels in each gate of PRE bins before to POST bins from the firing')
     ap.add_argument('--daq-trigger-kind', default='nhit', choices=('nhit', 'npe'), help='what the trigger sums: distinct channels or photoelectrons')
+    ap.add_argument('--daq-noise', default=None, type=float, metavar='RATE_HZ',
+                    help='with --daq-window, add PMT dark noise of RATE_HZ per channel to the pulses (and to what the trigger sees)')
     ap.add_argument('--save-photons-beg', action='store_true', help='also write the initial photons of every event (bin/chroma-sim:51-53)')
     ap.add_argument('--save-photons-end', action='store_true', help='also write the final photons of every event (bin/chroma-sim:54-56)')
     ap.add_argument('--track', action='store_true', help='also write every photon\'s state after each step (Simulation(photon_tracking=True))')
@@ -84,6 +86,11 @@ def main(argv=None):
             daq_trigger = DaqTrigger(*[int(x) for x in parts], kind=args.daq_trigger_kind)
         except ValueError as e:
             ap.error('--daq-trigger: %s' % e)
+    if args.daq_noise is not None:
+        if daq_window is None:
+            ap.error('--daq-noise needs --daq-window')
+        if not (args.daq_noise >= 0.0 and args.daq_noise < float('inf')):
+            ap.error('--daq-noise takes a finite rate that is not negative')
     t0 = time.time()
     detector = load_geometry_from_string(args.detector, cache_dir=args.cache_dir)
     print('geometry: %d triangles, BVH %d nodes (%.1f s)' % (len(detector.mesh.triangles), len(detector.bvh.nodes), time.time() - t0))
@@ -96,7 +103,8 @@ def main(argv=None):
     nhits = 0
     for ev in sim.simulate(events, keep_photons_beg=args.save_photons_beg, keep_photons_end=args.save_photons_end,
                            keep_hits=False, keep_flat_hits=hasattr(detector, 'num_channels'),
-                           run_daq=args.run_daq, max_steps=args.max_steps, daq_window=daq_window, daq_trigger=daq_trigger):
+                           run_daq=args.run_daq, max_steps=args.max_steps, daq_window=daq_window, daq_trigger=daq_trigger,
+                           daq_noise=args.daq_noise):
         key = 'ev%d' % ev.id
         for tag, ph in (('photons_beg', ev.photons_beg), ('photons_end', ev.photons_end)):
             if ph is not None:
@@ -135,6 +143,9 @@ def main(argv=None):
             out[key + '/pulse_q'] = ev.pulses.q
             out[key + '/pulse_t'] = ev.pulses.t_first
             out[key + '/pulse_outside'] = np.array([ev.pulses.early, ev.pulses.late], dtype=np.uint32)
+            if args.daq_noise is not None:
+                out[key + '/pulse_flags'] = ev.pulses.flags
+                out[key + '/pulse_noise'] = np.array(ev.pulses.noise, dtype=np.uint32)
         if ev.triggers is not None:
             out[key + '/trigger_bin'] = ev.triggers.bin
             out[key + '/trigger_time'] = ev.triggers.time

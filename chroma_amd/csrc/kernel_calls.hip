@@ -16,6 +16,7 @@
 #include "kernels_daq_render.h"
 
 #include "kernels_daq_pulses.h"
+#include "kernels_daq_noise.h"
 
 #include "kernels_daq_trigger.h"
 
@@ -510,22 +511,74 @@ static int pulses_block(const CallScope &scope, size_t need, uint32_t nrows, con
     return CHROMA_OK;
 }
 
-// the accepted in-window photons of the window (k_daq_pulses_count), with the bounds already in the block
+// what the calls with noise refuse besides (noise NULL: nothing)
+static int check_pulses_noise(const chroma_geometry *geom, uint32_t nrows, uint32_t nphotons, chroma_rng rng, const chroma_daq_noise *noise)
+{
+    if (!noise) return CHROMA_OK;
+    if (const char *why = daq_noise::check(noise)) return set_error(CHROMA_ERR_INVALID, "%s", why);
+    if ((uint64_t)nrows * geom->view.nchannels > 0xffffffffull)
+        return set_error(CHROMA_ERR_INVALID, "DAQ noise: %u rows of %u channels: more than 32-bit word indices hold, pass fewer rows", nrows, geom->view.nchannels);
+    const uint64_t last_id = rng.photon_id_base + (nphotons ? nphotons - 1u : 0u);
+    if (nphotons && ((rng.photon_id_base >> 32) == daq_noise::ID_HIGH || (last_id >> 32) == daq_noise::ID_HIGH || last_id < rng.photon_id_base))
+        return set_error(CHROMA_ERR_INVALID, "DAQ noise: the photon ids reach the high word 0xffffffff of the noise's pseudo-photons");
+    return CHROMA_OK;
+}
+
+static DaqNoiseView noise_view(const chroma_daq_noise *noise)
+{
+    DaqNoiseView v;
+    for (uint32_t j = 0; j < 64u; j++) v.count_cdf[j] = j < noise->ncount ? noise->count_cdf[j] : 0xffffffffu;
+    v.ncount = noise->ncount;
+    v.flag = noise->flag;
+    v.accept = noise->d_accept;
+    return v;
+}
+
+// The accepted in-window photons of the window (k_daq_pulses_count) and, with `noise`, the kept noise photoelectrons of the rows'
+// words (k_daq_noise_count), with the bounds already in the block.  The counters: word 0 the photons, word 1 the emits' cursor,
+// the 64-bit word behind them the noise.
 static int pulses_count(const CallScope &scope, chroma_geometry *geom, const chroma_daq_tables *tables, uint32_t nrows, uint32_t span,
                         uint32_t detection_state, const chroma_photon_arrays *photons, chroma_rng rng, uint32_t acquisition,
-                        float global_weight, const chroma_daq_window *window, uint32_t *naccepted)
+                        float global_weight, const chroma_daq_window *window, const chroma_daq_noise *noise, uint64_t *naccepted)
 {
     hipStream_t stream = scope.ctx->stream;
     const uint32_t *d_bounds = (const uint32_t *)scope.state().steps_scratch;
     uint32_t *d_count = (uint32_t *)((char *)scope.state().steps_scratch + round256(((size_t)nrows + 1) * sizeof(uint32_t)));
-    HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(uint32_t), stream));
-    hipLaunchKernelGGL(k_daq_pulses_count, dim3((span + DAQ_PULSES_SPAN - 1) / DAQ_PULSES_SPAN), dim3(DAQ_PULSES_BLOCK), 0, stream, geom->view,
-                       *tables, *window, nrows, d_bounds, detection_state, photons->t, photons->flags, photons->last_hit_triangles,
-                       photons->weights, rng.seed, rng.photon_id_base, acquisition, global_weight, d_count);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(naccepted, d_count, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemsetAsync(d_count, 0, 4 * sizeof(uint32_t), stream));
+    if (span) {
+        hipLaunchKernelGGL(k_daq_pulses_count, dim3((span + DAQ_PULSES_SPAN - 1) / DAQ_PULSES_SPAN), dim3(DAQ_PULSES_BLOCK), 0, stream, geom->view,
+                           *tables, *window, nrows, d_bounds, detection_state, photons->t, photons->flags, photons->last_hit_triangles,
+                           photons->weights, rng.seed, rng.photon_id_base, acquisition, global_weight, d_count);
+        HIP_TRY(hipGetLastError());
+    }
+    if (noise) {
+        const uint32_t nwords = nrows * geom->view.nchannels;
+        hipLaunchKernelGGL(k_daq_noise_count, dim3((nwords + DAQ_NOISE_SPAN - 1) / DAQ_NOISE_SPAN), dim3(DAQ_PULSES_BLOCK), 0, stream,
+                           noise_view(noise), geom->view.nchannels, nwords, rng.seed, acquisition, (unsigned long long *)(d_count + 2));
+        HIP_TRY(hipGetLastError());
+    }
+    uint32_t counts[4] = {0u, 0u, 0u, 0u};
+    HIP_TRY(hipMemcpyAsync(counts, d_count, sizeof(counts), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
+    *naccepted = (uint64_t)counts[0] + (((uint64_t)counts[3] << 32) | counts[2]);
     return CHROMA_OK;
+}
+
+// chroma_daq_count_pulses and chroma_daq_count_pulses_noise
+static int count_pulses(chroma_ctx *ctx, chroma_geometry *geom, const chroma_daq_tables *tables, uint32_t nrows, const uint32_t *bounds,
+                        uint32_t detection_state, const chroma_photon_arrays *photons, uint32_t nphotons, chroma_rng rng,
+                        uint32_t acquisition, float global_weight, const chroma_daq_window *window, const chroma_daq_noise *noise,
+                        uint64_t *naccepted)
+{
+    if (!naccepted) return set_error(CHROMA_ERR_INVALID, "bad argument");
+    int rc = check_pulses_call(ctx, geom, tables, nrows, bounds, photons, nphotons, window); if (rc) return rc;
+    rc = check_pulses_noise(geom, nrows, nphotons, rng, noise); if (rc) return rc;
+    *naccepted = 0;
+    const uint32_t span = bounds[nrows] - bounds[0];
+    if (span == 0 && !noise) return CHROMA_OK;
+    const CallScope scope(ctx);
+    rc = pulses_block(scope, round256(((size_t)nrows + 1) * sizeof(uint32_t)) + 256, nrows, bounds, false); if (rc) return rc;
+    return pulses_count(scope, geom, tables, nrows, span, detection_state, photons, rng, acquisition, global_weight, window, noise, naccepted);
 }
 
 int chroma_daq_count_pulses(chroma_ctx *ctx, chroma_geometry *geom, const chroma_daq_tables *tables, uint32_t nrows,
@@ -533,46 +586,56 @@ int chroma_daq_count_pulses(chroma_ctx *ctx, chroma_geometry *geom, const chroma
                             chroma_rng rng, uint32_t acquisition, float global_weight, const chroma_daq_window *window,
                             uint64_t *naccepted)
 {
-    if (!naccepted) return set_error(CHROMA_ERR_INVALID, "bad argument");
-    int rc = check_pulses_call(ctx, geom, tables, nrows, bounds, photons, nphotons, window); if (rc) return rc;
-    *naccepted = 0;
-    const uint32_t span = bounds[nrows] - bounds[0];
-    if (span == 0) return CHROMA_OK;
-    const CallScope scope(ctx);
-    rc = pulses_block(scope, round256(((size_t)nrows + 1) * sizeof(uint32_t)) + 256, nrows, bounds, false); if (rc) return rc;
-    uint32_t n = 0;
-    rc = pulses_count(scope, geom, tables, nrows, span, detection_state, photons, rng, acquisition, global_weight, window, &n);
-    *naccepted = n;
-    return rc;
+    return count_pulses(ctx, geom, tables, nrows, bounds, detection_state, photons, nphotons, rng, acquisition, global_weight, window, nullptr,
+                        naccepted);
 }
 
-int chroma_daq_acquire_pulses(chroma_ctx *ctx, chroma_geometry *geom, const chroma_daq_tables *tables, uint32_t nrows,
-                              const uint32_t *bounds, uint32_t detection_state, const chroma_photon_arrays *photons, uint32_t nphotons,
-                              chroma_rng rng, uint32_t acquisition, float global_weight, const chroma_daq_window *window,
-                              uint64_t capacity, uint32_t *d_offsets, int32_t *d_channel, uint32_t *d_bin, uint32_t *d_npe,
-                              uint32_t *d_q_int, float *d_t_first, uint32_t *d_flags, uint32_t *d_outside, uint64_t *npulses)
+int chroma_daq_count_pulses_noise(chroma_ctx *ctx, chroma_geometry *geom, const chroma_daq_tables *tables, uint32_t nrows,
+                                  const uint32_t *bounds, uint32_t detection_state, const chroma_photon_arrays *photons, uint32_t nphotons,
+                                  chroma_rng rng, uint32_t acquisition, float global_weight, const chroma_daq_window *window,
+                                  const chroma_daq_noise *noise, uint64_t *naccepted)
+{
+    return count_pulses(ctx, geom, tables, nrows, bounds, detection_state, photons, nphotons, rng, acquisition, global_weight, window, noise,
+                        naccepted);
+}
+
+// chroma_daq_acquire_pulses and chroma_daq_acquire_pulses_noise
+static int acquire_pulses(chroma_ctx *ctx, chroma_geometry *geom, const chroma_daq_tables *tables, uint32_t nrows, const uint32_t *bounds,
+                          uint32_t detection_state, const chroma_photon_arrays *photons, uint32_t nphotons, chroma_rng rng,
+                          uint32_t acquisition, float global_weight, const chroma_daq_window *window, const chroma_daq_noise *noise,
+                          uint64_t capacity, uint32_t *d_offsets, int32_t *d_channel, uint32_t *d_bin, uint32_t *d_npe, uint32_t *d_q_int,
+                          float *d_t_first, uint32_t *d_flags, uint32_t *d_outside, uint32_t *d_row_noise, uint64_t *npulses)
 {
     if (!d_offsets || !d_outside || !npulses || (capacity && (!d_channel || !d_bin || !d_npe || !d_q_int || !d_t_first || !d_flags)))
         return set_error(CHROMA_ERR_INVALID, "bad argument");
     int rc = check_pulses_call(ctx, geom, tables, nrows, bounds, photons, nphotons, window); if (rc) return rc;
+    rc = check_pulses_noise(geom, nrows, nphotons, rng, noise); if (rc) return rc;
     *npulses = 0;
     hipStream_t stream = ctx->stream;
     const size_t offsets_bytes = ((size_t)nrows + 1) * sizeof(uint32_t), outside_bytes = 2 * (size_t)nrows * sizeof(uint32_t);
+    const size_t row_noise_bytes = (size_t)nrows * sizeof(uint32_t);
     const uint32_t span = bounds[nrows] - bounds[0];
-    if (span == 0) {
+    if (span == 0 && !noise) {
         HIP_TRY(hipMemsetAsync(d_offsets, 0, offsets_bytes, stream));
         HIP_TRY(hipMemsetAsync(d_outside, 0, outside_bytes, stream));
+        if (d_row_noise) HIP_TRY(hipMemsetAsync(d_row_noise, 0, row_noise_bytes, stream));
         HIP_TRY(hipStreamSynchronize(stream));
         return CHROMA_OK;
     }
     const CallScope scope(ctx);
-    const size_t head_bytes = round256(offsets_bytes) + 256;          // the bounds and the counters (word 0: the count, then the emit's cursor)
-    rc = pulses_block(scope, head_bytes + round256(outside_bytes), nrows, bounds, false); if (rc) return rc;
-    uint32_t n = 0;
-    rc = pulses_count(scope, geom, tables, nrows, span, detection_state, photons, rng, acquisition, global_weight, window, &n); if (rc) return rc;
-    if (n >= 0x7fffffffu) return set_error(CHROMA_ERR_INVALID, "%u accepted photons: more than the scan's 31-bit count holds, pass fewer rows", n);
-    // the block: bounds, counters, the rows' early and late counts; then, per accepted photon, the keys and their positions before and
-    // behind the sort, charge count, time bits and history; the heads (n + 1); the workspaces of the sort and of the scan
+    const size_t head_bytes = round256(offsets_bytes) + 256;          // the bounds and the counters (pulses_count)
+    const size_t rows_bytes = round256(outside_bytes + row_noise_bytes);          // per row: early and late photons, then the noise
+    rc = pulses_block(scope, head_bytes + rows_bytes, nrows, bounds, false); if (rc) return rc;
+    uint64_t accepted = 0;
+    rc = pulses_count(scope, geom, tables, nrows, span, detection_state, photons, rng, acquisition, global_weight, window, noise, &accepted);
+    if (rc) return rc;
+    if (accepted >= 0x7fffffffull)
+        return set_error(CHROMA_ERR_INVALID, "%llu accepted photons and noise photoelectrons: more than the scan's 31-bit count holds, pass fewer rows",
+                         (unsigned long long)accepted);
+    const uint32_t n = (uint32_t)accepted;
+    // the block: bounds, counters, the rows' early, late and noise counts; then, per accepted photon and noise photoelectron, the keys
+    // and their positions before and behind the sort, charge count, time bits and history; the heads (n + 1); the workspaces of the
+    // sort and of the scan
     const uint64_t nkeys = (uint64_t)nrows * geom->view.nchannels * window->nbins;
     int end_bit = 1;
     while (end_bit < 64 && ((nkeys - 1) >> end_bit)) end_bit++;
@@ -583,13 +646,13 @@ int chroma_daq_acquire_pulses(chroma_ctx *ctx, chroma_geometry *geom, const chro
         HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, v, v, (int)(n + 1), stream));
     }
     const size_t key_bytes = round256((size_t)n * sizeof(uint64_t)), word_bytes = round256((size_t)n * sizeof(uint32_t));
-    const size_t need = head_bytes + round256(outside_bytes) + 2 * key_bytes + 5 * word_bytes + round256(((size_t)n + 1) * sizeof(uint32_t)) +
+    const size_t need = head_bytes + rows_bytes + 2 * key_bytes + 5 * word_bytes + round256(((size_t)n + 1) * sizeof(uint32_t)) +
                         round256(sort_bytes) + round256(scan_bytes);
     rc = pulses_block(scope, need, nrows, bounds, true); if (rc) return rc;
     char *p = (char *)scope.state().steps_scratch;
     const uint32_t *d_bounds = (const uint32_t *)p; p += round256(offsets_bytes);
     uint32_t *d_cursor = (uint32_t *)p + 1; p += 256;
-    uint32_t *d_rows_outside = (uint32_t *)p; p += round256(outside_bytes);
+    uint32_t *d_rows_outside = (uint32_t *)p, *d_rows_noise = d_rows_outside + 2 * (size_t)nrows; p += rows_bytes;
     uint64_t *d_keys = (uint64_t *)p; p += key_bytes;
     uint64_t *d_keys_sorted = (uint64_t *)p; p += key_bytes;
     uint32_t *d_order = (uint32_t *)p; p += word_bytes;
@@ -601,12 +664,22 @@ int chroma_daq_acquire_pulses(chroma_ctx *ctx, chroma_geometry *geom, const chro
     void *d_sort = p; p += round256(sort_bytes);
     void *d_scan = p;
     HIP_TRY(hipMemsetAsync(d_cursor, 0, sizeof(uint32_t), stream));
-    HIP_TRY(hipMemsetAsync(d_rows_outside, 0, outside_bytes, stream));
-    hipLaunchKernelGGL(k_daq_pulses_emit, dim3((span + DAQ_PULSES_SPAN - 1) / DAQ_PULSES_SPAN), dim3(DAQ_PULSES_BLOCK), 0, stream, geom->view,
-                       *tables, *window, nrows, d_bounds, detection_state, photons->t, photons->flags, photons->last_hit_triangles,
-                       photons->weights, rng.seed, rng.photon_id_base, acquisition, global_weight, n, d_cursor, d_keys, d_order, d_charge,
-                       d_time, d_history, d_rows_outside);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemsetAsync(d_rows_outside, 0, outside_bytes + row_noise_bytes, stream));
+    // both emits before the sort, onto one cursor: the photons' entries and the noise's lie among one another
+    if (span) {
+        hipLaunchKernelGGL(k_daq_pulses_emit, dim3((span + DAQ_PULSES_SPAN - 1) / DAQ_PULSES_SPAN), dim3(DAQ_PULSES_BLOCK), 0, stream, geom->view,
+                           *tables, *window, nrows, d_bounds, detection_state, photons->t, photons->flags, photons->last_hit_triangles,
+                           photons->weights, rng.seed, rng.photon_id_base, acquisition, global_weight, n, d_cursor, d_keys, d_order, d_charge,
+                           d_time, d_history, d_rows_outside);
+        HIP_TRY(hipGetLastError());
+    }
+    if (noise) {
+        const uint32_t nwords = nrows * geom->view.nchannels;
+        hipLaunchKernelGGL(k_daq_noise_emit, dim3((nwords + DAQ_NOISE_SPAN - 1) / DAQ_NOISE_SPAN), dim3(DAQ_PULSES_BLOCK), 0, stream,
+                           noise_view(noise), *tables, *window, geom->view.nchannels, nwords, rng.seed, acquisition, n, d_cursor, d_keys, d_order,
+                           d_charge, d_time, d_history, d_rows_noise);
+        HIP_TRY(hipGetLastError());
+    }
     uint32_t total = 0;
     if (n) {
         const dim3 grid((n + 1 + DAQ_PULSES_BLOCK - 1) / DAQ_PULSES_BLOCK), block(DAQ_PULSES_BLOCK);
@@ -631,8 +704,30 @@ int chroma_daq_acquire_pulses(chroma_ctx *ctx, chroma_geometry *geom, const chro
         HIP_TRY(hipMemsetAsync(d_offsets, 0, offsets_bytes, stream));
     }
     HIP_TRY(hipMemcpyAsync(d_outside, d_rows_outside, outside_bytes, hipMemcpyDeviceToDevice, stream));
+    if (d_row_noise) HIP_TRY(hipMemcpyAsync(d_row_noise, d_rows_noise, row_noise_bytes, hipMemcpyDeviceToDevice, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     return CHROMA_OK;
+}
+
+int chroma_daq_acquire_pulses(chroma_ctx *ctx, chroma_geometry *geom, const chroma_daq_tables *tables, uint32_t nrows,
+                              const uint32_t *bounds, uint32_t detection_state, const chroma_photon_arrays *photons, uint32_t nphotons,
+                              chroma_rng rng, uint32_t acquisition, float global_weight, const chroma_daq_window *window,
+                              uint64_t capacity, uint32_t *d_offsets, int32_t *d_channel, uint32_t *d_bin, uint32_t *d_npe,
+                              uint32_t *d_q_int, float *d_t_first, uint32_t *d_flags, uint32_t *d_outside, uint64_t *npulses)
+{
+    return acquire_pulses(ctx, geom, tables, nrows, bounds, detection_state, photons, nphotons, rng, acquisition, global_weight, window, nullptr,
+                          capacity, d_offsets, d_channel, d_bin, d_npe, d_q_int, d_t_first, d_flags, d_outside, nullptr, npulses);
+}
+
+int chroma_daq_acquire_pulses_noise(chroma_ctx *ctx, chroma_geometry *geom, const chroma_daq_tables *tables, uint32_t nrows,
+                                    const uint32_t *bounds, uint32_t detection_state, const chroma_photon_arrays *photons, uint32_t nphotons,
+                                    chroma_rng rng, uint32_t acquisition, float global_weight, const chroma_daq_window *window,
+                                    const chroma_daq_noise *noise, uint64_t capacity, uint32_t *d_offsets, int32_t *d_channel,
+                                    uint32_t *d_bin, uint32_t *d_npe, uint32_t *d_q_int, float *d_t_first, uint32_t *d_flags,
+                                    uint32_t *d_outside, uint32_t *d_row_noise, uint64_t *npulses)
+{
+    return acquire_pulses(ctx, geom, tables, nrows, bounds, detection_state, photons, nphotons, rng, acquisition, global_weight, window, noise,
+                          capacity, d_offsets, d_channel, d_bin, d_npe, d_q_int, d_t_first, d_flags, d_outside, d_row_noise, npulses);
 }
 
 // ---- the trigger of the time-binned DAQ (kernels_daq_trigger.h) ----

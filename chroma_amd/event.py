@@ -20,6 +20,7 @@ SURFACE_TRANSMIT = 0x1 << 8
 BULK_REEMIT = 0x1 << 9
 CHERENKOV = 0x1 << 10
 SCINTILLATION = 0x1 << 11
+DARK_NOISE = 0x1 << 12          # a PMT's dark count among a pulse's photoelectrons (gpu.DaqNoise): no photon made it
 NAN_ABORT = 0x1 << 31
 
 TERMINAL_MASK = NO_HIT | BULK_ABSORB | SURFACE_DETECT | SURFACE_ABSORB | NAN_ABORT

@@ -15,7 +15,9 @@ acquisition over a row of channels per event and reads the touched words back sp
 of their histories, only the bins that hold something (``EventPulses``, per event ``Pulses``).  With a ``DaqTrigger`` the pulses are
 triggered where they lie on the device (chroma_daq_trigger_pulses): the firings of a multiplicity or photoelectron sum over a
 coincidence window, and per firing the channels of its readout gate (``EventTriggers``, per event ``Triggers``);
-``EventPulses.trigger`` is the same computed in NumPy on the host arrays.
+``EventPulses.trigger`` is the same computed in NumPy on the host arrays.  With a ``DaqNoise`` the PMTs' dark counts are drawn on
+the device as further photoelectrons of the pulses (chroma_daq_acquire_pulses_noise), flagged ``event.DARK_NOISE``, and reach
+the trigger like any other; ``DaqNoise.sample`` draws the same ones on the host.
 """
 import ctypes
 
@@ -209,13 +211,15 @@ class DaqWindow(object):
 class Pulses(object):
     """The pulses of ONE event (``EventPulses.event(i)``, ``ev.pulses``): per (channel, time bin) that holds an accepted photon, in
     (channel, bin) order, ``npe`` photoelectrons of charge ``q`` (``q_int`` counts of the charge unit), the earliest at
-    ``t_first``, ``flags`` the OR of their histories; ``early`` and ``late``: the accepted photons before and behind the window."""
+    ``t_first``, ``flags`` the OR of their histories; ``early`` and ``late``: the accepted photons before and behind the window;
+    ``noise``: the dark-noise photoelectrons among the event's (0 without a ``DaqNoise``)."""
 
-    def __init__(self, window, nchannels, channel, bin, npe, q, q_int, t_first, flags, early, late):
+    def __init__(self, window, nchannels, channel, bin, npe, q, q_int, t_first, flags, early, late, noise=0):
         self.window = window
         self.nchannels = nchannels
         self.channel, self.bin, self.npe, self.q, self.q_int, self.t_first, self.flags = channel, bin, npe, q, q_int, t_first, flags
         self.early, self.late = early, late
+        self.noise = noise
 
     def __len__(self):
         return len(self.channel)
@@ -239,9 +243,10 @@ class Pulses(object):
 class EventPulses(object):
     """What ``GPUEventDaq.acquire_pulses`` returns: the pulses of every event of a batch in (event, channel, bin) order --
     ``channel`` (int32), ``bin``, ``npe``, ``q_int``, ``flags`` (uint32) and ``t_first`` (float32), ``offsets`` (len + 1) the
-    events' places in them, ``outside`` (len x 2) their early and late photons.  ``len()`` is the number of events."""
+    events' places in them, ``outside`` (len x 2) their early and late photons, ``noise`` (len, uint32) the dark-noise
+    photoelectrons of every event (zeros without a ``DaqNoise``).  ``len()`` is the number of events."""
 
-    def __init__(self, window, nchannels, charge_unit, offsets, channel, bin, npe, q_int, t_first, flags, outside):
+    def __init__(self, window, nchannels, charge_unit, offsets, channel, bin, npe, q_int, t_first, flags, outside, noise=None):
         self.window = window
         self.nchannels = nchannels
         self.charge_unit = charge_unit
@@ -250,6 +255,7 @@ class EventPulses(object):
         self.q = (q_int.astype(np.float32) * np.float32(charge_unit)).astype(np.float32)          # as k_daq_convert
         self._outside = outside
         self.nevents = len(offsets) - 1
+        self.noise = np.zeros(self.nevents, dtype=np.uint32) if noise is None else noise
         self.triggers = None                 # the EventTriggers of acquire_pulses(trigger=...)
 
     def __len__(self):
@@ -285,7 +291,7 @@ class EventPulses(object):
         w = self._slice(i)
         early, late = self.outside(i)
         return Pulses(self.window, self.nchannels, self.channel[w], self.bin[w], self.npe[w], self.q[w], self.q_int[w], self.t_first[w],
-                      self.flags[w], early, late)
+                      self.flags[w], early, late, int(self.noise[self._event(i)]))
 
     def waveform(self, i, channel):
         """(npe[nbins] uint32, q[nbins] float32) of one channel of event ``i``, dense."""
@@ -296,6 +302,99 @@ class EventPulses(object):
         arrays -- no GPU, no library: what ``GPUEventDaq.acquire_pulses(trigger=...)`` computes on the device, bit for bit."""
         return trigger_pulses_host(self.window, trigger, self.nchannels, self.charge_unit, self.offsets, self.channel, self.bin, self.npe,
                                    self.q_int, self.t_first, self.flags)
+
+
+class DaqNoise(object):
+    """PMT dark noise for the pulses of a ``DaqWindow`` (chroma_daq_noise): ``rate_hz`` is one dark rate for every channel or
+    one per channel, finite and not negative; all-zero rates mean no noise (``off``).  Per (event, channel) the device draws a
+    Poisson number of candidates at the LARGEST rate from an integer table and keeps each with probability rate / largest
+    rate; a kept one falls uniformly into the window, takes a charge from the detector's charge CDF and carries ``flag`` as
+    its history (include/chroma_hip.h, "dark noise").
+
+    ``tables`` builds the integer tables in float64.  With mu = max(rate) * 1e-9 * nbins * dt (dt in ns) the expected
+    candidates per (event, channel), the count table holds floor(P(X <= j) * 2^32) up to the first entry that saturates at
+    2^32 - 1, and it has 64 entries at most: that holds up to mu = 25.976 (where P(X > 63) passes 2^-32), so every mu up to
+    ``MAX_MU`` = 25.9 has its table and from mu = 26 on ``tables`` raises ValueError -- take a shorter window."""
+
+    MAX_COUNT = 64
+    MAX_MU = 25.9
+
+    def __init__(self, rate_hz, flag=event.DARK_NOISE):
+        rate = np.asarray(rate_hz, dtype=np.float64)
+        if rate.ndim > 1 or rate.size < 1 or not np.isfinite(rate).all() or (rate < 0).any():
+            raise ValueError('dark rates: a finite rate that is not negative, or one per channel')
+        self.rate_hz = rate
+        self.flag = int(flag)
+        if self.flag != flag or not 0 < self.flag <= 0xffffffff or self.flag & (self.flag - 1):
+            raise ValueError('the flag of the noise is one history bit')
+        self.off = not (rate > 0).any()
+
+    @classmethod
+    def of(cls, noise):
+        """``noise`` itself if it is a DaqNoise, or the DaqNoise of a rate (or of the rates per channel)."""
+        return noise if isinstance(noise, cls) else cls(noise)
+
+    def mu(self, window):
+        """The expected candidates per (event, channel): the largest rate over the whole window."""
+        window = DaqWindow.of(window)
+        return float(self.rate_hz.max()) * 1e-9 * window.nbins * window.dt
+
+    def tables(self, window, nchannels):
+        """(count_cdf, accept): the uint32 arrays of chroma_daq_noise for ``window`` and a detector of ``nchannels``."""
+        nchannels = int(nchannels)
+        if self.rate_hz.ndim == 1 and len(self.rate_hz) != nchannels:
+            raise ValueError('%d dark rates for %d channels' % (len(self.rate_hz), nchannels))
+        if self.off:
+            raise ValueError('no channel has a dark rate: there are no tables (DaqNoise.off)')
+        mu = self.mu(window)
+        top = float(self.rate_hz.max())
+        p = np.exp(-mu)
+        total = 0.0
+        cdf = []
+        for j in range(self.MAX_COUNT):
+            total += p
+            entry = min(int(np.floor(total * 2.0 ** 32)), 2 ** 32 - 1)
+            cdf.append(entry)
+            if entry == 2 ** 32 - 1:
+                break
+            p = p * mu / (j + 1)
+        else:
+            raise ValueError('mu = %g candidates per channel and event: more than a table of %d entries holds (mu <= %g)' % (mu, self.MAX_COUNT, self.MAX_MU))
+        accept = np.floor(np.broadcast_to(self.rate_hz, (nchannels,)) / top * 2.0 ** 31 + 0.5).astype(np.uint32)
+        return np.array(cdf, dtype=np.uint32), accept
+
+    def sample(self, window, nrows, nchannels, charge_cdf, charge_unit, seed=0, acquisition=0):
+        """The kept noise photoelectrons of ``nrows`` events on the HOST (chroma_daq_noise_host: no GPU), bit for bit what
+        ``GPUEventDaq.acquire_pulses(noise=self, acquisition=acquisition)`` mixes into the pulses of a context seeded with ``seed``:
+        a structured array of (row, channel, bin, time, charge_int) in (row, channel, candidate) order.  ``charge_cdf``: the (x, y)
+        of the detector's charge CDF as the DAQ holds it; ``charge_unit``: its charge unit."""
+        window = DaqWindow.of(window)
+        dtype = [('row', np.uint32), ('channel', np.uint32), ('bin', np.uint32), ('time', np.float32), ('charge_int', np.uint32)]
+        if self.off:
+            return np.zeros(0, dtype=dtype)
+        lib = _lib.load()
+        count_cdf, accept = self.tables(window, nchannels)
+        qx, qy = _padded_cdf(*charge_cdf)
+        qx, qy = np.ascontiguousarray(qx), np.ascontiguousarray(qy)
+        tables = _lib.DaqTables(None, None, 0, _lib.ptr(qx), _lib.ptr(qy), len(qx), float(charge_unit))
+        win = _lib.DaqWindow(window.t0, window.dt, window.nbins)
+        struct = _lib.DaqNoise(_lib.ptr(count_cdf), len(count_cdf), _lib.ptr(accept), self.flag)
+        n = ctypes.c_uint64(0)
+        capacity = 0
+        columns = [np.zeros(0, dtype=np.uint32) for _ in range(5)]
+        for attempt in range(2):
+            rc = lib.chroma_daq_noise_host(ctypes.byref(tables), ctypes.byref(win), ctypes.byref(struct), int(nrows), int(nchannels),
+                                           int(seed), int(acquisition) & 0xffffffff, capacity,
+                                           *([_lib.ptr(a) if capacity else None for a in columns] + [ctypes.byref(n)]))
+            if rc == 0 or attempt or n.value <= capacity:
+                break
+            capacity = int(n.value)
+            columns = [np.zeros(capacity, dtype=np.uint32) for _ in range(5)]
+        _lib.check(rc)
+        out = np.zeros(int(n.value), dtype=dtype)
+        for (name, kind), a in zip(dtype, columns):
+            out[name] = a[:len(out)].view(kind)
+        return out
 
 
 NO_TRIGGER = 0xffffffff          # pulse_trigger of a pulse that lies in no gate
@@ -580,6 +679,7 @@ class GPUEventDaq(object):
         self._sparse_gpu = None
         self._pulse_rows_gpu = None          # acquire_pulses' outputs: per row (offsets, outside), per pulse the six arrays
         self._pulses_gpu = None
+        self._noise_tables = None            # acquire_pulses(noise=...): ((noise, window), the chroma_daq_noise, its arrays), the last one
         self._trigger_rows_gpu = None        # acquire_pulses(trigger=...): per row the offsets; per trigger (bin, sum, hit offsets) in one
         self._triggers_gpu = None            # buffer; per hit the five arrays and per pulse its trigger in another
         self._trigger_hits_gpu = None
@@ -625,11 +725,20 @@ class GPUEventDaq(object):
 
     def _pulse_buffers(self, nrows, capacity):
         if self._pulse_rows_gpu is None or len(self._pulse_rows_gpu[0]) < nrows + 1:
-            self._pulse_rows_gpu = [empty(nrows + 1, np.uint32, self.ctx), empty(2 * nrows, np.uint32, self.ctx)]
+            self._pulse_rows_gpu = [empty(nrows + 1, np.uint32, self.ctx), empty(2 * nrows, np.uint32, self.ctx), empty(nrows, np.uint32, self.ctx)]
         if self._pulses_gpu is None or len(self._pulses_gpu[0]) < capacity:
             self._pulses_gpu = [empty(capacity, dtype, self.ctx)
                                 for dtype in (np.int32, np.uint32, np.uint32, np.uint32, np.float32, np.uint32)]
         return self._pulse_rows_gpu, self._pulses_gpu
+
+    def _noise_struct(self, noise, window):
+        """The chroma_daq_noise of ``noise`` under ``window`` on this context: built and uploaded once per (noise, window)."""
+        key = (noise, window)
+        if self._noise_tables is None or self._noise_tables[0] != key:
+            count_cdf, accept = noise.tables(window, self.nchannels)
+            d_accept = to_gpu(accept, ctx=self.ctx)
+            self._noise_tables = (key, _lib.DaqNoise(_lib.ptr(count_cdf), len(count_cdf), d_accept.ptr, noise.flag), (count_cdf, d_accept))
+        return self._noise_tables[1]
 
     def _trigger_chunk(self, win, trigger, nrows, d_offsets, arrays, npulses):
         """chroma_daq_trigger_pulses on the pulses of one chunk where acquire_pulses left them; the host arrays (offsets, bin, sum,
@@ -664,15 +773,23 @@ class GPUEventDaq(object):
         return [self._trigger_rows_gpu[:nrows + 1].get(), t[:nt], t[capacity:capacity + nt], t[2 * capacity:2 * capacity + nt + 1],
                 h[:nh].view(np.int32), h[n:n + nh], h[2 * n:2 * n + nh], h[3 * n:3 * n + nh].view(np.float32), h[4 * n:4 * n + nh], h[5 * n:6 * n]]
 
-    def acquire_pulses(self, gpuphotons, rng_states, bounds, window, acquisition=0, weight=1.0, trigger=None):
+    def acquire_pulses(self, gpuphotons, rng_states, bounds, window, acquisition=0, weight=1.0, trigger=None, noise=None):
         """The time-binned view of ``acquire`` with the same arguments: the same accepted photons, per (event, channel, bin of
         ``window``: a DaqWindow or (t0, dt, nbins)).  Counts first (chroma_daq_count_pulses), then acquires into buffers grown to
         the largest count seen, ``rows_per_chunk`` events at a time.  Returns an ``EventPulses``.
 
         ``trigger`` (a DaqTrigger or its tuple): each chunk's pulses are also triggered where they lie on the device, before they
         are read back (chroma_daq_trigger_pulses), and the result carries ``.triggers``, an ``EventTriggers``.  Events are
-        independent, so it does not depend on the chunking either; the pulses are what they are without it."""
+        independent, so it does not depend on the chunking either; the pulses are what they are without it.
+
+        ``noise`` (a DaqNoise, or a dark rate in Hz, or one per channel): every event's dark-noise photoelectrons are drawn on the
+        device and enter the pulses like accepted photons, flagged ``noise.flag`` (chroma_daq_count_pulses_noise /
+        chroma_daq_acquire_pulses_noise); the result's ``noise`` counts them per event.  Events without photons get theirs too.
+        The draws are counter-based (per event and channel): the chunking does not show.  Noise that is ``off`` is no noise."""
         window = DaqWindow.of(window)
+        if noise is not None:
+            noise = DaqNoise.of(noise)
+            noise = None if noise.off else noise
         if trigger is not None:
             trigger = DaqTrigger.of(trigger).check(window)
         bounds = np.asarray(bounds)
@@ -686,7 +803,9 @@ class GPUEventDaq(object):
         s = _structure(gpuphotons)
         lib, handle = self.ctx._lib, self.ctx.handle
         win = _lib.DaqWindow(window.t0, window.dt, window.nbins)
-        offsets, outside = [np.zeros(1, dtype=np.int64)], []
+        noise_arg = () if noise is None else (ctypes.byref(self._noise_struct(noise, window)),)
+        suffix = '' if noise is None else '_noise'
+        offsets, outside, row_noise = [np.zeros(1, dtype=np.int64)], [], []
         parts = [[] for _ in range(6)]
         total = 0
         triggered = [[np.zeros(1, dtype=np.int64)] if k in (0, 3) else [] for k in range(10)]
@@ -695,14 +814,17 @@ class GPUEventDaq(object):
             nrows = min(self.rows_per_chunk, nevents - first)
             b = bounds[first:first + nrows + 1]
             args = (handle, self.gpu_detector.handle, ctypes.byref(self.tables), nrows, _lib.ptr(b), event.SURFACE_DETECT, ctypes.byref(s),
-                    len(gpuphotons.pos), rng, (int(acquisition) + first) & 0xffffffff, float(weight), ctypes.byref(win))
+                    len(gpuphotons.pos), rng, (int(acquisition) + first) & 0xffffffff, float(weight), ctypes.byref(win)) + noise_arg
             naccepted = ctypes.c_uint64(0)
-            _lib.check(lib.chroma_daq_count_pulses(*(args + (ctypes.byref(naccepted),))))
+            _lib.check(getattr(lib, 'chroma_daq_count_pulses' + suffix)(*(args + (ctypes.byref(naccepted),))))
             capacity = int(naccepted.value)
-            (d_offsets, d_outside), arrays = self._pulse_buffers(nrows, capacity)
+            (d_offsets, d_outside, d_row_noise), arrays = self._pulse_buffers(nrows, capacity)
             npulses = ctypes.c_uint64(0)
-            _lib.check(lib.chroma_daq_acquire_pulses(*(args + (capacity, d_offsets.ptr) + tuple(a.ptr for a in arrays) +
-                                                       (d_outside.ptr, ctypes.byref(npulses)))))
+            _lib.check(getattr(lib, 'chroma_daq_acquire_pulses' + suffix)(*(args + (capacity, d_offsets.ptr) + tuple(a.ptr for a in arrays) +
+                                                                             (d_outside.ptr,) + (() if noise is None else (d_row_noise.ptr,)) +
+                                                                             (ctypes.byref(npulses),))))
+            if noise is not None:
+                row_noise.append(d_row_noise[:nrows].get())
             offsets.append(d_offsets[:nrows + 1].get()[1:].astype(np.int64) + total)
             outside.append(d_outside[:2 * nrows].get().reshape(nrows, 2))
             for part, a in zip(parts, arrays):
@@ -720,7 +842,8 @@ class GPUEventDaq(object):
         dtypes = (np.int32, np.uint32, np.uint32, np.uint32, np.float32, np.uint32)
         columns = [np.concatenate(part) if part else np.zeros(0, dtype=dtype) for part, dtype in zip(parts, dtypes)]
         outside = np.concatenate(outside) if outside else np.zeros((0, 2), dtype=np.uint32)
-        pulses = EventPulses(window, self.nchannels, self.charge_unit, np.concatenate(offsets), *columns, outside=outside)
+        pulses = EventPulses(window, self.nchannels, self.charge_unit, np.concatenate(offsets), *columns, outside=outside,
+                             noise=np.concatenate(row_noise) if row_noise else None)
         if trigger is not None:
             kinds = (np.int64, np.uint32, np.uint32, np.int64, np.int32, np.uint32, np.uint32, np.float32, np.uint32, np.uint32)
             pulses.triggers = EventTriggers(window, trigger, self.nchannels, self.charge_unit, pulses.offsets,

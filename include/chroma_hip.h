@@ -493,6 +493,68 @@ int chroma_daq_acquire_pulses(chroma_ctx *ctx, chroma_geometry *geom, const chro
                               uint64_t capacity, uint32_t *d_offsets, int32_t *d_channel, uint32_t *d_bin,
                               uint32_t *d_npe, uint32_t *d_q_int, float *d_t_first, uint32_t *d_flags,
                               uint32_t *d_outside, uint64_t *npulses);
+/* ---- dark noise of the time-binned DAQ ------------------------------------------------------------
+ * PMT dark counts as further photoelectrons of a pulse acquisition, drawn on the device.  Noise is
+ * drawn per (row r, channel c) WORD of the acquisition, from the Philox stream 1 + acquisition + r (the
+ * stream row r's photons use) of the pseudo-photon 0xffffffff00000000 | c.  Word w of a stream is word
+ * w & 3 of block w >> 2, as cm_rng (include/chroma_math.h) has it.
+ *
+ *   The count:  k = #{ j < ncount : word 0 >= count_cdf[j] }.  count_cdf is non-decreasing; the caller
+ *     puts a scaled Poisson CDF there (entry j: P(X <= j) * 2^32), the device only compares integers.
+ *   Candidate j = 0 .. k - 1 has the words a = 1 + 3 j, b = 2 + 3 j, c = 3 + 3 j and is
+ *     KEPT iff (word a >> 1) < d_accept[channel]: the thinning of a channel's rate against the largest one; 2^31
+ *       keeps every candidate, 0 none.  A channel whose accept word is 0 is skipped without a draw (it
+ *       needs no Philox block; the result is the same).
+ *     Its bin: with P = (uint64)b * nbins, bin = (uint32)(P >> 32) -- always inside the window -- and
+ *       f = (float)((uint32)P >> 8) * 2^-24 (exact); time = t0 + ((float)bin + f) * dt in float32, each
+ *       operation rounded once.  THE BIN IS THE DRAWN ONE, whatever rounding makes of `time` (a time
+ *       that rounds up to the next bin's edge stays in its bin; (time - t0) / dt is not consulted).
+ *     Its charge, as a photon's: charge = interp_table(cm_u32_to_uniform(c), the charge CDF) and
+ *       charge_int = (uint32)cm_roundf(charge / charge_unit).
+ *     Its history: `flag`.
+ * A kept noise photoelectron enters the pulses exactly like an accepted in-window photon of row r: it
+ * counts in npe, adds to the wrapping q_int, competes for t_first and ORs `flag` into flags.  A pulse
+ * may mix light and noise.  Rows without photons, and a call whose photon span is empty, still get
+ * their noise; early and late (d_outside) count photons only.  Everything is counter-based: the result
+ * does not depend on the launch shape or on how a batch is cut into calls (row r of a call with
+ * `acquisition` a is row 0 of a call with a + r). */
+typedef struct chroma_daq_noise {
+    const uint32_t *count_cdf;   /* HOST array of `ncount` words, non-decreasing */
+    uint32_t ncount;             /* 1 .. 64: the most candidates a word can have */
+    const uint32_t *d_accept;    /* DEVICE array, nchannels words, each 0 .. 2^31 */
+    uint32_t flag;               /* exactly one history bit */
+} chroma_daq_noise;
+/* chroma_daq_count_pulses / chroma_daq_acquire_pulses with noise; `noise` NULL gives the bits of those
+ * calls.  *naccepted is the accepted in-window photons PLUS the kept noise photoelectrons; the capacity
+ * rules are unchanged.  d_row_noise (nrows words, or NULL): the kept noise photoelectrons of each row,
+ * written, not accumulated -- the truth counterpart of d_outside.  Beyond `capacity` nothing of the
+ * caller's is written, d_row_noise included, and *npulses holds what is needed.
+ * Refused before anything is launched, besides what those calls refuse: with noise, ncount outside
+ * 1 .. 64, a descending count_cdf, a flag that is not exactly one bit, a NULL array, nrows * nchannels of
+ * 2^32 or more, and photon ids (rng.photon_id_base + [0, nphotons)) that reach the high word 0xffffffff
+ * of the pseudo-photons. */
+int chroma_daq_count_pulses_noise(chroma_ctx *ctx, chroma_geometry *geom, const chroma_daq_tables *tables,
+                                  uint32_t nrows, const uint32_t *bounds, uint32_t detection_state,
+                                  const chroma_photon_arrays *photons, uint32_t nphotons, chroma_rng rng,
+                                  uint32_t acquisition, float global_weight, const chroma_daq_window *window,
+                                  const chroma_daq_noise *noise, uint64_t *naccepted);
+int chroma_daq_acquire_pulses_noise(chroma_ctx *ctx, chroma_geometry *geom, const chroma_daq_tables *tables,
+                                    uint32_t nrows, const uint32_t *bounds, uint32_t detection_state,
+                                    const chroma_photon_arrays *photons, uint32_t nphotons, chroma_rng rng,
+                                    uint32_t acquisition, float global_weight, const chroma_daq_window *window,
+                                    const chroma_daq_noise *noise, uint64_t capacity, uint32_t *d_offsets,
+                                    int32_t *d_channel, uint32_t *d_bin, uint32_t *d_npe, uint32_t *d_q_int,
+                                    float *d_t_first, uint32_t *d_flags, uint32_t *d_outside,
+                                    uint32_t *d_row_noise, uint64_t *npulses);
+/* The same draws on the host (no GPU, no context): the kept noise photoelectrons of `nrows` rows in
+ * (row, channel, candidate) order -- row, channel, bin, time bits, charge count, `capacity` entries each
+ * (may be NULL when capacity is 0).  Here the charge CDF of `tables` (the time CDF is not read) and
+ * noise->d_accept are HOST arrays.  *n: their number; beyond `capacity` the first `capacity` are written
+ * and the call is CHROMA_ERR_INVALID.  Refuses what the calls above refuse of the noise and the window. */
+int chroma_daq_noise_host(const chroma_daq_tables *tables, const chroma_daq_window *window,
+                          const chroma_daq_noise *noise, uint32_t nrows, uint32_t nchannels, uint64_t seed,
+                          uint32_t acquisition, uint64_t capacity, uint32_t *row, uint32_t *channel,
+                          uint32_t *bin, uint32_t *time_bits, uint32_t *charge_int, uint64_t *n);
 /* ---- the trigger of the time-binned DAQ: firings and their readout gates ------------------------
  * A second, purely integer stage on the pulses of chroma_daq_acquire_pulses (no random draws): a
  * multiplicity or photoelectron sum over a sliding coincidence window, a level trigger with lockout on
