@@ -2,7 +2,7 @@
 // of WALKS each), what a chroma_propagate* call runs (CallPlan, resolved from those rows), the call itself (PropagateCall: its
 // state in one object, its launches, step loop and tail as members), the settings and statistics that go with it, and the two calls that run this path's device
 // code on rays of their own: chroma_intersect_mesh (the same ray-cast kernels) and the hybrid render (k_propagate's step functions:
-// the compiler specialises those for their callers, so the family compiles as it did only beside k_propagate).  The other entry points of include/chroma_hip.h: context.hip, geometry.hip, kernel_calls.hip, comm.hip,
+// the compiler specialises those for their callers, so the family compiles as it did only beside k_propagate).  The other entry points of include/chroma_hip.h: context.hip, geometry.hip, kernel_calls.hip, daq_calls.hip, steps_calls.hip, comm.hip,
 // bvh_device.hip, wide_device.hip.
 //
 // The kernels of this path live in one header per family, included below in dependency order (each family is compiled in

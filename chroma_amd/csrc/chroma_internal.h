@@ -56,7 +56,10 @@ struct CallState {
     uint2 *coop_spill = nullptr;           // [rays in flight of the largest cooperative cast][COOP_SPILL]
     hipEvent_t ev_start = nullptr, ev_stop = nullptr, ev_mid = nullptr;
     hipStream_t aux_stream = nullptr;          // k_finalize_hits beside the tail kernel (launch_tail)
-    void *steps_scratch = nullptr; size_t steps_scratch_bytes = 0;     // chroma_steps_*: the source's tables, the counts, the scan's workspace; chroma_daq_*_events: the bounds, the flags and their scan
+    // One pooled block that the multi-launch calls lay their arrays out on, each from the block's start (grow_call_scratch, Carver):
+    // chroma_steps_* (the total, the source's tables, the counts, the scan's workspace), chroma_daq_acquire_events (the bounds),
+    // chroma_daq_compact_events (the flags and their scan), the four pulse calls (PulsesBlock) and chroma_daq_trigger_pulses (TriggerBlock)
+    void *call_scratch = nullptr; size_t call_scratch_bytes = 0;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     // ---- the settings: chroma_set_* and the CHROMA_* environment write them, a call reads them when it starts (CallPlan) ----
     int counting = 0;
@@ -191,6 +194,47 @@ static inline std::array<QueueBuffer, 9> queue_buffers(CallState &c)
 // behind chroma_malloc / chroma_free is given back first (defined next to the pool)
 CHROMA_LOCAL hipError_t ctx_malloc(chroma_ctx *ctx, void **ptr, size_t bytes);
 
+// ---- the context's pooled scratch block (CallState::call_scratch) ----
+// The one function that grows it.  A grown block is a NEW one (the stream drained, the old block freed): what a call had in it
+// is lost, and `*grew` says so.
+static int grow_call_scratch(const CallScope &scope, size_t need, bool *grew = nullptr)
+{
+    CallState &cs = scope.state();
+    if (grew) *grew = false;
+    if (cs.call_scratch_bytes >= need) return CHROMA_OK;
+    HIP_TRY(hipStreamSynchronize(scope.ctx->stream));
+    if (cs.call_scratch) { HIP_TRY(hipFree(cs.call_scratch)); cs.call_scratch = nullptr; cs.call_scratch_bytes = 0; }
+    HIP_TRY(ctx_malloc(scope.ctx, &cs.call_scratch, need));
+    cs.call_scratch_bytes = need;
+    if (grew) *grew = true;
+    return CHROMA_OK;
+}
+
+// A walk over a block: take<T>(count) is the next array, each rounded up to 256 bytes.  Without a block it only adds up.  A
+// pipeline describes its block ONCE, as a function of a Carver and its sizes; carve_call_scratch runs that description on no
+// block for the bytes it needs and on the grown block for the pointers, so the sum and the carving cannot disagree.
+static inline size_t round256(size_t b) { return (b + 255) & ~(size_t)255; }
+struct Carver {
+    char *base = nullptr;
+    size_t offset = 0;
+    template <class T> T *take(size_t count)
+    {
+        T *p = base ? (T *)(base + offset) : nullptr;
+        offset += round256(count * sizeof(T));
+        return p;
+    }
+};
+template <class Lay>
+static int carve_call_scratch(const CallScope &scope, Lay &&lay, bool *grew = nullptr)
+{
+    Carver size;
+    lay(size);
+    int rc = grow_call_scratch(scope, size.offset, grew); if (rc) return rc;
+    Carver block{(char *)scope.state().call_scratch};
+    lay(block);
+    return CHROMA_OK;
+}
+
 // chroma_init's share of the propagate path: the ray-cast grids and the launch policy, from the device and the CHROMA_*
 // environment (chroma_hip.hip: it knows the kernels' residency)
 CHROMA_LOCAL int propagate_settings(const CallScope &scope);
@@ -204,6 +248,14 @@ int chroma_internal_sort_pairs(chroma_ctx *ctx, const uint32_t *d_keys, uint32_t
 // (kernel_calls.hip) exclusive sum of n counts, in place; queued on the context's stream
 int chroma_internal_exclusive_sum(chroma_ctx *ctx, uint32_t *d_counts, uint32_t n);
 }
+// (kernel_calls.hip) hipCUB for the units that bring their own workspace, in one place so that its kernels are compiled once, each
+// as the workspace's size and the call queued on `stream`: the exclusive sum of n words of d_in into d_out (the same array: in
+// place), and the stable radix sort of n (64-bit key, value) pairs on bits [0, end_bit) of the keys
+CHROMA_LOCAL int scan_workspace_bytes(size_t n, hipStream_t stream, size_t *bytes);
+CHROMA_LOCAL int exclusive_sum(void *workspace, size_t bytes, uint32_t *d_in, uint32_t *d_out, size_t n, hipStream_t stream);
+CHROMA_LOCAL int sort_pairs_workspace_bytes(size_t n, int end_bit, hipStream_t stream, size_t *bytes);
+CHROMA_LOCAL int sort_pairs(void *workspace, size_t bytes, const uint64_t *d_keys, uint64_t *d_keys_out, const uint32_t *d_values,
+                            uint32_t *d_values_out, size_t n, int end_bit, hipStream_t stream);
 
 // ---------------------------------------------------------------------------------------------------
 // host helpers

@@ -132,7 +132,7 @@ int chroma_shutdown(chroma_ctx *ctx)
         if (cs.wide_spill) hipFree(cs.wide_spill);
         if (cs.coop_spill) hipFree(cs.coop_spill);
         if (cs.d_step) hipFree(cs.d_step);
-        if (cs.steps_scratch) hipFree(cs.steps_scratch);
+        if (cs.call_scratch) hipFree(cs.call_scratch);
         if (cs.h_step) hipHostFree(cs.h_step);
         for (hipEvent_t e : cs.step_events) hipEventDestroy(e);
         hipFree(cs.d_counters);

@@ -2,7 +2,7 @@
 // for the device kernels (kernels_daq_noise.h) and for the host loop (daq_noise_host.cpp).  The contract is in
 // include/chroma_hip.h ("dark noise").  Like steps_common.h it is plain arithmetic under CM_FN: integer compares, one 64-bit
 // product, and single IEEE single-precision operations, and both sides are compiled with -ffp-contract=off, so the two produce
-// the same bits.  interp_table (kernels_daq_render.h) is restated here with the same operation order, because the host side
+// the same bits.  interp_table (device_common.h) is restated here with the same operation order, because the host side
 // cannot include it.
 #pragma once
 
@@ -63,7 +63,7 @@ DAQ_NOISE_FN uint32_t count(uint32_t word0, const uint32_t *count_cdf, uint32_t 
 // the thinning of a candidate against the largest rate (accept: 0 never .. 2^31 always)
 DAQ_NOISE_FN bool kept(uint32_t a, uint32_t accept) { return (a >> 1) < accept; }
 
-// interp_table (kernels_daq_render.h)
+// interp_table (device_common.h)
 DAQ_NOISE_FN float interp_table(float x, int n, const float *xp, const float *fp)
 {
     int lower = 0;

@@ -38,6 +38,23 @@ __device__ inline v3 normalize(v3 a) { return a / norm(a); }
 __device__ inline v3 load3(const float *p, size_t i) { return mk3(p[3 * i], p[3 * i + 1], p[3 * i + 2]); }
 __device__ inline void store3(float *p, size_t i, v3 v) { p[3 * i] = v.x; p[3 * i + 1] = v.y; p[3 * i + 2] = v.z; }
 
+// interp (interpolate.h:32-57) as used by sample_cdf(rng, n, cdf_x, cdf_y) (random.h:26-31): the DAQ kernels' draws (kernels_daq.h,
+// kernels_daq_pulses.h) and k_probe (kernels_render.h)
+__device__ inline float interp_table(float x, int n, const float *xp, const float *fp)
+{
+    int lower = 0;
+    int upper = n - 1;
+    if (x <= xp[lower]) return fp[lower];
+    if (x >= xp[upper]) return fp[upper];
+    while (lower < upper - 1) {
+        int half = (lower + upper) / 2;
+        if (x < xp[half]) upper = half; else lower = half;
+    }
+    float df = fp[upper] - fp[lower];
+    float dx = xp[upper] - xp[lower];
+    return fp[lower] + df * (x - xp[lower]) / dx;
+}
+
 // ---- device view of an uploaded geometry ------------------------------------------------
 // Layout in HBM (see DESIGN.md "Data layout"):
 //   nodes   uint4[nnodes]            16 B packed node, as chroma/cuda/geometry_types.h:57-67

@@ -1,6 +1,6 @@
 // kernels_daq_noise.h -- PMT dark noise of the time-binned DAQ (chroma_daq_count_pulses_noise / chroma_daq_acquire_pulses_noise;
 // the contract is in include/chroma_hip.h, the draws of one word in daq_noise_common.h).  One of the kernel families of
-// libchroma_hip.so; included by kernel_calls.hip alone, behind kernels_daq_pulses.h.
+// libchroma_hip.so; included by daq_calls.hip alone, behind kernels_daq_pulses.h.
 //
 // Noise photoelectrons are further entries of the pulses' pipeline: k_daq_noise_emit puts them, behind the same cursor, into the
 // arrays k_daq_pulses_emit fills (key, position, charge count, time bits, history), and the sort, the heads, open, reduce and

@@ -1,7 +1,7 @@
 // kernels_daq_pulses.h -- the time-binned DAQ: per (event, channel, time bin) the pulses of the photoelectrons that k_run_daq_events
 // accumulates per (event, channel), kept sparse (chroma_daq_count_pulses / chroma_daq_acquire_pulses; the contract is in
-// include/chroma_hip.h).  One of the kernel families of libchroma_hip.so; included by kernel_calls.hip alone, behind
-// kernels_daq_render.h (interp_table, daq_row_of).
+// include/chroma_hip.h).  One of the kernel families of libchroma_hip.so; included by daq_calls.hip alone, behind
+// kernels_daq.h (daq_row_of; interp_table is device_common.h's).
 //
 // The pipeline of an acquisition of n accepted in-window photons:
 //   k_daq_pulses_emit     a lane per photon of the window: gate, time, charge and bin as k_run_daq_events draws them; the accepted

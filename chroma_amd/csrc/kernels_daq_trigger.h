@@ -1,7 +1,7 @@
 // kernels_daq_trigger.h -- the trigger of the time-binned DAQ: a multiplicity (NHIT) or photoelectron (NPE) sum over a sliding
 // coincidence window of the pulses chroma_daq_acquire_pulses wrote, a level trigger with lockout on it, and per firing the pulses
 // of its readout gate reduced per channel (chroma_daq_trigger_pulses; the contract is in include/chroma_hip.h).  One of the kernel
-// families of libchroma_hip.so; included by kernel_calls.hip alone, behind kernels_daq_pulses.h (daq_time_image, and
+// families of libchroma_hip.so; included by daq_calls.hip alone, behind kernels_daq_pulses.h (daq_time_image, and
 // k_daq_pulses_heads / _open / _finish, which the gated hits reuse as they stand).
 //
 // The pipeline of a call over npulses pulses of nrows rows:

@@ -1,5 +1,5 @@
 // kernels_steps.h -- photons from charged-particle steps on the device (chroma_steps_count / chroma_steps_generate,
-// kernel_calls.hip).  What a segment and a photon compute is steps_common.h, shared with the host loops of steps_host.cpp.
+// steps_calls.hip, which alone includes it).  What a segment and a photon compute is steps_common.h, shared with the host loops of steps_host.cpp.
 #pragma once
 
 #include "steps_common.h"

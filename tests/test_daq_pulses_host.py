@@ -31,7 +31,7 @@ def uniform(word):
 
 
 def interp_table(x, xp, fp):
-    """interp_table of kernels_daq_render.h (interpolate.h:32-57) in float32, each operation rounded once."""
+    """interp_table of device_common.h (interpolate.h:32-57) in float32, each operation rounded once."""
     lower, upper = 0, len(xp) - 1
     if x <= xp[lower]:
         return fp[lower]
