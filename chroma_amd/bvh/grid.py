@@ -99,7 +99,23 @@ def _count_unique_sorted(a):
     return int(np.count_nonzero(a[1:] != a[:-1])) + 1
 
 
+def _check_target_degree(target_degree):
+    """A degree of 1 never ends: with distinct codes a layer of n nodes gets n one-child parents, layer after layer."""
+    if target_degree < 2:
+        raise ValueError('target_degree must be at least 2, not %r' % (target_degree,))
+
+
+def _check_frame(world_coords):
+    """The frame must quantise: (v - origin) / scale is NaN or inf otherwise, and the builders disagree on its integer."""
+    scale = float(world_coords.world_scale)
+    if not (np.isfinite(scale) and scale > 0 and np.isfinite(world_coords.world_origin).all()):
+        raise ValueError('the mesh has no extent or has non-finite vertices: no fixed-point frame (origin %s, scale %r)'
+                         % (np.asarray(world_coords.world_origin).tolist(), scale))
+
+
 def _build_numpy(vertices, triangles, world_coords, target_degree):
+    _check_target_degree(target_degree)
+    _check_frame(world_coords)
     leaf_nodes, morton = make_leaves_numpy(vertices, triangles, world_coords)
     order = np.argsort(morton, kind='stable')
     leaf_nodes = leaf_nodes[order]
@@ -170,13 +186,16 @@ def make_recursive_grid_bvh(mesh, target_degree=3, verbose=False, backend=None, 
     for bit.  ``cuda_device``: the GPU a device build runs on (chroma/loader.py:150 builds on ``create_cuda_context(cuda_device)``)
     -- the current context when it is on that device, else a context made for the build and released afterwards, so loading
     a geometry leaves no context behind.  A device build that runs out of memory gives the pool back, and if that is not
-    enough the host cores build the same tree."""
+    enough the host cores build the same tree.  ValueError, before a backend is chosen, for ``target_degree`` < 2 (a degree
+    of 1 never closes the tree) and for a mesh without extent or with non-finite vertices (no fixed-point frame)."""
     import os
     vertices = np.ascontiguousarray(mesh.vertices, dtype=np.float32)
     triangles = np.ascontiguousarray(mesh.triangles, dtype=np.uint32)
     if len(triangles) >= 2 ** CHILD_BITS:
         raise ValueError('mesh has too many triangles for 28-bit child indices')
+    _check_target_degree(target_degree)
     world_coords = world_coords_for(vertices)
+    _check_frame(world_coords)
     backend = backend or os.environ.get('CHROMA_BVH_BACKEND') or 'auto'
     ctx, created = None, False
     if backend in ('auto', 'device'):

@@ -20,7 +20,16 @@
 #include "host_utils.h"
 #include "bvh_result.h"
 
+// (context.hip: the calling thread's chroma_last_error() message; chroma_internal.h declares it for the device units.
+//  Weak: this file is also built without the device units -- tools/asan_host.sh -- and then returns the bare code.)
+__attribute__((weak, visibility("hidden"))) int set_error(int code, const char *fmt, ...);
+
 namespace {
+int refuse(const char *why)
+{
+    return set_error ? set_error(CHROMA_ERR_INVALID, "chroma_bvh_build: %s", why) : CHROMA_ERR_INVALID;
+}
+
 struct Timer {
     std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
     bool on = getenv("CHROMA_BVH_VERBOSE") != nullptr;
@@ -101,14 +110,15 @@ int chroma_bvh_build(const float *vertices, uint32_t nvertices, const uint32_t *
                      const float world_origin[3], float world_scale, int32_t target_degree,
                      void **handle, uint64_t *nnodes, uint32_t *nlayers)
 {
-    if (!vertices || !triangles || !handle || ntriangles == 0 || ntriangles >= (1u << CHROMA_CHILD_BITS) || target_degree < 1)
-        return CHROMA_ERR_INVALID;
+    if (!vertices || !triangles || !handle || ntriangles == 0 || ntriangles >= (1u << CHROMA_CHILD_BITS))
+        return refuse("bad argument");
+    if (const char *why = chroma_host::bvh_refusal(world_origin, world_scale, target_degree)) return refuse(why);
     {
         std::vector<int> bad(1, 0);
         chroma_host::parallel_for((size_t)ntriangles * 3, [&](size_t lo, size_t hi) {
             for (size_t i = lo; i < hi; i++) if (triangles[i] >= nvertices) { bad[0] = 1; return; }
         });
-        if (bad[0]) return CHROMA_ERR_INVALID;
+        if (bad[0]) return refuse("a triangle names a vertex outside the mesh");
     }
 
     Timer timer;
@@ -219,7 +229,7 @@ int chroma_bvh_build(const float *vertices, uint32_t nvertices, const uint32_t *
     res->layer_bounds.assign(nl + 1, 0);
     for (size_t l = 0; l < nl; l++) res->layer_bounds[l + 1] = res->layer_bounds[l] + layers[nl - 1 - l].size();
     uint64_t total = res->layer_bounds[nl];
-    if (total >= (1ull << CHROMA_CHILD_BITS)) { delete res; return CHROMA_ERR_INVALID; }
+    if (total >= (1ull << CHROMA_CHILD_BITS)) { delete res; return refuse("the nodes do not fit 28-bit child indices"); }
     res->nodes.resize(total);
     for (size_t l = 0; l < nl; l++) {
         std::vector<Node> &src = layers[nl - 1 - l];

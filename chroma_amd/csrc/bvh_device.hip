@@ -227,8 +227,10 @@ int chroma_bvh_build_device(chroma_ctx *ctx, const float *vertices, uint32_t nve
                             const float world_origin[3], float world_scale, int32_t target_degree,
                             void **handle, uint64_t *nnodes, uint32_t *nlayers)
 {
-    if (!ctx || !vertices || !triangles || !handle || ntriangles == 0 || ntriangles >= (1u << CHROMA_CHILD_BITS) || target_degree < 1)
+    if (!ctx || !vertices || !triangles || !handle || ntriangles == 0 || ntriangles >= (1u << CHROMA_CHILD_BITS))
         return set_error(CHROMA_ERR_INVALID, "chroma_bvh_build_device: bad argument");
+    if (const char *why = chroma_host::bvh_refusal(world_origin, world_scale, target_degree))
+        return set_error(CHROMA_ERR_INVALID, "chroma_bvh_build_device: %s", why);
     hipStream_t stream = ctx->stream;
     HIP_TRY(hipSetDevice(ctx->device));
     Lap lap(stream);

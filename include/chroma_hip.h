@@ -856,7 +856,12 @@ int chroma_probe(chroma_ctx *ctx, int32_t fn, uint64_t n, const float *d_x, cons
  * kernels it drives -- make_leaves, make_parents_detailed, copy_and_offset, collapse_child
  * (chroma/cuda/bvh.cu:149-203,270-308,365-384,530-543; hosts chroma/gpu/bvh.py:18-130,239-267).
  * Runs on the host cores (no device needed).  Two-phase: build returns a handle and the sizes,
- * fetch copies nodes ([nnodes][4] uint32) and layer bounds ([nlayers+1] uint64), free releases. */
+ * fetch copies nodes ([nnodes][4] uint32) and layer bounds ([nlayers+1] uint64), free releases.
+ * Both builders return CHROMA_ERR_INVALID with a message, before any work is done, for target_degree < 2 (with
+ * distinct Morton codes a degree of 1 gives every node a parent of its own and the tree never closes) and for a frame
+ * that cannot quantise: world_scale not finite or <= 0 (a mesh without extent), or a non-finite world_origin (a mesh
+ * with non-finite vertices).  For vertices outside [origin, origin + 65535 * scale] the result is unspecified: the
+ * conversion of the quantised float to uint32 saturates on the device and wraps on the host. */
 int chroma_bvh_build(const float *vertices, uint32_t nvertices, const uint32_t *triangles, uint32_t ntriangles,
                      const float world_origin[3], float world_scale, int32_t target_degree,
                      void **handle, uint64_t *nnodes, uint32_t *nlayers);

@@ -108,3 +108,113 @@ def test_direction_sort_is_argsort_direction_on_the_device(gpu, oracle_mod):
         a, b = getattr(got, name), getattr(exact, name)
         differ = np.flatnonzero((a.view(np.uint32) != b.view(np.uint32)).reshape(len(a), -1).any(axis=1))
         assert len(differ) == 0, '%s: %d rows are not where the contract codes put them (first: row %d)' % (name, len(differ), differ[0])
+
+
+# ---- the device builder at its size and run edges (the cases and the NumPy trees of tests/test_bvh.py) ------------------------
+@pytest.fixture(scope='module')
+def ctx(gpu):
+    from chroma_amd.gpu import tools
+    return tools._current
+
+
+def _edge_case_names():
+    from test_bvh import EDGE_CASES
+    return list(EDGE_CASES)
+
+
+@pytest.mark.parametrize('name', _edge_case_names())
+def test_device_builder_on_the_edge_cases(ctx, name):
+    """Bit for bit the host builder's and the NumPy restatement's nodes and layer bounds; and again on the same context,
+    where every scratch array of the second build is a block the first one gave back to the pool."""
+    from test_bvh import EDGE_CASES, native_tree, numpy_tree, assert_same_tree
+    for degree in EDGE_CASES[name][2]:
+        what = '%s, degree %d' % (name, degree)
+        first = native_tree(name, degree, ctx=ctx)
+        assert_same_tree(first, numpy_tree(name, degree), what + ': device against numpy')
+        assert_same_tree(first, native_tree(name, degree), what + ': device against native')
+        assert_same_tree(native_tree(name, degree, ctx=ctx), first, what + ': second device build')
+
+
+def test_device_builder_refuses_a_bad_index_at_the_arrays_ends(ctx):
+    """k_bvh_check_indices over 771 indices: the first and the last one.  The refused calls leave nothing behind: what the
+    pool holds and what a good build takes from it afterwards are what they are without a refusal."""
+    from chroma_amd import _lib
+    from test_bvh import edge_case, native_tree, numpy_tree, assert_same_tree
+    vertices, triangles, wc = edge_case('soup-257')
+
+    def good_build():
+        before = ctx.pool_stats()
+        tree = native_tree('soup-257', 3, ctx=ctx)
+        ctx.synchronize()
+        after = ctx.pool_stats()
+        return tree, (after[0], after[1] - before[1], after[2] - before[2])     # (parked bytes, blocks reused, blocks allocated)
+    good_build()                                                               # (the pool now holds every block of this build)
+    want, stats = good_build()
+    assert stats[2] == 0, stats
+    for row, slot in ((0, 0), (len(triangles) - 1, 2)):
+        bad = triangles.copy()
+        bad[row, slot] = len(vertices)
+        with pytest.raises(_lib.ChromaError, match='outside the mesh'):
+            _lib.bvh_build(vertices, bad, wc.world_origin, wc.world_scale, 3, ctx=ctx)
+        ctx.synchronize()
+    assert ctx.pool_stats()[0] == stats[0]
+    got, stats_after = good_build()
+    assert stats_after == stats
+    assert_same_tree(got, want, 'after the refusals')
+    assert_same_tree(got, native_tree('soup-257', 3), 'after the refusals: device against native')
+    assert_same_tree(got, numpy_tree('soup-257', 3), 'after the refusals: device against numpy')
+
+
+def test_device_builder_refuses_a_target_degree_below_two(ctx):
+    from chroma_amd import _lib
+    from chroma_amd.bvh.grid import make_recursive_grid_bvh
+    from test_bvh import SAFE_FOR_ANY_DEGREE, BAD_DEGREES, _as_mesh, edge_case, native_tree, numpy_tree, assert_same_tree
+    for name in SAFE_FOR_ANY_DEGREE:
+        vertices, triangles, wc = edge_case(name)
+        for degree in BAD_DEGREES:
+            with pytest.raises(_lib.ChromaError, match='target_degree'):
+                _lib.bvh_build(vertices, triangles, wc.world_origin, wc.world_scale, degree, ctx=ctx)
+            with pytest.raises(ValueError, match='target_degree'):
+                make_recursive_grid_bvh(_as_mesh(vertices, triangles), target_degree=degree, backend='device')
+        assert_same_tree(native_tree(name, 2, ctx=ctx), numpy_tree(name, 2), name + ' after the refusals')
+
+
+def test_device_builder_refuses_a_frame_that_cannot_quantise(ctx):
+    from chroma_amd import _lib
+    from chroma_amd.bvh.grid import make_recursive_grid_bvh, world_coords_for
+    from test_bvh import unquantisable_meshes, _as_mesh, _words, edge_case, native_tree, numpy_tree, assert_same_tree
+    for name, vertices, triangles in unquantisable_meshes():
+        with pytest.raises(ValueError, match='no extent or has non-finite vertices'):
+            make_recursive_grid_bvh(_as_mesh(vertices, triangles), backend='device')
+        wc = world_coords_for(vertices)
+        with pytest.raises(_lib.ChromaError, match='world_scale|world_origin'):
+            _lib.bvh_build(vertices, triangles, wc.world_origin, wc.world_scale, 3, ctx=ctx)
+    good_v, good_t, good = edge_case('soup-257')
+    for scale in (0.0, -good.world_scale, np.nan, np.inf):
+        with pytest.raises(_lib.ChromaError, match='world_scale'):
+            _lib.bvh_build(good_v, good_t, good.world_origin, scale, 3, ctx=ctx)
+    for value in (np.nan, np.inf, -np.inf):
+        origin = good.world_origin.copy()
+        origin[2] = value
+        with pytest.raises(_lib.ChromaError, match='world_origin'):
+            _lib.bvh_build(good_v, good_t, origin, good.world_scale, 3, ctx=ctx)
+    assert_same_tree(native_tree('soup-257', 3, ctx=ctx), numpy_tree('soup-257', 3), 'soup-257 after the refusals')
+    bvh = make_recursive_grid_bvh(_as_mesh(good_v, good_t), backend='device')
+    assert np.array_equal(_words(bvh.nodes), numpy_tree('soup-257', 3)[0])
+
+
+@pytest.mark.parametrize('name', ['identical-3376', 'soup-65537'])
+def test_wide_tree_over_the_device_built_edge_trees(ctx, name):
+    """The derived 8-wide tree, built on the device over DEVICE-built nodes that the test above has pinned, equals the host
+    twin over the same nodes (tests/test_gpu_wide.py builds its soups' nodes on the device and compares them with nothing)."""
+    from chroma_amd import _lib
+    from chroma_amd.bvh.bvh import uint4
+    from test_bvh import edge_case, native_tree, numpy_tree, assert_same_tree
+    from test_gpu_wide import _host_levels, _same
+    words, bounds = native_tree(name, 3, ctx=ctx)
+    assert_same_tree((words, bounds), numpy_tree(name, 3), name)
+    nodes = np.ascontiguousarray(words).view(uint4)[:, 0]
+    nt = len(edge_case(name)[1])
+    dev = _lib.wide_build(nodes, nt, ctx=ctx)
+    _same(dev, _host_levels(nodes, nt), name)
+    assert _lib.wide_validate(dev, nt), name
