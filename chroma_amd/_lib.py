@@ -261,6 +261,7 @@ SIGNATURES = {
     'chroma_allreduce_hits': (c_int32, [c_void_p, c_void_p, c_void_p, c_uint32]),
     'chroma_allreduce_daq': (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_uint32]),
     'chroma_probe': (c_int32, [c_void_p, c_int32, c_uint64, c_void_p, c_void_p, c_void_p, c_uint32, c_float, c_float, c_void_p]),
+    'chroma_probe_math': (c_int32, [c_void_p, c_int32, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p]),
     'chroma_bvh_build': (c_int32, [c_void_p, c_uint32, c_void_p, c_uint32, POINTER(c_float), c_float, c_int32,
                                    POINTER(c_void_p), POINTER(c_uint64), POINTER(c_uint32)]),
     'chroma_bvh_build_device': (c_int32, [c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, POINTER(c_float), c_float, c_int32,

@@ -16,6 +16,8 @@
 
 #include "kernels_render.h"
 
+#include "kernels_probe_math.h"
+
 #include "kernels_pdf.h"
 
 // The count and copy calls: the hit word cleared, the launch it is given run on it (none for an empty range), the word read back
@@ -266,6 +268,19 @@ int chroma_probe(chroma_ctx *ctx, int32_t fn, uint64_t n, const float *d_x, cons
     if (n == 0) return CHROMA_OK;
     hipLaunchKernelGGL(k_probe, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (int)fn, n, d_x, d_tab_x, d_tab_f,
                        ntab, start, step, d_out);
+    HIP_TRY(hipGetLastError());
+    return CHROMA_OK;
+}
+
+int chroma_probe_math(chroma_ctx *ctx, int32_t op, uint64_t n, const void *d_x, const void *d_y, const void *d_z, void *d_out)
+{
+    if (!ctx || !d_x || !d_out || op < 0 || op >= PROBE_MATH_NOPS) return set_error(CHROMA_ERR_INVALID, "bad argument");
+    if (((op == 7 || (op >= 15 && op <= 18)) && !d_y) || (op == 18 && !d_z))
+        return set_error(CHROMA_ERR_INVALID, "probe_math %d: operand array missing", op);
+    if (n >= (1ull << 31)) return set_error(CHROMA_ERR_INVALID, "probe_math: too many elements");
+    if (n == 0) return CHROMA_OK;
+    hipLaunchKernelGGL(k_probe_math, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (int)op, n, (const uint32_t *)d_x,
+                       (const uint32_t *)d_y, (const uint32_t *)d_z, (uint32_t *)d_out);
     HIP_TRY(hipGetLastError());
     return CHROMA_OK;
 }

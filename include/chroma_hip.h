@@ -851,6 +851,22 @@ int chroma_allreduce_daq(chroma_ctx *ctx, uint32_t *d_earliest_time_int, uint32_
 int chroma_probe(chroma_ctx *ctx, int32_t fn, uint64_t n, const float *d_x, const float *d_tab_x, const float *d_tab_f,
                  uint32_t ntab, float start, float step, float *d_out);
 
+/* Test probe of the numeric contract: ONE call per element of a single primitive of include/chroma_math.h as compiled
+ * for the device, so that tests (tests/test_gpu_math_contract.py) can hold it bit for bit to the host compiler's build of
+ * the same header (the CPU oracle: oracle_math, oracle_rng_probe, same numbering).  All pointers are device pointers to
+ * 32-bit words: a float travels as its bits, integer results are written as they are.  Arrays an op does not read may
+ * be NULL.  n < 2^31.
+ *   op  0 cm_logf    1 cm_expf    2 cm_sinf    3 cm_cosf   4 cm_tanf   5 cm_asinf   6 cm_acosf      d_x[n] -> d_out[n]
+ *       8 cm_sqrtf  10 cm_atanf  11 cm_floorf 12 cm_roundf                                           d_x[n] -> d_out[n]
+ *       9 cm_u32_to_uniform (d_x[n]: the words)   13 cm_f2i   14 cm_f2u32 (d_out[n]: the integers)   d_x[n] -> d_out[n]
+ *       7 cm_atan2f(x, y)   15 x / y   16 cm_fminf(x, y)   17 cm_fmaxf(x, y)                  d_x[n], d_y[n] -> d_out[n]
+ *      18 cm_fmaf(x, y, z)                                                            d_x[n], d_y[n], d_z[n] -> d_out[n]
+ *      19 cm_philox4x32_10   d_x[6 n] = counter words 0..3, key words 0..1 -> d_out[4 n]
+ *      20 cm_rng_uniform     d_x[6 n] = seed lo, seed hi, photon id lo, id hi, stream word, start counter
+ *                            -> d_out[8 n]: the 8 draws that follow
+ *      21 cm_rng_normal      d_x[6 n] as for 20 -> d_out[4 n]: the 4 normal deviates (two uniforms each) that follow */
+int chroma_probe_math(chroma_ctx *ctx, int32_t op, uint64_t n, const void *d_x, const void *d_y, const void *d_z, void *d_out);
+
 /* ---- host-side BVH construction -------------------------------------------------------
  * Recursive-grid builder: replaces make_recursive_grid_bvh (chroma/bvh/grid.py:11-95) and the
  * kernels it drives -- make_leaves, make_parents_detailed, copy_and_offset, collapse_child

@@ -17,8 +17,53 @@
  * and which therefore has no bit-level definition to match.
  *
  * The approximations are the classic single-precision minimax forms (Cephes
- * lineage): relative error <= ~2 ulp over the domains the path uses.
- * tests/test_math_contract.py checks them against libm in double precision.
+ * lineage).  What they promise, and the worst error measured against libm in
+ * double precision (tests/test_math_contract.py: the host build, strided sweeps
+ * of ~4e6 bit patterns over each WHOLE declared domain -- every 509th positive
+ * float for log, every 521st for exp, every 587th for the trigonometric
+ * functions, every 541st for asin/acos, all 255 x 255 finite exponent pairs x 4
+ * mantissas x 4 sign pairs for atan2 -- plus the +-8 ulp neighbours of every
+ * branch constant below):
+ *
+ *   cm_logf   x > 0, subnormals included       < 1.5 ulp        0.82 ulp (at 0.70708358)
+ *   cm_expf   [-87.33654475, 88.72283905],     < 1.5 ulp        1.00 ulp (at -38.469646)
+ *             results >= FLT_MIN; exactly 0 below, exactly +inf above and AT
+ *             the upper limit (0x42b17218 lies 3e-7 above log(FLT_MAX))
+ *   cm_sinf   [-8192, 8192], NaN beyond        < 1.5e-7 ABSOLUTE   7.65e-8 (at 6536.8652)
+ *   cm_cosf   [-8192, 8192], NaN beyond        < 1.5e-7 ABSOLUTE   7.82e-8 (at 1698.8168)
+ *   cm_tanf   [-8192, 8192], NaN beyond        < 1.5e-7 as an ANGLE, |t - tan x| / (1 + tan^2 x)
+ *                                                               9.10e-8 (at 834.87781)
+ *   cm_asinf  [-1, 1], NaN beyond              < 3 ulp          2.32 ulp (at 0.50042373)
+ *   cm_acosf  [-1, 1], NaN beyond              < 2 ulp          1.23 ulp (at -0.51448303)
+ *   cm_atanf  all finite x                     < 3 ulp          2.60 ulp (at 0.4362869)
+ *   cm_atan2f all pairs                        < 4e-7 ABSOLUTE  2.2e-7
+ *
+ * The trigonometric functions are an ABSOLUTE-error contract: the three-part
+ * Cody-Waite reduction leaves an absolute error in the reduced argument that
+ * grows with |x|, so sin and cos lose relative accuracy next to their zeros,
+ * and tan's RELATIVE error grows next to its zeros and poles with the argument:
+ * < 5e-7 on [-20, 20] (4.6e-7 measured, next to an octant border), 6.6e-5 at
+ * 8092.7427.  As an angle (the error of atan(tan x)) it stays at the sin/cos
+ * figure over the whole domain.
+ *
+ * Signs of zero, as they are (pinned by the tests; the engine, the oracle and the
+ * reference-physics libraries all produce these bits from this one header):
+ * cm_sinf(-0) and cm_tanf(-0) give +0 (`sneg` is x < 0); cm_asinf(-0) and
+ * cm_sqrtf(-0) give -0; cm_atanf(-0) gives +0; cm_atan2f(+-0, -0) = +-pi and
+ * cm_atan2f(+-0, +0) = +-0 as in C, but for x > 0 the result is formed as
+ * 0.0f + atan(y / x), so cm_atan2f(-0, x > 0), cm_atan2f(y < 0, +inf) and a
+ * negative quotient that underflows give +0 where C gives -0.
+ *
+ * On the device: tests/test_gpu_math_contract.py runs every primitive below, one
+ * call per element (chroma_probe_math), on ~2.1e6 inputs per one-operand op and
+ * ~2.6e6 per two-operand op -- every exponent field with the extreme and 4093
+ * random mantissas in both signs, NaNs and subnormals included, and the same
+ * branch-constant neighbours -- and finds hipcc's gfx950 build of this header
+ * equal to the host build BIT FOR BIT on every element (two NaNs counting as
+ * equal).  The device's worst errors against float64 over those inputs
+ * (measured on an MI355X, and therefore the host's on the same inputs): log
+ * 0.75 ulp, exp 1.00 ulp, sin 7.65e-8, cos 7.82e-8, tan 9.10e-8 as an angle,
+ * asin 2.10 ulp, acos 1.21 ulp, atan 2.61 ulp, atan2 2.68e-7 absolute.
  *
  * The includer may define CM_FN (e.g. `__host__ __device__ static inline`).
  */

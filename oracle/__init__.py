@@ -302,15 +302,40 @@ def run_daq_many(packed, photons, tables_host, charge_unit, seed, ndaq, photon_i
     return t, (q_int.astype(np.float32) * np.float32(charge_unit)).astype(np.float32), hist, t < 1e8
 
 
-def math_fn(fn, x, y=None, variant='contract'):
-    names = {'log': 0, 'exp': 1, 'sin': 2, 'cos': 3, 'tan': 4, 'asin': 5, 'acos': 6, 'atan2': 7, 'sqrt': 8, 'uniform': 9}
+# one primitive of include/chroma_math.h per element: the op numbers of oracle_math3, oracle_rng_probe and the engine's
+# chroma_probe_math ('uniform' takes its words, 'f2i' and 'f2u32' give their integers, as the bits of float32 arrays)
+MATH_OPS = {'log': 0, 'exp': 1, 'sin': 2, 'cos': 3, 'tan': 4, 'asin': 5, 'acos': 6, 'atan2': 7, 'sqrt': 8, 'uniform': 9,
+            'atan': 10, 'floor': 11, 'round': 12, 'f2i': 13, 'f2u32': 14, 'div': 15, 'fmin': 16, 'fmax': 17, 'fma': 18,
+            'philox': 19, 'rng_uniform': 20, 'rng_normal': 21}
+RNG_PROBE_WIDTH = {'philox': 4, 'rng_uniform': 8, 'rng_normal': 4}
+
+
+def math_fn(fn, x, y=None, z=None, variant='contract'):
     lib = load(variant)
     x = np.ascontiguousarray(x, dtype=np.float32)
     y = x if y is None else np.ascontiguousarray(y, dtype=np.float32)
+    z = x if z is None else np.ascontiguousarray(z, dtype=np.float32)
+    assert x.size == y.size == z.size and MATH_OPS[fn] <= 18
     out = np.empty_like(x)
-    rc = lib.oracle_math(names[fn], x.size, x.ctypes.data, y.ctypes.data, out.ctypes.data)
+    lib.oracle_math3.restype = c_int32
+    lib.oracle_math3.argtypes = [c_int32, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p]
+    rc = lib.oracle_math3(MATH_OPS[fn], x.size, x.ctypes.data, y.ctypes.data, z.ctypes.data, out.ctypes.data)
     assert rc == 0
     return out
+
+
+def rng_probe(fn, words, variant='contract'):
+    """'philox': words [n][6] = counter 0..3, key 0..1 -> [n][4] uint32.  'rng_uniform' / 'rng_normal': words [n][6] =
+    seed lo, seed hi, photon id lo, id hi, stream word, start counter -> the 8 uniforms / 4 normal deviates that follow,
+    [n][8] / [n][4] float32."""
+    lib = load(variant)
+    lib.oracle_rng_probe.restype = c_int32
+    lib.oracle_rng_probe.argtypes = [c_int32, c_uint64, c_void_p, c_void_p]
+    w = np.ascontiguousarray(words, dtype=np.uint32).reshape(-1, 6)
+    out = np.empty((len(w), RNG_PROBE_WIDTH[fn]), dtype=np.uint32)
+    rc = lib.oracle_rng_probe(MATH_OPS[fn], len(w), w.ctypes.data, out.ctypes.data)
+    assert rc == 0
+    return out if fn == 'philox' else out.view(np.float32)
 
 
 def render(packed, origins, directions, alpha_depth=10, bg_color=0, state=None, variant='contract'):

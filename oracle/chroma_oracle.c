@@ -1312,11 +1312,24 @@ int oracle_generate_bomb(const chroma_photon_arrays *a, uint64_t n, uint64_t see
 }
 
 /* ---- probes used by tests/ to pin the numeric contract ---------------------------- */
-/* fn: 0 log 1 exp 2 sin 3 cos 4 tan 5 asin 6 acos 7 atan2(x,y) 8 sqrt 9 uniform(u32 bits) */
-int oracle_math(int fn, uint64_t n, const float *x, const float *y, float *out)
+/* fn: 0 log 1 exp 2 sin 3 cos 4 tan 5 asin 6 acos 7 atan2(x,y) 8 sqrt 9 uniform(u32 bits)
+ * 10 atan 11 floor 12 round 13 f2i (result as bits) 14 f2u32 (result as bits) 15 x / y 16 fmin(x,y) 17 fmax(x,y)
+ * 18 fma(x,y,z) -- the numbering of the engine's chroma_probe_math.  10..18 are the contract's in both builds of the
+ * oracle (the path calls them as cm_* everywhere); y may be NULL where only x is read, z is read by 18 alone. */
+int oracle_math3(int fn, uint64_t n, const float *x, const float *y, const float *z, float *out)
 {
+    if (((fn == 7 || (fn >= 15 && fn <= 18)) && !y) || (fn == 18 && !z)) return -1;
     for (uint64_t i = 0; i < n; i++) {
         switch (fn) {
+        case 10: out[i] = cm_atanf(x[i]); break;
+        case 11: out[i] = cm_floorf(x[i]); break;
+        case 12: out[i] = cm_roundf(x[i]); break;
+        case 13: out[i] = cm_u2f((uint32_t)cm_f2i(x[i])); break;
+        case 14: out[i] = cm_u2f(cm_f2u32(x[i])); break;
+        case 15: out[i] = x[i] / y[i]; break;
+        case 16: out[i] = cm_fminf(x[i], y[i]); break;
+        case 17: out[i] = cm_fmaxf(x[i], y[i]); break;
+        case 18: out[i] = cm_fmaf(x[i], y[i], z[i]); break;
         case 0: out[i] = M_LOGF(x[i]); break;
         case 1: out[i] = M_EXPF(x[i]); break;
         case 2: out[i] = M_SINF(x[i]); break;
@@ -1329,6 +1342,30 @@ int oracle_math(int fn, uint64_t n, const float *x, const float *y, float *out)
         case 9: out[i] = cm_u32_to_uniform(cm_f2u(x[i])); break;
         default: return -1;
         }
+    }
+    return 0;
+}
+
+int oracle_math(int fn, uint64_t n, const float *x, const float *y, float *out) { return oracle_math3(fn, n, x, y, NULL, out); }
+
+/* The generator, one element per six words, as chroma_probe_math's ops 19..21:
+ * 19 Philox itself: w = counter words 0..3, key words 0..1 -> out[4]
+ * 20 / 21 a stream WITH its stream word (oracle_uniform_stream has stream 0 only): w = seed lo, seed hi, photon id lo,
+ * id hi, stream word, start counter -> the 8 uniform draws (20) or the 4 normal deviates (21) that follow, as bits */
+int oracle_rng_probe(int op, uint64_t n, const uint32_t *words, uint32_t *out)
+{
+    for (uint64_t i = 0; i < n; i++) {
+        const uint32_t *w = words + 6 * i;
+        if (op == 19) {
+            cm_philox4x32_10(w[0], w[1], w[2], w[3], w[4], w[5], out + 4 * i);
+            continue;
+        }
+        if (op != 20 && op != 21) return -1;
+        cm_rng r;
+        cm_rng_init(&r, (uint64_t)w[0] | ((uint64_t)w[1] << 32), (uint64_t)w[2] | ((uint64_t)w[3] << 32), w[5]);
+        r.stream = w[4];
+        if (op == 20) for (int k = 0; k < 8; k++) out[8 * i + k] = cm_f2u(cm_rng_uniform(&r));
+        else for (int k = 0; k < 4; k++) out[4 * i + k] = cm_f2u(cm_rng_normal(&r));
     }
     return 0;
 }
