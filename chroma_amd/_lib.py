@@ -117,6 +117,12 @@ class DaqTrigger(Structure):
                 ('post', c_uint32)]
 
 
+class DaqDigitizer(Structure):
+    """chroma_daq_digitizer (taps and noise_cdf: host pointers)"""
+    _fields_ = [('taps', c_void_p), ('ntaps', c_uint32), ('shift', c_uint32), ('pedestal', c_int32), ('bits', c_uint32),
+                ('noise_cdf', c_void_p), ('nnoise', c_uint32), ('noise_lo', c_int32)]
+
+
 class LightSource(Structure):
     """chroma_light_source (host pointers)"""
     _fields_ = [('refractive_index', c_void_p), ('scintillation_cdf', c_void_p), ('time_cdf', c_void_p),
@@ -216,6 +222,12 @@ SIGNATURES = {
                                             c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p,
                                             c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_uint64),
                                             POINTER(c_uint64)]),
+    'chroma_daq_digitize_gates': (c_int32, [c_void_p, c_uint32, c_uint32, POINTER(DaqWindow), POINTER(DaqTrigger), POINTER(DaqDigitizer), c_uint64,
+                                            c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_uint64, c_void_p,
+                                            c_void_p, c_uint64, c_uint64, c_uint64, c_uint64, c_void_p, c_void_p]),
+    'chroma_daq_digitize_host': (c_int32, [c_uint32, c_uint32, POINTER(DaqWindow), POINTER(DaqTrigger), POINTER(DaqDigitizer), c_uint64,
+                                           c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_uint64, c_void_p,
+                                           c_void_p, c_uint64, c_uint64, c_uint64, c_uint64, c_void_p, c_void_p]),
     'chroma_daq_convert': (c_int32, [c_void_p, c_uint32, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     'chroma_pdf_bin_hits': (c_int32, [c_void_p, c_uint32, c_int32, c_uint32, c_void_p, c_void_p, c_int32, c_float, c_float,
                                       c_int32, c_float, c_float, c_void_p, c_void_p]),

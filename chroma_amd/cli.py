@@ -5,7 +5,7 @@ GEANT4 and writes a ROOT file; neither GEANT4 nor ROOT is part of this engine, s
 keeps the command-line shape (detector string, -n/--nevents, -o/--output, -s/--seed, -j device)
 but the particle source is the isotropic photon bomb of chroma/benchmark.py:77-83 and the output is
 an ``.npz``: per event the flat hits (channel, t, wavelength, pos, flags), with --run-daq the channel
-times and charges, with --daq-window T0,DT,NBINS also the pulses per (channel, time bin), with --daq-trigger the triggers on them, with --daq-noise RATE_HZ dark noise among them, with --save-photons-beg/--save-photons-end the photons themselves and with --track or
+times and charges, with --daq-window T0,DT,NBINS also the pulses per (channel, time bin), with --daq-trigger the triggers on them, with --daq-digitize the ADC traces of their gates, with --daq-noise RATE_HZ dark noise among them, with --save-photons-beg/--save-photons-end the photons themselves and with --track or
 --device-tracks every photon's state after each step.
 """
 import argparse
@@ -54,6 +54,9 @@ def main(argv=None):
     ap.add_argument('--daq-trigger-kind', default='nhit', choices=('nhit', 'npe'), help='what the trigger sums: distinct channels or photoelectrons')
     ap.add_argument('--daq-noise', default=None, type=float, metavar='RATE_HZ',
                     help='with --daq-window, add PMT dark noise of RATE_HZ per channel to the pulses (and to what the trigger sees)')
+    ap.add_argument('--daq-digitize', default=None, metavar='AMPLITUDE,RISE_NS,FALL_NS[,BITS[,PEDESTAL[,SIGMA]]]',
+                    help='with --daq-trigger, also write the ADC trace of every channel in every gate: a biexponential pulse of AMPLITUDE counts per '
+                         'unit charge, read with BITS bits on PEDESTAL counts and electronics noise of SIGMA counts')
     ap.add_argument('--save-photons-beg', action='store_true', help='also write the initial photons of every event (bin/chroma-sim:51-53)')
     ap.add_argument('--save-photons-end', action='store_true', help='also write the final photons of every event (bin/chroma-sim:54-56)')
     ap.add_argument('--track', action='store_true', help='also write every photon\'s state after each step (Simulation(photon_tracking=True))')
@@ -91,6 +94,20 @@ def main(argv=None):
             ap.error('--daq-noise needs --daq-window')
         if not (args.daq_noise >= 0.0 and args.daq_noise < float('inf')):
             ap.error('--daq-noise takes a finite rate that is not negative')
+    daq_digitizer = None
+    if args.daq_digitize is not None:
+        if daq_trigger is None:
+            ap.error('--daq-digitize needs --daq-trigger')
+        parts = args.daq_digitize.split(',')
+        if not 3 <= len(parts) <= 6:
+            ap.error('--daq-digitize takes AMPLITUDE,RISE_NS,FALL_NS[,BITS[,PEDESTAL[,SIGMA]]]')
+        from chroma_amd.gpu.daq import DaqDigitizer
+        try:
+            kw = dict(bits=int(parts[3]) if len(parts) > 3 else 14, pedestal=int(parts[4]) if len(parts) > 4 else 0,
+                      noise_sigma=float(parts[5]) if len(parts) > 5 else 0.0)
+            daq_digitizer = DaqDigitizer.biexponential(float(parts[0]), float(parts[1]), float(parts[2]), daq_window[1], **kw).check(daq_trigger)
+        except ValueError as e:
+            ap.error('--daq-digitize: %s' % e)
     t0 = time.time()
     detector = load_geometry_from_string(args.detector, cache_dir=args.cache_dir)
     print('geometry: %d triangles, BVH %d nodes (%.1f s)' % (len(detector.mesh.triangles), len(detector.bvh.nodes), time.time() - t0))
@@ -104,7 +121,7 @@ def main(argv=None):
     for ev in sim.simulate(events, keep_photons_beg=args.save_photons_beg, keep_photons_end=args.save_photons_end,
                            keep_hits=False, keep_flat_hits=hasattr(detector, 'num_channels'),
                            run_daq=args.run_daq, max_steps=args.max_steps, daq_window=daq_window, daq_trigger=daq_trigger,
-                           daq_noise=args.daq_noise):
+                           daq_noise=args.daq_noise, daq_digitizer=daq_digitizer):
         key = 'ev%d' % ev.id
         for tag, ph in (('photons_beg', ev.photons_beg), ('photons_end', ev.photons_end)):
             if ph is not None:
@@ -156,6 +173,9 @@ def main(argv=None):
             out[key + '/trigger_hit_q'] = ev.triggers.hit_q
             out[key + '/trigger_hit_t'] = ev.triggers.hit_t_first
             out[key + '/pulse_trigger'] = ev.triggers.pulse_trigger
+            if ev.triggers.traces is not None:
+                out[key + '/trigger_adc'] = ev.triggers.traces
+                out[key + '/trigger_trace_flags'] = ev.triggers.trace_flags
     dt = time.time() - t0
     np.savez_compressed(args.output, **out)
     print('%d events, %d photons, %d hits in %.2f s (%.1f events/s, %.3g photons/s) -> %s' % (

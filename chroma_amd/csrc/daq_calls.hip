@@ -1,6 +1,6 @@
 // daq_calls.hip -- the DAQ's entry points: the single-launch acquisitions (chroma/cuda/daq.cu's, as kernel_calls.hip has its calls)
-// and the pipelines behind them -- the per-event acquisition and its compaction, the time-binned DAQ with its dark noise, and its
-// trigger.  A pipeline is several launches with a sort, a scan or a read-back between them, on the context's pooled scratch
+// and the pipelines behind them -- the per-event acquisition and its compaction, the time-binned DAQ with its dark noise, its
+// trigger and its digitiser.  A pipeline is several launches with a sort, a scan or a read-back between them, on the context's pooled scratch
 // block, which each lays out through ONE description (chroma_internal.h: Carver).
 #include <stdint.h>
 #include <algorithm>
@@ -13,6 +13,7 @@
 #include "kernels_daq_pulses.h"
 #include "kernels_daq_noise.h"
 #include "kernels_daq_trigger.h"
+#include "kernels_daq_digitize.h"
 
 // ---- what more than one call refuses ----
 static int check_daq_tables(const chroma_daq_tables *tables)
@@ -549,6 +550,39 @@ int chroma_daq_trigger_pulses(chroma_ctx *ctx, uint32_t nrows, uint32_t nchannel
     } else {
         HIP_TRY(hipMemsetAsync(d_hit_offsets, 0, ((size_t)total + 1) * sizeof(uint32_t), stream));
     }
+    HIP_TRY(hipStreamSynchronize(stream));
+    return CHROMA_OK;
+}
+
+int chroma_daq_digitize_gates(chroma_ctx *ctx, uint32_t nrows, uint32_t nchannels, const chroma_daq_window *window,
+                              const chroma_daq_trigger *trigger, const chroma_daq_digitizer *digitizer, uint64_t seed, uint32_t acquisition,
+                              const uint32_t *d_offsets, const int32_t *d_channel, const uint32_t *d_bin, const uint32_t *d_q_int, uint64_t npulses,
+                              const uint32_t *d_trig_offsets, const uint32_t *d_trig_bin, uint64_t ntriggers, const uint32_t *d_hit_offsets,
+                              const int32_t *d_hit_channel, uint64_t nhits, uint64_t first_hit, uint64_t nhits_call, uint64_t sample_capacity,
+                              uint16_t *d_adc, uint32_t *d_trace_flags)
+{
+    if (!ctx || !window || !trigger || !digitizer || !d_offsets || !d_trig_offsets || !d_hit_offsets || (npulses && (!d_channel || !d_bin || !d_q_int)) ||
+        (ntriggers && !d_trig_bin) || (nhits && !d_hit_channel) || (nhits_call && (!d_adc || !d_trace_flags)))
+        return set_error(CHROMA_ERR_INVALID, "bad argument");
+    if (const char *why = daq_digitize::check(nrows, nchannels, window, trigger, digitizer, npulses, ntriggers, nhits, first_hit, nhits_call, sample_capacity))
+        return set_error(CHROMA_ERR_INVALID, "%s", why);
+    if (nhits_call == 0) return CHROMA_OK;
+    hipStream_t stream = ctx->stream;
+    const CallScope scope(ctx);
+    DaqDigitizeView v;
+    for (uint32_t j = 0; j < 64u; j++) v.noise_cdf[j] = j < digitizer->nnoise ? digitizer->noise_cdf[j] : 0xffffffffu;
+    v.nnoise = digitizer->nnoise; v.noise_lo = digitizer->noise_lo;
+    v.ntaps = digitizer->ntaps; v.shift = digitizer->shift; v.pedestal = digitizer->pedestal; v.bits = digitizer->bits;
+    int32_t *d_taps = nullptr;          // the block: the taps
+    int rc = carve_call_scratch(scope, [&](Carver &c) { d_taps = c.take<int32_t>(digitizer->ntaps); }); if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(d_taps, digitizer->taps, (size_t)digitizer->ntaps * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipStreamSynchronize(stream));          // (the caller's taps are his again when the call returns)
+    v.taps = d_taps;
+    const uint32_t ntraces = (uint32_t)nhits_call;          // (<= nhits < 2^32)
+    hipLaunchKernelGGL(k_daq_digitize, dim3((ntraces - 1u) / DAQ_DIGITIZE_WAVES + 1u), dim3(DAQ_DIGITIZE_BLOCK), 0, stream, v, nrows, nchannels,
+                       trigger->pre, trigger->pre + trigger->post, seed, acquisition, d_offsets, d_channel, d_bin, d_q_int, (uint32_t)npulses, d_trig_offsets,
+                       d_trig_bin, (uint32_t)ntriggers, d_hit_offsets, d_hit_channel, (uint32_t)first_hit, ntraces, d_adc, d_trace_flags);
+    HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(stream));
     return CHROMA_OK;
 }

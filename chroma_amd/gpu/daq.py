@@ -467,22 +467,168 @@ class DaqTrigger(object):
             self.threshold, self.width, self.holdoff, self.pre, self.post, self.kind)
 
 
+CLIPPED_HIGH, CLIPPED_LOW = 1, 2          # the bits of a trace's flag word: some sample clipped at the top, some at 0
+
+
+class DaqDigitizer(object):
+    """The digitiser of a trigger's gates (chroma_daq_digitizer): every gated (firing, channel) is read out as a trace of
+    ``pre + post`` ADC samples, one per bin from ``pre`` bins before the firing on.  ``shape`` is the response to one unit of the
+    detector's charge, in ADC counts per bin from the pulse's own bin on (1 .. 1024 bins; it may be negative); pulses pile up, and
+    pulses from before the gate have their tails in it.  ``pedestal`` (ADC counts) is added, then electronics noise -- a Gaussian
+    of ``noise_sigma`` ADC counts rounded to whole counts, one draw per (event, channel, bin) whichever firing reads it -- and the
+    sample is clipped to ``bits`` bits; ``trace_flags`` says where that happened (``CLIPPED_HIGH``, ``CLIPPED_LOW``).  The
+    arithmetic is fixed point with ``shift`` fractional bits (include/chroma_hip.h, "digitiser").
+
+    ``tables`` builds the integer tables in float64: tap d = round(shape[d] * charge_unit * 2^shift), the response to one charge
+    COUNT, and for the noise ``noise_lo = -32`` and 64 entries floor(Phi((noise_lo + j + 0.5) / sigma) * 2^32), saturated at
+    2^32 - 1 -- every sigma up to ``MAX_SIGMA`` = 8 out to 4 sigma."""
+
+    MAX_TAPS = 1024
+    MAX_NOISE = 64
+    NOISE_LO = -32
+    MAX_SIGMA = 8.0
+
+    def __init__(self, shape, pedestal=0, bits=14, shift=16, noise_sigma=0.0):
+        shape = np.array(shape, dtype=np.float64)
+        if shape.ndim != 1 or not 1 <= len(shape) <= self.MAX_TAPS or not np.isfinite(shape).all():
+            raise ValueError('a digitiser\'s shape is 1 .. %d finite values' % self.MAX_TAPS)
+        shape.setflags(write=False)
+        self.shape = shape
+        for name, value, lo, hi in (('pedestal', pedestal, -2 ** 31, 2 ** 31 - 1), ('bits', bits, 1, 16), ('shift', shift, 0, 31)):
+            try:
+                whole = int(value)
+            except (TypeError, ValueError):
+                raise ValueError('a digitiser\'s %s is a whole number' % name)
+            if whole != value or not lo <= whole <= hi:
+                raise ValueError('a digitiser\'s %s is a whole number of %d .. %d' % (name, lo, hi))
+            setattr(self, name, whole)
+        self.noise_sigma = float(noise_sigma)
+        if not 0.0 <= self.noise_sigma <= self.MAX_SIGMA:
+            raise ValueError('a digitiser\'s noise has a sigma of 0 .. %g ADC counts: the table holds no more' % self.MAX_SIGMA)
+
+    @classmethod
+    def biexponential(cls, amplitude, rise_ns, fall_ns, dt, length=None, **kw):
+        """The digitiser whose shape is exp(-t / fall_ns) - exp(-t / rise_ns), scaled so that the curve peaks at ``amplitude``
+        ADC counts per unit charge, sampled at the centres t = (d + 0.5) dt of the bins (``dt`` in ns) from the pulse's own on.
+        ``length`` bins; by default up to where the curve has fallen to a thousandth of its peak, 1024 at the most."""
+        amplitude, rise, fall, dt = float(amplitude), float(rise_ns), float(fall_ns), float(dt)
+        if not (0.0 < rise < fall < float('inf')) or not (0.0 < dt < float('inf')) or not np.isfinite(amplitude):
+            raise ValueError('a biexponential pulse needs 0 < rise_ns < fall_ns, a positive dt and a finite amplitude')
+        t_peak = np.log(fall / rise) * rise * fall / (fall - rise)
+        peak = np.exp(-t_peak / fall) - np.exp(-t_peak / rise)
+        if length is None:
+            length = int(min(cls.MAX_TAPS, max(1, np.ceil((t_peak + fall * np.log(1000.0)) / dt))))
+        if int(length) != length or not 1 <= int(length) <= cls.MAX_TAPS:
+            raise ValueError('a digitiser\'s shape has 1 .. %d bins' % cls.MAX_TAPS)
+        t = (np.arange(int(length), dtype=np.float64) + 0.5) * dt
+        return cls(amplitude * (np.exp(-t / fall) - np.exp(-t / rise)) / peak, **kw)
+
+    @classmethod
+    def of(cls, digitizer):
+        """``digitizer`` itself if it is a DaqDigitizer, or the biexponential one of an (amplitude, rise_ns, fall_ns, dt[, bits[,
+        pedestal[, sigma]]]) tuple."""
+        if isinstance(digitizer, cls):
+            return digitizer
+        try:
+            parts = tuple(digitizer)
+        except TypeError:
+            raise ValueError('a DAQ digitiser is (amplitude, rise_ns, fall_ns, dt[, bits[, pedestal[, sigma]]])')
+        if not 4 <= len(parts) <= 7:
+            raise ValueError('a DAQ digitiser is (amplitude, rise_ns, fall_ns, dt[, bits[, pedestal[, sigma]]])')
+        kw = dict(zip(('bits', 'pedestal', 'noise_sigma'), parts[4:]))
+        try:
+            return cls.biexponential(*[float(x) for x in parts[:4]], **kw)
+        except TypeError:
+            raise ValueError('a DAQ digitiser is (amplitude, rise_ns, fall_ns, dt[, bits[, pedestal[, sigma]]])')
+
+    def check(self, trigger):
+        """Raises ValueError unless ``trigger``'s gate is one this digitiser can read: pre + post of 65536 samples at the most."""
+        if trigger.pre + trigger.post > 65536:
+            raise ValueError('a gate of %d samples: a trace holds 65536' % (trigger.pre + trigger.post))
+        return self
+
+    def tables(self, charge_unit):
+        """(taps int32, noise_cdf uint32 -- empty without noise --, noise_lo) of chroma_daq_digitizer for a detector whose
+        charge counts are of ``charge_unit``."""
+        charge_unit = float(charge_unit)
+        if not (0.0 < charge_unit < float('inf')):
+            raise ValueError('a charge unit is finite and positive')
+        taps = np.rint(self.shape * charge_unit * 2.0 ** self.shift)
+        if not np.isfinite(taps).all() or (taps > 2 ** 31 - 1).any() or (taps < -2 ** 31).any():
+            raise ValueError('the taps do not fit 32 bits: a smaller shift, or a smaller shape')
+        cdf = np.zeros(0, dtype=np.uint32)
+        if self.noise_sigma > 0.0:
+            import math
+            x = (self.NOISE_LO + np.arange(self.MAX_NOISE, dtype=np.float64) + 0.5) / self.noise_sigma
+            phi = np.array([0.5 * (1.0 + math.erf(v / math.sqrt(2.0))) for v in x], dtype=np.float64)
+            cdf = np.minimum(np.floor(phi * 2.0 ** 32), 2.0 ** 32 - 1).astype(np.uint32)
+        return taps.astype(np.int32), cdf, self.NOISE_LO
+
+    def struct(self, charge_unit):
+        """(the chroma_daq_digitizer, the host arrays it points to: keep them alive as long as it is used)"""
+        taps, cdf, lo = self.tables(charge_unit)
+        return _lib.DaqDigitizer(_lib.ptr(taps), len(taps), self.shift, self.pedestal, self.bits, _lib.ptr(cdf) if len(cdf) else None,
+                                 len(cdf), lo), (taps, cdf)
+
+    def _key(self):
+        return (self.shape.tobytes(), self.pedestal, self.bits, self.shift, self.noise_sigma)
+
+    def __eq__(self, other):
+        return isinstance(other, DaqDigitizer) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        return 'DaqDigitizer(shape=<%d bins, peak %g>, pedestal=%d, bits=%d, shift=%d, noise_sigma=%r)' % (
+            len(self.shape), float(np.abs(self.shape).max()), self.pedestal, self.bits, self.shift, self.noise_sigma)
+
+
 class Triggers(object):
     """The triggers of ONE event (``EventTriggers.event(i)``, ``ev.triggers``): ``bin`` and ``sum`` of every firing, ascending;
     ``sparse(k)`` the channels in the gate of firing k, ``channels(k)`` the same as a dense ``event.Channels``; ``pulse_trigger``:
-    per pulse of the event's ``Pulses`` the firing (numbered within the event) whose gate holds it, or ``NO_TRIGGER``."""
+    per pulse of the event's ``Pulses`` the firing (numbered within the event) whose gate holds it, or ``NO_TRIGGER``.  With a
+    ``DaqDigitizer`` also ``adc(k)``, ``trace(k, channel)`` and ``sample_times(k)``: the ADC traces of firing k's channels, and
+    ``traces`` (hits x samples, uint16) and ``trace_flags``, a word per hit (``CLIPPED_HIGH``, ``CLIPPED_LOW``); None without one,
+    as is ``digitizer``."""
 
     def __init__(self, window, trigger, nchannels, charge_unit, bin, sum, hit_offsets, hit_channel, hit_npe, hit_q_int, hit_t_first,
-                 hit_flags, pulse_trigger):
+                 hit_flags, pulse_trigger, adc=None, trace_flags=None, digitizer=None):
         self.window, self.trigger, self.nchannels, self.charge_unit = window, trigger, nchannels, charge_unit
         self.bin, self.sum = bin, sum
         self.hit_offsets = hit_offsets          # (len + 1, into the hit arrays; the first is 0)
         self.hit_channel, self.hit_npe, self.hit_q_int, self.hit_t_first, self.hit_flags = hit_channel, hit_npe, hit_q_int, hit_t_first, hit_flags
         self.hit_q = (hit_q_int.astype(np.float32) * np.float32(charge_unit)).astype(np.float32)          # as k_daq_convert
         self.pulse_trigger = pulse_trigger
+        self.traces, self.trace_flags, self.digitizer = adc, trace_flags, digitizer          # (hits x samples, uint16; hits, uint32)
 
     def __len__(self):
         return len(self.bin)
+
+    def adc(self, k):
+        """(channel, traces) of firing ``k``: the channels read out, ascending, and their traces (len(channel) x (pre + post),
+        uint16), as slices (no copy)."""
+        if self.traces is None:
+            raise ValueError('these triggers were not digitised (daq_digitizer / digitizer=...)')
+        w = self._slice(k)
+        return self.hit_channel[w], self.traces[w]
+
+    def trace(self, k, channel):
+        """The trace of ``channel`` in firing ``k``; KeyError for a channel without a pulse in the gate: it was not read out."""
+        channels, traces = self.adc(k)
+        channel = int(channel)
+        if not 0 <= channel < self.nchannels:
+            raise IndexError('channel %d of %d' % (channel, self.nchannels))
+        at = int(np.searchsorted(channels, channel))
+        if at == len(channels) or channels[at] != channel:
+            raise KeyError('channel %d has no pulse in the gate of firing %d' % (channel, k))
+        return traces[at]
+
+    def sample_times(self, k):
+        """The nominal lower edges t0 + (bin - pre + s) dt of the samples of firing ``k``'s traces (float64)."""
+        self._slice(k)
+        first = int(self.bin[k]) - self.trigger.pre
+        return self.window.t0 + self.window.dt * (first + np.arange(self.trigger.pre + self.trigger.post, dtype=np.float64))
 
     @property
     def time(self):
@@ -520,15 +666,57 @@ class EventTriggers(object):
     ``EventPulses.trigger(...)``): firings in (event, bin) order -- ``bin``, ``sum`` (uint32), ``offsets`` (len + 1) the events'
     places in them; gated hits in (firing, channel) order -- ``hit_channel`` (int32), ``hit_npe``, ``hit_q_int``, ``hit_flags``
     (uint32), ``hit_t_first`` (float32), ``hit_offsets`` (firings + 1); ``pulse_trigger`` (uint32, per pulse of the batch): the
-    firing, numbered within the batch, whose gate holds the pulse, or ``NO_TRIGGER``."""
+    firing, numbered within the batch, whose gate holds the pulse, or ``NO_TRIGGER``.  Digitised (``acquire_pulses(digitizer=...)``
+    or ``digitize``): ``adc`` (hits x (pre + post), uint16), the ADC trace of every gated hit, ``trace_flags`` (hits, uint32) and
+    ``digitizer``; None otherwise.  ``pulses``: the (channel, bin, q_int) columns of the batch's pulses, which ``digitize`` reads."""
 
     def __init__(self, window, trigger, nchannels, charge_unit, pulse_offsets, offsets, bin, sum, hit_offsets, hit_channel, hit_npe,
-                 hit_q_int, hit_t_first, hit_flags, pulse_trigger):
+                 hit_q_int, hit_t_first, hit_flags, pulse_trigger, adc=None, trace_flags=None, digitizer=None, pulses=None):
         self.window, self.trigger, self.nchannels, self.charge_unit = window, trigger, nchannels, charge_unit
         self.pulse_offsets, self.offsets, self.bin, self.sum, self.hit_offsets = pulse_offsets, offsets, bin, sum, hit_offsets
         self.hit_channel, self.hit_npe, self.hit_q_int, self.hit_t_first, self.hit_flags = hit_channel, hit_npe, hit_q_int, hit_t_first, hit_flags
         self.pulse_trigger = pulse_trigger
+        self.adc, self.trace_flags, self.digitizer = adc, trace_flags, digitizer
+        self.pulses = pulses
         self.nevents = len(offsets) - 1
+
+    def digitize(self, digitizer, seed=0, acquisition=0):
+        """These triggers with the traces of their gated hits under ``digitizer``, computed on the HOST (chroma_daq_digitize_host: no
+        GPU) from the pulses and triggers held here -- bit for bit what ``GPUEventDaq.acquire_pulses(trigger=..., digitizer=digitizer,
+        acquisition=acquisition)`` reads back on a context seeded with ``seed``.  Event i is acquisition ``acquisition + i``.  Returns
+        a new ``EventTriggers`` over the same arrays."""
+        digitizer = DaqDigitizer.of(digitizer).check(self.trigger)
+        if self.pulses is None:
+            raise ValueError('these triggers do not hold their pulses')
+        lib = _lib.load()
+        struct, keep = digitizer.struct(self.charge_unit)
+        win = _lib.DaqWindow(self.window.t0, self.window.dt, self.window.nbins)
+        trig = self.trigger.struct()
+        G = self.trigger.pre + self.trigger.post
+        nhits = len(self.hit_channel)
+        adc = np.zeros((nhits, G), dtype=np.uint16)
+        trace_flags = np.zeros(nhits, dtype=np.uint32)
+        channel, bin, q_int = [np.ascontiguousarray(a, dtype=kind) for a, kind in zip(self.pulses, (np.int32, np.uint32, np.uint32))]
+        u32 = lambda a: np.ascontiguousarray(a, dtype=np.uint32)
+        rows_at_once = max(1, (2 ** 31 - 1) // self.window.nbins)
+        for first in range(0, self.nevents, rows_at_once):
+            last = min(self.nevents, first + rows_at_once)
+            p0, p1 = int(self.pulse_offsets[first]), int(self.pulse_offsets[last])
+            t0, t1 = int(self.offsets[first]), int(self.offsets[last])
+            h0, h1 = int(self.hit_offsets[t0]), int(self.hit_offsets[t1])
+            if h1 == h0:
+                continue
+            offsets, trig_offsets, hit_offsets = u32(self.pulse_offsets[first:last + 1] - p0), u32(self.offsets[first:last + 1] - t0), u32(self.hit_offsets[t0:t1 + 1] - h0)
+            trig_bin, hit_channel = u32(self.bin[t0:t1]), np.ascontiguousarray(self.hit_channel[h0:h1], dtype=np.int32)
+            part, part_flags = adc[h0:h1], trace_flags[h0:h1]
+            _lib.check(lib.chroma_daq_digitize_host(last - first, self.nchannels, ctypes.byref(win), ctypes.byref(trig), ctypes.byref(struct), int(seed),
+                                                    (int(acquisition) + first) & 0xffffffff, _lib.ptr(offsets), _lib.ptr(channel[p0:p1]), _lib.ptr(bin[p0:p1]),
+                                                    _lib.ptr(q_int[p0:p1]), p1 - p0, _lib.ptr(trig_offsets), _lib.ptr(trig_bin), t1 - t0, _lib.ptr(hit_offsets),
+                                                    _lib.ptr(hit_channel), h1 - h0, 0, h1 - h0, part.size, _lib.ptr(part), _lib.ptr(part_flags)))
+        del keep
+        return EventTriggers(self.window, self.trigger, self.nchannels, self.charge_unit, self.pulse_offsets, self.offsets, self.bin, self.sum,
+                             self.hit_offsets, self.hit_channel, self.hit_npe, self.hit_q_int, self.hit_t_first, self.hit_flags, self.pulse_trigger,
+                             adc=adc, trace_flags=trace_flags, digitizer=digitizer, pulses=self.pulses)
 
     def __len__(self):
         return self.nevents
@@ -546,7 +734,8 @@ class EventTriggers(object):
         of = np.where(of == NO_TRIGGER, of, of - np.uint32(a)).astype(np.uint32)
         return Triggers(self.window, self.trigger, self.nchannels, self.charge_unit, self.bin[a:b], self.sum[a:b],
                         self.hit_offsets[a:b + 1] - self.hit_offsets[a], self.hit_channel[h], self.hit_npe[h], self.hit_q_int[h],
-                        self.hit_t_first[h], self.hit_flags[h], of)
+                        self.hit_t_first[h], self.hit_flags[h], of, adc=None if self.adc is None else self.adc[h],
+                        trace_flags=None if self.trace_flags is None else self.trace_flags[h], digitizer=self.digitizer)
 
 
 def _time_image(bits):
@@ -650,7 +839,7 @@ def trigger_pulses_host(window, trigger, nchannels, charge_unit, offsets, channe
     hit_offsets = np.searchsorted(hit_key // nch, np.arange(ntriggers + 1))
     return EventTriggers(window, trigger, nch, charge_unit, offsets, trig_offsets.astype(np.int64), t_bin.astype(np.uint32),
                          t_sum.astype(np.uint32), hit_offsets.astype(np.int64), (hit_key % nch).astype(np.int32), hit_npe.astype(np.uint32),
-                         hit_q.astype(np.uint32), hit_t.view(np.float32), hit_flags.astype(np.uint32), pulse_trigger)
+                         hit_q.astype(np.uint32), hit_t.view(np.float32), hit_flags.astype(np.uint32), pulse_trigger, pulses=(channel, bin, q_int))
 
 
 class GPUEventDaq(object):
@@ -669,7 +858,8 @@ class GPUEventDaq(object):
         self.nchannels = int(gpu_detector.nchannels)
         if self.nchannels < 1:
             raise ValueError('the detector has no channels')
-        self.rows_per_chunk = max(1, int(max_entries) // self.nchannels)
+        self.max_entries = max(1, int(max_entries))
+        self.rows_per_chunk = max(1, self.max_entries // self.nchannels)
         n = self.rows_per_chunk * self.nchannels
         self.earliest_time_int_gpu = empty(n, np.uint32, self.ctx)
         self.channel_q_int_gpu = empty(n, np.uint32, self.ctx)
@@ -683,6 +873,9 @@ class GPUEventDaq(object):
         self._trigger_rows_gpu = None        # acquire_pulses(trigger=...): per row the offsets; per trigger (bin, sum, hit offsets) in one
         self._triggers_gpu = None            # buffer; per hit the five arrays and per pulse its trigger in another
         self._trigger_hits_gpu = None
+        self._trigger_device = None          # what the last _trigger_chunk left on the device, for the digitiser
+        self._adc_gpu = None                 # acquire_pulses(digitizer=...): the samples of one slice of hits ...
+        self._trace_flags_gpu = None         # ... and its flag words, each grown on its own (a shorter gate: fewer samples, more traces)
 
     def _compaction_buffers(self, nrows, capacity):
         if self._offsets_gpu is None or len(self._offsets_gpu) < nrows + 1:
@@ -768,12 +961,39 @@ class GPUEventDaq(object):
             self._triggers_gpu = empty(3 * grown + 1, np.uint32, self.ctx)
         _lib.check(rc)
         nt, nh = int(ntriggers.value), int(nhits.value)
+        self._trigger_device = (self._trigger_rows_gpu, per_trigger[0], per_trigger[2], per_pulse[0], nt, nh)
         t = self._triggers_gpu[:3 * capacity + 1].get()
         h = self._trigger_hits_gpu[:6 * n].get()
         return [self._trigger_rows_gpu[:nrows + 1].get(), t[:nt], t[capacity:capacity + nt], t[2 * capacity:2 * capacity + nt + 1],
                 h[:nh].view(np.int32), h[n:n + nh], h[2 * n:2 * n + nh], h[3 * n:3 * n + nh].view(np.float32), h[4 * n:4 * n + nh], h[5 * n:6 * n]]
 
-    def acquire_pulses(self, gpuphotons, rng_states, bounds, window, acquisition=0, weight=1.0, trigger=None, noise=None):
+    def _digitize_chunk(self, win, trigger, struct, seed, acquisition, nrows, d_offsets, arrays, npulses):
+        """chroma_daq_digitize_gates on the pulses, triggers and hits of one chunk where acquire_pulses and _trigger_chunk left
+        them, in slices of hits of at most ``max_entries`` samples; the host arrays (adc, trace_flags)."""
+        lib, handle = self.ctx._lib, self.ctx.handle
+        d_trig_offsets, d_trig_bin, d_hit_offsets, d_hit_channel, nt, nh = self._trigger_device
+        G = trigger.pre + trigger.post
+        per_slice = max(1, self.max_entries // G)
+        ntraces = min(nh, per_slice)          # the traces of the largest slice
+        if self._adc_gpu is None or len(self._adc_gpu) < ntraces * G:
+            self._adc_gpu = empty(ntraces * G, np.uint16, self.ctx)
+        if self._trace_flags_gpu is None or len(self._trace_flags_gpu) < ntraces:
+            self._trace_flags_gpu = empty(ntraces, np.uint32, self.ctx)
+        d_adc, d_flags = self._adc_gpu, self._trace_flags_gpu
+        trig = trigger.struct()
+        adc, flags = np.zeros((nh, G), dtype=np.uint16), np.zeros(nh, dtype=np.uint32)
+        for first in range(0, nh, per_slice):
+            n = min(per_slice, nh - first)
+            assert n * G <= len(d_adc) and n <= len(d_flags)          # (the call sees the room for samples only)
+            _lib.check(lib.chroma_daq_digitize_gates(handle, nrows, self.nchannels, ctypes.byref(win), ctypes.byref(trig), ctypes.byref(struct), int(seed),
+                                                     int(acquisition) & 0xffffffff, d_offsets.ptr, arrays[0].ptr, arrays[1].ptr, arrays[3].ptr, int(npulses),
+                                                     d_trig_offsets.ptr, d_trig_bin.ptr, nt, d_hit_offsets.ptr, d_hit_channel.ptr, nh, first, n,
+                                                     len(d_adc), d_adc.ptr, d_flags.ptr))
+            adc[first:first + n] = d_adc[:n * G].get().reshape(n, G)
+            flags[first:first + n] = d_flags[:n].get()
+        return adc, flags
+
+    def acquire_pulses(self, gpuphotons, rng_states, bounds, window, acquisition=0, weight=1.0, trigger=None, noise=None, digitizer=None):
         """The time-binned view of ``acquire`` with the same arguments: the same accepted photons, per (event, channel, bin of
         ``window``: a DaqWindow or (t0, dt, nbins)).  Counts first (chroma_daq_count_pulses), then acquires into buffers grown to
         the largest count seen, ``rows_per_chunk`` events at a time.  Returns an ``EventPulses``.
@@ -785,8 +1005,16 @@ class GPUEventDaq(object):
         ``noise`` (a DaqNoise, or a dark rate in Hz, or one per channel): every event's dark-noise photoelectrons are drawn on the
         device and enter the pulses like accepted photons, flagged ``noise.flag`` (chroma_daq_count_pulses_noise /
         chroma_daq_acquire_pulses_noise); the result's ``noise`` counts them per event.  Events without photons get theirs too.
-        The draws are counter-based (per event and channel): the chunking does not show.  Noise that is ``off`` is no noise."""
+        The draws are counter-based (per event and channel): the chunking does not show.  Noise that is ``off`` is no noise.
+
+        ``digitizer`` (a DaqDigitizer; needs ``trigger``): each chunk's gated hits are also digitised where they lie on the device,
+        after its trigger call (chroma_daq_digitize_gates, in slices of hits of at most ``max_entries`` samples), and ``.triggers``
+        carries ``adc`` and ``trace_flags``.  The electronics noise is counter-based too (per event, channel and bin)."""
         window = DaqWindow.of(window)
+        if digitizer is not None:
+            if trigger is None:
+                raise ValueError('a digitiser reads the gates of a trigger: digitizer needs trigger')
+            digitizer = DaqDigitizer.of(digitizer)
         if noise is not None:
             noise = DaqNoise.of(noise)
             noise = None if noise.off else noise
@@ -803,6 +1031,14 @@ class GPUEventDaq(object):
         s = _structure(gpuphotons)
         lib, handle = self.ctx._lib, self.ctx.handle
         win = _lib.DaqWindow(window.t0, window.dt, window.nbins)
+        if digitizer is not None:
+            digitizer.check(trigger)
+            digitizer_struct, digitizer_arrays = digitizer.struct(self.charge_unit)
+            # the electronics noise draws from the pseudo-photons 0xffffffff00000000 | channel, as the dark noise does
+            n_ids, base = len(gpuphotons.pos), int(rng.photon_id_base)
+            if digitizer.noise_sigma > 0.0 and n_ids and ((base >> 32) == 0xffffffff or ((base + n_ids - 1) >> 32) >= 0xffffffff):
+                raise ValueError('the photon ids reach the high word 0xffffffff of the noise\'s pseudo-photons')
+            traces = [[], []]
         noise_arg = () if noise is None else (ctypes.byref(self._noise_struct(noise, window)),)
         suffix = '' if noise is None else '_noise'
         offsets, outside, row_noise = [np.zeros(1, dtype=np.int64)], [], []
@@ -838,6 +1074,10 @@ class GPUEventDaq(object):
                     triggered[k].append(got[k])
                 ntriggers += len(got[1])
                 nhits += len(got[4])
+                if digitizer is not None:
+                    for part, a in zip(traces, self._digitize_chunk(win, trigger, digitizer_struct, rng.seed, int(acquisition) + first, nrows, d_offsets,
+                                                                    arrays, int(npulses.value))):
+                        part.append(a)
             total += int(npulses.value)
         dtypes = (np.int32, np.uint32, np.uint32, np.uint32, np.float32, np.uint32)
         columns = [np.concatenate(part) if part else np.zeros(0, dtype=dtype) for part, dtype in zip(parts, dtypes)]
@@ -847,5 +1087,11 @@ class GPUEventDaq(object):
         if trigger is not None:
             kinds = (np.int64, np.uint32, np.uint32, np.int64, np.int32, np.uint32, np.uint32, np.float32, np.uint32, np.uint32)
             pulses.triggers = EventTriggers(window, trigger, self.nchannels, self.charge_unit, pulses.offsets,
-                                            *[np.concatenate(part) if part else np.zeros(0, dtype=dtype) for part, dtype in zip(triggered, kinds)])
+                                            *[np.concatenate(part) if part else np.zeros(0, dtype=dtype) for part, dtype in zip(triggered, kinds)],
+                                            pulses=(pulses.channel, pulses.bin, pulses.q_int))
+            if digitizer is not None:
+                G = trigger.pre + trigger.post
+                pulses.triggers.adc = np.concatenate(traces[0]) if traces[0] else np.zeros((0, G), dtype=np.uint16)
+                pulses.triggers.trace_flags = np.concatenate(traces[1]) if traces[1] else np.zeros(0, dtype=np.uint32)
+                pulses.triggers.digitizer = digitizer
         return pulses

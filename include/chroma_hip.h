@@ -624,6 +624,90 @@ int chroma_daq_trigger_pulses(chroma_ctx *ctx, uint32_t nrows, uint32_t nchannel
                               int32_t *d_hit_channel, uint32_t *d_hit_npe, uint32_t *d_hit_q_int,
                               float *d_hit_t_first, uint32_t *d_hit_flags, uint32_t *d_pulse_trigger,
                               uint64_t *ntriggers, uint64_t *nhits);
+/* ---- the digitiser of the time-binned DAQ: a shaped ADC trace per gated hit -------------------------
+ * A third integer stage, on the outputs of chroma_daq_acquire_pulses and chroma_daq_trigger_pulses where
+ * they lie: every photoelectron charge count becomes a pulse of `ntaps` bins, pulses pile up, the tail of
+ * light from before the gate is on the line, the electronics add a pedestal and noise, and the converter
+ * clips.  The reference has no counterpart; this is the definition.
+ *
+ * A TRACE belongs to a gated hit.  Hit i is (trigger k, channel c) as chroma_daq_trigger_pulses wrote it
+ * (d_hit_offsets[k] <= i < d_hit_offsets[k + 1], c = d_hit_channel[i]); trigger k fires at bin b =
+ * d_trig_bin[k] of row r (d_trig_offsets[r] <= k < d_trig_offsets[r + 1]).  One trace per hit is
+ * zero-suppressed readout: a channel is read iff it has a pulse in the gate.  Every trace has G = pre +
+ * post samples (of the trigger, NOT clipped to the window); sample s stands for the signed bin number
+ * B(s) = b - pre + s, which may lie before bin 0 or at or beyond nbins: no pulses there, but the ADC keeps
+ * sampling.
+ *
+ * The signal.  Over ALL pulses p of (row r, channel c) with 0 <= B(s) - bin[p] < ntaps -- not the gate's
+ * alone: pulses before the gate and in an earlier firing's gate have their tails on the line --
+ *   acc(s) = sum of (uint64)(int64)((int64)q_int[p] * taps[B(s) - bin[p]]),
+ * summed as 64-bit unsigned, wrapping, and then read as signed.  The sample is
+ *   v(s) = clip(pedestal + (acc(s) >> shift, arithmetic) + e(s), 0, 2^bits - 1)
+ * in int64, stored as uint16 (the sum of the three terms is the exact one: it is not left to wrap).
+ *
+ * The electronics noise.  e(s) = 0 when nnoise == 0; otherwise e(s) = noise_lo + #{ j < nnoise : w >=
+ * noise_cdf[j] } with w one Philox word of (acquisition + row, channel, ABSOLUTE bin), whichever firing
+ * reads it and however the hits are sliced: with u = (uint32)(B(s) + 65536) (>= 0: pre <= G <= 65536), w
+ * is word u & 3 of cm_philox4x32_10(0x80000000 | (u >> 2), 1 + acquisition + r, c, 0xffffffff, seed lo,
+ * seed hi) -- the dark noise's pseudo-photon of channel c in the stream of row r, in blocks whose top
+ * bit is set, so that they never meet the dark noise's blocks 0 .. 48.  As with the dark noise, photon
+ * ids must not reach the high word 0xffffffff; this call sees no photons and cannot check it
+ * (GPUEventDaq does, before any call).  The caller puts a scaled CDF into noise_cdf (for a Gaussian of
+ * sigma ADC counts: noise_lo = -32, entry j = floor(Phi((noise_lo + j + 0.5) / sigma) * 2^32), saturated);
+ * the device only compares integers.
+ *
+ * d_trace_flags, a word per trace: bit 0 some sample was clipped at the top, bit 1 some at 0. */
+typedef struct chroma_daq_digitizer {
+    const int32_t *taps;       /* HOST array: the response to one charge count, tap d = d bins after the pulse's bin, fixed point */
+    uint32_t ntaps;            /* 1 .. 1024 */
+    uint32_t shift;            /* 0 .. 31: the fixed point's fractional bits */
+    int32_t  pedestal;         /* ADC counts */
+    uint32_t bits;             /* 1 .. 16: samples are clipped to [0, 2^bits - 1] */
+    const uint32_t *noise_cdf; /* HOST array, non-decreasing, or NULL */
+    uint32_t nnoise;           /* 0 (no electronics noise) .. 64 */
+    int32_t  noise_lo;         /* the noise value when the drawn word is below every entry */
+} chroma_daq_digitizer;
+/* Writes d_adc[(i - first_hit) * G + s] and d_trace_flags[i - first_hit] for the hits i of [first_hit,
+ * first_hit + nhits_call): the slice lets a caller bound the memory of one call, and a slice is that part
+ * of the whole.  d_adc has `sample_capacity` entries.  Inputs: the pulses (d_offsets, nrows + 1 words;
+ * d_channel, d_bin, d_q_int, npulses entries in (row, channel, bin) order), the triggers (d_trig_offsets,
+ * nrows + 1 words; d_trig_bin, ntriggers entries) and the hits (d_hit_offsets, ntriggers + 1 words;
+ * d_hit_channel, nhits entries) of the calls above, with the window, the trigger and the number of
+ * channels they were made with, the context's seed and the acquisition number of row 0 (row r of a call
+ * is row 0 of a call with acquisition + r).
+ *
+ * Refused, CHROMA_ERR_INVALID before anything is launched and with nothing written: what
+ * chroma_daq_trigger_pulses refuses of window, trigger, nrows and nchannels; G > 65536; ntaps outside
+ * 1 .. 1024, shift > 31, bits outside 1 .. 16, nnoise > 64; a descending noise_cdf; npulses, ntriggers or
+ * nhits of 2^32 or more; a NULL array that is needed (taps; noise_cdf when nnoise; the pulse arrays when
+ * npulses, d_trig_bin when ntriggers, d_hit_channel when nhits, d_adc and d_trace_flags when nhits_call;
+ * the three offset arrays always); a slice that ends beyond nhits; sample_capacity < nhits_call * G.
+ * nhits_call == 0 is CHROMA_OK and launches nothing.
+ *
+ * Every search runs over a fixed index range, whatever the arrays hold.  A hit whose channel is outside
+ * [0, nchannels), or whose trigger the offsets put in no row, has no signal: its trace is pedestal plus
+ * noise (of row 0 where there is no row, and with b = 0 where the hit offsets put the hit in no trigger;
+ * the channel word of the noise is the hit's channel as it stands).  Input that is not sorted gives
+ * unspecified values, but no access outside the caller's arrays.
+ *
+ * Runs on the context's stream and returns when the arrays are written.  Scratch: the taps. */
+int chroma_daq_digitize_gates(chroma_ctx *ctx, uint32_t nrows, uint32_t nchannels, const chroma_daq_window *window,
+                              const chroma_daq_trigger *trigger, const chroma_daq_digitizer *digitizer, uint64_t seed,
+                              uint32_t acquisition, const uint32_t *d_offsets, const int32_t *d_channel,
+                              const uint32_t *d_bin, const uint32_t *d_q_int, uint64_t npulses,
+                              const uint32_t *d_trig_offsets, const uint32_t *d_trig_bin, uint64_t ntriggers,
+                              const uint32_t *d_hit_offsets, const int32_t *d_hit_channel, uint64_t nhits,
+                              uint64_t first_hit, uint64_t nhits_call, uint64_t sample_capacity, uint16_t *d_adc,
+                              uint32_t *d_trace_flags);
+/* The same on the host (no GPU, no context), a plain loop over trace, sample and pulse: the same arguments
+ * on HOST arrays, the same refusals, the same bits. */
+int chroma_daq_digitize_host(uint32_t nrows, uint32_t nchannels, const chroma_daq_window *window,
+                             const chroma_daq_trigger *trigger, const chroma_daq_digitizer *digitizer, uint64_t seed,
+                             uint32_t acquisition, const uint32_t *offsets, const int32_t *channel, const uint32_t *bin,
+                             const uint32_t *q_int, uint64_t npulses, const uint32_t *trig_offsets,
+                             const uint32_t *trig_bin, uint64_t ntriggers, const uint32_t *hit_offsets,
+                             const int32_t *hit_channel, uint64_t nhits, uint64_t first_hit, uint64_t nhits_call,
+                             uint64_t sample_capacity, uint16_t *adc, uint32_t *trace_flags);
 /* `convert_sortable_int_to_float` + `convert_charge_int_to_float` (daq.cu:152-173) */
 int chroma_daq_convert(chroma_ctx *ctx, uint32_t nchannels, float charge_unit, const uint32_t *d_earliest_time_int,
                        const uint32_t *d_channel_q_int, float *d_earliest_time, float *d_channel_q);
