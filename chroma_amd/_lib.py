@@ -123,6 +123,12 @@ class DaqDigitizer(Structure):
                 ('noise_cdf', c_void_p), ('nnoise', c_uint32), ('noise_lo', c_int32)]
 
 
+class DaqReducer(Structure):
+    """chroma_daq_reducer"""
+    _fields_ = [('polarity', c_int32), ('nbaseline', c_uint32), ('pedestal', c_uint32), ('baseline_spread', c_uint32), ('threshold', c_uint32),
+                ('min_width', c_uint32), ('lead', c_uint32), ('lag', c_uint32), ('cfd', c_uint32)]
+
+
 class LightSource(Structure):
     """chroma_light_source (host pointers)"""
     _fields_ = [('refractive_index', c_void_p), ('scintillation_cdf', c_void_p), ('time_cdf', c_void_p),
@@ -228,6 +234,10 @@ SIGNATURES = {
     'chroma_daq_digitize_host': (c_int32, [c_uint32, c_uint32, POINTER(DaqWindow), POINTER(DaqTrigger), POINTER(DaqDigitizer), c_uint64,
                                            c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_uint64, c_void_p,
                                            c_void_p, c_uint64, c_uint64, c_uint64, c_uint64, c_void_p, c_void_p]),
+    'chroma_daq_reduce_traces': (c_int32, [c_void_p, POINTER(DaqReducer), c_uint32, c_uint64, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_uint64)]),
+    'chroma_daq_reduce_host': (c_int32, [POINTER(DaqReducer), c_uint32, c_uint64, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_uint64)]),
     'chroma_daq_convert': (c_int32, [c_void_p, c_uint32, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     'chroma_pdf_bin_hits': (c_int32, [c_void_p, c_uint32, c_int32, c_uint32, c_void_p, c_void_p, c_int32, c_float, c_float,
                                       c_int32, c_float, c_float, c_void_p, c_void_p]),

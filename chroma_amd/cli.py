@@ -5,7 +5,7 @@ GEANT4 and writes a ROOT file; neither GEANT4 nor ROOT is part of this engine, s
 keeps the command-line shape (detector string, -n/--nevents, -o/--output, -s/--seed, -j device)
 but the particle source is the isotropic photon bomb of chroma/benchmark.py:77-83 and the output is
 an ``.npz``: per event the flat hits (channel, t, wavelength, pos, flags), with --run-daq the channel
-times and charges, with --daq-window T0,DT,NBINS also the pulses per (channel, time bin), with --daq-trigger the triggers on them, with --daq-digitize the ADC traces of their gates, with --daq-noise RATE_HZ dark noise among them, with --save-photons-beg/--save-photons-end the photons themselves and with --track or
+times and charges, with --daq-window T0,DT,NBINS also the pulses per (channel, time bin), with --daq-trigger the triggers on them, with --daq-digitize the ADC traces of their gates, with --daq-reduce the pulses found in the traces, with --daq-noise RATE_HZ dark noise among them, with --save-photons-beg/--save-photons-end the photons themselves and with --track or
 --device-tracks every photon's state after each step.
 """
 import argparse
@@ -57,6 +57,11 @@ def main(argv=None):
     ap.add_argument('--daq-digitize', default=None, metavar='AMPLITUDE,RISE_NS,FALL_NS[,BITS[,PEDESTAL[,SIGMA]]]',
                     help='with --daq-trigger, also write the ADC trace of every channel in every gate: a biexponential pulse of AMPLITUDE counts per '
                          'unit charge, read with BITS bits on PEDESTAL counts and electronics noise of SIGMA counts')
+    ap.add_argument('--daq-reduce', default=None, metavar='THRESHOLD[,LEAD,LAG[,CFD[,NBASELINE[,MIN_WIDTH]]]]',
+                    help='with --daq-digitize, also write the pulses found in the traces (trigger_found_*, trigger_trace_base): runs of MIN_WIDTH samples '
+                         'THRESHOLD counts above the baseline (the digitiser\'s pedestal, or the mean of the first NBASELINE samples), integrated from LEAD '
+                         'samples before to LAG behind, timed at the fraction CFD of the peak')
+    ap.add_argument('--daq-drop-traces', action='store_true', help='with --daq-reduce, do not read the traces back: trigger_adc is not written')
     ap.add_argument('--save-photons-beg', action='store_true', help='also write the initial photons of every event (bin/chroma-sim:51-53)')
     ap.add_argument('--save-photons-end', action='store_true', help='also write the final photons of every event (bin/chroma-sim:54-56)')
     ap.add_argument('--track', action='store_true', help='also write every photon\'s state after each step (Simulation(photon_tracking=True))')
@@ -108,6 +113,21 @@ def main(argv=None):
             daq_digitizer = DaqDigitizer.biexponential(float(parts[0]), float(parts[1]), float(parts[2]), daq_window[1], **kw).check(daq_trigger)
         except ValueError as e:
             ap.error('--daq-digitize: %s' % e)
+    daq_reducer = None
+    if args.daq_reduce is not None:
+        if daq_digitizer is None:
+            ap.error('--daq-reduce needs --daq-digitize')
+        parts = args.daq_reduce.split(',')
+        if len(parts) not in (1, 3, 4, 5, 6):
+            ap.error('--daq-reduce takes THRESHOLD[,LEAD,LAG[,CFD[,NBASELINE[,MIN_WIDTH]]]]')
+        from chroma_amd.gpu.daq import DaqReducer
+        try:
+            kw = dict(zip(('lead', 'lag', 'cfd', 'nbaseline', 'min_width'), [float(x) if k == 2 else int(x) for k, x in enumerate(parts[1:])]))
+            daq_reducer = DaqReducer.for_digitizer(daq_digitizer, int(parts[0]), **kw).check(daq_trigger.pre + daq_trigger.post)
+        except ValueError as e:
+            ap.error('--daq-reduce: %s' % e)
+    elif args.daq_drop_traces:
+        ap.error('--daq-drop-traces needs --daq-reduce')
     t0 = time.time()
     detector = load_geometry_from_string(args.detector, cache_dir=args.cache_dir)
     print('geometry: %d triangles, BVH %d nodes (%.1f s)' % (len(detector.mesh.triangles), len(detector.bvh.nodes), time.time() - t0))
@@ -121,7 +141,8 @@ def main(argv=None):
     for ev in sim.simulate(events, keep_photons_beg=args.save_photons_beg, keep_photons_end=args.save_photons_end,
                            keep_hits=False, keep_flat_hits=hasattr(detector, 'num_channels'),
                            run_daq=args.run_daq, max_steps=args.max_steps, daq_window=daq_window, daq_trigger=daq_trigger,
-                           daq_noise=args.daq_noise, daq_digitizer=daq_digitizer):
+                           daq_noise=args.daq_noise, daq_digitizer=daq_digitizer, daq_reducer=daq_reducer,
+                           daq_keep_traces=not args.daq_drop_traces):
         key = 'ev%d' % ev.id
         for tag, ph in (('photons_beg', ev.photons_beg), ('photons_end', ev.photons_end)):
             if ph is not None:
@@ -175,7 +196,15 @@ def main(argv=None):
             out[key + '/pulse_trigger'] = ev.triggers.pulse_trigger
             if ev.triggers.traces is not None:
                 out[key + '/trigger_adc'] = ev.triggers.traces
+            if ev.triggers.trace_flags is not None:
                 out[key + '/trigger_trace_flags'] = ev.triggers.trace_flags
+            if ev.triggers.reducer is not None:
+                from chroma_amd.gpu.daq import FOUND_COLUMNS
+                out[key + '/trigger_found_offsets'] = ev.triggers.found_offsets
+                for name, _ in FOUND_COLUMNS:
+                    out['%s/trigger_%s' % (key, name)] = getattr(ev.triggers, name)
+                out[key + '/trigger_trace_base'] = ev.triggers.trace_base
+                out[key + '/trigger_reduced_flags'] = ev.triggers.reduced_flags
     dt = time.time() - t0
     np.savez_compressed(args.output, **out)
     print('%d events, %d photons, %d hits in %.2f s (%.1f events/s, %.3g photons/s) -> %s' % (

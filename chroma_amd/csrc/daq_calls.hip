@@ -1,6 +1,6 @@
 // daq_calls.hip -- the DAQ's entry points: the single-launch acquisitions (chroma/cuda/daq.cu's, as kernel_calls.hip has its calls)
 // and the pipelines behind them -- the per-event acquisition and its compaction, the time-binned DAQ with its dark noise, its
-// trigger and its digitiser.  A pipeline is several launches with a sort, a scan or a read-back between them, on the context's pooled scratch
+// trigger, its digitiser and the reduction of its traces.  A pipeline is several launches with a sort, a scan or a read-back between them, on the context's pooled scratch
 // block, which each lays out through ONE description (chroma_internal.h: Carver).
 #include <stdint.h>
 #include <algorithm>
@@ -14,6 +14,7 @@
 #include "kernels_daq_noise.h"
 #include "kernels_daq_trigger.h"
 #include "kernels_daq_digitize.h"
+#include "kernels_daq_reduce.h"
 
 // ---- what more than one call refuses ----
 static int check_daq_tables(const chroma_daq_tables *tables)
@@ -584,6 +585,43 @@ int chroma_daq_digitize_gates(chroma_ctx *ctx, uint32_t nrows, uint32_t nchannel
                        d_trig_bin, (uint32_t)ntriggers, d_hit_offsets, d_hit_channel, (uint32_t)first_hit, ntraces, d_adc, d_trace_flags);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(stream));
+    return CHROMA_OK;
+}
+
+int chroma_daq_reduce_traces(chroma_ctx *ctx, const chroma_daq_reducer *reducer, uint32_t G, uint64_t ntraces, const uint16_t *d_adc,
+                             uint64_t found_capacity, uint32_t *d_found_offsets, int32_t *d_trace_base, uint32_t *d_reduced_flags,
+                             uint32_t *d_found_start, uint32_t *d_found_width, uint32_t *d_found_peak, uint32_t *d_found_peak_sample,
+                             int64_t *d_found_integral, uint32_t *d_found_time, uint32_t *d_found_flags, uint64_t *nfound)
+{
+    if (!ctx || !reducer || !nfound || (ntraces && (!d_adc || !d_found_offsets || !d_trace_base || !d_reduced_flags)) ||
+        (ntraces && found_capacity && (!d_found_start || !d_found_width || !d_found_peak || !d_found_peak_sample || !d_found_integral || !d_found_time || !d_found_flags)))
+        return set_error(CHROMA_ERR_INVALID, "bad argument");
+    if (const char *why = daq_reduce::check(reducer, G, ntraces)) return set_error(CHROMA_ERR_INVALID, "%s", why);
+    *nfound = 0;
+    if (ntraces == 0) return CHROMA_OK;
+    hipStream_t stream = ctx->stream;
+    const CallScope scope(ctx);
+    const uint32_t n = (uint32_t)ntraces;          // (< 2^31 - 1)
+    size_t scan_bytes = 0;
+    int rc = scan_workspace_bytes((size_t)n + 1, stream, &scan_bytes); if (rc) return rc;
+    void *d_scan = nullptr;          // the block: the scan's workspace
+    rc = carve_call_scratch(scope, [&](Carver &c) { d_scan = c.take<char>(scan_bytes); }); if (rc) return rc;
+    // count (a wave per trace, and one for the word behind the counts), scan in place, fill
+    hipLaunchKernelGGL(k_daq_reduce_count, dim3(n / DAQ_REDUCE_WAVES + 1u), dim3(DAQ_REDUCE_BLOCK), 0, stream, *reducer, G, n, d_adc, d_found_offsets,
+                       d_trace_base, d_reduced_flags);
+    HIP_TRY(hipGetLastError());
+    rc = exclusive_sum(d_scan, scan_bytes, d_found_offsets, d_found_offsets, (size_t)n + 1, stream); if (rc) return rc;
+    uint32_t total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, d_found_offsets + n, sizeof(total), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    *nfound = total;
+    if (total > found_capacity) return set_error(CHROMA_ERR_INVALID, "room for %llu found pulses, the traces hold %u", (unsigned long long)found_capacity, total);
+    if (total) {
+        const DaqFoundArrays out{d_found_start, d_found_width, d_found_peak, d_found_peak_sample, d_found_integral, d_found_time, d_found_flags};
+        hipLaunchKernelGGL(k_daq_reduce_fill, dim3((n - 1u) / DAQ_REDUCE_WAVES + 1u), dim3(DAQ_REDUCE_BLOCK), 0, stream, *reducer, G, n, d_adc, d_found_offsets, out);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(stream));
+    }
     return CHROMA_OK;
 }
 

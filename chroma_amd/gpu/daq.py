@@ -584,18 +584,178 @@ class DaqDigitizer(object):
             len(self.shape), float(np.abs(self.shape).max()), self.pedestal, self.bits, self.shift, self.noise_sigma)
 
 
+TIME_AT_EDGE, OPEN_AT_START, OPEN_AT_END = 1, 2, 4          # the bits of a found pulse's flag word
+BASELINE_BUSY = 1                                           # the bit of a reduced trace's flag word
+# the per-pulse arrays of a trace reduction, in the order of chroma_daq_reduce_traces' arguments
+FOUND_COLUMNS = (('found_start', np.uint32), ('found_width', np.uint32), ('found_peak', np.uint32), ('found_peak_sample', np.uint32),
+                 ('found_integral', np.int64), ('found_time', np.uint32), ('found_flags', np.uint32))
+
+
+class DaqReducer(object):
+    """The reduction of digitised traces (chroma_daq_reducer): what the electronics make of a trace -- the pulses in it, the
+    charge of each and a constant-fraction time.  The baseline is the mean of the first ``nbaseline`` samples (0 .. 64), or
+    ``pedestal`` when that is 0 (``BASELINE_BUSY`` when they spread by more than ``baseline_spread`` counts); a pulse is
+    ``min_width`` or more consecutive samples ``threshold`` ADC counts or more above it (below, with ``polarity=-1``), integrated from
+    ``lead`` samples before to ``lag`` samples behind it but never into a neighbour's window, and timed where its leading edge
+    crosses the fraction ``cfd`` (1/256 .. 1) of its peak, interpolated to 1/256 of a sample.  The arithmetic is integer
+    (include/chroma_hip.h, "trace reduction").
+
+    ``time_offset_ns`` is subtracted from the times ``Triggers.found`` and ``reco`` give (the shape's rise to the fraction);
+    ``gain``, ADC counts x bins per unit of the detector's charge (``for_digitizer``: the sum of the shape), turns integrals into
+    charges."""
+
+    def __init__(self, threshold, polarity=1, nbaseline=0, pedestal=0, baseline_spread=0, min_width=1, lead=0, lag=0, cfd=0.5, time_offset_ns=0.0,
+                 gain=None):
+        ranges = (('threshold', threshold, 1, 65535), ('polarity', polarity, -1, 1), ('nbaseline', nbaseline, 0, 64), ('pedestal', pedestal, 0, 65535),
+                  ('baseline_spread', baseline_spread, 0, 0xffffffff), ('min_width', min_width, 1, 65536), ('lead', lead, 0, 65535), ('lag', lag, 0, 65535))
+        for name, value, lo, hi in ranges:
+            try:
+                whole = int(value)
+            except (TypeError, ValueError):
+                raise ValueError('a reducer\'s %s is a whole number' % name)
+            if whole != value or not lo <= whole <= hi or (name == 'polarity' and whole == 0):
+                raise ValueError('a reducer\'s %s is a whole number of %d .. %d%s' % (name, lo, hi, ', not 0' if name == 'polarity' else ''))
+            setattr(self, name, whole)
+        try:
+            fraction = float(cfd)
+        except (TypeError, ValueError):
+            raise ValueError('a reducer\'s constant fraction is a number')
+        if not (fraction == fraction) or not 1 <= int(round(fraction * 256)) <= 256:
+            raise ValueError('a reducer\'s constant fraction is 1/256 .. 1')
+        self.cfd = int(round(fraction * 256))          # in 1/256
+        self.time_offset_ns = float(time_offset_ns)
+        self.gain = None if gain is None else float(gain)
+        if not np.isfinite(self.time_offset_ns) or (self.gain is not None and not (np.isfinite(self.gain) and self.gain != 0.0)):
+            raise ValueError('a reducer\'s time offset is finite, its gain finite and not 0')
+
+    @classmethod
+    def for_digitizer(cls, digitizer, threshold, **kw):
+        """The reducer that fits ``digitizer``'s traces: the polarity of its shape's largest excursion, its pedestal, and
+        ``gain = sum(shape)``, ADC counts x bins per unit charge."""
+        shape = digitizer.shape
+        kw.setdefault('polarity', 1 if shape[int(np.argmax(np.abs(shape)))] >= 0.0 else -1)
+        kw.setdefault('pedestal', digitizer.pedestal)
+        gain = float(shape.sum())
+        kw.setdefault('gain', gain if gain != 0.0 else None)
+        return cls(threshold, **kw)
+
+    @classmethod
+    def of(cls, reducer):
+        """``reducer`` itself if it is a DaqReducer, or the one of a (threshold[, lead, lag[, cfd[, nbaseline[, min_width]]]]) tuple."""
+        if isinstance(reducer, cls):
+            return reducer
+        try:
+            parts = tuple(reducer)
+        except TypeError:
+            raise ValueError('a DAQ reducer is (threshold[, lead, lag[, cfd[, nbaseline[, min_width]]]])')
+        if len(parts) not in (1, 3, 4, 5, 6):
+            raise ValueError('a DAQ reducer is (threshold[, lead, lag[, cfd[, nbaseline[, min_width]]]])')
+        return cls(parts[0], **dict(zip(('lead', 'lag', 'cfd', 'nbaseline', 'min_width'), parts[1:])))
+
+    def check(self, G):
+        """Raises ValueError unless traces of ``G`` samples can be reduced: 1 .. 65536 of them, the baseline's at least."""
+        if not 1 <= G <= 65536 or self.nbaseline > G:
+            raise ValueError('a reducer with a baseline of %d samples on traces of %d: traces have 1 .. 65536 samples, the baseline\'s at least' % (self.nbaseline, G))
+        return self
+
+    @property
+    def N(self):
+        """What ``found_integral`` and ``found_peak`` are scaled by: max(nbaseline, 1)."""
+        return max(self.nbaseline, 1)
+
+    def struct(self):
+        return _lib.DaqReducer(self.polarity, self.nbaseline, self.pedestal, self.baseline_spread, self.threshold, self.min_width, self.lead, self.lag, self.cfd)
+
+    def _key(self):
+        return (self.threshold, self.polarity, self.nbaseline, self.pedestal, self.baseline_spread, self.min_width, self.lead, self.lag, self.cfd,
+                self.time_offset_ns, self.gain)
+
+    def __eq__(self, other):
+        return isinstance(other, DaqReducer) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        return ('DaqReducer(threshold=%d, polarity=%d, nbaseline=%d, pedestal=%d, baseline_spread=%d, min_width=%d, lead=%d, lag=%d, cfd=%d/256, '
+                'time_offset_ns=%r, gain=%r)' % (self.threshold, self.polarity, self.nbaseline, self.pedestal, self.baseline_spread, self.min_width,
+                                                self.lead, self.lag, self.cfd, self.time_offset_ns, self.gain))
+
+
+def reduce_traces_host(adc, reducer):
+    """chroma_daq_reduce_host (no GPU) on ``adc`` (traces x samples, uint16) under ``reducer``: (found_offsets int64 (traces + 1),
+    trace_base int32, reduced_flags uint32, then the arrays of ``FOUND_COLUMNS``).  Called twice: the first call counts."""
+    adc = np.ascontiguousarray(adc, dtype=np.uint16)
+    if adc.ndim != 2:
+        raise ValueError('traces are a (traces, samples) array')
+    ntraces, G = adc.shape
+    reducer = DaqReducer.of(reducer).check(G)
+    lib = _lib.load()
+    struct = reducer.struct()
+    offsets, base, flags = np.zeros(ntraces + 1, dtype=np.uint32), np.zeros(ntraces, dtype=np.int32), np.zeros(ntraces, dtype=np.uint32)
+    nfound = ctypes.c_uint64(0)
+    columns = [np.zeros(0, dtype=kind) for _, kind in FOUND_COLUMNS]
+    for attempt in range(2):
+        capacity = len(columns[0])
+        rc = lib.chroma_daq_reduce_host(ctypes.byref(struct), G, ntraces, _lib.ptr(adc), capacity, _lib.ptr(offsets), _lib.ptr(base), _lib.ptr(flags),
+                                        *([_lib.ptr(a) if capacity else None for a in columns] + [ctypes.byref(nfound)]))
+        if rc == 0 or attempt or nfound.value <= capacity:
+            break
+        columns = [np.zeros(int(nfound.value), dtype=kind) for _, kind in FOUND_COLUMNS]
+    _lib.check(rc)
+    return [offsets.astype(np.int64), base, flags] + [a[:int(nfound.value)] for a in columns]
+
+
+def _set_found(self, found):
+    """The attributes of a trace reduction on a ``Triggers`` or an ``EventTriggers``: ``found`` is (reducer, found_offsets,
+    trace_base, reduced_flags, the arrays of FOUND_COLUMNS) or None."""
+    self.reducer = self.found_offsets = self.trace_base = self.reduced_flags = None
+    for name, _ in FOUND_COLUMNS:
+        setattr(self, name, None)
+    if found is None:
+        return
+    self.reducer, self.found_offsets, self.trace_base, self.reduced_flags = found[:4]
+    for (name, _), a in zip(FOUND_COLUMNS, found[4]):
+        setattr(self, name, a)
+
+
+def _slice_found(self, h):
+    """``found`` of the hits ``h`` (a slice), the offsets rebased to 0"""
+    if self.reducer is None:
+        return None
+    f = slice(int(self.found_offsets[h.start]), int(self.found_offsets[h.stop]))
+    return (self.reducer, self.found_offsets[h.start:h.stop + 1] - self.found_offsets[h.start], self.trace_base[h], self.reduced_flags[h],
+            [getattr(self, name)[f] for name, _ in FOUND_COLUMNS])
+
+
+class FoundPulses(object):
+    """The pulses found in ONE trace (``Triggers.found``): the arrays of ``FOUND_COLUMNS`` without their prefix (``start``,
+    ``width``, ``peak``, ``peak_sample``, ``integral``, ``time``, ``flags``), ``t`` (ns, float64) and ``q`` (float64: the detector's
+    charge units where the reducer knows a gain, else ADC counts x samples)."""
+
+    def __init__(self, columns, t, q):
+        for (name, _), a in zip(FOUND_COLUMNS, columns):
+            setattr(self, name[len('found_'):], a)
+        self.t, self.q = t, q
+
+    def __len__(self):
+        return len(self.t)
+
+
 class Triggers(object):
     """The triggers of ONE event (``EventTriggers.event(i)``, ``ev.triggers``): ``bin`` and ``sum`` of every firing, ascending;
     ``sparse(k)`` the channels in the gate of firing k, ``channels(k)`` the same as a dense ``event.Channels``; ``pulse_trigger``:
     per pulse of the event's ``Pulses`` the firing (numbered within the event) whose gate holds it, or ``NO_TRIGGER``.  With a
     ``DaqDigitizer`` also ``adc(k)``, ``trace(k, channel)`` and ``sample_times(k)``: the ADC traces of firing k's channels, and
     ``traces`` (hits x samples, uint16) and ``trace_flags``, a word per hit (``CLIPPED_HIGH``, ``CLIPPED_LOW``); None without one,
-    as is ``digitizer``."""
+    as is ``digitizer``.  With a ``DaqReducer`` also ``found(k, channel)``, ``reco(k)`` and ``reco_channels(k)``: the pulses found in the
+    traces, and ``found_offsets`` (hits + 1), the ``found_*`` arrays of ``FOUND_COLUMNS``, ``trace_base``, ``reduced_flags`` and ``reducer``."""
 
     def __init__(self, window, trigger, nchannels, charge_unit, bin, sum, hit_offsets, hit_channel, hit_npe, hit_q_int, hit_t_first,
-                 hit_flags, pulse_trigger, adc=None, trace_flags=None, digitizer=None):
+                 hit_flags, pulse_trigger, adc=None, trace_flags=None, digitizer=None, found=None):
         self.window, self.trigger, self.nchannels, self.charge_unit = window, trigger, nchannels, charge_unit
         self.bin, self.sum = bin, sum
+        _set_found(self, found)
         self.hit_offsets = hit_offsets          # (len + 1, into the hit arrays; the first is 0)
         self.hit_channel, self.hit_npe, self.hit_q_int, self.hit_t_first, self.hit_flags = hit_channel, hit_npe, hit_q_int, hit_t_first, hit_flags
         self.hit_q = (hit_q_int.astype(np.float32) * np.float32(charge_unit)).astype(np.float32)          # as k_daq_convert
@@ -629,6 +789,67 @@ class Triggers(object):
         self._slice(k)
         first = int(self.bin[k]) - self.trigger.pre
         return self.window.t0 + self.window.dt * (first + np.arange(self.trigger.pre + self.trigger.post, dtype=np.float64))
+
+    def _found_of(self, w):
+        """the slice of the found pulses of the hits ``w``"""
+        if self.reducer is None:
+            raise ValueError('these triggers were not reduced (daq_reducer / reducer=... / reduce)')
+        return slice(int(self.found_offsets[w.start]), int(self.found_offsets[w.stop]))
+
+    def _found_times(self, k, time):
+        """t0 + dt * (bin[k] - pre + time / 256) - time_offset_ns, as ``sample_times`` counts the samples (float64)"""
+        first = int(self.bin[k]) - self.trigger.pre
+        return self.window.t0 + self.window.dt * (first + time.astype(np.float64) / 256.0) - self.reducer.time_offset_ns
+
+    def _found_charges(self, integral):
+        """integral / (N * gain) where the reducer knows a gain (the detector's charge units); integral / N otherwise"""
+        r = self.reducer
+        scale = float(r.N) * (r.polarity * r.gain if r.gain is not None else 1.0)
+        return integral.astype(np.float64) / scale
+
+    def found(self, k, channel):
+        """The ``FoundPulses`` of ``channel``'s trace in firing ``k``; KeyError for a channel that was not read out."""
+        w = self._slice(k)
+        channel = int(channel)
+        if not 0 <= channel < self.nchannels:
+            raise IndexError('channel %d of %d' % (channel, self.nchannels))
+        channels = self.hit_channel[w]
+        at = int(np.searchsorted(channels, channel))
+        if at == len(channels) or channels[at] != channel:
+            raise KeyError('channel %d has no pulse in the gate of firing %d' % (channel, k))
+        f = self._found_of(slice(w.start + at, w.start + at + 1))
+        columns = [getattr(self, name)[f] for name, _ in FOUND_COLUMNS]
+        return FoundPulses(columns, self._found_times(k, self.found_time[f]), self._found_charges(self.found_integral[f]))
+
+    def reco(self, k):
+        """(channel, t, q, npulses, flags) of the channels of firing ``k`` with at least one found pulse, in channel order: the
+        time of the trace's first found pulse (ns, float64), the charge summed over its pulses (float64, as ``FoundPulses.q``), their
+        number and the OR of their flags."""
+        w = self._slice(k)
+        f = self._found_of(w)
+        counts = np.diff(self.found_offsets[w.start:w.stop + 1])
+        has = counts > 0
+        first = (self.found_offsets[w.start:w.stop] - f.start)[has]
+        time, integral, flags = self.found_time[f], self.found_integral[f], self.found_flags[f]
+        if len(first):
+            t = self._found_times(k, time[first])
+            q = self._found_charges(np.add.reduceat(integral, first))
+            fl = np.bitwise_or.reduceat(flags, first)
+        else:
+            t, q, fl = np.zeros(0, dtype=np.float64), np.zeros(0, dtype=np.float64), np.zeros(0, dtype=np.uint32)
+        return self.hit_channel[w][has], t, q, counts[has].astype(np.uint32), fl.astype(np.uint32)
+
+    def reco_channels(self, k):
+        """The dense ``event.Channels`` of what was FOUND in the traces of firing ``k``: the reconstructed counterpart of
+        ``channels(k)`` (t = 1e9 and not hit where no pulse was found), ready for ``Likelihood.set_event``."""
+        channel, ts, qs, _, fs = self.reco(k)
+        t = np.full(self.nchannels, 1e9, dtype=np.float32)
+        q = np.zeros(self.nchannels, dtype=np.float32)
+        flags = np.zeros(self.nchannels, dtype=np.uint32)
+        t[channel] = ts
+        q[channel] = qs
+        flags[channel] = fs
+        return event.Channels(t < 1e8, t, q, flags)
 
     @property
     def time(self):
@@ -668,11 +889,16 @@ class EventTriggers(object):
     (uint32), ``hit_t_first`` (float32), ``hit_offsets`` (firings + 1); ``pulse_trigger`` (uint32, per pulse of the batch): the
     firing, numbered within the batch, whose gate holds the pulse, or ``NO_TRIGGER``.  Digitised (``acquire_pulses(digitizer=...)``
     or ``digitize``): ``adc`` (hits x (pre + post), uint16), the ADC trace of every gated hit, ``trace_flags`` (hits, uint32) and
-    ``digitizer``; None otherwise.  ``pulses``: the (channel, bin, q_int) columns of the batch's pulses, which ``digitize`` reads."""
+    ``digitizer``; None otherwise.  ``pulses``: the (channel, bin, q_int) columns of the batch's pulses, which ``digitize`` reads.
+    Reduced (``acquire_pulses(reducer=...)`` or ``reduce``): ``found_offsets`` (hits + 1, int64), the places of the traces' found pulses
+    in ``found_start``, ``found_width``, ``found_peak``, ``found_peak_sample`` (uint32), ``found_integral`` (int64), ``found_time`` (1/256 of a
+    sample) and ``found_flags`` (``TIME_AT_EDGE``, ``OPEN_AT_START``, ``OPEN_AT_END``); per trace ``trace_base`` (int32) and
+    ``reduced_flags`` (``BASELINE_BUSY``); ``reducer``.  None otherwise."""
 
     def __init__(self, window, trigger, nchannels, charge_unit, pulse_offsets, offsets, bin, sum, hit_offsets, hit_channel, hit_npe,
-                 hit_q_int, hit_t_first, hit_flags, pulse_trigger, adc=None, trace_flags=None, digitizer=None, pulses=None):
+                 hit_q_int, hit_t_first, hit_flags, pulse_trigger, adc=None, trace_flags=None, digitizer=None, pulses=None, found=None):
         self.window, self.trigger, self.nchannels, self.charge_unit = window, trigger, nchannels, charge_unit
+        _set_found(self, found)
         self.pulse_offsets, self.offsets, self.bin, self.sum, self.hit_offsets = pulse_offsets, offsets, bin, sum, hit_offsets
         self.hit_channel, self.hit_npe, self.hit_q_int, self.hit_t_first, self.hit_flags = hit_channel, hit_npe, hit_q_int, hit_t_first, hit_flags
         self.pulse_trigger = pulse_trigger
@@ -718,6 +944,19 @@ class EventTriggers(object):
                              self.hit_offsets, self.hit_channel, self.hit_npe, self.hit_q_int, self.hit_t_first, self.hit_flags, self.pulse_trigger,
                              adc=adc, trace_flags=trace_flags, digitizer=digitizer, pulses=self.pulses)
 
+    def reduce(self, reducer):
+        """These triggers with the pulses found in their traces under ``reducer``, computed on the HOST (chroma_daq_reduce_host: no
+        GPU) from the ``adc`` held here -- bit for bit what ``GPUEventDaq.acquire_pulses(..., reducer=reducer)`` reads back.  Returns
+        a new ``EventTriggers`` over the same arrays."""
+        if self.adc is None:
+            raise ValueError('these triggers hold no traces (daq_digitizer / digitizer=... with keep_traces, or digitize)')
+        reducer = DaqReducer.of(reducer)
+        got = reduce_traces_host(self.adc, reducer)
+        return EventTriggers(self.window, self.trigger, self.nchannels, self.charge_unit, self.pulse_offsets, self.offsets, self.bin, self.sum,
+                             self.hit_offsets, self.hit_channel, self.hit_npe, self.hit_q_int, self.hit_t_first, self.hit_flags, self.pulse_trigger,
+                             adc=self.adc, trace_flags=self.trace_flags, digitizer=self.digitizer, pulses=self.pulses,
+                             found=(reducer, got[0], got[1], got[2], got[3:]))
+
     def __len__(self):
         return self.nevents
 
@@ -735,7 +974,8 @@ class EventTriggers(object):
         return Triggers(self.window, self.trigger, self.nchannels, self.charge_unit, self.bin[a:b], self.sum[a:b],
                         self.hit_offsets[a:b + 1] - self.hit_offsets[a], self.hit_channel[h], self.hit_npe[h], self.hit_q_int[h],
                         self.hit_t_first[h], self.hit_flags[h], of, adc=None if self.adc is None else self.adc[h],
-                        trace_flags=None if self.trace_flags is None else self.trace_flags[h], digitizer=self.digitizer)
+                        trace_flags=None if self.trace_flags is None else self.trace_flags[h], digitizer=self.digitizer,
+                        found=_slice_found(self, h))
 
 
 def _time_image(bits):
@@ -876,6 +1116,8 @@ class GPUEventDaq(object):
         self._trigger_device = None          # what the last _trigger_chunk left on the device, for the digitiser
         self._adc_gpu = None                 # acquire_pulses(digitizer=...): the samples of one slice of hits ...
         self._trace_flags_gpu = None         # ... and its flag words, each grown on its own (a shorter gate: fewer samples, more traces)
+        self._found_rows_gpu = None          # acquire_pulses(reducer=...): per trace of a slice (offsets + 1, base, flags) in one buffer ...
+        self._found_gpu = None               # ... and per found pulse the arrays of FOUND_COLUMNS, grown to what a call reports
 
     def _compaction_buffers(self, nrows, capacity):
         if self._offsets_gpu is None or len(self._offsets_gpu) < nrows + 1:
@@ -967,9 +1209,36 @@ class GPUEventDaq(object):
         return [self._trigger_rows_gpu[:nrows + 1].get(), t[:nt], t[capacity:capacity + nt], t[2 * capacity:2 * capacity + nt + 1],
                 h[:nh].view(np.int32), h[n:n + nh], h[2 * n:2 * n + nh], h[3 * n:3 * n + nh].view(np.float32), h[4 * n:4 * n + nh], h[5 * n:6 * n]]
 
-    def _digitize_chunk(self, win, trigger, struct, seed, acquisition, nrows, d_offsets, arrays, npulses):
+    def _reduce_slice(self, struct, G, n, d_adc):
+        """chroma_daq_reduce_traces on the ``n`` traces a digitise call left in ``d_adc``; the host arrays (found offsets (n + 1,
+        uint32), trace base, reduced flags, the arrays of FOUND_COLUMNS).  The pulse arrays grow to what a call reports, and the
+        call is made again."""
+        lib, handle = self.ctx._lib, self.ctx.handle
+        if self._found_rows_gpu is None or len(self._found_rows_gpu) < 3 * n + 1:
+            self._found_rows_gpu = empty(3 * n + 1, np.uint32, self.ctx)
+        if self._found_gpu is None:
+            self._found_gpu = [empty(1024, kind, self.ctx) for _, kind in FOUND_COLUMNS]
+        rows = self._found_rows_gpu
+        per_trace = [rows[:n + 1], rows[n + 1:2 * n + 1], rows[2 * n + 1:3 * n + 1]]
+        nfound = ctypes.c_uint64(0)
+        for attempt in range(2):
+            capacity = len(self._found_gpu[0])
+            rc = lib.chroma_daq_reduce_traces(handle, ctypes.byref(struct), G, n, d_adc.ptr, capacity, *([a.ptr for a in per_trace] +
+                                              [a.ptr for a in self._found_gpu] + [ctypes.byref(nfound)]))
+            if rc == 0 or attempt or nfound.value <= capacity:
+                break
+            grown = int(nfound.value) + int(nfound.value) // 4
+            self._found_gpu = [empty(grown, kind, self.ctx) for _, kind in FOUND_COLUMNS]
+        _lib.check(rc)
+        r = rows[:3 * n + 1].get()
+        return [r[:n + 1], r[n + 1:2 * n + 1].view(np.int32), r[2 * n + 1:]] + [a[:int(nfound.value)].get() for a in self._found_gpu]
+
+    def _digitize_chunk(self, win, trigger, struct, seed, acquisition, nrows, d_offsets, arrays, npulses, reducer=None, keep_traces=True):
         """chroma_daq_digitize_gates on the pulses, triggers and hits of one chunk where acquire_pulses and _trigger_chunk left
-        them, in slices of hits of at most ``max_entries`` samples; the host arrays (adc, trace_flags)."""
+        them, in slices of hits of at most ``max_entries`` samples; the host arrays (adc, trace_flags, found).  With ``reducer`` every
+        slice is reduced where it lies, right behind its digitise call (``found``: found offsets (hits + 1, int64), trace base, reduced
+        flags and the arrays of FOUND_COLUMNS; None without one); without ``keep_traces`` the samples stay on the device and adc is
+        None."""
         lib, handle = self.ctx._lib, self.ctx.handle
         d_trig_offsets, d_trig_bin, d_hit_offsets, d_hit_channel, nt, nh = self._trigger_device
         G = trigger.pre + trigger.post
@@ -981,7 +1250,10 @@ class GPUEventDaq(object):
             self._trace_flags_gpu = empty(ntraces, np.uint32, self.ctx)
         d_adc, d_flags = self._adc_gpu, self._trace_flags_gpu
         trig = trigger.struct()
-        adc, flags = np.zeros((nh, G), dtype=np.uint16), np.zeros(nh, dtype=np.uint32)
+        adc, flags = np.zeros((nh, G), dtype=np.uint16) if keep_traces else None, np.zeros(nh, dtype=np.uint32)
+        reducer_struct = None if reducer is None else reducer.struct()
+        found = [[np.zeros(1, dtype=np.int64)]] + [[] for _ in range(2 + len(FOUND_COLUMNS))]
+        nfound = 0
         for first in range(0, nh, per_slice):
             n = min(per_slice, nh - first)
             assert n * G <= len(d_adc) and n <= len(d_flags)          # (the call sees the room for samples only)
@@ -989,11 +1261,22 @@ class GPUEventDaq(object):
                                                      int(acquisition) & 0xffffffff, d_offsets.ptr, arrays[0].ptr, arrays[1].ptr, arrays[3].ptr, int(npulses),
                                                      d_trig_offsets.ptr, d_trig_bin.ptr, nt, d_hit_offsets.ptr, d_hit_channel.ptr, nh, first, n,
                                                      len(d_adc), d_adc.ptr, d_flags.ptr))
-            adc[first:first + n] = d_adc[:n * G].get().reshape(n, G)
+            if keep_traces:
+                adc[first:first + n] = d_adc[:n * G].get().reshape(n, G)
             flags[first:first + n] = d_flags[:n].get()
-        return adc, flags
+            if reducer is not None:
+                got = self._reduce_slice(reducer_struct, G, n, d_adc)
+                found[0].append(got[0][1:].astype(np.int64) + nfound)
+                for part, a in zip(found[1:], got[1:]):
+                    part.append(a)
+                nfound += len(got[3])
+        if reducer is None:
+            return adc, flags, None
+        kinds = [np.int64, np.int32, np.uint32] + [kind for _, kind in FOUND_COLUMNS]
+        return adc, flags, [np.concatenate(part) if part else np.zeros(0, dtype=kind) for part, kind in zip(found, kinds)]
 
-    def acquire_pulses(self, gpuphotons, rng_states, bounds, window, acquisition=0, weight=1.0, trigger=None, noise=None, digitizer=None):
+    def acquire_pulses(self, gpuphotons, rng_states, bounds, window, acquisition=0, weight=1.0, trigger=None, noise=None, digitizer=None,
+                       reducer=None, keep_traces=True):
         """The time-binned view of ``acquire`` with the same arguments: the same accepted photons, per (event, channel, bin of
         ``window``: a DaqWindow or (t0, dt, nbins)).  Counts first (chroma_daq_count_pulses), then acquires into buffers grown to
         the largest count seen, ``rows_per_chunk`` events at a time.  Returns an ``EventPulses``.
@@ -1009,8 +1292,17 @@ class GPUEventDaq(object):
 
         ``digitizer`` (a DaqDigitizer; needs ``trigger``): each chunk's gated hits are also digitised where they lie on the device,
         after its trigger call (chroma_daq_digitize_gates, in slices of hits of at most ``max_entries`` samples), and ``.triggers``
-        carries ``adc`` and ``trace_flags``.  The electronics noise is counter-based too (per event, channel and bin)."""
+        carries ``adc`` and ``trace_flags``.  The electronics noise is counter-based too (per event, channel and bin).
+
+        ``reducer`` (a DaqReducer or its tuple; needs ``digitizer``): every digitised slice is also reduced where it lies, right behind
+        its digitise call (chroma_daq_reduce_traces), and ``.triggers`` carries the found pulses (``found_offsets``, ``found_*``,
+        ``trace_base``, ``reduced_flags``, ``reducer``).  With ``keep_traces=False`` the samples are not copied to the host:
+        ``triggers.adc`` is None, ``trace_flags`` still comes back."""
         window = DaqWindow.of(window)
+        if reducer is not None:
+            if digitizer is None:
+                raise ValueError('a reducer reads the traces of a digitiser: reducer needs digitizer')
+            reducer = DaqReducer.of(reducer)
         if digitizer is not None:
             if trigger is None:
                 raise ValueError('a digitiser reads the gates of a trigger: digitizer needs trigger')
@@ -1033,12 +1325,16 @@ class GPUEventDaq(object):
         win = _lib.DaqWindow(window.t0, window.dt, window.nbins)
         if digitizer is not None:
             digitizer.check(trigger)
+            if reducer is not None:
+                reducer.check(trigger.pre + trigger.post)
             digitizer_struct, digitizer_arrays = digitizer.struct(self.charge_unit)
             # the electronics noise draws from the pseudo-photons 0xffffffff00000000 | channel, as the dark noise does
             n_ids, base = len(gpuphotons.pos), int(rng.photon_id_base)
             if digitizer.noise_sigma > 0.0 and n_ids and ((base >> 32) == 0xffffffff or ((base + n_ids - 1) >> 32) >= 0xffffffff):
                 raise ValueError('the photon ids reach the high word 0xffffffff of the noise\'s pseudo-photons')
             traces = [[], []]
+            found = [[np.zeros(1, dtype=np.int64)]] + [[] for _ in range(2 + len(FOUND_COLUMNS))]
+            nfound = 0
         noise_arg = () if noise is None else (ctypes.byref(self._noise_struct(noise, window)),)
         suffix = '' if noise is None else '_noise'
         offsets, outside, row_noise = [np.zeros(1, dtype=np.int64)], [], []
@@ -1075,9 +1371,15 @@ class GPUEventDaq(object):
                 ntriggers += len(got[1])
                 nhits += len(got[4])
                 if digitizer is not None:
-                    for part, a in zip(traces, self._digitize_chunk(win, trigger, digitizer_struct, rng.seed, int(acquisition) + first, nrows, d_offsets,
-                                                                    arrays, int(npulses.value))):
-                        part.append(a)
+                    adc, flags, got = self._digitize_chunk(win, trigger, digitizer_struct, rng.seed, int(acquisition) + first, nrows, d_offsets,
+                                                           arrays, int(npulses.value), reducer=reducer, keep_traces=keep_traces)
+                    traces[0].append(adc)
+                    traces[1].append(flags)
+                    if got is not None:
+                        found[0].append(got[0][1:] + nfound)
+                        for part, a in zip(found[1:], got[1:]):
+                            part.append(a)
+                        nfound += len(got[3])
             total += int(npulses.value)
         dtypes = (np.int32, np.uint32, np.uint32, np.uint32, np.float32, np.uint32)
         columns = [np.concatenate(part) if part else np.zeros(0, dtype=dtype) for part, dtype in zip(parts, dtypes)]
@@ -1091,7 +1393,12 @@ class GPUEventDaq(object):
                                             pulses=(pulses.channel, pulses.bin, pulses.q_int))
             if digitizer is not None:
                 G = trigger.pre + trigger.post
-                pulses.triggers.adc = np.concatenate(traces[0]) if traces[0] else np.zeros((0, G), dtype=np.uint16)
+                if keep_traces:
+                    pulses.triggers.adc = np.concatenate(traces[0]) if traces[0] else np.zeros((0, G), dtype=np.uint16)
                 pulses.triggers.trace_flags = np.concatenate(traces[1]) if traces[1] else np.zeros(0, dtype=np.uint32)
                 pulses.triggers.digitizer = digitizer
+                if reducer is not None:
+                    kinds = [np.int64, np.int32, np.uint32] + [kind for _, kind in FOUND_COLUMNS]
+                    got = [np.concatenate(part) if part else np.zeros(0, dtype=kind) for part, kind in zip(found, kinds)]
+                    _set_found(pulses.triggers, (reducer, got[0], got[1], got[2], got[3:]))
         return pulses

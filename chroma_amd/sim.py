@@ -109,7 +109,7 @@ class Simulation(object):
 
     def _simulate_batch(self, batch_events, keep_photons_beg=False, keep_photons_end=False, keep_hits=True,
                         keep_flat_hits=True, run_daq=False, max_steps=100, verbose=False, uploaded=None, gpu_geometry=None,
-                        daq_window=None, daq_trigger=None, daq_noise=None, daq_digitizer=None):
+                        daq_window=None, daq_trigger=None, daq_noise=None, daq_digitizer=None, daq_reducer=None, daq_keep_traces=True):
         """Propagate the photons of all ``batch_events`` in one go and split the results
         back per event (by evidx).  Yields the events.  ``uploaded``: what _upload_batch returned for them;
         ``gpu_geometry``: the geometry of the lane this batch runs on (default: the simulation's own)."""
@@ -163,7 +163,8 @@ class Simulation(object):
                 # (under the acquisition numbers of the events' channels: both describe the same photoelectrons)
                 event_pulses = self._gpu_event_daq.acquire_pulses(gpu_photons, self.rng_states, bounds, daq_window,
                                                                   acquisition=self.gpu_daq.acquisition, trigger=daq_trigger,
-                                                                  noise=daq_noise, digitizer=daq_digitizer)
+                                                                  noise=daq_noise, digitizer=daq_digitizer, reducer=daq_reducer,
+                                                                  keep_traces=daq_keep_traces)
             self.gpu_daq.acquisition += len(batch_events)
         for i, (ev, lo, hi) in enumerate(zip(batch_events, bounds[:-1], bounds[1:])):
             if not keep_photons_beg:
@@ -211,7 +212,7 @@ class Simulation(object):
 
     def simulate(self, iterable, keep_photons_beg=False, keep_photons_end=False, keep_hits=True,
                  keep_flat_hits=True, run_daq=False, max_steps=1000, photons_per_batch=1000000, evid_start=0, daq_window=None,
-                 daq_trigger=None, daq_noise=None, daq_digitizer=None):
+                 daq_trigger=None, daq_noise=None, daq_digitizer=None, daq_reducer=None, daq_keep_traces=True):
         """Simulate Photons objects (or Events that already carry ``photons_beg``); events are
         batched until ``photons_per_batch`` photons are collected (chroma/sim.py:141-186).
 
@@ -224,7 +225,10 @@ class Simulation(object):
         ``event.DARK_NOISE``, and reach the trigger; ``ev.pulses.noise`` counts them.  ``ev.channels`` does not see them.
         ``daq_digitizer`` (with ``daq_trigger``; a gpu.DaqDigitizer): every gated channel of every firing is read out as a shaped ADC
         trace (``ev.triggers.adc(k)``, ``.trace(k, channel)``, ``.trace_flags``, ``.sample_times(k)``), under the acquisition number
-        of the event's channels.
+        of the event's channels.  ``daq_reducer`` (with ``daq_digitizer``; a gpu.DaqReducer or (threshold[, lead, lag[, cfd[,
+        nbaseline[, min_width]]]])): the traces are reduced on the device to the pulses found in them, with charge and
+        constant-fraction time (``ev.triggers.found(k, channel)``, ``.reco(k)``, ``.reco_channels(k)``: an event.Channels of what was
+        reconstructed, for Likelihood.set_event); with ``daq_keep_traces=False`` the samples are not read back.
 
         With ``Simulation(prefetch=True)`` (the default) the NEXT batch is taken from ``iterable`` and uploaded by a second
         thread while the current one propagates: the iterable is consumed one batch ahead of the events this generator
@@ -236,6 +240,8 @@ class Simulation(object):
             raise ValueError('daq_noise needs daq_window')
         if daq_digitizer is not None and daq_trigger is None:
             raise ValueError('daq_digitizer needs daq_trigger')
+        if daq_reducer is not None and daq_digitizer is None:
+            raise ValueError('daq_reducer needs daq_digitizer')
         if isinstance(iterable, event.Photons):
             first, iterable = iterable, [iterable]
         else:
@@ -262,9 +268,11 @@ class Simulation(object):
                     daq_noise.tables(daq_window, self.gpu_geometry.nchannels)          # (raises what does not fit the window or the detector)
             if daq_digitizer is not None:
                 daq_digitizer = gpu.DaqDigitizer.of(daq_digitizer).check(daq_trigger)
+            if daq_reducer is not None:
+                daq_reducer = gpu.DaqReducer.of(daq_reducer).check(daq_trigger.pre + daq_trigger.post)
         kwargs = dict(keep_photons_beg=keep_photons_beg, keep_photons_end=keep_photons_end, keep_hits=keep_hits,
                       keep_flat_hits=keep_flat_hits, run_daq=run_daq, max_steps=max_steps, daq_window=daq_window, daq_trigger=daq_trigger,
-                      daq_noise=daq_noise, daq_digitizer=daq_digitizer)
+                      daq_noise=daq_noise, daq_digitizer=daq_digitizer, daq_reducer=daq_reducer, daq_keep_traces=daq_keep_traces)
         if isinstance(first, event.Event) and first.photons_beg is None:
             yield from self._simulate_stepped(iterable, photons_per_batch, evid_start, kwargs)
             return

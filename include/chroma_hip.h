@@ -708,6 +708,80 @@ int chroma_daq_digitize_host(uint32_t nrows, uint32_t nchannels, const chroma_da
                              const uint32_t *trig_bin, uint64_t ntriggers, const uint32_t *hit_offsets,
                              const int32_t *hit_channel, uint64_t nhits, uint64_t first_hit, uint64_t nhits_call,
                              uint64_t sample_capacity, uint16_t *adc, uint32_t *trace_flags);
+/* ---- the trace reduction of the time-binned DAQ: found pulses, their charge and their time ----------
+ * A fourth integer stage, on the samples chroma_daq_digitize_gates left on the device: what the
+ * electronics make of a trace -- the pulses in it, the charge of each and a constant-fraction time.  A
+ * function of the traces alone (d_adc: ntraces traces of G samples each) and of the parameters below.
+ * The reference has no counterpart; this is the definition.  All sums are of integers: their order does
+ * not show, and the host twin gives the same bits.
+ *
+ * Per trace, with samples v(s), s in [0, G): N = max(nbaseline, 1); base = the sum of v(s) over s <
+ * nbaseline when nbaseline > 0, else pedestal; y(s) = polarity * (N * v(s) - base) as int32 (|y| < 2^22);
+ * T = N * threshold.
+ *
+ * Runs and pulses.  A RUN [a, e) is a maximal stretch of consecutive samples with y(s) >= T, over the
+ * whole trace, the baseline samples included.  A PULSE is a run with e - a >= min_width; the pulses of a
+ * trace are numbered j = 0 .. n - 1 by ascending a.  The samples of a rejected run are ordinary samples.
+ *
+ * The integration window [begin_j, stop_j) of pulse j, non-overlapping by construction:
+ *   stop_j  = min(e_j + lag, a_{j+1} if there is a pulse j + 1, G),
+ *   begin_j = max(a_j - lead clamped at 0, stop_{j-1} if j > 0).
+ *
+ * Per found pulse: start = a_j; width = e_j - a_j; peak = the largest y of the run; peak_sample = the
+ * FIRST sample of the run that attains it; integral (int64: 65536 samples of 2^22) = the sum of y(s) over
+ * the window; time, in 1/256 of a sample; flags: bit 0 TIME_AT_EDGE, bit 1 OPEN_AT_START (a_j == 0), bit
+ * 2 OPEN_AT_END (e_j == G).
+ *
+ * The time.  L = max(1, (peak * cfd) >> 8); s_c = the smallest s of [begin_j, peak_sample] with y(u) >= L
+ * for every u of [s, peak_sample].  If s_c == begin_j and (begin_j == 0 or y(begin_j - 1) >= L): time =
+ * 256 * s_c and TIME_AT_EDGE is set.  Otherwise, with y0 = y(s_c - 1) < L <= y1 = y(s_c),
+ *   time = 256 * (s_c - 1) + ((L - y0) * 256) / (y1 - y0),
+ * an unsigned 32-bit floor division of operands below 2^31; the fraction lies in (0, 256].
+ *
+ * Per trace: d_found_offsets (ntraces + 1 words, the first 0), the trace's place in the pulse arrays;
+ * d_trace_base (int32) = base; d_reduced_flags: bit 0 BASELINE_BUSY iff nbaseline > 0 and the largest
+ * minus the smallest baseline sample exceeds baseline_spread. */
+typedef struct chroma_daq_reducer {   /* 36 bytes */
+    int32_t  polarity;         /* +1: pulses rise; -1: they fall */
+    uint32_t nbaseline;        /* 0 .. 64 and <= G: the leading samples the baseline is measured over; 0: `pedestal` */
+    uint32_t pedestal;         /* 0 .. 65535, used iff nbaseline == 0 */
+    uint32_t baseline_spread;  /* the largest allowed max - min over the baseline samples */
+    uint32_t threshold;        /* 1 .. 65535 ADC counts above baseline */
+    uint32_t min_width;        /* 1 .. 65536: the shortest run of samples that counts as a pulse */
+    uint32_t lead, lag;        /* 0 .. 65535 each: samples integrated before and behind a pulse */
+    uint32_t cfd;              /* 1 .. 256: the constant fraction, in 1/256 */
+} chroma_daq_reducer;
+#define CHROMA_FOUND_TIME_AT_EDGE 1u
+#define CHROMA_FOUND_OPEN_AT_START 2u
+#define CHROMA_FOUND_OPEN_AT_END 4u
+#define CHROMA_REDUCED_BASELINE_BUSY 1u
+/* Count, scan, fill: a pass counts the pulses per trace, an exclusive sum makes d_found_offsets, a pass
+ * fills the pulse arrays (`found_capacity` entries each).  *nfound, the offsets, d_trace_base and
+ * d_reduced_flags are always written.  If *nfound > found_capacity the pulse arrays stay untouched and the
+ * call is CHROMA_ERR_INVALID, as chroma_daq_trigger_pulses' is with too few trigger entries: grow them
+ * and call again.
+ *
+ * Refused, CHROMA_ERR_INVALID before anything is launched and with nothing written: a parameter outside
+ * the ranges above; G outside 1 .. 65536; ntraces * G of 2^32 or more, or ntraces of 2^31 - 1 or more
+ * (the scan's count); a NULL array that is needed (d_adc and the three per-trace arrays when ntraces; the
+ * pulse arrays when ntraces and found_capacity; reducer and nfound always).  ntraces == 0 is CHROMA_OK: it launches
+ * nothing, writes nothing but *nfound = 0.  Every uint16 is a valid sample: no input makes an access
+ * outside the arrays.
+ *
+ * Runs on the context's stream and returns when the arrays are written.  Scratch: the scan's workspace. */
+int chroma_daq_reduce_traces(chroma_ctx *ctx, const chroma_daq_reducer *reducer, uint32_t G, uint64_t ntraces,
+                             const uint16_t *d_adc, uint64_t found_capacity, uint32_t *d_found_offsets,
+                             int32_t *d_trace_base, uint32_t *d_reduced_flags, uint32_t *d_found_start,
+                             uint32_t *d_found_width, uint32_t *d_found_peak, uint32_t *d_found_peak_sample,
+                             int64_t *d_found_integral, uint32_t *d_found_time, uint32_t *d_found_flags,
+                             uint64_t *nfound);
+/* The same on the host (no GPU, no context), plain loops over trace, sample and pulse: the same
+ * arguments on HOST arrays, the same refusals, the same bits. */
+int chroma_daq_reduce_host(const chroma_daq_reducer *reducer, uint32_t G, uint64_t ntraces, const uint16_t *adc,
+                           uint64_t found_capacity, uint32_t *found_offsets, int32_t *trace_base,
+                           uint32_t *reduced_flags, uint32_t *found_start, uint32_t *found_width,
+                           uint32_t *found_peak, uint32_t *found_peak_sample, int64_t *found_integral,
+                           uint32_t *found_time, uint32_t *found_flags, uint64_t *nfound);
 /* `convert_sortable_int_to_float` + `convert_charge_int_to_float` (daq.cu:152-173) */
 int chroma_daq_convert(chroma_ctx *ctx, uint32_t nchannels, float charge_unit, const uint32_t *d_earliest_time_int,
                        const uint32_t *d_channel_q_int, float *d_earliest_time, float *d_channel_q);
