@@ -71,6 +71,9 @@ def load(variant='contract'):
     lib.oracle_propagate.restype = c_int32
     lib.oracle_propagate.argtypes = [POINTER(_abi.GeometryDesc), POINTER(_abi.PhotonArrays), c_uint64, _abi.Rng,
                                      c_int32, c_int32, c_int32, c_int32, POINTER(_abi.PropagateStats)]
+    lib.oracle_to_diffuse.restype = c_int32
+    lib.oracle_to_diffuse.argtypes = [POINTER(_abi.GeometryDesc), POINTER(_abi.PhotonArrays), c_uint64, _abi.Rng, c_int32, c_void_p,
+                                      c_void_p, POINTER(_abi.PropagateStats)]
     lib.oracle_distance_to_mesh.restype = c_int32
     lib.oracle_distance_to_mesh.argtypes = [POINTER(_abi.GeometryDesc), c_uint64, c_void_p, c_void_p, c_void_p, c_void_p,
                                             POINTER(_abi.PropagateStats)]
@@ -161,6 +164,22 @@ def propagate(packed, photons, seed, photon_id_base=0, max_steps=10, use_weights
     return hp.photons(), hp.rng_counters, stats.as_dict()
 
 
+def to_diffuse(packed, photons, seed, photon_id_base=0, max_steps=10, rng_counters=None, active=None, variant='contract'):
+    """to_diffuse of the hybrid render (hybrid_render.cu:20-58) on ``photons``: the step loop without propagate's division of
+    direction and polarisation by their norms on load, left after the first step that sets REFLECT_DIFFUSE.  ``active``:
+    boolean mask of the photons to run (the others come back as they are).  Returns (Photons, rng_counters, side), ``side``
+    the inside_to_outside of the last triangle each photon hit (0 where it hit none)."""
+    lib = load(variant)
+    hp = HostPhotons(photons, rng_counters=rng_counters)
+    mask = None if active is None else np.ascontiguousarray(active, dtype=np.uint8)
+    side = np.zeros(hp.n, dtype=np.uint32)
+    rc = lib.oracle_to_diffuse(ctypes.byref(packed.desc), ctypes.byref(hp.struct), hp.n, _abi.Rng(int(seed), int(photon_id_base)),
+                               int(max_steps), None if mask is None else mask.ctypes.data, side.ctypes.data, None)
+    if rc != 0:
+        raise RuntimeError('oracle_to_diffuse failed (%d)' % rc)
+    return hp.photons(), hp.rng_counters, side
+
+
 def ref_propagate(packed, photons, seed, photon_id_base=0, max_steps=10, use_weights=False, scatter_first=0,
                   rng_counters=None, variant='contract'):
     """``propagate`` through the reference's own kernel and its host loop (ref_phys_propagate).  Returns
@@ -210,9 +229,10 @@ def ref_single(packed, which, photon, seed=0, photon_id=0, counter=0, normal=(0.
                    absorption_length, scattering_length, material1, surface_index, distance_to_boundary, use_weights, scatter_first)
 
 
-def distance_to_mesh(packed, origins, directions, variant='contract', last_hits=None):
+def distance_to_mesh(packed, origins, directions, variant='contract', last_hits=None, normalize=True):
     """(distance, triangle) for a ray bundle; misses give distance nan-filled here and triangle -1.
-    ``last_hits``: per-ray triangle the ray must not hit (intersect_mesh's last_hit_triangle)."""
+    ``last_hits``: per-ray triangle the ray must not hit (intersect_mesh's last_hit_triangle).
+    ``normalize=False``: intersect_mesh on the directions as they are, not distance_to_mesh's direction / norm(direction)."""
     lib = load(variant)
     o = np.ascontiguousarray(origins, dtype=np.float32)
     d = np.ascontiguousarray(directions, dtype=np.float32)
@@ -221,11 +241,11 @@ def distance_to_mesh(packed, origins, directions, variant='contract', last_hits=
     tri = np.empty(n, dtype=np.int32)
     stats = _abi.PropagateStats()
     lh = None if last_hits is None else np.ascontiguousarray(last_hits, dtype=np.int32)
-    lib.oracle_intersect_mesh.restype = c_int32
-    lib.oracle_intersect_mesh.argtypes = [POINTER(_abi.GeometryDesc), c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                          POINTER(_abi.PropagateStats)]
-    lib.oracle_intersect_mesh(ctypes.byref(packed.desc), n, o.ctypes.data, d.ctypes.data, None if lh is None else lh.ctypes.data,
-                              dist.ctypes.data, tri.ctypes.data, ctypes.byref(stats))
+    cast = lib.oracle_intersect_mesh if normalize else lib.oracle_intersect_mesh_as_given
+    cast.restype = c_int32
+    cast.argtypes = [POINTER(_abi.GeometryDesc), c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(_abi.PropagateStats)]
+    cast(ctypes.byref(packed.desc), n, o.ctypes.data, d.ctypes.data, None if lh is None else lh.ctypes.data, dist.ctypes.data,
+         tri.ctypes.data, ctypes.byref(stats))
     return dist, tri, stats.as_dict()
 
 

@@ -887,16 +887,20 @@ static int propagate_at_surface(Photon *p, State *s, cm_rng *rng, Geo *g, int us
     }
 }
 
-/* ---- propagate.cu:217-319, one photon ------------------------------------------ */
+/* ---- propagate.cu:217-319, one photon ------------------------------------------
+ * side != NULL: to_diffuse (hybrid_render.cu:20-58) instead -- the same step loop on a photon the caller has made itself
+ * (direction and polarisation are taken as they are, not divided by their norms on load), left after the first step that
+ * sets REFLECT_DIFFUSE; *side is State::inside_to_outside of the last triangle hit.  (The NaN abort stays: the engine's
+ * to_diffuse has it too.) */
 static void propagate_one(Geo *g, const chroma_photon_arrays *a, size_t photon_id, chroma_rng rng_desc,
-                          int max_steps, int use_weights, int scatter_first, Counters *cnt)
+                          int max_steps, int use_weights, int scatter_first, uint32_t *side, Counters *cnt)
 {
     Photon p;
     p.position = mk3(a->pos[3 * photon_id], a->pos[3 * photon_id + 1], a->pos[3 * photon_id + 2]);
     p.direction = mk3(a->dir[3 * photon_id], a->dir[3 * photon_id + 1], a->dir[3 * photon_id + 2]);
-    p.direction = div3s(p.direction, norm3(p.direction));
+    if (!side) p.direction = div3s(p.direction, norm3(p.direction));
     p.polarization = mk3(a->pol[3 * photon_id], a->pol[3 * photon_id + 1], a->pol[3 * photon_id + 2]);
-    p.polarization = div3s(p.polarization, norm3(p.polarization));
+    if (!side) p.polarization = div3s(p.polarization, norm3(p.polarization));
     p.wavelength = a->wavelengths[photon_id];
     p.time = a->t[photon_id];
     p.last_hit_triangle = a->last_hit_triangles[photon_id];
@@ -922,6 +926,7 @@ static void propagate_one(Geo *g, const chroma_photon_arrays *a, size_t photon_i
         cnt->photon_steps++;
         fill_state(&s, &p, g, cnt);
         if (p.last_hit_triangle == -1) break;
+        if (side) *side = (uint32_t)s.inside_to_outside;
 
         command = propagate_to_boundary(&p, &s, &rng, g, use_weights, scatter_first);
         scatter_first = 0;
@@ -930,6 +935,7 @@ static void propagate_one(Geo *g, const chroma_photon_arrays *a, size_t photon_i
 
         if (s.surface_index != -1) {
             command = propagate_at_surface(&p, &s, &rng, g, use_weights);
+            if (side && (p.history & CHROMA_REFLECT_DIFFUSE)) break;          /* hybrid_render.cu:44-45 */
             if (command == BREAK) break;
             if (command == CONTINUE) continue;
         }
@@ -967,7 +973,7 @@ static void *job_main(void *arg)
         if (begin >= j->n) break;
         size_t end = begin + JOB_BLOCK < j->n ? begin + JOB_BLOCK : j->n;
         for (size_t i = begin; i < end; i++)
-            propagate_one(j->g, j->a, j->ids[i], j->rng, j->max_steps, j->use_weights, j->scatter_first, &cnt);
+            propagate_one(j->g, j->a, j->ids[i], j->rng, j->max_steps, j->use_weights, j->scatter_first, NULL, &cnt);
     }
     j->cnt = cnt;
     return NULL;
@@ -1039,16 +1045,37 @@ int oracle_propagate(const chroma_geometry_desc *g, const chroma_photon_arrays *
     return 0;
 }
 
+/* to_diffuse (hybrid_render.cu:20-58) for HOST photon arrays: one call of the loop per photon with active[i] != 0 (NULL:
+ * all), the others untouched; side[i] = inside_to_outside of the last triangle photon i hit (untouched when it hit none). */
+int oracle_to_diffuse(const chroma_geometry_desc *g, const chroma_photon_arrays *a, uint64_t nphotons, chroma_rng rng,
+                      int32_t max_steps, const uint8_t *active, uint32_t *side, chroma_propagate_stats *stats)
+{
+    if (!side) return -1;
+    Counters cnt; memset(&cnt, 0, sizeof cnt);
+    for (uint64_t i = 0; i < nphotons; i++)
+        if (!active || active[i]) propagate_one(g, a, (size_t)i, rng, max_steps, 0, 0, &side[i], &cnt);
+    if (stats) {
+        stats->photon_steps += cnt.photon_steps;
+        stats->nodes_visited += cnt.nodes_visited;
+        stats->triangles_tested += cnt.triangles_tested;
+        stats->stack_overflows += cnt.stack_overflows;
+    }
+    return 0;
+}
+
 /* distance_to_mesh kernel (mesh.h:124-151) + the triangle id; misses leave distance untouched */
 /* mesh.h:124-151 (last_hits == NULL), and intersect_mesh (mesh.h:42-118) with its last_hit_triangle argument */
-int oracle_intersect_mesh(const chroma_geometry_desc *g, uint64_t n, const float *origin, const float *direction,
-                          const int32_t *last_hits, float *distance, int32_t *triangle, chroma_propagate_stats *stats)
+/* normalise 1: distance_to_mesh (mesh.h:124-151), which divides the direction by its norm; 0: the direction as it is, for a
+ * kernel that has normalised it itself and calls intersect_mesh (hybrid_render.cu:84-87) -- a second division can move a
+ * direction whose f32 norm is not exactly 1 by an ulp, and a grazing ray to another triangle */
+static int cast_rays(const chroma_geometry_desc *g, uint64_t n, const float *origin, const float *direction, int normalise,
+                     const int32_t *last_hits, float *distance, int32_t *triangle, chroma_propagate_stats *stats)
 {
     Counters cnt; memset(&cnt, 0, sizeof cnt);
     for (uint64_t i = 0; i < n; i++) {
         f3 o = mk3(origin[3 * i], origin[3 * i + 1], origin[3 * i + 2]);
         f3 d = mk3(direction[3 * i], direction[3 * i + 1], direction[3 * i + 2]);
-        d = div3s(d, norm3(d));
+        if (normalise) d = div3s(d, norm3(d));
         float dist;
         int tri = intersect_mesh(o, d, g, &dist, last_hits ? last_hits[i] : -1, &cnt);
         if (tri != -1) distance[i] = dist;
@@ -1060,6 +1087,18 @@ int oracle_intersect_mesh(const chroma_geometry_desc *g, uint64_t n, const float
         stats->stack_overflows += cnt.stack_overflows;
     }
     return 0;
+}
+
+int oracle_intersect_mesh(const chroma_geometry_desc *g, uint64_t n, const float *origin, const float *direction,
+                          const int32_t *last_hits, float *distance, int32_t *triangle, chroma_propagate_stats *stats)
+{
+    return cast_rays(g, n, origin, direction, 1, last_hits, distance, triangle, stats);
+}
+
+int oracle_intersect_mesh_as_given(const chroma_geometry_desc *g, uint64_t n, const float *origin, const float *direction,
+                                   const int32_t *last_hits, float *distance, int32_t *triangle, chroma_propagate_stats *stats)
+{
+    return cast_rays(g, n, origin, direction, 0, last_hits, distance, triangle, stats);
 }
 
 int oracle_distance_to_mesh(const chroma_geometry_desc *g, uint64_t n, const float *origin, const float *direction,

@@ -131,6 +131,20 @@ def _step_to_diffuse(oracle_mod, packed, normals, photons, active, seed, id_base
     return tri, np.where(diffuse, side, 0).astype(np.uint32), np.where(active, cur[6], 0).astype(np.uint32), ctr
 
 
+def _to_diffuse(oracle_mod, packed, photons, active, seed, id_base, counters, max_steps):
+    """oracle.to_diffuse: the reference's own loop (hybrid_render.cu:20-58), which takes direction and polarisation as the
+    kernel made them.  _step_to_diffuse goes through oracle.propagate, which divides both by their norms at every step as
+    propagate.cu does on load: the same samples, but for a ray that grazes a triangle (where an ulp of the direction decides
+    what it meets next).  Returns (triangle or -1, side, history, counters) like _step_to_diffuse."""
+    active = np.asarray(active, bool)
+    out, ctr, side = oracle_mod.to_diffuse(packed, photons, seed, photon_id_base=id_base, max_steps=max_steps, rng_counters=counters,
+                                           active=active)
+    flags = np.asarray(out.flags, np.uint32)
+    diffuse = active & ((flags & REFLECT_DIFFUSE) != 0)
+    tri = np.where(diffuse, out.last_hit_triangles, -1).astype(np.int32)
+    return tri, np.where(diffuse, side, 0).astype(np.uint32), np.where(active, flags, 0).astype(np.uint32), ctr
+
+
 def oracle_lookup(oracle_mod, packed, geometry, seed, id_base, counters, nthreads, offset, source, wavelength, max_steps):
     """One update_xyz_lookup launch restated.  Returns (triangle, side, history, cos_theta, counters) of its samples."""
     from chroma_amd.event import Photons
@@ -145,7 +159,9 @@ def oracle_lookup(oracle_mod, packed, geometry, seed, id_base, counters, nthread
     pos = np.tile(np.asarray(source, f32), (n, 1))
     d = ((a[:, None] * v0 + b[:, None] * v1) + c[:, None] * v2) - pos
     d = d / np.sqrt(_dot(d, d))[:, None]
-    _, first, _ = oracle_mod.distance_to_mesh(packed, pos, d)
+    # update_xyz_lookup casts the direction it has normalised itself (hybrid_render.cu:84-87); distance_to_mesh would divide
+    # it by its norm once more and move a grazing ray by an ulp onto another triangle
+    _, first, _ = oracle_mod.distance_to_mesh(packed, pos, d, normalize=False)
     mine = first == np.arange(offset, offset + n)
     nrm = _normals(geometry)[offset:offset + n]
     cos = _dot(nrm, -d)
@@ -155,7 +171,7 @@ def oracle_lookup(oracle_mod, packed, geometry, seed, id_base, counters, nthread
     photons = Photons(pos, d, pol, np.full(n, wavelength, f32), np.zeros(n, f32), np.full(n, -1, np.int32),
                       np.zeros(n, np.uint32), np.ones(n, f32), np.zeros(n, np.uint32))
     start = np.where(mine, c0 + 4, c0 + 2).astype(np.uint32)
-    tri, side, hist, ctr = _step_to_diffuse(oracle_mod, packed, _normals(geometry), photons, mine, seed, id_base, start, max_steps)
+    tri, side, hist, ctr = _to_diffuse(oracle_mod, packed, photons, mine, seed, id_base, start, max_steps)
     return tri, side, hist, cos, ctr, mine
 
 
@@ -165,10 +181,12 @@ def oracle_image(oracle_mod, packed, geometry, seed, id_base, counters, origins,
     c0 = np.asarray(counters, np.uint32)[:n]
     u = _draws(oracle_mod, seed, id_base, c0, 2)
     pol = _uniform_sphere(oracle_mod, u[:, 0], u[:, 1])
-    photons = Photons(np.asarray(origins, f32), np.asarray(directions, f32), pol, np.full(n, wavelength, f32), np.zeros(n, f32),
+    d = np.asarray(directions, f32).reshape(-1, 3)
+    with np.errstate(invalid='ignore', divide='ignore'):            # a zero or NaN direction gives NaN, as on the device
+        d = d / np.sqrt(_dot(d, d))[:, None]                        # update_xyz_image's direction /= norm(direction), in f32
+    photons = Photons(np.asarray(origins, f32), d, pol, np.full(n, wavelength, f32), np.zeros(n, f32),
                       np.full(n, -1, np.int32), np.zeros(n, np.uint32), np.ones(n, f32), np.zeros(n, np.uint32))
-    tri, side, hist, ctr = _step_to_diffuse(oracle_mod, packed, _normals(geometry), photons, np.ones(n, bool), seed, id_base,
-                                            c0 + 2, max_steps)
+    tri, side, hist, ctr = _to_diffuse(oracle_mod, packed, photons, np.ones(n, bool), seed, id_base, c0 + 2, max_steps)
     return tri, side, hist, ctr
 
 
@@ -326,7 +344,7 @@ def test_lambertian_room(oracle_mod):
             pos = np.tile(np.asarray(source, f32), (ntri, 1))
             d = ((a[:, None] * v0 + b[:, None] * v1) + c[:, None] * v2) - pos
             d = d / np.sqrt(_dot(d, d))[:, None]
-            _, first, _ = oracle_mod.distance_to_mesh(packed, pos, d)
+            _, first, _ = oracle_mod.distance_to_mesh(packed, pos, d, normalize=False)
             mine = first == np.arange(ntri)
             assert mine.any()
             assert np.array_equal(tri[:ntri][mine], np.arange(ntri)[mine]) and (tri[:ntri][~mine] == -1).all()
