@@ -152,6 +152,31 @@ class StepSegments(Structure):
                 ('qedep', c_void_p), ('evidx', c_void_p), ('n', c_uint64), ('segment_base', c_uint64)]
 
 
+class StoppingMediaDesc(Structure):
+    """chroma_stopping_media_desc (host pointers)"""
+    _fields_ = [('nmedia', c_uint32), ('nke', c_uint32), ('ke_min', c_float), ('log_step', c_float),
+                ('stopping_power', c_void_p), ('radiation_length', c_void_p), ('birks', c_void_p)]
+
+
+class ParticleArrays(Structure):
+    """chroma_particle_arrays (device or host pointers, depending on the callee)"""
+    _fields_ = [('pos', c_void_p), ('dir', c_void_p), ('ke', c_void_p), ('t', c_void_p), ('last_hit', c_void_p), ('species', c_void_p),
+                ('z', c_void_p), ('mass', c_void_p), ('evidx', c_void_p), ('nsteps', c_void_p), ('rng_counter', c_void_p),
+                ('status', c_void_p), ('n', c_uint64), ('particle_base', c_uint64)]
+
+
+class ParticleOptions(Structure):
+    """chroma_particle_options"""
+    _fields_ = [('max_steps', c_int32), ('max_step', c_float), ('max_loss', c_float), ('ke_cut', c_float), ('scatter', c_int32),
+                ('outside', c_int32)]
+
+
+class ParticlePoints(Structure):
+    """chroma_particle_points (device or host pointers, depending on the callee)"""
+    _fields_ = [('pos', c_void_p), ('t', c_void_p), ('dir', c_void_p), ('ke', c_void_p), ('edep', c_void_p), ('qedep', c_void_p),
+                ('medium', c_void_p)]
+
+
 # name -> (restype, argtypes); every symbol include/chroma_hip.h declares
 SIGNATURES = {
     'chroma_last_error': (c_char_p, []),
@@ -265,6 +290,22 @@ SIGNATURES = {
                                                 POINTER(c_uint64)]),
     'chroma_steps_generate_media_host': (c_int32, [POINTER(LightMediaDesc), POINTER(StepSegments), c_void_p, c_uint64, c_void_p,
                                                    POINTER(PhotonArrays), c_uint64]),
+    'chroma_stopping_media_create': (c_int32, [c_void_p, POINTER(StoppingMediaDesc), POINTER(c_void_p)]),
+    'chroma_stopping_media_destroy': (c_int32, [c_void_p]),
+    'chroma_particles_advance': (c_int32, [c_void_p, c_void_p, POINTER(ParticleArrays), POINTER(ParticleOptions), c_uint64, c_void_p, c_void_p,
+                                           c_void_p, POINTER(ParticlePoints)]),
+    'chroma_particles_advance_host': (c_int32, [POINTER(StoppingMediaDesc), POINTER(ParticleArrays), POINTER(ParticleOptions), c_uint64, c_void_p,
+                                                c_void_p, c_void_p, POINTER(ParticlePoints)]),
+    'chroma_particles_track': (c_int32, [c_void_p, c_void_p, c_void_p, POINTER(ParticleArrays), POINTER(ParticleOptions), c_uint64,
+                                         POINTER(c_uint64)]),
+    'chroma_particles_track_host': (c_int32, [POINTER(StoppingMediaDesc), POINTER(ParticleArrays), POINTER(ParticleOptions), c_uint64,
+                                              POINTER(ParticlePoints), POINTER(c_uint64)]),
+    'chroma_particles_points': (c_int32, [c_void_p, POINTER(ParticlePoints), c_void_p, c_uint64]),
+    'chroma_particles_segments': (c_int32, [c_void_p, POINTER(StepSegments), c_void_p, c_uint64]),
+    'chroma_particles_points_host': (c_int32, [POINTER(ParticleArrays), c_int32, POINTER(ParticlePoints), POINTER(ParticlePoints), c_void_p,
+                                               c_uint64]),
+    'chroma_particles_segments_host': (c_int32, [POINTER(ParticleArrays), c_int32, POINTER(ParticlePoints), POINTER(StepSegments), c_void_p,
+                                                 c_uint64]),
     'chroma_render': (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32]),
     'chroma_hybrid_lookup': (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, POINTER(c_float), Rng, c_void_p, c_uint32,
                                        c_float, POINTER(c_float), c_void_p, c_void_p, c_uint32, c_int32, c_void_p, c_void_p,

@@ -44,6 +44,12 @@ def main(argv=None):
     ap.add_argument('--nphotons', type=int, default=100000, help='photons per event')
     ap.add_argument('--wavelength', default='400', help='nm, or "lo:hi" for a uniform range')
     ap.add_argument('--pos', default='0,0,0')
+    ap.add_argument('--particle', default=None, metavar='NAME',
+                    help='instead of a photon bomb: one charged particle per event at --pos (e-, e+, mu-, mu+, pi+, pi-, K+, K-, p, alpha), '
+                         'stepped through the detector on the GPU (continuous slowing down, no secondaries: Simulation(stepper=\'csda\'))')
+    ap.add_argument('--ke', type=float, default=None, metavar='MEV', help='with --particle: its kinetic energy')
+    ap.add_argument('--dir', default='0,0,1', metavar='X,Y,Z', help='with --particle: its direction')
+    ap.add_argument('--save-steps', action='store_true', help='with --particle: also write the step points of every event')
     ap.add_argument('--max-steps', type=int, default=100)
     ap.add_argument('--run-daq', action='store_true')
     ap.add_argument('--daq-window', default=None, metavar='T0,DT,NBINS',
@@ -75,6 +81,19 @@ def main(argv=None):
 
     wl = tuple(float(x) for x in args.wavelength.split(':')) if ':' in args.wavelength else float(args.wavelength)
     pos = [float(x) for x in args.pos.split(',')]
+    if args.particle is not None:
+        from chroma_amd.generator.particles import PDG_CODES
+        if args.particle not in PDG_CODES:
+            ap.error('--particle: one of %s' % ', '.join(sorted(PDG_CODES)))
+        if args.ke is None or not args.ke > 0:
+            ap.error('--particle needs --ke MEV above 0')
+        direction = [float(x) for x in args.dir.split(',')]
+        if len(direction) != 3 or not any(direction):
+            ap.error('--dir takes X,Y,Z, not all zero')
+        if args.track or args.device_tracks:
+            ap.error('--particle does not go with --track or --device-tracks')
+    elif args.ke is not None or args.save_steps:
+        ap.error('--ke and --save-steps need --particle')
     daq_window = None
     if args.daq_window is not None:
         parts = args.daq_window.split(',')
@@ -132,22 +151,35 @@ def main(argv=None):
     detector = load_geometry_from_string(args.detector, cache_dir=args.cache_dir)
     print('geometry: %d triangles, BVH %d nodes (%.1f s)' % (len(detector.mesh.triangles), len(detector.bvh.nodes), time.time() - t0))
     sim = Simulation(detector, seed=args.seed, cuda_device=args.device, geant4_processes=0,
-                     photon_tracking='device' if args.device_tracks else args.track, exact=args.exact)
+                     photon_tracking='device' if args.device_tracks else args.track, exact=args.exact,
+                     stepper='csda' if args.particle is not None else None, particle_tracking=args.save_steps)
     rng = np.random.default_rng(sim.seed)
-    events = (bomb_event(args.nphotons, wl, pos, rng) for _ in range(args.nevents))
+    if args.particle is not None:
+        from chroma_amd import event
+        events = (event.Event(vertices=[event.Vertex(args.particle, pos, direction, args.ke, pdgcode=PDG_CODES[args.particle])])
+                  for _ in range(args.nevents))
+    else:
+        events = (bomb_event(args.nphotons, wl, pos, rng) for _ in range(args.nevents))
     out = {'nevents': np.array(args.nevents), 'nphotons': np.array(args.nphotons), 'seed': np.array(sim.seed)}
     t0 = time.time()
-    nhits = 0
+    nhits = nphotons = 0
     for ev in sim.simulate(events, keep_photons_beg=args.save_photons_beg, keep_photons_end=args.save_photons_end,
                            keep_hits=False, keep_flat_hits=hasattr(detector, 'num_channels'),
                            run_daq=args.run_daq, max_steps=args.max_steps, daq_window=daq_window, daq_trigger=daq_trigger,
                            daq_noise=args.daq_noise, daq_digitizer=daq_digitizer, daq_reducer=daq_reducer,
                            daq_keep_traces=not args.daq_drop_traces):
         key = 'ev%d' % ev.id
+        nphotons += ev.nphotons
+        if args.particle is not None:
+            out[key + '/nphotons'] = np.array(ev.nphotons)          # (what the particle's track emitted: --nphotons is not used)
         for tag, ph in (('photons_beg', ev.photons_beg), ('photons_end', ev.photons_end)):
             if ph is not None:
                 for name in ('pos', 'dir', 'pol', 'wavelengths', 't', 'flags', 'last_hit_triangles', 'weights'):
                     out['%s/%s/%s' % (key, tag, name)] = getattr(ph, name)
+        if args.save_steps:
+            steps = ev.vertices[0].steps
+            for name in ('x', 'y', 'z', 't', 'dx', 'dy', 'dz', 'ke', 'edep', 'qedep'):
+                out['%s/steps/%s' % (key, name)] = getattr(steps, name)
         if args.device_tracks and getattr(ev, 'photon_tracks', None) is not None:
             # the same keys straight from the flat rows (PhotonTracks)
             tracks = ev.photon_tracks
@@ -208,7 +240,7 @@ def main(argv=None):
     dt = time.time() - t0
     np.savez_compressed(args.output, **out)
     print('%d events, %d photons, %d hits in %.2f s (%.1f events/s, %.3g photons/s) -> %s' % (
-        args.nevents, args.nevents * args.nphotons, nhits, dt, args.nevents / dt, args.nevents * args.nphotons / dt, args.output))
+        args.nevents, nphotons, nhits, dt, args.nevents / dt, nphotons / dt, args.output))
     return 0
 
 

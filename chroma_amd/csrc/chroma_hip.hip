@@ -812,10 +812,20 @@ int chroma_intersect_mesh(chroma_ctx *ctx, chroma_geometry *geom, int32_t nthrea
 {
     if (!ctx || !geom || !d_origin || !d_direction || !d_distance) return set_error(CHROMA_ERR_INVALID, "bad argument");
     if (nthreads <= 0) return CHROMA_OK;
-    int rc = check_stack(geom); if (rc) return rc;
     const CallScope scope(ctx);          // (the fast path uses the context's queues and ray records, as a propagate call does)
+    return intersect_mesh_in_scope(scope, geom, nthreads, d_origin, d_direction, d_last_hit, d_distance, d_triangle);
+}
+
+}  // extern "C"
+
+// chroma_intersect_mesh behind its checks and its lock (chroma_internal.h: the particle loop of steps_calls.hip calls it too)
+int intersect_mesh_in_scope(const CallScope &scope, chroma_geometry *geom, int32_t nthreads, const float *d_origin, const float *d_direction,
+                            const int32_t *d_last_hit, float *d_distance, int32_t *d_triangle)
+{
+    chroma_ctx *ctx = scope.ctx;
     CallState &cs = scope.state();
     CallPlan plan;
+    int rc = check_stack(geom); if (rc) return rc;
     rc = make_plan(cs, geom, -1, -1, -1, &plan); if (rc) return rc;
     if (!plan.isect_quad) {
         const dim3 grid((unsigned)((nthreads + PROP_BLOCK - 1) / PROP_BLOCK)), block(PROP_BLOCK);
@@ -849,6 +859,8 @@ int chroma_intersect_mesh(chroma_ctx *ctx, chroma_geometry *geom, int32_t nthrea
     HIP_TRY(hipGetLastError());
     return CHROMA_OK;
 }
+
+extern "C" {
 
 // The ray cast of chroma_intersect_mesh over rays that share one direction, then the material from each ray's triangle.  The
 // cast's own per-slot results are its scratch: the distances go back where they came from, and the triangle ids take the

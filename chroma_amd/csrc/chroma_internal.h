@@ -58,8 +58,13 @@ struct CallState {
     hipStream_t aux_stream = nullptr;          // k_finalize_hits beside the tail kernel (launch_tail)
     // One pooled block that the multi-launch calls lay their arrays out on, each from the block's start (grow_call_scratch, Carver):
     // chroma_steps_* (the total, the source's tables, the counts, the scan's workspace), chroma_daq_acquire_events (the bounds),
-    // chroma_daq_compact_events (the flags and their scan), the four pulse calls (PulsesBlock) and chroma_daq_trigger_pulses (TriggerBlock)
+    // chroma_daq_compact_events (the flags and their scan), the four pulse calls (PulsesBlock), chroma_daq_trigger_pulses (TriggerBlock)
+    // and chroma_particles_track (ParticlesBlock: the matrix of step points, the queues, the live particles' rays and casts)
     void *call_scratch = nullptr; size_t call_scratch_bytes = 0;
+    // what the last chroma_particles_track left in that block for chroma_particles_points / _segments (steps_calls.hip): the block
+    // it was laid on (another block since: the points are gone), the caller's particle arrays and the matrix's max_steps
+    bool particles_have = false; const void *particles_block = nullptr; size_t particles_block_bytes = 0;
+    chroma_particle_arrays particles_run = {}; int32_t particles_max_steps = 0;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     // ---- the settings: chroma_set_* and the CHROMA_* environment write them, a call reads them when it starts (CallPlan) ----
     int counting = 0;
@@ -238,6 +243,9 @@ static int carve_call_scratch(const CallScope &scope, Lay &&lay, bool *grew = nu
 // chroma_init's share of the propagate path: the ray-cast grids and the launch policy, from the device and the CHROMA_*
 // environment (chroma_hip.hip: it knows the kernels' residency)
 CHROMA_LOCAL int propagate_settings(const CallScope &scope);
+// chroma_intersect_mesh for a caller that holds the call lock already (chroma_hip.hip: the ray-cast kernels are compiled there, once)
+CHROMA_LOCAL int intersect_mesh_in_scope(const CallScope &scope, chroma_geometry *geom, int32_t nthreads, const float *d_origin,
+                                         const float *d_direction, const int32_t *d_last_hit, float *d_distance, int32_t *d_triangle);
 
 extern "C" {
 // (bvh_device.hip) d_order[n] = the photons 0..n-1 ordered by a 16-bit cell of their direction; queued on the context's stream

@@ -10,3 +10,4 @@ from chroma_amd.gpu.pdf import GPUPDF, GPUKernelPDF
 from chroma_amd.gpu.funcs import get_cu_module, GPUFuncs
 from chroma_amd.gpu.render import GPURays, GPUHybridRender
 from chroma_amd.gpu import steps
+from chroma_amd.gpu import particles

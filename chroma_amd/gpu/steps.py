@@ -88,7 +88,8 @@ def _drop_media(ctx_ref, key):
 
 def generate_photons(vertices_or_segments, source, seed, ctx=None, evidx=0, segment_base=0, return_offsets=False, medium=None,
                      gpu_geometry=None, outside=-1, return_medium=False):
-    """The photons ``source`` emits along the segments (a Segments, or the vertices whose steps make them): a GPUPhotonsSlice
+    """The photons ``source`` emits along the segments (a Segments, the vertices whose steps make them, or the
+    ``gpu.particles.DeviceSegments`` of tracks made on the device, whose own ``medium`` is the default): a GPUPhotonsSlice
     in segment order, a segment's Cherenkov photons before its scintillation photons; ``evidx`` follows the segment,
     ``rng_counters`` is 0.  ``return_offsets``: also the scanned counts as a host array (uint32, 2 n + 1: the photons of segment
     s are ``offsets[2 s] .. offsets[2 s + 2]``).
@@ -99,12 +100,19 @@ def generate_photons(vertices_or_segments, source, seed, ctx=None, evidx=0, segm
     (``locate_materials``; ``outside``: the row of a segment outside every solid) -- the media are then those of
     ``LightMedia.from_geometry``.  The located rows go into the count and generate calls where they are; ``return_medium``:
     also that GPUArray."""
-    ctx = ctx or (gpu_geometry.ctx if gpu_geometry is not None else get_context())
+    ctx = ctx or (gpu_geometry.ctx if gpu_geometry is not None else getattr(vertices_or_segments, 'ctx', None) or get_context())
     lib = ctx._lib
-    segments = _as_segments(vertices_or_segments, evidx, segment_base)
     seed = int(seed) & (2 ** 64 - 1)
-    device = {name: to_gpu(getattr(segments, name).reshape(-1), ctx) for name in _SEGMENT_FIELDS}
-    seg = segments.struct({name: a.ptr for name, a in device.items()})
+    from chroma_amd.gpu.particles import DeviceSegments
+    if isinstance(vertices_or_segments, DeviceSegments):
+        # (segments the particle stepper left on the device, with the medium each was made in: used where they are)
+        segments, seg = vertices_or_segments, vertices_or_segments.struct()
+        if medium is None:
+            medium = segments.medium[:len(segments)]
+    else:
+        segments = _as_segments(vertices_or_segments, evidx, segment_base)
+        device = {name: to_gpu(getattr(segments, name).reshape(-1), ctx) for name in _SEGMENT_FIELDS}
+        seg = segments.struct({name: a.ptr for name, a in device.items()})
     d_offsets = empty(2 * len(segments) + 1, np.uint32, ctx)
     total = ctypes.c_uint64()
     if isinstance(source, LightMedia):

@@ -21,16 +21,34 @@ def pick_seed():
     return int(time.time()) ^ (os.getpid() << 16) & 2 ** 32 - 1
 
 
+def _with_outside(stepper, outside):
+    """``stepper`` with another ``outside`` row"""
+    import copy
+    other = copy.copy(stepper)
+    other.outside = int(outside)
+    return other
+
+
 class Simulation(object):
     def __init__(self, detector, seed=None, cuda_device=None, particle_tracking=False, photon_tracking=False,
                  geant4_processes=0, nthreads_per_block=64, max_blocks=1024, exact=False, prefetch=True, lanes=1,
-                 light_medium=None):
+                 light_medium=None, stepper=None):
         # ``light_medium``: the Material whose Cherenkov and scintillation light the steps of Events without photons emit
         # (simulate(); chroma_amd.gpu.steps.LightSource); None: the detector's ``detector_material``; 'located': every segment
         # emits the light of the material it lies in, found on the device in this geometry (chroma_amd.gpu.steps.locate_materials:
         # a LightMedia with a row per material of the detector; a segment outside every solid is in ``detector_material``, or
         # emits nothing when the detector has none)
         self.light_medium = light_medium
+        # ``stepper``: a chroma_amd.generator.particles.Stepper, or 'csda' for one with the defaults over the detector's materials
+        # (StoppingMedia.from_geometry): simulate() then also takes bare Vertex objects, lists of them, and Events whose vertices
+        # have neither photons nor steps -- the vertices are tracked through the geometry on the device (continuous slowing down,
+        # no secondaries: chroma_amd.gpu.particles) and emit the light of the medium each step was made in.  None: they are refused.
+        if isinstance(stepper, str) and stepper != 'csda':
+            raise ValueError("stepper: a Stepper, None or 'csda'")
+        self.stepper = stepper               # ('csda': made below, once the detector is flattened)
+        self.particle_tracking = bool(particle_tracking)
+        self._tracked_media = None           # the LightMedia of the detector's materials, made on first use
+        self._particle_base = 0              # particles tracked so far: a particle's random stream is keyed by its global index
         self._light_source = None
         self._outside_row = -1
         self._segment_base = 0               # segments generated so far: a segment's random streams are keyed by its global index
@@ -78,6 +96,9 @@ class Simulation(object):
             from chroma_amd.gpu.geometry import pack_geometry
             packed = pack_geometry(detector)          # packed once, uploaded once per lane
         self.gpu_geometry = make(detector, packed=packed)
+        if isinstance(self.stepper, str):
+            from chroma_amd.generator.particles import Stepper, StoppingMedia
+            self.stepper = Stepper(StoppingMedia.from_geometry(detector))
         if hasattr(detector, 'num_channels'):
             self.gpu_daq = gpu.GPUDaq(self.gpu_geometry)
         self._gpu_event_daq = None           # the GPUEventDaq of simulate(run_daq=True), made on first use
@@ -242,7 +263,10 @@ class Simulation(object):
             raise ValueError('daq_digitizer needs daq_trigger')
         if daq_reducer is not None and daq_digitizer is None:
             raise ValueError('daq_reducer needs daq_digitizer')
+        tracked = False
         if isinstance(iterable, event.Photons):
+            first, iterable = iterable, [iterable]
+        elif isinstance(iterable, event.Vertex) and self.stepper is not None:
             first, iterable = iterable, [iterable]
         else:
             first, iterable = itertoolset.peek(iterable)
@@ -250,7 +274,12 @@ class Simulation(object):
             iterable = (event.Event(photons_beg=x) for x in iterable)
         elif isinstance(first, event.Event):
             if first.photons_beg is None and not self._has_steps(first):
-                raise NotImplementedError('events without photons need the GEANT4 generator, which is out of scope')
+                if self.stepper is None:
+                    raise NotImplementedError('events without photons need the GEANT4 generator, which is out of scope')
+                tracked = True
+        elif self.stepper is not None and self._is_vertices(first):
+            iterable = (event.Event(vertices=[x] if isinstance(x, event.Vertex) else list(x)) for x in iterable)
+            tracked = True
         else:
             raise NotImplementedError('Vertex input needs the GEANT4 generator, which is out of scope')
 
@@ -273,6 +302,9 @@ class Simulation(object):
         kwargs = dict(keep_photons_beg=keep_photons_beg, keep_photons_end=keep_photons_end, keep_hits=keep_hits,
                       keep_flat_hits=keep_flat_hits, run_daq=run_daq, max_steps=max_steps, daq_window=daq_window, daq_trigger=daq_trigger,
                       daq_noise=daq_noise, daq_digitizer=daq_digitizer, daq_reducer=daq_reducer, daq_keep_traces=daq_keep_traces)
+        if tracked:
+            yield from self._simulate_tracked(iterable, photons_per_batch, evid_start, kwargs)
+            return
         if isinstance(first, event.Event) and first.photons_beg is None:
             yield from self._simulate_stepped(iterable, photons_per_batch, evid_start, kwargs)
             return
@@ -386,6 +418,73 @@ class Simulation(object):
             cuts = 2 * np.cumsum([0] + [len(s) for _, s in batch])
             bounds = offsets[cuts].astype(np.int64)
             events = [ev for ev, _ in batch]
+            photons_beg = gpu_photons.get() if kwargs['keep_photons_beg'] else None
+            for ev, lo, hi in zip(events, bounds[:-1], bounds[1:]):
+                ev.nphotons = int(hi - lo)
+                if photons_beg is not None:
+                    ev.photons_beg = photons_beg[int(lo):int(hi)]
+            yield from self._simulate_batch(events, uploaded=(gpu_photons, bounds), **kwargs)
+
+    # ---- vertices that carry nothing: tracked on the device (Simulation(stepper=...)) ---------------------------------
+    @staticmethod
+    def _is_vertices(x):
+        return isinstance(x, event.Vertex) or (isinstance(x, (list, tuple)) and len(x) > 0 and all(isinstance(v, event.Vertex) for v in x))
+
+    def _simulate_tracked(self, iterable, photons_per_batch, evid_start, kwargs):
+        """Events whose vertices have neither photons nor steps.  A batch stays in device memory from its vertices to its hits:
+        the vertices are tracked through the geometry (chroma_amd.gpu.particles.track_segments; a particle with no triangle
+        ahead is in ``stepper.outside`` or, when that is -1, in the detector's ``detector_material`` if it is one of the
+        geometry's materials), the segments and the medium each was made in go to the light source (a LightMedia of the
+        detector's materials) where they are, and the photons are propagated where they are generated.  Particles and
+        segments are numbered on in iterable order from one simulate() call to the next, so nothing depends on the batching.
+
+        Batches are cut before anything is tracked, by ``Stepper.expected_photons_at_most``: every particle loses all its
+        kinetic energy at the smallest stopping power of its species, radiating at beta = 1 in the brightest medium all the
+        way.  That over-estimates, so a batch is closed early rather than late.  With ``particle_tracking=True`` the points
+        are read back and the events' vertices are copies that carry them as ``steps``."""
+        stepper = self.stepper
+        if self._tracked_media is None:
+            self._tracked_media = gpu.steps.LightMedia.from_geometry(self.detector)
+        media = self._tracked_media
+        outside = stepper.outside
+        if outside < 0:
+            material = getattr(self.detector, 'detector_material', None)
+            outside = stepper.media.index(material) if material is not None else -1
+        options_stepper = stepper if outside == stepper.outside else _with_outside(stepper, outside)
+
+        def batches():
+            expected, batch, evid = 0.0, [], evid_start
+            for ev in iterable:
+                if ev.photons_beg is not None or self._has_steps(ev):
+                    raise NotImplementedError('events to be tracked and events with photons or steps in one simulate() call')
+                ev.id = evid
+                evid += 1
+                expected += stepper.expected_photons_at_most(ev.vertices, media)
+                batch.append(ev)
+                if expected >= photons_per_batch:
+                    yield batch
+                    expected, batch = 0.0, []
+            if batch:
+                yield batch
+
+        for events in batches():
+            vertices = [v for ev in events for v in ev.vertices]
+            evidx = np.array([i for i, ev in enumerate(events) for _ in ev.vertices], dtype=np.uint32)
+            made = gpu.particles.track_segments(vertices, options_stepper, self.seed, gpu_geometry=self.gpu_geometry, ctx=self.context,
+                                                particle_base=self._particle_base, evidx=evidx, segment_base=self._segment_base,
+                                                return_tracks=self.particle_tracking)
+            segments = made[0] if self.particle_tracking else made
+            self._particle_base += len(vertices)
+            self._segment_base += len(segments)
+            gpu_photons, offsets = gpu.steps.generate_photons(segments, media, self.seed, ctx=self.context, return_offsets=True)
+            if self.particle_tracking:
+                stepped = iter(made[1])
+                for ev in events:
+                    ev.vertices = [next(stepped) for _ in ev.vertices]
+            # (segments, and so photons, are in event order: an event's bounds from its segments' -- their event indices and the
+            #  scanned counts are all that is read back, 12 bytes a segment)
+            cuts = np.searchsorted(segments.arrays['evidx'].get()[:len(segments)], np.arange(len(events) + 1))
+            bounds = offsets[2 * cuts].astype(np.int64)
             photons_beg = gpu_photons.get() if kwargs['keep_photons_beg'] else None
             for ev, lo, hi in zip(events, bounds[:-1], bounds[1:]):
                 ev.nphotons = int(hi - lo)

@@ -922,6 +922,111 @@ int chroma_steps_generate_media_host(const chroma_light_media_desc *desc, const 
                                      uint64_t seed, const uint32_t *offsets, const chroma_photon_arrays *photons,
                                      uint64_t capacity);
 
+/* ---- charged particles stepped through the detector (continuous slowing down) ----
+ * What makes the step points the calls above start from.  Units: MeV, mm, ns.  A particle loses the MEAN stopping power of the
+ * medium it is in (a table per medium and species, read by linear interpolation in log ke, the end nodes' values beyond them),
+ * in steps limited by `max_step`, by the fraction `max_loss` of its kinetic energy, and by the next volume boundary (the
+ * engine's own ray cast); at the end of a step its direction is scattered by the Highland formula.  No secondaries, no
+ * straggling, no lateral displacement: see DESIGN.md 3.8.
+ *
+ * Random streams: particle p = particle_base + its index draws from Philox stream word 0 of id 0x9A27000000000000 + p, from
+ * its own counter (rng_counter) on: a track does not depend on how particles are split over calls. */
+#define CHROMA_PARTICLE_SPECIES 6      /* the rows of a medium, by |pdg code|: e, mu, pi, K, p, alpha */
+#define CHROMA_PARTICLE_ALIVE     0u
+#define CHROMA_PARTICLE_STOPPED   1u   /* its kinetic energy fell below ke_cut: all of it deposited          */
+#define CHROMA_PARTICLE_LEFT      2u   /* in no medium of the table, or in vacuum with no triangle ahead      */
+#define CHROMA_PARTICLE_TRUNCATED 3u   /* max_steps steps made                                                */
+#define CHROMA_PARTICLE_UNTRACKED 4u   /* unknown or neutral species, or no kinetic energy: the vertex alone  */
+#define CHROMA_PARTICLE_NAN_ABORT 5u   /* a NaN in its position or direction                                  */
+
+typedef struct chroma_stopping_media_desc {
+    uint32_t nmedia, nke;
+    float ke_min, log_step;           /* node j: ke_min * exp(j * log_step) MeV                                   */
+    const float *stopping_power;      /* [nmedia][CHROMA_PARTICLE_SPECIES][nke] MeV/mm, finite and not negative   */
+    const float *radiation_length;    /* [nmedia] mm, above 0; +inf: no scattering (vacuum)                       */
+    const float *birks;               /* [nmedia] mm/MeV: qedep = edep / (1 + birks * S)                          */
+} chroma_stopping_media_desc;         /* HOST pointers */
+typedef struct chroma_stopping_media chroma_stopping_media;
+
+/* The table on the device of `ctx` (one block of chroma_malloc's pool); the desc's arrays are the caller's again on return. */
+int chroma_stopping_media_create(chroma_ctx *ctx, const chroma_stopping_media_desc *desc, chroma_stopping_media **media);
+/* Before chroma_shutdown of its context.  NULL: nothing. */
+int chroma_stopping_media_destroy(chroma_stopping_media *media);
+
+/* The particles of one call as arrays (DEVICE pointers for the device calls, host pointers for the _host calls); all are read
+ * and, but for species, z, mass and evidx, written.  A particle enters with status ALIVE and nsteps 0. */
+typedef struct chroma_particle_arrays {
+    float *pos, *dir;                 /* [n][3] mm; unit vector                                                   */
+    float *ke, *t;                    /* [n] kinetic energy MeV, time ns                                          */
+    int32_t *last_hit;                /* [n] the triangle the last step ended on (the next cast excludes it), -1  */
+    int32_t *species;                 /* [n] row 0 .. 5 of the medium's table; -1: unknown or neutral             */
+    float *z, *mass;                  /* [n] charge in e, mass in MeV                                             */
+    uint32_t *evidx;                  /* [n] event index handed to the segments                                   */
+    uint32_t *nsteps;                 /* [n] steps made: the particle has nsteps + 1 points                       */
+    uint32_t *rng_counter;            /* [n] draws taken from the particle's stream                               */
+    uint32_t *status;                 /* [n] CHROMA_PARTICLE_*                                                    */
+    uint64_t n;
+    uint64_t particle_base;           /* global index of particle 0                                               */
+} chroma_particle_arrays;
+
+typedef struct chroma_particle_options {
+    int32_t max_steps;                /* steps per particle, 1 .. 2^20                                            */
+    float max_step;                   /* mm                                                                       */
+    float max_loss;                   /* largest fraction of ke lost in one step, (0, 1]                          */
+    float ke_cut;                     /* MeV: a particle that would fall below deposits the rest and stops        */
+    int32_t scatter;                  /* 0: straight tracks                                                       */
+    int32_t outside;                  /* the medium row of a particle with no triangle ahead; -1: none            */
+} chroma_particle_options;
+
+/* Step points as columns: point 0 of a particle is its vertex (zero deposits, medium -1), point k the end of step k with the
+ * kinetic energy left, the step's deposit, its quenched deposit and the medium it was made in.  As a MATRIX of the calls
+ * below: point k of particle i is row k * n + i of n * (max_steps + 1) rows. */
+typedef struct chroma_particle_points {
+    float *pos, *t, *dir, *ke, *edep, *qedep;      /* [rows][3], [rows], [rows][3], [rows] ...  */
+    int32_t *medium;                               /* [rows]                                    */
+} chroma_particle_points;
+
+/* ONE iteration for every ALIVE particle i, given the nearest triangle along its direction (d_distance[i], d_triangle[i]: a
+ * triangle < 0 or a distance that is not finite means none; NULL arrays: none for all) and the medium row on the particle's
+ * side of it (d_medium[i]; NULL: options->outside for all).  A particle's first iteration writes its vertex as well.  Points
+ * go to the matrix `points`.  Queued on the context's stream. */
+int chroma_particles_advance(chroma_ctx *ctx, const chroma_stopping_media *media, const chroma_particle_arrays *particles,
+                             const chroma_particle_options *options, uint64_t seed, const float *d_distance,
+                             const int32_t *d_triangle, const int32_t *d_medium, const chroma_particle_points *points);
+int chroma_particles_advance_host(const chroma_stopping_media_desc *desc, const chroma_particle_arrays *particles,
+                                  const chroma_particle_options *options, uint64_t seed, const float *distance,
+                                  const int32_t *triangle, const int32_t *medium, const chroma_particle_points *points);
+
+/* Every particle to its end: per iteration the ray cast of chroma_intersect_mesh for the live particles (pos, dir, last_hit),
+ * the medium from the hit triangle's side by fill_state's rule on the particle's own direction (outer material when
+ * dot(normal, -dir) > 0, inner otherwise; no triangle: options->outside), one iteration as above, and the particles still
+ * ALIVE queued for the next.  `geom` NULL: no boundaries, every particle in row options->outside.  The points stay in the
+ * context's pooled scratch as a matrix until another call of the context uses it; chroma_particles_points /
+ * chroma_particles_segments, called next, read them, and `particles` has to live until then.  *total_points = the sum of
+ * nsteps + 1.  CHROMA_ERR_INVALID with a message when the matrix cannot be allocated.  Returns when the tracks are done. */
+int chroma_particles_track(chroma_ctx *ctx, chroma_geometry *geom, const chroma_stopping_media *media,
+                           const chroma_particle_arrays *particles, const chroma_particle_options *options, uint64_t seed,
+                           uint64_t *total_points);
+/* The loop with geom == NULL on the host, into the caller's matrix `points`. */
+int chroma_particles_track_host(const chroma_stopping_media_desc *desc, const chroma_particle_arrays *particles,
+                                const chroma_particle_options *options, uint64_t seed, const chroma_particle_points *points,
+                                uint64_t *total_points);
+
+/* The points of the last chroma_particles_track of `ctx` as flat arrays in particle order: d_offsets[n + 1] (uint32) gets the
+ * exclusive sum of the particles' point counts, the points of particle i are [d_offsets[i], d_offsets[i + 1]) of `out`.
+ * `capacity` below the total: CHROMA_ERR_INVALID and nothing is written.  Queued on the context's stream. */
+int chroma_particles_points(chroma_ctx *ctx, const chroma_particle_points *out, uint32_t *d_offsets, uint64_t capacity);
+/* ... and its sum of nsteps segments (points k -> k + 1 of one particle) in particle order, straight into the arrays of a
+ * chroma_step_segments (`out`: its eight arrays, written; n and segment_base are not read) and d_medium, for
+ * chroma_steps_count_media / chroma_steps_generate_media: beta = 0.5f * (beta_a + beta_b) of the two points' kinetic energies,
+ * qedep and medium those of point k + 1.  `capacity` below the total: CHROMA_ERR_INVALID and nothing is written. */
+int chroma_particles_segments(chroma_ctx *ctx, const chroma_step_segments *out, int32_t *d_medium, uint64_t capacity);
+/* The same from a host matrix (`particles`: nsteps, z, mass, evidx are read; `max_steps`: the matrix's). */
+int chroma_particles_points_host(const chroma_particle_arrays *particles, int32_t max_steps, const chroma_particle_points *matrix,
+                                 const chroma_particle_points *out, uint32_t *offsets, uint64_t capacity);
+int chroma_particles_segments_host(const chroma_particle_arrays *particles, int32_t max_steps, const chroma_particle_points *matrix,
+                                   const chroma_step_segments *out, int32_t *medium, uint64_t capacity);
+
 /* tools.argsort_direction (chroma/tools.py:175-193) and the reordering it serves, for a photon set on the device: the
  * photons are put in the order of a 32-bit Morton code of (theta, phi) of their directions (stable), every array of
  * the set gathered accordingly.  The reference's own benchmark does this to its photons before it starts the clock
