@@ -33,16 +33,29 @@
 #define QUAD_KEEP 7          // a triangle phase runs rounds until no ray with node work left holds more than this many (7: one round unless a ray holds 12+; -5 % against 0)
 #endif
 
+// Reductions inside a quad, two DPP steps each.  A step hands the value itself to update_dpp as the `old` operand with
+// bound_ctrl set (a quad permutation reads no invalid lane, so `old` is never taken): no zero to initialise, and the DPP
+// combiner may fold the move into its consumer -- v_<op>_dpp on the value.  It folds only a move with ONE consumer in the
+// move's own block, and two things took that away from the last step (profiles/r22/isa_quad_before.txt): the last max was
+// sunk below the stack push, into another block (the empty asm statement pins the reduced value where it is made), and the
+// last OR was merged with a mask that followed into a v_bitop3 while the OR stayed for its other readers (the caller now
+// takes that mask with a bit-field extract, see below).  Same value in every lane as the plain form.
+template <int QUAD_PERM>       // 0xB1: lanes [1,0,3,2] of the quad, 0x4E: lanes [2,3,0,1]
+__device__ inline uint32_t quad_xchg(uint32_t v)
+{
+    return (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, QUAD_PERM, 0xF, 0xF, true);
+}
 __device__ inline uint32_t quad_min_u32(uint32_t v)
 {
-    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, false));
-    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, false));
+    v = min(v, quad_xchg<0xB1>(v));
+    v = min(v, quad_xchg<0x4E>(v));
     return v;
 }
 __device__ inline uint32_t quad_max_u32(uint32_t v)
 {
-    v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, false));
-    v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, false));
+    v = max(v, quad_xchg<0xB1>(v));
+    v = max(v, quad_xchg<0x4E>(v));
+    asm volatile("" : "+v"(v));
     return v;
 }
 
@@ -82,8 +95,8 @@ __device__ inline void box_interval_signed(float ax, float ay, float az, uint32_
 }
 __device__ inline uint32_t quad_or_u32(uint32_t v)
 {
-    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, false);
-    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, false);
+    v |= quad_xchg<0xB1>(v);
+    v |= quad_xchg<0x4E>(v);
     return v;
 }
 
@@ -242,15 +255,23 @@ k_raycast_quad(GeoView g, const float4 *rays, int first_photon, StepState *st,
                 const bool pb = !(tb > fb) & !(tb > prune_t);
                 // (the photon's last hit is left out when its turn to be tested comes: one compare per triangle
                 //  round instead of two per visit)
-                const bool fa_leaf = (int)ea.w < 0, fb_leaf = (int)eb.w < 0;
+                // (the flag compared into a wave mask and read back per lane: `pa & !fa_leaf` is then a scalar and-not of two
+                //  masks.  Written as a plain bool, the negation is folded into a second v_cmp of the same word: a mask
+                //  computed twice, on the vector unit.  Predicate 40: signed less than.)
+                const bool fa_leaf = __builtin_amdgcn_inverse_ballot_w64(__builtin_amdgcn_sicmp((int)ea.w, 0, 40)),
+                           fb_leaf = __builtin_amdgcn_inverse_ballot_w64(__builtin_amdgcn_sicmp((int)eb.w, 0, 40));
                 const bool la = pa & fa_leaf, lb = pb & fb_leaf;
                 const bool ia = pa & !fa_leaf, ib = pb & !fb_leaf;
                 const uint32_t qm = quad_or_u32((((ib ? 2u * jbit : 0u) | (ia ? jbit : 0u)) << 8) | (lb ? 2u * jbit : 0u) | (la ? jbit : 0u));
                 // postponed triangles: ring slots after the ones already there, lower lanes first
                 {
-                    uint32_t off = phead + (uint32_t)npend + __popc(qm & below2);
-                    if (la) pending[off & (QUAD_PENDING - 1u)] = ea.w & 0x7FFFFFFFu;
-                    if (lb) pending[(off + (la ? 1u : 0u)) & (QUAD_PENDING - 1u)] = eb.w & 0x7FFFFFFFu;
+                    // (the leaf word goes in as it is, flag and all: the round that takes it out compares it with the last
+                    //  hit's word directly and clears the flag once per lane, not twice per visit here)
+                    // (qm & below2 as a bit-field extract of the low 2j bits: an AND here is merged with quad_or_u32's last OR
+                    //  into one v_bitop3, which leaves that OR a second reader and its DPP move unfolded)
+                    const uint32_t sa = (phead + (uint32_t)npend + __popc(__builtin_amdgcn_ubfe(qm, 0u, 2u * j))) & (QUAD_PENDING - 1u);
+                    if (la) pending[sa] = ea.w;
+                    if (lb) pending[(sa + (la ? 1u : 0u)) & (QUAD_PENDING - 1u)] = eb.w;
                     npend += __popc(qm & 0xFFu);
                 }
                 cur = WIDE_NONE;
@@ -261,7 +282,10 @@ k_raycast_quad(GeoView g, const float4 *rays, int first_photon, StepState *st,
                     const uint32_t ka = ia ? ((__float_as_uint(ta) & ~7u) | (2u * j)) : 0xFFFFFFFFu;
                     const uint32_t kb = ib ? ((__float_as_uint(tb) & ~7u) | (2u * j + 1u)) : 0xFFFFFFFFu;
                     const uint32_t ne = quad_min_u32(min(ka, kb)) & 7u;          // entry number of the nearest
-                    const bool na = ia && ne == 2u * j, nb = ib && ne == 2u * j + 1u;
+                    // (wave masks again, predicate 32: equal -- `ia && !na` below is then scalar, not a v_cmp_ne beside the v_cmp_eq)
+                    const bool ea_near = __builtin_amdgcn_inverse_ballot_w64(__builtin_amdgcn_uicmp(ne, 2u * j, 32)),
+                               eb_near = __builtin_amdgcn_inverse_ballot_w64(__builtin_amdgcn_uicmp(ne, 2u * j + 1u, 32));
+                    const bool na = ia & ea_near, nb = ib & eb_near;
                     cur = quad_max_u32(na ? ea.w : (nb ? eb.w : 0u));
                     // every other inner child goes on the stack at its own slot
                     const bool qa = ia && !na, qb = ib && !nb;
@@ -303,7 +327,9 @@ k_raycast_quad(GeoView g, const float4 *rays, int first_photon, StepState *st,
 #endif
 
         // ---- leaf phase: up to 4 postponed triangles of a ray at once, one per lane
-        while (__any(npend > (active ? QUAD_KEEP : 0))) {
+        // (entered through an `if` and closed by `do ... while`: as a plain `while` loop it copied the five per-ray values it
+        //  carries at the head of every round, profiles/r22/isa_quad_before.txt)
+        if (__any(npend > (active ? QUAD_KEEP : 0))) do {
 #if QUAD_TIMING
             tq_rounds++; tq_tests += (unsigned)__popcll(__ballot(npend > 0 && (int)j < min(npend, 4)));
 #endif
@@ -314,9 +340,10 @@ k_raycast_quad(GeoView g, const float4 *rays, int first_photon, StepState *st,
                 const int take = min(npend, 4);
                 bool hit = false;
                 float distance = 0.0f;
-                uint32_t tri = 0, rank = 0xFFFFFFFFu;
-                if ((int)j < take) tri = pending[(phead + j) & (QUAD_PENDING - 1u)];
-                if ((int)j < take && (0x80000000u | tri) != last_hit_w) {
+                uint32_t tri_w = 0, rank = 0xFFFFFFFFu;          // (tri_w: the leaf word, flag set)
+                if ((int)j < take) tri_w = pending[(phead + j) & (QUAD_PENDING - 1u)];
+                const uint32_t tri = tri_w & 0x7FFFFFFFu;
+                if ((int)j < take && tri_w != last_hit_w) {
                     if (COUNT) cnt.tris++;
                     hit = intersect_triangle_edges((f32x2){ray_od[0], ray_od[1]}, (f32x2){ray_od[2], ray_od[3]}, (f32x2){ray_od[4], ray_od[5]},
                                                    g.tri_isect + 3 * (size_t)tri, distance, rank);
@@ -335,7 +362,7 @@ k_raycast_quad(GeoView g, const float4 *rays, int first_photon, StepState *st,
                 phead = (phead + (uint32_t)take) & (QUAD_PENDING - 1u);
                 npend -= take;
             }
-        }
+        } while (__any(npend > (active ? QUAD_KEEP : 0)));
 
 
 #if QUAD_TIMING
