@@ -129,6 +129,12 @@ class DaqReducer(Structure):
                 ('min_width', c_uint32), ('lead', c_uint32), ('lag', c_uint32), ('cfd', c_uint32)]
 
 
+class VertexSeeder(Structure):
+    """chroma_vertex_seeder"""
+    _fields_ = [('slowness', c_uint32), ('bin_ticks', c_uint32), ('nbins', c_uint32), ('nshape', c_uint32), ('step', c_uint32),
+                ('nlevels', c_uint32), ('shape', c_uint32 * 16)]
+
+
 class LightSource(Structure):
     """chroma_light_source (host pointers)"""
     _fields_ = [('refractive_index', c_void_p), ('scintillation_cdf', c_void_p), ('time_cdf', c_void_p),
@@ -263,6 +269,10 @@ SIGNATURES = {
                                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_uint64)]),
     'chroma_daq_reduce_host': (c_int32, [POINTER(DaqReducer), c_uint32, c_uint64, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_uint64)]),
+    'chroma_vertex_seed': (c_int32, [c_void_p, POINTER(VertexSeeder), c_uint32, c_void_p, c_uint32, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'chroma_vertex_seed_host': (c_int32, [POINTER(VertexSeeder), c_uint32, c_void_p, c_uint32, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'chroma_daq_convert': (c_int32, [c_void_p, c_uint32, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     'chroma_pdf_bin_hits': (c_int32, [c_void_p, c_uint32, c_int32, c_uint32, c_void_p, c_void_p, c_int32, c_float, c_float,
                                       c_int32, c_float, c_float, c_void_p, c_void_p]),

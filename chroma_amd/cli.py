@@ -67,6 +67,11 @@ def main(argv=None):
                     help='with --daq-digitize, also write the pulses found in the traces (trigger_found_*, trigger_trace_base): runs of MIN_WIDTH samples '
                          'THRESHOLD counts above the baseline (the digitiser\'s pedestal, or the mean of the first NBASELINE samples), integrated from LEAD '
                          'samples before to LAG behind, timed at the fraction CFD of the peak')
+    ap.add_argument('--daq-seed', default=None, metavar='SPEED_MM_PER_NS[,SPACING_MM[,LEVELS]]',
+                    help='with --daq-trigger, also write a seed vertex per firing (seed_pos in mm, seed_t0 in ns, seed_score, seed_outside): the '
+                         'position and time at which the time residuals of the firing pile up best for light at SPEED_MM_PER_NS, searched on a '
+                         'grid of SPACING_MM (default: the detector radius / 8) and refined on LEVELS shrinking lattices (default 6); from the '
+                         'found pulses with --daq-reduce, else from the truth-level hits of the gate')
     ap.add_argument('--daq-drop-traces', action='store_true', help='with --daq-reduce, do not read the traces back: trigger_adc is not written')
     ap.add_argument('--save-photons-beg', action='store_true', help='also write the initial photons of every event (bin/chroma-sim:51-53)')
     ap.add_argument('--save-photons-end', action='store_true', help='also write the final photons of every event (bin/chroma-sim:54-56)')
@@ -147,6 +152,17 @@ def main(argv=None):
             ap.error('--daq-reduce: %s' % e)
     elif args.daq_drop_traces:
         ap.error('--daq-drop-traces needs --daq-reduce')
+    daq_seeder = None
+    if args.daq_seed is not None:
+        if daq_trigger is None:
+            ap.error('--daq-seed needs --daq-trigger')
+        parts = args.daq_seed.split(',')
+        try:
+            daq_seeder = tuple([float(x) for x in parts[:2]] + [int(x) for x in parts[2:]])
+            if not 1 <= len(parts) <= 3 or not daq_seeder[0] > 0:
+                raise ValueError('a positive speed')
+        except ValueError:
+            ap.error('--daq-seed takes SPEED_MM_PER_NS[,SPACING_MM[,LEVELS]]')
     t0 = time.time()
     detector = load_geometry_from_string(args.detector, cache_dir=args.cache_dir)
     print('geometry: %d triangles, BVH %d nodes (%.1f s)' % (len(detector.mesh.triangles), len(detector.bvh.nodes), time.time() - t0))
@@ -167,7 +183,7 @@ def main(argv=None):
                            keep_hits=False, keep_flat_hits=hasattr(detector, 'num_channels'),
                            run_daq=args.run_daq, max_steps=args.max_steps, daq_window=daq_window, daq_trigger=daq_trigger,
                            daq_noise=args.daq_noise, daq_digitizer=daq_digitizer, daq_reducer=daq_reducer,
-                           daq_keep_traces=not args.daq_drop_traces):
+                           daq_keep_traces=not args.daq_drop_traces, daq_seeder=daq_seeder):
         key = 'ev%d' % ev.id
         nphotons += ev.nphotons
         if args.particle is not None:
@@ -226,6 +242,11 @@ def main(argv=None):
             out[key + '/trigger_hit_q'] = ev.triggers.hit_q
             out[key + '/trigger_hit_t'] = ev.triggers.hit_t_first
             out[key + '/pulse_trigger'] = ev.triggers.pulse_trigger
+            if ev.triggers.vertices is not None:
+                out[key + '/seed_pos'] = ev.triggers.vertices.pos
+                out[key + '/seed_t0'] = ev.triggers.vertices.t0
+                out[key + '/seed_score'] = ev.triggers.vertices.score
+                out[key + '/seed_outside'] = ev.triggers.vertices.outside
             if ev.triggers.traces is not None:
                 out[key + '/trigger_adc'] = ev.triggers.traces
             if ev.triggers.trace_flags is not None:

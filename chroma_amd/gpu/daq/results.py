@@ -222,9 +222,24 @@ class Triggers(object):
         self.hit_q = (hit_q_int.astype(np.float32) * np.float32(charge_unit)).astype(np.float32)          # as k_daq_convert
         self.pulse_trigger = pulse_trigger
         self.traces, self.trace_flags, self.digitizer = adc, trace_flags, digitizer          # (hits x samples, uint16; hits, uint32)
+        self.vertices = None          # (Simulation(daq_seeder=...): the ``chroma_amd.seed.SeedFits`` of the firings)
 
     def __len__(self):
         return len(self.bin)
+
+    def seed_rows(self, k, source='reco'):
+        """(channel, t, weight) of firing ``k`` as a vertex seed takes them: 'reco' -- ``reco(k)``'s channels, times and charges
+        (raises as ``reco`` does without a reducer); 'gate' -- the gate's channels, earliest times and photoelectrons."""
+        if source == 'reco':
+            return self.reco(k)[:3]
+        if source == 'gate':
+            channel, npe, _, t, _ = self.sparse(k)
+            return channel, t, npe
+        raise ValueError("source: 'reco' or 'gate'")
+
+    def seed(self, k, seeder, source='reco'):
+        """The ``SeedFits`` (one fit) of firing ``k`` under the ``chroma_amd.seed.VertexSeeder`` ``seeder``, on the host."""
+        return seeder.fit(*self.seed_rows(k, source))
 
     def adc(self, k):
         """(channel, traces) of firing ``k``: the channels read out, ascending, and their traces (len(channel) x (pre + post),
@@ -400,6 +415,20 @@ class EventTriggers(object):
             raise ValueError('these triggers hold no traces (daq_digitizer / digitizer=... with keep_traces, or digitize)')
         reducer = DaqReducer.of(reducer)
         return self.replace(found=dict(zip(FOUND_FIELDS, [reducer] + reduce_traces_host(self.adc, reducer))))
+
+    def seed(self, seeder, source='reco', gpu=None):
+        """The ``chroma_amd.seed.SeedFits`` of EVERY firing of the batch, in firing order, under the ``VertexSeeder`` ``seeder``, in ONE
+        call: on the host (``gpu`` None: chroma_vertex_seed_host) or on the device (``gpu``: a ``chroma_amd.gpu.seed.GPUVertexSeeder``
+        or a context) -- the same bits.  ``source`` as ``Triggers.seed_rows``.  The fits of event i are [offsets[i], offsets[i + 1])."""
+        if source == 'reco' and self.reducer is None:
+            raise ValueError('these triggers were not reduced (daq_reducer / reducer=... / reduce)')
+        rows = []
+        for i in range(self.nevents):
+            triggers = self.event(i)
+            rows.extend(triggers.seed_rows(k, source) for k in range(len(triggers)))
+        offsets = np.concatenate([[0], np.cumsum([len(r[0]) for r in rows], dtype=np.int64)]).astype(np.int64)
+        column = lambda j, kind: np.concatenate([np.asarray(r[j], dtype=kind) for r in rows]) if rows else np.zeros(0, dtype=kind)
+        return seeder.fit_many(offsets, column(0, np.int32), column(1, np.float64), column(2, np.float64), gpu=gpu)
 
     def __len__(self):
         return self.nevents

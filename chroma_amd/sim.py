@@ -32,7 +32,10 @@ def _with_outside(stepper, outside):
 class Simulation(object):
     def __init__(self, detector, seed=None, cuda_device=None, particle_tracking=False, photon_tracking=False,
                  geant4_processes=0, nthreads_per_block=64, max_blocks=1024, exact=False, prefetch=True, lanes=1,
-                 light_medium=None, stepper=None):
+                 light_medium=None, stepper=None, daq_seeder=None):
+        # ``daq_seeder``: what simulate(daq_trigger=...) takes for its ``daq_seeder`` when that is None
+        self.daq_seeder = daq_seeder
+        self._gpu_seeder = None              # the GPUVertexSeeder of the seeder simulate() saw last
         # ``light_medium``: the Material whose Cherenkov and scintillation light the steps of Events without photons emit
         # (simulate(); chroma_amd.gpu.steps.LightSource); None: the detector's ``detector_material``; 'located': every segment
         # emits the light of the material it lies in, found on the device in this geometry (chroma_amd.gpu.steps.locate_materials:
@@ -130,7 +133,8 @@ class Simulation(object):
 
     def _simulate_batch(self, batch_events, keep_photons_beg=False, keep_photons_end=False, keep_hits=True,
                         keep_flat_hits=True, run_daq=False, max_steps=100, verbose=False, uploaded=None, gpu_geometry=None,
-                        daq_window=None, daq_trigger=None, daq_noise=None, daq_digitizer=None, daq_reducer=None, daq_keep_traces=True):
+                        daq_window=None, daq_trigger=None, daq_noise=None, daq_digitizer=None, daq_reducer=None, daq_keep_traces=True,
+                        daq_seeder=None):
         """Propagate the photons of all ``batch_events`` in one go and split the results
         back per event (by evidx).  Yields the events.  ``uploaded``: what _upload_batch returned for them;
         ``gpu_geometry``: the geometry of the lane this batch runs on (default: the simulation's own)."""
@@ -187,6 +191,13 @@ class Simulation(object):
                                                                   noise=daq_noise, digitizer=daq_digitizer, reducer=daq_reducer,
                                                                   keep_traces=daq_keep_traces)
             self.gpu_daq.acquisition += len(batch_events)
+        vertices = None
+        if daq_seeder is not None and event_pulses is not None and event_pulses.triggers is not None:
+            # every firing of the batch in ONE device call, from what the electronics found where the traces were reduced
+            if self._gpu_seeder is None or self._gpu_seeder.seeder is not daq_seeder:
+                from chroma_amd.gpu.seed import GPUVertexSeeder
+                self._gpu_seeder = GPUVertexSeeder(self.context, daq_seeder)
+            vertices = event_pulses.triggers.seed(daq_seeder, source='reco' if daq_reducer is not None else 'gate', gpu=self._gpu_seeder)
         for i, (ev, lo, hi) in enumerate(zip(batch_events, bounds[:-1], bounds[1:])):
             if not keep_photons_beg:
                 ev.photons_beg = None
@@ -223,6 +234,8 @@ class Simulation(object):
                     ev.pulses = event_pulses.event(i)
                     if event_pulses.triggers is not None:
                         ev.triggers = event_pulses.triggers.event(i)
+                        if vertices is not None:
+                            ev.triggers.vertices = vertices[int(event_pulses.triggers.offsets[i]):int(event_pulses.triggers.offsets[i + 1])]
             elif hasattr(self, 'gpu_daq') and run_daq:
                 # (a detector without channels: one acquisition per event, as the reference, chroma/sim.py:128-137)
                 self.gpu_daq.begin_acquire()
@@ -233,7 +246,7 @@ class Simulation(object):
 
     def simulate(self, iterable, keep_photons_beg=False, keep_photons_end=False, keep_hits=True,
                  keep_flat_hits=True, run_daq=False, max_steps=1000, photons_per_batch=1000000, evid_start=0, daq_window=None,
-                 daq_trigger=None, daq_noise=None, daq_digitizer=None, daq_reducer=None, daq_keep_traces=True):
+                 daq_trigger=None, daq_noise=None, daq_digitizer=None, daq_reducer=None, daq_keep_traces=True, daq_seeder=None):
         """Simulate Photons objects (or Events that already carry ``photons_beg``); events are
         batched until ``photons_per_batch`` photons are collected (chroma/sim.py:141-186).
 
@@ -249,7 +262,11 @@ class Simulation(object):
         of the event's channels.  ``daq_reducer`` (with ``daq_digitizer``; a gpu.DaqReducer or (threshold[, lead, lag[, cfd[,
         nbaseline[, min_width]]]])): the traces are reduced on the device to the pulses found in them, with charge and
         constant-fraction time (``ev.triggers.found(k, channel)``, ``.reco(k)``, ``.reco_channels(k)``: an event.Channels of what was
-        reconstructed, for Likelihood.set_event); with ``daq_keep_traces=False`` the samples are not read back.
+        reconstructed, for Likelihood.set_event); with ``daq_keep_traces=False`` the samples are not read back.  ``daq_seeder`` (with
+        ``daq_trigger``; a chroma_amd.seed.VertexSeeder, or a speed in mm/ns or (speed[, spacing_mm[, levels]]) for one over the
+        detector's channels; None: the constructor's ``daq_seeder``, which is used only where there is a trigger): every event's
+        ``ev.triggers.vertices`` are the ``SeedFits`` of its firings -- a seed vertex and time per firing, fitted on the device for the
+        whole batch in one call, from ``reco(k)`` where there is a reducer and from the gate's truth-level hits otherwise.
 
         With ``Simulation(prefetch=True)`` (the default) the NEXT batch is taken from ``iterable`` and uploaded by a second
         thread while the current one propagates: the iterable is consumed one batch ahead of the events this generator
@@ -263,6 +280,10 @@ class Simulation(object):
             raise ValueError('daq_digitizer needs daq_trigger')
         if daq_reducer is not None and daq_digitizer is None:
             raise ValueError('daq_reducer needs daq_digitizer')
+        if daq_seeder is not None and daq_trigger is None:
+            raise ValueError('daq_seeder needs daq_trigger')
+        if daq_seeder is None and daq_trigger is not None:
+            daq_seeder = self.daq_seeder
         tracked = False
         if isinstance(iterable, event.Photons):
             first, iterable = iterable, [iterable]
@@ -299,9 +320,12 @@ class Simulation(object):
                 daq_digitizer = gpu.DaqDigitizer.of(daq_digitizer).check(daq_trigger)
             if daq_reducer is not None:
                 daq_reducer = gpu.DaqReducer.of(daq_reducer).check(daq_trigger.pre + daq_trigger.post)
+            if daq_seeder is not None:
+                from chroma_amd.seed import VertexSeeder
+                daq_seeder = VertexSeeder.of(daq_seeder, self.detector)
         kwargs = dict(keep_photons_beg=keep_photons_beg, keep_photons_end=keep_photons_end, keep_hits=keep_hits,
                       keep_flat_hits=keep_flat_hits, run_daq=run_daq, max_steps=max_steps, daq_window=daq_window, daq_trigger=daq_trigger,
-                      daq_noise=daq_noise, daq_digitizer=daq_digitizer, daq_reducer=daq_reducer, daq_keep_traces=daq_keep_traces)
+                      daq_noise=daq_noise, daq_digitizer=daq_digitizer, daq_reducer=daq_reducer, daq_keep_traces=daq_keep_traces, daq_seeder=daq_seeder)
         if tracked:
             yield from self._simulate_tracked(iterable, photons_per_batch, evid_start, kwargs)
             return

@@ -786,6 +786,78 @@ int chroma_daq_reduce_host(const chroma_daq_reducer *reducer, uint32_t G, uint64
 int chroma_daq_convert(chroma_ctx *ctx, uint32_t nchannels, float charge_unit, const uint32_t *d_earliest_time_int,
                        const uint32_t *d_channel_q_int, float *d_earliest_time, float *d_channel_q);
 
+/* ---- vertex seed: a time-residual fit over a lattice of positions --------------------------------------
+ * What turns the (channel, time, charge) rows of a firing into a position and a time to start a
+ * likelihood from: for a hypothesised position the hits' times less their straight-line times of flight
+ * pile up in one bin of a histogram when the position is right; the score of a position is the fullest
+ * stretch of that histogram under a short shape, and the search takes the best of a list of candidates and
+ * refines it on shrinking 5 x 5 x 5 lattices.  The reference has no counterpart; this is the definition.
+ * All quantities are integers -- positions in position units, times in ticks; what a unit and a tick are
+ * is the caller's business -- and all sums are of integers: their order does not show, and the host twin
+ * gives the same bits.
+ *
+ * Fit f holds the hits [offsets[f], offsets[f + 1]).  For fit f and a position x, hit i of the fit is
+ * placed so: a hit whose channel is not in [0, nchannels) is OUTSIDE.  Otherwise w_i = min(hit_weight,
+ * 255); D2 = the sum of the three squared coordinate differences between the channel's position and x
+ * (below 2^53); d_i = floor(sqrt(D2)); tof_i = (d_i * slowness + 32768) >> 16 in 64 bits; tau_i =
+ * hit_time - tof_i as int64.  If tau_i < tau0[f] the hit is OUTSIDE; otherwise b_i = (tau_i - tau0[f]) /
+ * bin_ticks, and b_i >= nbins is OUTSIDE.  H[b] is the sum of w_i over the hits with b_i = b, and H[b] = 0
+ * for b >= nbins.
+ *
+ * A[s] = the sum over j < K of shape[j] * H[s + j], s in [0, nbins); score(f, x) = the largest A[s] (it fits
+ * 32 bits: 255 * 65535 * 255 < 2^32) and bin(f, x) = the smallest s that attains it.  A fit without hits
+ * inside has score 0 and bin 0.
+ *
+ * Level 0: the candidate with the greatest score, the lowest index among equals: best_cand, and
+ * level_score[0] its score.  Levels l = 1 .. L: s_l = step >> (l - 1); the 125 points x = best + ((i - 2),
+ * (j - 2), (k - 2)) * s_l, i, j, k in 0 .. 4, m = i + 5 j + 25 k; the greatest score wins, a tie goes to the
+ * centre (m = 62) if it is among the tied points, else to the lowest m; level_score[l] is the winner's
+ * score.  The centre takes part, so level_score never decreases.  After level L: best_pos, best_score and
+ * best_bin are those of the final point and `outside` is the number of its OUTSIDE hits. */
+typedef struct chroma_vertex_seeder {   /* 88 bytes */
+    uint32_t slowness;    /* 1 .. 2^24: ticks per position unit, in 1/65536 */
+    uint32_t bin_ticks;   /* 1 .. 2^20 */
+    uint32_t nbins;       /* 1 .. 1024 */
+    uint32_t nshape;      /* K, 1 .. 16 */
+    uint32_t step;        /* 0 .. 2^21: lattice spacing of refinement level 1, position units */
+    uint32_t nlevels;     /* L, 0 .. 8 */
+    uint32_t shape[16];   /* each 0 .. 255; the largest of shape[0 .. K) is >= 1; entries from K on are ignored */
+} chroma_vertex_seeder;
+/* d_channel_pos (int32, 3 per channel), d_cand (int32, 3 per candidate: the level-0 candidates, shared by
+ * all fits), the hit arrays (d_hit_channel int32, d_hit_time int32 ticks, d_hit_weight uint32) and the
+ * outputs are DEVICE arrays; `offsets` (nfits + 1 words) and `tau0` (nfits) are HOST arrays.  Per fit:
+ * d_best_pos (int32, 3), d_best_score, d_best_bin, d_best_cand, d_outside (uint32) and d_level_score
+ * (uint32, L + 1 per fit).  d_scores (uint32, nfits * ncand: score(f, cand[c]) at f * ncand + c) may be
+ * NULL.
+ *
+ * The function is total: no content of the hit, channel or candidate arrays makes an access outside the
+ * arrays.  Refused, CHROMA_ERR_INVALID before a fit is launched and with nothing written: a seeder field
+ * outside its range; ncand of 0 or above 2^20; nchannels above (2^32 - 1) / 3 or nfits above 2^31 - 1
+ * (32-bit indices); a coordinate of d_channel_pos or d_cand beyond 2^23 in
+ * magnitude (the two device arrays are checked by a validation pass of their own, whose verdict is read
+ * back before the first fit is launched); offsets not starting at 0, descending, or with a fit of more
+ * than 65535 hits; nfits * ncand of 2^32 or more when d_scores is asked for; a NULL array that is needed
+ * (seeder always; the candidates, offsets, tau0 and the per-fit outputs when nfits; the channel positions
+ * when nchannels and nfits; the hit arrays when there are hits).  nfits == 0 is CHROMA_OK and writes
+ * nothing.
+ *
+ * Runs on the context's stream and returns when the outputs are written.  Scratch: the offsets, tau0, the
+ * level-0 maxima (a 64-bit word per fit) and the validation's verdict. */
+int chroma_vertex_seed(chroma_ctx *ctx, const chroma_vertex_seeder *seeder, uint32_t nchannels,
+                       const int32_t *d_channel_pos, uint32_t ncand, const int32_t *d_cand, uint32_t nfits,
+                       const uint32_t *offsets, const int32_t *tau0, const int32_t *d_hit_channel,
+                       const int32_t *d_hit_time, const uint32_t *d_hit_weight, int32_t *d_best_pos,
+                       uint32_t *d_best_score, uint32_t *d_best_bin, uint32_t *d_best_cand, uint32_t *d_outside,
+                       uint32_t *d_level_score, uint32_t *d_scores);
+/* The same on the host (no GPU, no context), plain loops over fit, position and hit on one thread: the same
+ * arguments on HOST arrays, the same refusals, the same bits. */
+int chroma_vertex_seed_host(const chroma_vertex_seeder *seeder, uint32_t nchannels, const int32_t *channel_pos,
+                            uint32_t ncand, const int32_t *cand, uint32_t nfits, const uint32_t *offsets,
+                            const int32_t *tau0, const int32_t *hit_channel, const int32_t *hit_time,
+                            const uint32_t *hit_weight, int32_t *best_pos, uint32_t *best_score,
+                            uint32_t *best_bin, uint32_t *best_cand, uint32_t *outside, uint32_t *level_score,
+                            uint32_t *scores);
+
 /* ---- PDFs and likelihood terms over DAQ output (chroma/cuda/pdf.cu) ------------------------
  * Every call reads the GPUChannels layout: `ndaq` copies of `nchannels` entries, copy i at
  * [i * stride, i * stride + nchannels) (stride >= nchannels).  An MC time >= 1e8 means "not hit".
