@@ -7,7 +7,7 @@ entry point raises immediately and says how to build it.
 import ctypes
 import os
 import sys
-from ctypes import (POINTER, Structure, c_char_p, c_double, c_float, c_int32, c_size_t, c_uint32,
+from ctypes import (POINTER, Structure, c_char_p, c_double, c_float, c_int32, c_size_t, c_uint8, c_uint32,
                     c_uint64, c_void_p)
 
 import numpy as np
@@ -133,6 +133,12 @@ class VertexSeeder(Structure):
     """chroma_vertex_seeder"""
     _fields_ = [('slowness', c_uint32), ('bin_ticks', c_uint32), ('nbins', c_uint32), ('nshape', c_uint32), ('step', c_uint32),
                 ('nlevels', c_uint32), ('shape', c_uint32 * 16)]
+
+
+class DirectionSeeder(Structure):
+    """chroma_direction_seeder"""
+    _fields_ = [('log2_ncos', c_uint32), ('step', c_uint32), ('nlevels', c_uint32), ('first', c_uint32), ('width', c_uint32),
+                ('profile', c_uint8 * 256)]
 
 
 class LightSource(Structure):
@@ -273,6 +279,12 @@ SIGNATURES = {
                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'chroma_vertex_seed_host': (c_int32, [POINTER(VertexSeeder), c_uint32, c_void_p, c_uint32, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'chroma_direction_seed': (c_int32, [c_void_p, POINTER(DirectionSeeder), POINTER(VertexSeeder), c_uint32, c_void_p, c_uint32, c_void_p, c_uint32, c_void_p,
+                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_void_p]),
+    'chroma_direction_seed_host': (c_int32, [POINTER(DirectionSeeder), POINTER(VertexSeeder), c_uint32, c_void_p, c_uint32, c_void_p, c_uint32, c_void_p,
+                                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                             c_void_p, c_void_p]),
     'chroma_daq_convert': (c_int32, [c_void_p, c_uint32, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     'chroma_pdf_bin_hits': (c_int32, [c_void_p, c_uint32, c_int32, c_uint32, c_void_p, c_void_p, c_int32, c_float, c_float,
                                       c_int32, c_float, c_float, c_void_p, c_void_p]),

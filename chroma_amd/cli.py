@@ -72,6 +72,11 @@ def main(argv=None):
                          'position and time at which the time residuals of the firing pile up best for light at SPEED_MM_PER_NS, searched on a '
                          'grid of SPACING_MM (default: the detector radius / 8) and refined on LEVELS shrinking lattices (default 6); from the '
                          'found pulses with --daq-reduce, else from the truth-level hits of the gate')
+    ap.add_argument('--daq-direction', default=None, metavar='COS_C[,SIGMA_COS[,FILL[,LEVELS]]]',
+                    help='with --daq-seed, also write a seed direction per firing (dir_dir, dir_score, dir_inside, dir_outside, dir_level_score): '
+                         'the axis about which the firing\'s hits, seen from the seed vertex, best fill a cone of cosine COS_C -- a Gaussian '
+                         'profile of SIGMA_COS (default 0.1), FILL (0 .. 1) of its peak inside the cone (default 0) -- searched on a grid of 864 '
+                         'directions and refined on LEVELS shrinking lattices (default 6)')
     ap.add_argument('--daq-drop-traces', action='store_true', help='with --daq-reduce, do not read the traces back: trigger_adc is not written')
     ap.add_argument('--save-photons-beg', action='store_true', help='also write the initial photons of every event (bin/chroma-sim:51-53)')
     ap.add_argument('--save-photons-end', action='store_true', help='also write the final photons of every event (bin/chroma-sim:54-56)')
@@ -163,6 +168,17 @@ def main(argv=None):
                 raise ValueError('a positive speed')
         except ValueError:
             ap.error('--daq-seed takes SPEED_MM_PER_NS[,SPACING_MM[,LEVELS]]')
+    daq_direction = None
+    if args.daq_direction is not None:
+        if daq_seeder is None:
+            ap.error('--daq-direction needs --daq-seed')
+        parts = args.daq_direction.split(',')
+        try:
+            daq_direction = tuple([float(x) for x in parts[:3]] + [int(x) for x in parts[3:]])
+            if not 1 <= len(parts) <= 4 or not -1.0 <= daq_direction[0] <= 1.0:
+                raise ValueError('a cosine')
+        except ValueError:
+            ap.error('--daq-direction takes COS_C[,SIGMA_COS[,FILL[,LEVELS]]]')
     t0 = time.time()
     detector = load_geometry_from_string(args.detector, cache_dir=args.cache_dir)
     print('geometry: %d triangles, BVH %d nodes (%.1f s)' % (len(detector.mesh.triangles), len(detector.bvh.nodes), time.time() - t0))
@@ -183,7 +199,7 @@ def main(argv=None):
                            keep_hits=False, keep_flat_hits=hasattr(detector, 'num_channels'),
                            run_daq=args.run_daq, max_steps=args.max_steps, daq_window=daq_window, daq_trigger=daq_trigger,
                            daq_noise=args.daq_noise, daq_digitizer=daq_digitizer, daq_reducer=daq_reducer,
-                           daq_keep_traces=not args.daq_drop_traces, daq_seeder=daq_seeder):
+                           daq_keep_traces=not args.daq_drop_traces, daq_seeder=daq_seeder, daq_direction=daq_direction):
         key = 'ev%d' % ev.id
         nphotons += ev.nphotons
         if args.particle is not None:
@@ -247,6 +263,12 @@ def main(argv=None):
                 out[key + '/seed_t0'] = ev.triggers.vertices.t0
                 out[key + '/seed_score'] = ev.triggers.vertices.score
                 out[key + '/seed_outside'] = ev.triggers.vertices.outside
+            if ev.triggers.directions is not None:
+                out[key + '/dir_dir'] = ev.triggers.directions.dir
+                out[key + '/dir_score'] = ev.triggers.directions.score
+                out[key + '/dir_inside'] = ev.triggers.directions.inside
+                out[key + '/dir_outside'] = ev.triggers.directions.outside
+                out[key + '/dir_level_score'] = ev.triggers.directions.level_score
             if ev.triggers.traces is not None:
                 out[key + '/trigger_adc'] = ev.triggers.traces
             if ev.triggers.trace_flags is not None:

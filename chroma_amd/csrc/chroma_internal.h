@@ -59,8 +59,9 @@ struct CallState {
     // One pooled block that the multi-launch calls lay their arrays out on, each from the block's start (grow_call_scratch, Carver):
     // chroma_steps_* (the total, the source's tables, the counts, the scan's workspace), chroma_daq_acquire_events (the bounds),
     // chroma_daq_compact_events (the flags and their scan), the four pulse calls (PulsesBlock), chroma_daq_trigger_pulses (TriggerBlock)
-    // chroma_particles_track (ParticlesBlock: the matrix of step points, the queues, the live particles' rays and casts) and
-    // chroma_vertex_seed (SeedScratch: the offsets, tau0, the level-0 maxima)
+    // chroma_particles_track (ParticlesBlock: the matrix of step points, the queues, the live particles' rays and casts),
+    // chroma_vertex_seed (SeedScratch: the offsets, tau0, the level-0 maxima) and chroma_direction_seed (DirScratch: the same and a
+    // record per hit)
     void *call_scratch = nullptr; size_t call_scratch_bytes = 0;
     // what the last chroma_particles_track left in that block for chroma_particles_points / _segments (steps_calls.hip): the block
     // it was laid on (another block since: the points are gone), the caller's particle arrays and the matrix's max_steps

@@ -20,6 +20,7 @@
 #pragma once
 
 #include "seed_common.h"
+#include "seed_wave.h"
 
 #define SEED_BLOCK 512
 #define SEED_WAVES (SEED_BLOCK / 64)
@@ -35,24 +36,6 @@ struct SeedLds {
     uint32_t weight[SEED_CHUNK];
     uint32_t shape[16];
 };
-
-// what orders a wave's own LDS traffic: its clears before its adds before its reads, across lanes
-__device__ __forceinline__ void seed_wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
-__device__ __forceinline__ uint64_t seed_wave_max(uint64_t k)
-{
-    for (int d = 32; d; d >>= 1) {
-        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)k, d), hi = (uint32_t)__shfl_xor((int)(uint32_t)(k >> 32), d);
-        const uint64_t o = ((uint64_t)hi << 32) | lo;
-        k = o > k ? o : k;
-    }
-    return k;
-}
-__device__ __forceinline__ uint32_t seed_wave_sum(uint32_t x) { for (int d = 32; d; d >>= 1) x += (uint32_t)__shfl_xor((int)x, d); return x; }
 
 __device__ __forceinline__ void seed_load_shape(const chroma_vertex_seeder &p, SeedLds &lds)
 {

@@ -64,7 +64,8 @@ SEED_FN void lattice(uint32_t m, uint32_t s, int32_t bx, int32_t by, int32_t bz,
     *y = by + ((int32_t)(m / 5u % 5u) - 2) * (int32_t)s;
     *z = bz + ((int32_t)(m / 25u) - 2) * (int32_t)s;
 }
-SEED_FN uint32_t level_spacing(const chroma_vertex_seeder &p, uint32_t level) { return p.step >> (level - 1u); }
+// (of a chroma_vertex_seeder, or of a chroma_direction_seeder: dirseed_common.h)
+template <class Seeder> SEED_FN uint32_t level_spacing(const Seeder &p, uint32_t level) { return p.step >> (level - 1u); }
 
 SEED_FN bool coordinate_ok(int32_t c) { return c >= -MAX_COORD && c <= MAX_COORD; }
 

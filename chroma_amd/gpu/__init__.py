@@ -11,4 +11,4 @@ from chroma_amd.gpu.funcs import get_cu_module, GPUFuncs
 from chroma_amd.gpu.render import GPURays, GPUHybridRender
 from chroma_amd.gpu import steps
 from chroma_amd.gpu import particles
-from chroma_amd.gpu.seed import GPUVertexSeeder
+from chroma_amd.gpu.seed import GPUVertexSeeder, GPUDirectionSeeder

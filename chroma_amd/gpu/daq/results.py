@@ -223,6 +223,7 @@ class Triggers(object):
         self.pulse_trigger = pulse_trigger
         self.traces, self.trace_flags, self.digitizer = adc, trace_flags, digitizer          # (hits x samples, uint16; hits, uint32)
         self.vertices = None          # (Simulation(daq_seeder=...): the ``chroma_amd.seed.SeedFits`` of the firings)
+        self.directions = None        # (Simulation(daq_direction=...): the ``chroma_amd.seed.DirFits`` of the firings)
 
     def __len__(self):
         return len(self.bin)
@@ -240,6 +241,11 @@ class Triggers(object):
     def seed(self, k, seeder, source='reco'):
         """The ``SeedFits`` (one fit) of firing ``k`` under the ``chroma_amd.seed.VertexSeeder`` ``seeder``, on the host."""
         return seeder.fit(*self.seed_rows(k, source))
+
+    def direction(self, k, seeder, vertex, source='reco'):
+        """The ``DirFits`` (one fit) of firing ``k`` under the ``chroma_amd.seed.DirectionSeeder`` ``seeder`` about ``vertex`` (the
+        firing's ``SeedFits``: ``seed(k, ...)``, or ``vertices[k:k + 1]``), on the host."""
+        return seeder.fit(vertex, *self.seed_rows(k, source))
 
     def adc(self, k):
         """(channel, traces) of firing ``k``: the channels read out, ascending, and their traces (len(channel) x (pre + post),
@@ -420,6 +426,10 @@ class EventTriggers(object):
         """The ``chroma_amd.seed.SeedFits`` of EVERY firing of the batch, in firing order, under the ``VertexSeeder`` ``seeder``, in ONE
         call: on the host (``gpu`` None: chroma_vertex_seed_host) or on the device (``gpu``: a ``chroma_amd.gpu.seed.GPUVertexSeeder``
         or a context) -- the same bits.  ``source`` as ``Triggers.seed_rows``.  The fits of event i are [offsets[i], offsets[i + 1])."""
+        return seeder.fit_many(*self.seed_rows(source), gpu=gpu)
+
+    def seed_rows(self, source='reco'):
+        """(offsets, channel, t, weight) of EVERY firing of the batch, in firing order, as ``fit_many`` takes them."""
         if source == 'reco' and self.reducer is None:
             raise ValueError('these triggers were not reduced (daq_reducer / reducer=... / reduce)')
         rows = []
@@ -428,7 +438,13 @@ class EventTriggers(object):
             rows.extend(triggers.seed_rows(k, source) for k in range(len(triggers)))
         offsets = np.concatenate([[0], np.cumsum([len(r[0]) for r in rows], dtype=np.int64)]).astype(np.int64)
         column = lambda j, kind: np.concatenate([np.asarray(r[j], dtype=kind) for r in rows]) if rows else np.zeros(0, dtype=kind)
-        return seeder.fit_many(offsets, column(0, np.int32), column(1, np.float64), column(2, np.float64), gpu=gpu)
+        return offsets, column(0, np.int32), column(1, np.float64), column(2, np.float64)
+
+    def direction(self, seeder, vertices, source='reco', gpu=None):
+        """The ``chroma_amd.seed.DirFits`` of EVERY firing of the batch, in firing order, under the ``DirectionSeeder`` ``seeder`` about
+        ``vertices`` (the ``SeedFits`` of ``seed(...)`` with the same source), in ONE call: on the host (``gpu`` None:
+        chroma_direction_seed_host) or on the device (a ``chroma_amd.gpu.seed.GPUDirectionSeeder`` or a context) -- the same bits."""
+        return seeder.fit_many(vertices, *self.seed_rows(source), gpu=gpu)
 
     def __len__(self):
         return self.nevents

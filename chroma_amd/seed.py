@@ -2,7 +2,10 @@
 include/chroma_hip.h, "vertex seed").  ``VertexSeeder`` turns channel positions, a speed of light and (channel, time, weight)
 rows into the integers of chroma_vertex_seed_host / chroma_vertex_seed and the integers that come back into mm and ns.  It is a
 SEED: one straight-line speed, no scattering, no direction -- what a likelihood starts from, not what it ends at.  No GPU is
-needed here; ``chroma_amd.gpu.seed.GPUVertexSeeder`` runs the same fits on the device."""
+needed here; ``chroma_amd.gpu.seed.GPUVertexSeeder`` runs the same fits on the device.
+
+``DirectionSeeder`` adds the direction about such a vertex ("direction seed" in the same header: a cone fit, chroma_direction_seed_host
+/ chroma_direction_seed, ``chroma_amd.gpu.seed.GPUDirectionSeeder``), and ``to_vertices`` makes ``event.Vertex`` of the two."""
 import ctypes
 import math
 
@@ -234,3 +237,201 @@ class VertexSeeder(object):
     def fit(self, channel, t_ns, weight=None, gpu=None, scores=False):
         """``fit_many`` of one fit."""
         return self.fit_many([0, len(np.asarray(channel).reshape(-1))], channel, t_ns, weight, gpu=gpu, scores=scores)
+
+
+# ---- the direction seed (include/chroma_hip.h, "direction seed") ----
+ONE, MAX_COMPONENT, MAX_DIR_STEP, MAX_FIRST, MAX_WIDTH = 2 ** 14, 2 ** 15, 2 ** 13, 1040, 2048
+
+
+class DirFits(object):
+    """The fits of one ``DirectionSeeder.fit_many``: ``dir`` (n x 3 float64 unit vectors; zeros where the fit has none), ``dir_int``
+    (n x 3 int32, Q14), ``score``, ``cand`` (the level-0 candidate), ``level_score`` (n x (levels + 1)), ``inside`` (the summed
+    weight of the hits that took part: an energy proxy), ``outside`` (hits that did not), ``nhits`` (uint32) and, when asked for,
+    ``cos_hist`` (n x 2^log2_ncos, uint32: the weight per bin of the cosine to ``dir``)."""
+
+    NAMES = ('dir', 'dir_int', 'score', 'cand', 'level_score', 'inside', 'outside', 'nhits')
+
+    def __init__(self, dir, dir_int, score, cand, level_score, inside, outside, nhits, cos_hist=None):
+        self.dir, self.dir_int, self.score, self.cand, self.level_score = dir, dir_int, score, cand, level_score
+        self.inside, self.outside, self.nhits, self.cos_hist = inside, outside, nhits, cos_hist
+
+    def __len__(self):
+        return len(self.score)
+
+    def __getitem__(self, key):
+        """The fits ``key`` (a slice) as a ``DirFits`` of their own."""
+        if not isinstance(key, slice):
+            raise TypeError('DirFits takes slices')
+        return DirFits(*[getattr(self, n)[key] for n in self.NAMES], cos_hist=None if self.cos_hist is None else self.cos_hist[key])
+
+
+class PreparedDirFits(object):
+    """What one call takes (``DirectionSeeder.prepare``): the ``_lib.DirectionSeeder`` struct, ``timing`` (the vertex seeder's struct of
+    the same rows), ``offsets``, ``tau0``, ``vertex`` (int32, fits x 3), ``bin`` (uint32) and the hit arrays; ``time`` is None
+    where no prompt cut is made."""
+
+    def __init__(self, struct, timing, offsets, tau0, vertex, bin, channel, time, weight):
+        self.struct, self.timing, self.offsets, self.tau0, self.vertex, self.bin = struct, timing, offsets, tau0, vertex, bin
+        self.channel, self.time, self.weight = channel, time, weight
+        self.nfits = len(offsets) - 1
+
+
+class DirectionSeeder(object):
+    """The direction a ``VertexSeeder``'s fits lack: ``vertex_seeder`` lends its units, timing, weights and channel positions;
+    ``profile`` up to 2^``log2_ncos`` integers 0 .. 255 over the cosine between a hit (seen from the vertex) and the direction, bin k
+    covering [k, k + 1) * 2 / 2^log2_ncos - 1 (default: ``cherenkov_profile(0.75, 0.1)``); ``directions`` the level-0 candidates (default:
+    a cube-sphere grid of 6 * ``grid``^2); ``levels`` refinement levels, the first on a lattice of half the grid's angular spacing;
+    ``prompt_ns``: None -- every hit with a channel takes part -- or (before, after): only hits whose time residual about the
+    vertex lies within that window about the seed's t0."""
+
+    def __init__(self, vertex_seeder, profile=None, log2_ncos=6, directions=None, grid=12, levels=6, prompt_ns=None):
+        if not 4 <= int(log2_ncos) <= 8:
+            raise ValueError('log2_ncos is 4 .. 8')
+        if not 0 <= int(levels) <= MAX_LEVELS:
+            raise ValueError('0 .. %d levels' % MAX_LEVELS)
+        if not int(grid) >= 1:
+            raise ValueError('the grid has 1 cell a face edge at the least')
+        self.vertex_seeder, self.log2_ncos, self.levels, self.grid = vertex_seeder, int(log2_ncos), int(levels), int(grid)
+        profile = self.cherenkov_profile(0.75, 0.1, log2_ncos=self.log2_ncos) if profile is None else profile
+        self.profile = np.asarray(profile, dtype=np.int64).reshape(-1)
+        if len(self.profile) != 2 ** self.log2_ncos or self.profile.min() < 0 or self.profile.max() > 255 or self.profile.max() < 1:
+            raise ValueError('the profile has 2^log2_ncos entries of 0 .. 255, one of them positive')
+        if directions is None:
+            directions = self.cube_sphere(self.grid)
+            spacing = 0.5 * math.pi / self.grid
+        else:
+            directions = np.asarray(directions, dtype=np.float64).reshape(-1, 3)
+            spacing = math.sqrt(4.0 * math.pi / max(1, len(directions)))
+        if not 1 <= len(directions) <= MAX_CAND:
+            raise ValueError('1 .. 2^20 candidate directions (%d)' % len(directions))
+        cand = _round_half_up(ONE * np.asarray(directions, dtype=np.float64))
+        if not np.all(np.abs(cand) <= MAX_COMPONENT):
+            raise ValueError('a candidate direction is longer than 2')
+        self.cand = np.ascontiguousarray(cand.astype(np.int32).reshape(-1, 3))
+        self.step = min(MAX_DIR_STEP, int(_round_half_up(0.5 * spacing * ONE)))
+        self.first, self.width = 0, 1
+        self.prompt = None
+        if prompt_ns is not None:
+            before, after = float(prompt_ns[0]), float(prompt_ns[1])
+            if not (before >= 0 and after >= 0):
+                raise ValueError('prompt_ns is (before, after), neither negative')
+            # bins about the one under the shape's first maximum, which lies `peak` bins behind the seed's bin
+            lo = vertex_seeder.peak - int(math.ceil(before / vertex_seeder.bin_ns))
+            hi = vertex_seeder.peak + int(math.ceil(after / vertex_seeder.bin_ns))
+            self.first = min(MAX_FIRST, max(0, lo))
+            self.width = min(MAX_WIDTH, max(1, hi - self.first + 1))
+            self.prompt = (before, after)
+
+    @staticmethod
+    def cube_sphere(grid):
+        """6 * grid^2 unit vectors: the centres of an equal-angle grid on each face of the cube, face by face (+x, -x, +y, -y, +z, -z)."""
+        a = (np.arange(grid) + 0.5) / grid * (0.5 * math.pi) - 0.25 * math.pi
+        v, u = np.meshgrid(np.tan(a), np.tan(a), indexing='ij')          # (u runs fastest)
+        u, v, one = u.ravel(), v.ravel(), np.ones(grid * grid)
+        faces = [(one, u, v), (-one, u, v), (u, one, v), (u, -one, v), (u, v, one), (u, v, -one)]
+        d = np.concatenate([np.stack(f, axis=1) for f in faces])
+        return d / np.sqrt((d ** 2).sum(axis=1))[:, None]
+
+    @staticmethod
+    def cherenkov_profile(cos_c, sigma_cos, fill=0.0, log2_ncos=6):
+        """2^log2_ncos integers 0 .. 255: a Gaussian of ``sigma_cos`` about ``cos_c`` sampled at the bins' centres, 255 at its
+        highest entry, and ``fill`` (0 .. 1 of that) at the least inside the cone, in the bins centred above ``cos_c``."""
+        n = 2 ** int(log2_ncos)
+        centres = [(k + 0.5) * 2.0 / n - 1.0 for k in range(n)]
+        values = [math.exp(-0.5 * ((c - cos_c) / sigma_cos) ** 2) if sigma_cos > 0 else 0.0 for c in centres]
+        top = max(values)
+        if top > 0:
+            values = [v / top for v in values]
+        else:          # (a width of 0, or a peak out of every centre's reach: the bin that holds cos_c)
+            values[min(n - 1, max(0, int(math.floor((cos_c + 1.0) * n / 2.0))))] = 1.0
+        values = [max(v, float(fill)) if c > cos_c else v for c, v in zip(centres, values)]
+        return [int(math.floor(255.0 * min(v, 1.0) + 0.5)) for v in values]
+
+    @classmethod
+    def of(cls, value, vertex_seeder):
+        """``value`` if it is a ``DirectionSeeder`` (of ``vertex_seeder``); else the one of ``vertex_seeder`` for a cos_c or a (cos_c[,
+        sigma_cos[, fill[, levels]]])."""
+        if isinstance(value, cls):
+            if value.vertex_seeder is not vertex_seeder:
+                raise ValueError('the DirectionSeeder was made for another VertexSeeder')
+            return value
+        parts = list(value) if isinstance(value, (tuple, list)) else [value]
+        if not 1 <= len(parts) <= 4:
+            raise ValueError('a direction seeder: a DirectionSeeder, a cos_c or (cos_c[, sigma_cos[, fill[, levels]]])')
+        sigma = float(parts[1]) if len(parts) > 1 else 0.1
+        fill = float(parts[2]) if len(parts) > 2 else 0.0
+        kw = {'levels': int(parts[3])} if len(parts) > 3 else {}
+        return cls(vertex_seeder, profile=cls.cherenkov_profile(float(parts[0]), sigma, fill), **kw)
+
+    def struct(self):
+        s = _lib.DirectionSeeder(self.log2_ncos, self.step, self.levels, self.first, self.width)
+        for k, v in enumerate(self.profile):
+            s.profile[k] = int(v)
+        return s
+
+    def prepare(self, seed_fits, offsets, channel, t_ns=None, weight=None, prepared=None):
+        """The integers of one call about ``seed_fits`` (a ``SeedFits`` of the same rows: its ``pos_int`` and ``bin``).  The rows are
+        quantised by the vertex seeder's own ``prepare`` (``prepared``: what it returned for them, if at hand), so ticks, tau0 and
+        bins mean what they meant to the vertex seed; without ``prompt_ns`` no times are passed."""
+        v = self.vertex_seeder
+        if prepared is None:
+            n = len(np.asarray(channel).reshape(-1))
+            if self.prompt is not None and t_ns is None:
+                raise ValueError('a prompt cut needs the hit times')
+            prepared = v.prepare(offsets, channel, np.zeros(n) if t_ns is None else t_ns, weight)
+        if len(seed_fits) != prepared.nfits:
+            raise ValueError('%d fits by the offsets, %d seed fits' % (prepared.nfits, len(seed_fits)))
+        timed = self.prompt is not None
+        return PreparedDirFits(self.struct(), prepared.struct, prepared.offsets, prepared.tau0, np.ascontiguousarray(seed_fits.pos_int, dtype=np.int32).reshape(-1, 3),
+                               np.ascontiguousarray(seed_fits.bin, dtype=np.uint32), prepared.channel, prepared.time if timed else None, prepared.weight)
+
+    def outputs(self, nfits, cos_hist):
+        """zeroed host arrays in the order of the calls' output arguments"""
+        return [np.zeros((nfits, 3), dtype=np.int32)] + [np.zeros(nfits, dtype=np.uint32) for _ in range(4)] + \
+               [np.zeros((nfits, self.levels + 1), dtype=np.uint32), np.zeros((nfits, 2 ** self.log2_ncos), dtype=np.uint32) if cos_hist else None]
+
+    def run_host(self, prepared, cos_hist=False):
+        """chroma_direction_seed_host on ``prepared``: (best_dir, best_score, best_cand, inside, outside, level_score, cos_hist or None)."""
+        lib = _lib.load()
+        v = self.vertex_seeder
+        out = self.outputs(prepared.nfits, cos_hist)
+        _lib.check(lib.chroma_direction_seed_host(ctypes.byref(prepared.struct), ctypes.byref(prepared.timing), v.nchannels, _lib.ptr(v.channel_pos), len(self.cand),
+                                                  _lib.ptr(self.cand), prepared.nfits, _lib.ptr(prepared.offsets), _lib.ptr(prepared.tau0), _lib.ptr(prepared.vertex),
+                                                  _lib.ptr(prepared.bin), _lib.ptr(prepared.channel), _lib.ptr(prepared.time), _lib.ptr(prepared.weight),
+                                                  *[_lib.ptr(a) for a in out]))
+        return out
+
+    def finish(self, prepared, out):
+        """The ``DirFits`` of a call's output arrays."""
+        best_dir, best_score, best_cand, inside, outside, level_score, cos_hist = out
+        length = np.sqrt((best_dir.astype(np.float64) ** 2).sum(axis=1))
+        unit = best_dir.astype(np.float64) / np.where(length > 0, length, 1.0)[:, None]
+        return DirFits(unit, best_dir, best_score, best_cand, level_score, inside, outside, np.diff(prepared.offsets.astype(np.int64)).astype(np.uint32), cos_hist)
+
+    def fit_many(self, seed_fits, offsets, channel, t_ns=None, weight=None, gpu=None, cos_hist=False):
+        """The ``DirFits`` of the fits [offsets[f], offsets[f + 1]) of the hit rows about ``seed_fits``, in ONE call: on the host
+        (``gpu`` None: chroma_direction_seed_host) or on the device (``gpu``: a ``chroma_amd.gpu.seed.GPUDirectionSeeder`` of this
+        seeder, or a context to make one on) -- the same bits."""
+        prepared = self.prepare(seed_fits, offsets, channel, t_ns, weight)
+        if gpu is None:
+            return self.finish(prepared, self.run_host(prepared, cos_hist))
+        from chroma_amd.gpu.seed import GPUDirectionSeeder
+        runner = gpu if isinstance(gpu, GPUDirectionSeeder) else GPUDirectionSeeder(gpu, self)
+        if runner.seeder is not self:
+            raise ValueError('the GPUDirectionSeeder was made for another seeder')
+        return self.finish(prepared, runner.run(prepared, cos_hist))
+
+    def fit(self, seed_fits, channel, t_ns=None, weight=None, gpu=None, cos_hist=False):
+        """``fit_many`` of one fit."""
+        return self.fit_many(seed_fits, [0, len(np.asarray(channel).reshape(-1))], channel, t_ns, weight, gpu=gpu, cos_hist=cos_hist)
+
+
+def to_vertices(seed_fits, dir_fits, particle_name, ke):
+    """The ``event.Vertex`` list a likelihood or the stepper starts from: fit k's seed position (mm) and time (ns), its seeded
+    direction, and the caller's particle and kinetic energy (one for all, or one per fit) -- the seeds give no energy."""
+    from chroma_amd import event
+    if len(seed_fits) != len(dir_fits):
+        raise ValueError('%d seed fits, %d direction fits' % (len(seed_fits), len(dir_fits)))
+    energies = np.broadcast_to(np.asarray(ke, dtype=np.float64), (len(seed_fits),))
+    return [event.Vertex(particle_name, np.array(seed_fits.pos[k], dtype=np.float64), np.array(dir_fits.dir[k], dtype=np.float64), float(energies[k]),
+                         t0=float(seed_fits.t0[k])) for k in range(len(seed_fits))]

@@ -32,10 +32,16 @@ def _with_outside(stepper, outside):
 class Simulation(object):
     def __init__(self, detector, seed=None, cuda_device=None, particle_tracking=False, photon_tracking=False,
                  geant4_processes=0, nthreads_per_block=64, max_blocks=1024, exact=False, prefetch=True, lanes=1,
-                 light_medium=None, stepper=None, daq_seeder=None):
+                 light_medium=None, stepper=None, daq_seeder=None, daq_direction=None):
         # ``daq_seeder``: what simulate(daq_trigger=...) takes for its ``daq_seeder`` when that is None
         self.daq_seeder = daq_seeder
         self._gpu_seeder = None              # the GPUVertexSeeder of the seeder simulate() saw last
+        # ``daq_direction``: likewise simulate()'s ``daq_direction`` (it needs a ``daq_seeder``, here or there)
+        if daq_direction is not None and daq_seeder is None:
+            raise ValueError('daq_direction needs daq_seeder')
+        self.daq_direction = daq_direction
+        self._direction_of = None            # (what simulate() was given, the DirectionSeeder made of it)
+        self._gpu_direction = None           # the GPUDirectionSeeder of the direction seeder simulate() saw last
         # ``light_medium``: the Material whose Cherenkov and scintillation light the steps of Events without photons emit
         # (simulate(); chroma_amd.gpu.steps.LightSource); None: the detector's ``detector_material``; 'located': every segment
         # emits the light of the material it lies in, found on the device in this geometry (chroma_amd.gpu.steps.locate_materials:
@@ -134,7 +140,7 @@ class Simulation(object):
     def _simulate_batch(self, batch_events, keep_photons_beg=False, keep_photons_end=False, keep_hits=True,
                         keep_flat_hits=True, run_daq=False, max_steps=100, verbose=False, uploaded=None, gpu_geometry=None,
                         daq_window=None, daq_trigger=None, daq_noise=None, daq_digitizer=None, daq_reducer=None, daq_keep_traces=True,
-                        daq_seeder=None):
+                        daq_seeder=None, daq_direction=None):
         """Propagate the photons of all ``batch_events`` in one go and split the results
         back per event (by evidx).  Yields the events.  ``uploaded``: what _upload_batch returned for them;
         ``gpu_geometry``: the geometry of the lane this batch runs on (default: the simulation's own)."""
@@ -191,13 +197,21 @@ class Simulation(object):
                                                                   noise=daq_noise, digitizer=daq_digitizer, reducer=daq_reducer,
                                                                   keep_traces=daq_keep_traces)
             self.gpu_daq.acquisition += len(batch_events)
-        vertices = None
+        vertices = directions = None
         if daq_seeder is not None and event_pulses is not None and event_pulses.triggers is not None:
             # every firing of the batch in ONE device call, from what the electronics found where the traces were reduced
             if self._gpu_seeder is None or self._gpu_seeder.seeder is not daq_seeder:
                 from chroma_amd.gpu.seed import GPUVertexSeeder
                 self._gpu_seeder = GPUVertexSeeder(self.context, daq_seeder)
-            vertices = event_pulses.triggers.seed(daq_seeder, source='reco' if daq_reducer is not None else 'gate', gpu=self._gpu_seeder)
+            source = 'reco' if daq_reducer is not None else 'gate'
+            if daq_direction is None:
+                vertices = event_pulses.triggers.seed(daq_seeder, source=source, gpu=self._gpu_seeder)
+            else:
+                # the direction about every seed in a second call, on the rows, positions and bins the first left on the device
+                if self._gpu_direction is None or self._gpu_direction.seeder is not daq_direction:
+                    from chroma_amd.gpu.seed import GPUDirectionSeeder
+                    self._gpu_direction = GPUDirectionSeeder(self.context, daq_direction, vertex=self._gpu_seeder)
+                vertices, directions = self._gpu_direction.fit_both(self._gpu_seeder, *event_pulses.triggers.seed_rows(source))
         for i, (ev, lo, hi) in enumerate(zip(batch_events, bounds[:-1], bounds[1:])):
             if not keep_photons_beg:
                 ev.photons_beg = None
@@ -236,6 +250,8 @@ class Simulation(object):
                         ev.triggers = event_pulses.triggers.event(i)
                         if vertices is not None:
                             ev.triggers.vertices = vertices[int(event_pulses.triggers.offsets[i]):int(event_pulses.triggers.offsets[i + 1])]
+                        if directions is not None:
+                            ev.triggers.directions = directions[int(event_pulses.triggers.offsets[i]):int(event_pulses.triggers.offsets[i + 1])]
             elif hasattr(self, 'gpu_daq') and run_daq:
                 # (a detector without channels: one acquisition per event, as the reference, chroma/sim.py:128-137)
                 self.gpu_daq.begin_acquire()
@@ -246,7 +262,8 @@ class Simulation(object):
 
     def simulate(self, iterable, keep_photons_beg=False, keep_photons_end=False, keep_hits=True,
                  keep_flat_hits=True, run_daq=False, max_steps=1000, photons_per_batch=1000000, evid_start=0, daq_window=None,
-                 daq_trigger=None, daq_noise=None, daq_digitizer=None, daq_reducer=None, daq_keep_traces=True, daq_seeder=None):
+                 daq_trigger=None, daq_noise=None, daq_digitizer=None, daq_reducer=None, daq_keep_traces=True, daq_seeder=None,
+                 daq_direction=None):
         """Simulate Photons objects (or Events that already carry ``photons_beg``); events are
         batched until ``photons_per_batch`` photons are collected (chroma/sim.py:141-186).
 
@@ -267,6 +284,10 @@ class Simulation(object):
         detector's channels; None: the constructor's ``daq_seeder``, which is used only where there is a trigger): every event's
         ``ev.triggers.vertices`` are the ``SeedFits`` of its firings -- a seed vertex and time per firing, fitted on the device for the
         whole batch in one call, from ``reco(k)`` where there is a reducer and from the gate's truth-level hits otherwise.
+        ``daq_direction`` (with ``daq_seeder``; a chroma_amd.seed.DirectionSeeder of that seeder, or a cos_c or (cos_c[, sigma_cos[,
+        fill[, levels]]]) for a Cherenkov profile; None: the constructor's, used only where there is a seeder): every event's
+        ``ev.triggers.directions`` are the ``DirFits`` of its firings about those seeds -- a cone fit per firing, in a second device
+        call on the same rows (``chroma_amd.seed.to_vertices`` makes event.Vertex of the two).
 
         With ``Simulation(prefetch=True)`` (the default) the NEXT batch is taken from ``iterable`` and uploaded by a second
         thread while the current one propagates: the iterable is consumed one batch ahead of the events this generator
@@ -284,6 +305,10 @@ class Simulation(object):
             raise ValueError('daq_seeder needs daq_trigger')
         if daq_seeder is None and daq_trigger is not None:
             daq_seeder = self.daq_seeder
+        if daq_direction is not None and daq_seeder is None:
+            raise ValueError('daq_direction needs daq_seeder')
+        if daq_direction is None and daq_seeder is not None:
+            daq_direction = self.daq_direction
         tracked = False
         if isinstance(iterable, event.Photons):
             first, iterable = iterable, [iterable]
@@ -323,9 +348,18 @@ class Simulation(object):
             if daq_seeder is not None:
                 from chroma_amd.seed import VertexSeeder
                 daq_seeder = VertexSeeder.of(daq_seeder, self.detector)
+                if daq_direction is not None:
+                    from chroma_amd.seed import DirectionSeeder
+                    given = daq_direction
+                    if self._direction_of is not None and self._direction_of[0] is given and self._direction_of[1].vertex_seeder is daq_seeder:
+                        daq_direction = self._direction_of[1]
+                    else:
+                        daq_direction = DirectionSeeder.of(given, daq_seeder)
+                        self._direction_of = (given, daq_direction)
         kwargs = dict(keep_photons_beg=keep_photons_beg, keep_photons_end=keep_photons_end, keep_hits=keep_hits,
                       keep_flat_hits=keep_flat_hits, run_daq=run_daq, max_steps=max_steps, daq_window=daq_window, daq_trigger=daq_trigger,
-                      daq_noise=daq_noise, daq_digitizer=daq_digitizer, daq_reducer=daq_reducer, daq_keep_traces=daq_keep_traces, daq_seeder=daq_seeder)
+                      daq_noise=daq_noise, daq_digitizer=daq_digitizer, daq_reducer=daq_reducer, daq_keep_traces=daq_keep_traces, daq_seeder=daq_seeder,
+                      daq_direction=daq_direction)
         if tracked:
             yield from self._simulate_tracked(iterable, photons_per_batch, evid_start, kwargs)
             return

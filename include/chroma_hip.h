@@ -858,6 +858,90 @@ int chroma_vertex_seed_host(const chroma_vertex_seeder *seeder, uint32_t nchanne
                             uint32_t *best_bin, uint32_t *best_cand, uint32_t *outside, uint32_t *level_score,
                             uint32_t *scores);
 
+/* ---- direction seed: a cone fit about the vertex --------------------------------------------------------
+ * What gives a seed vertex the direction it lacks: seen from the vertex, the hits of a Cherenkov ring lie
+ * at one angle to the particle's direction.  The score of a hypothesised direction is the sum over the
+ * hits of a profile of the cosine between the hit's direction from the vertex and the hypothesis; the
+ * search takes the best of a list of candidate directions and refines it on shrinking 5 x 5 x 5 lattices,
+ * every point renormalised.  The reference has no counterpart; this is the definition.  Everything that
+ * shows is an integer; sums are of integers, so their order does not show, and the host twin gives the
+ * same bits.  Positions are in the vertex seed's position units; a direction is an integer 3-vector, a
+ * UNIT direction has length about 2^14 (Q14), a cosine is an integer in [-16384, 16383].
+ *
+ * Fit f holds the hits [offsets[f], offsets[f + 1]) and is seen from its vertex v_f (int32 x 3).  A hit
+ * whose channel is not in [0, nchannels) is OUTSIDE.  Otherwise (dx, dy, dz) = the channel's position -
+ * v_f in 64 bits and d = floor(sqrt(dx^2 + dy^2 + dz^2)) (the vertex seed's); d == 0 is OUTSIDE (no
+ * direction).  Where hit times are given (d_hit_time != NULL): b = the vertex seed's bin of the hit with
+ * `timing`'s slowness, bin_ticks and nbins and tau0[f] (tof = (d * slowness + 32768) >> 16; tau = time -
+ * tof; tau < tau0[f] or (tau - tau0[f]) / bin_ticks >= nbins is OUTSIDE), and b < bin[f] + first or b >=
+ * bin[f] + first + width, compared in 64 bits, is OUTSIDE: the prompt-light cut about the seed's own
+ * best_bin.  Without times no cut is made.  Otherwise the hit is INSIDE with w = min(hit_weight, 255) and
+ * n = (trunc(dx * 16384 / d), trunc(dy * 16384 / d), trunc(dz * 16384 / d)), C's truncation toward zero:
+ * every component within +-16384.  inside[f] is the sum of w over the INSIDE hits (an energy proxy),
+ * outside[f] the number of OUTSIDE hits.
+ *
+ * A point a (int32 x 3, every component within +-2^15): L = floor(sqrt(a . a)); if L == 0 its unit vector
+ * is (0, 0, 0); otherwise u = (trunc(a_x * 16384 / L), ...), every component within +-16384.  A unit
+ * vector u of (0, 0, 0) scores 0.  Otherwise, per INSIDE hit, c = clamp((n . u) >> 14, -16384, 16383)
+ * (the shift arithmetic, the dot product in int32: 3 * 2^28 < 2^31), k = (c + 16384) >> (15 - m) for a
+ * profile of 2^m entries, and score(f, u) = the sum of w * profile[k] (it fits 32 bits: 65535 * 255 * 255
+ * < 2^32).
+ *
+ * Level 0: the candidate whose unit vector scores greatest, the lowest index among equals: best_cand;
+ * best_dir is its unit vector and level_score[0] its score.  Levels l = 1 .. L: s_l = step >> (l - 1);
+ * the 125 points best_dir + ((i - 2), (j - 2), (k - 2)) * s_l, m = i + 5 j + 25 k, each renormalised as
+ * above -- but the centre (m = 62), which is taken as it is, so level_score never decreases; the greatest
+ * score wins, a tie goes to the centre if it is among the tied points, else to the lowest m; best_dir
+ * becomes the winner's unit vector and level_score[l] its score.  After level L: best_dir, best_score (=
+ * level_score[L]), best_cand, level_score, inside, outside and, if asked for, cos_hist[f][k] = the sum of
+ * w over the INSIDE hits whose k about best_dir is k (2^m words per fit; about a best_dir of (0, 0, 0)
+ * every hit's c is 0): the ring's opening-angle distribution. */
+typedef struct chroma_direction_seeder {   /* 276 bytes */
+    uint32_t log2_ncos;    /* m, 4 .. 8: the profile has 2^m entries */
+    uint32_t step;         /* 0 .. 2^13: lattice spacing of refinement level 1, Q14 */
+    uint32_t nlevels;      /* L, 0 .. 8 */
+    uint32_t first;        /* 0 .. 1040: the prompt window begins `first` bins behind bin[f] ... */
+    uint32_t width;        /* 1 .. 2048: ... and has so many bins */
+    uint8_t  profile[256]; /* some entry among the first 2^m is >= 1; entries from 2^m on are ignored */
+} chroma_direction_seeder;
+/* d_channel_pos (int32, 3 per channel), d_cand (int32, 3 per candidate: the level-0 candidates, shared by
+ * all fits), d_vertex (int32, 3 per fit), d_bin (uint32, one per fit), the hit arrays and the outputs are
+ * DEVICE arrays -- a vertex seed's d_best_pos and d_best_bin can be passed as they lie; `offsets` (nfits +
+ * 1 words) and `tau0` (nfits) are HOST arrays.  `timing` is read only with times (d_hit_time != NULL),
+ * and of it only slowness, bin_ticks and nbins, with the vertex seed's ranges; d_bin and tau0 likewise are
+ * needed only with times.  Per fit: d_best_dir (int32, 3), d_best_score, d_best_cand, d_inside, d_outside
+ * (uint32), d_level_score (uint32, L + 1 per fit) and d_cos_hist (uint32, 2^m per fit; may be NULL).
+ *
+ * The function is total: no content of the hit, channel, vertex or bin arrays makes an access outside an
+ * array.  Refused, CHROMA_ERR_INVALID before anything is launched on the fits and with nothing written: a
+ * field of the seeder (or, with times, of `timing`) outside its range, a profile whose first 2^m entries
+ * are all 0; ncand of 0 or above 2^20; nchannels above (2^32 - 1) / 3 or nfits above 2^31 - 1; a
+ * candidate component beyond 2^15, a channel or vertex coordinate beyond 2^23 in magnitude (the device
+ * arrays are checked by a validation pass whose verdict is read back first); offsets not starting at 0,
+ * descending, or with a fit of more than 65535 hits; a NULL array that is needed (seeder always; the
+ * candidates, offsets, vertices and the per-fit outputs but d_cos_hist when nfits; the channel positions
+ * when nchannels and nfits; d_hit_channel and d_hit_weight when there are hits; timing, tau0 and d_bin with
+ * times).  nfits == 0 is CHROMA_OK and writes nothing.
+ *
+ * Runs on the context's stream and returns when the outputs are written.  Scratch: the offsets, tau0, the
+ * level-0 maxima (a 64-bit word per fit), the validation's verdict and an 8-byte record per hit. */
+int chroma_direction_seed(chroma_ctx *ctx, const chroma_direction_seeder *seeder, const chroma_vertex_seeder *timing,
+                          uint32_t nchannels, const int32_t *d_channel_pos, uint32_t ncand, const int32_t *d_cand,
+                          uint32_t nfits, const uint32_t *offsets, const int32_t *tau0, const int32_t *d_vertex,
+                          const uint32_t *d_bin, const int32_t *d_hit_channel, const int32_t *d_hit_time,
+                          const uint32_t *d_hit_weight, int32_t *d_best_dir, uint32_t *d_best_score,
+                          uint32_t *d_best_cand, uint32_t *d_inside, uint32_t *d_outside, uint32_t *d_level_score,
+                          uint32_t *d_cos_hist);
+/* The same on the host (no GPU, no context), plain loops on one thread: the same arguments on HOST arrays,
+ * the same refusals, the same bits. */
+int chroma_direction_seed_host(const chroma_direction_seeder *seeder, const chroma_vertex_seeder *timing,
+                               uint32_t nchannels, const int32_t *channel_pos, uint32_t ncand, const int32_t *cand,
+                               uint32_t nfits, const uint32_t *offsets, const int32_t *tau0, const int32_t *vertex,
+                               const uint32_t *bin, const int32_t *hit_channel, const int32_t *hit_time,
+                               const uint32_t *hit_weight, int32_t *best_dir, uint32_t *best_score,
+                               uint32_t *best_cand, uint32_t *inside, uint32_t *outside, uint32_t *level_score,
+                               uint32_t *cos_hist);
+
 /* ---- PDFs and likelihood terms over DAQ output (chroma/cuda/pdf.cu) ------------------------
  * Every call reads the GPUChannels layout: `ndaq` copies of `nchannels` entries, copy i at
  * [i * stride, i * stride + nchannels) (stride >= nchannels).  An MC time >= 1e8 means "not hit".
