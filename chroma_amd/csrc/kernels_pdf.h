@@ -3,6 +3,8 @@
 // Every kernel reads the GPUChannels layout: `ndaq` copies of `nchannels` entries, copy i at [i * stride, i * stride +
 // nchannels).  A channel time >= 1e8 means "not hit in the MC" (the DAQ writes 1e9).  The copies of one channel are
 // taken in copy order inside one thread (or one wave), so K copies in one call give the same bits as K calls of one copy.
+// Every window test is written in the positive form (t >= tmin && t <= tmax): a NaN time or charge is "not hit" in all
+// five kernels, where the reference's negative forms (t < tmin || t > tmax) let it through.
 
 // ---- bin_hits (pdf.cu:9-32) --------------------------------------------------------------------------
 // One thread per channel.  Charge truncated to an unsigned integer (negative or NaN -> 0, saturating at 2^32 - 1).
@@ -44,17 +46,18 @@ __global__ void __launch_bounds__(256) k_pdf_eval_hitcount(uint32_t nchannels, i
     uint32_t count = 0;
     for (int i = 0; i < ndaq; i++) {
         const float mc = mc_time[(size_t)i * stride + c];
-        if (mc >= 1e8f || mc < tmin || mc > tmax) continue;
+        if (!(mc < 1e8f && mc >= tmin && mc <= tmax)) continue;
         count++;
     }
     if (count) hitcount[c] += count;
 }
 
 // Hit channels: one wave64 per channel in hit_channels[], 64 copies per round.
-//  - valid copy: MC time < 1e8 and inside [tmin, tmax] -> hitcount += 1
+//  - valid copy: MC time < 1e8 and inside [tmin, tmax] (a NaN is neither) -> hitcount += 1
 //  - in the minimum bin: |mc - event_time| < min_twidth / 2 -> bincount += 1
 //  - candidate: valid and the running bincount (after this copy) < min_bin_content; the running count of lane L is the
-//    count before the round plus the in-bin lanes <= L (ballot + mbcnt)
+//    count before the round plus the in-bin lanes <= L (ballot + mbcnt).  A NaN distance (NaN event time) is never a
+//    candidate: the sorting network's fminf / fmaxf would drop it and duplicate its partner
 //  - nearest[h * k .. h * k + k) holds the k = min_bin_content smallest candidate distances so far, ascending, padded
 //    with 1e9.  A round's candidates are sorted across the wave (bitonic network on lane shuffles) and merged into it
 //    by rank: old entry i goes to i + #(new < it), new entry j to j + #(old <= it); ranks >= k are dropped.  In place:
@@ -83,12 +86,12 @@ __global__ void __launch_bounds__(64 * PDF_EVAL_WAVES) k_pdf_eval_accumulate(
         const int i = base + lane;
         float mc = 1e9f;
         if (i < ndaq) mc = mc_time[(size_t)i * stride + c];
-        const bool valid = !(mc >= 1e8f || mc < tmin || mc > tmax);
+        const bool valid = mc < 1e8f && mc >= tmin && mc <= tmax;
         const float d = fabsf(mc - et);
         const bool inbin = valid && d < half_twidth;
         const uint64_t binmask = __ballot(inbin);
         const uint32_t running = nbin + pdf_lane_prefix(binmask) + (inbin ? 1u : 0u);
-        const bool cand = valid && running < (uint32_t)k;
+        const bool cand = valid && d == d && running < (uint32_t)k;
         const uint64_t candmask = __ballot(cand);
         nvalid += (uint32_t)__popcll(__ballot(valid));
         nbin += (uint32_t)__popcll(binmask);
@@ -157,14 +160,14 @@ __global__ void __launch_bounds__(256) k_pdf_moments(int time_only, uint32_t nch
     for (int i = 0; i < ndaq; i++) {
         const size_t at = (size_t)i * stride + c;
         const float t = mc_time[at];
-        if (t < tmin || t > tmax) continue;
+        if (!(t >= tmin && t <= tmax)) continue;
         if (time_only) {
             m0 += 1;
             t1 += t;
             t2 += t * t;
         } else {
             const float q = mc_charge[at];
-            if (q < qmin || q > qmax) continue;
+            if (!(q >= qmin && q <= qmax)) continue;
             m0 += 1;
             t1 += t;
             t2 += t * t;
@@ -208,11 +211,11 @@ __global__ void __launch_bounds__(256) k_pdf_kernel_eval(int time_only, uint32_t
     for (int i = 0; i < ndaq; i++) {
         const size_t at = (size_t)i * stride + c;
         const float t = mc_time[at];
-        if (t < tmin || t > tmax) continue;
+        if (!(t >= tmin && t <= tmax)) continue;
         float q = 0.0f;
         if (!time_only) {
             q = mc_charge[at];
-            if (q < qmin || q > qmax) continue;
+            if (!(q >= qmin && q <= qmax)) continue;
         }
         count += 1;
         if (!hit) continue;

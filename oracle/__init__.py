@@ -34,14 +34,25 @@ def have_ref_physics():
     return all(os.path.exists(ref_physics_path(v)) for v in REF_PHYSICS_LIBS)
 
 
+def ref_pdf_path():
+    return os.path.join(_HERE, '_ref', 'libchroma_ref_pdf.so')
+
+
+def have_ref_pdf():
+    return os.path.exists(ref_pdf_path())
+
+
 def build(force=False):
     """Compile liboracle.so / liboracle_libm.so (and oracle/_ref when the reference is present).  The host builds of
-    the reference's physics (oracle/_ref/libchroma_ref_physics_*.so) are made on their own when only they are missing:
-    the Makefile's `ref-physics` target compiles them if the reference tree is there and says so if it is not."""
+    the reference's physics (oracle/_ref/libchroma_ref_physics_*.so) and of its PDF kernels (libchroma_ref_pdf.so) are
+    made on their own when only they are missing: the Makefile's `ref-physics` and `ref-pdf` targets compile them if
+    the reference tree is there and say so if it is not."""
     have = all(os.path.exists(os.path.join(_HERE, n)) for n in ('liboracle.so', 'liboracle_libm.so'))
     if have and not force:
         if not have_ref_physics():
             subprocess.check_call(['make', '-C', _HERE, 'ref-physics'], stdout=subprocess.DEVNULL)
+        if not have_ref_pdf():
+            subprocess.check_call(['make', '-C', _HERE, 'ref-pdf'], stdout=subprocess.DEVNULL)
         return
     subprocess.check_call(['make', '-C', _HERE, 'all'], stdout=subprocess.DEVNULL)
 
@@ -121,6 +132,127 @@ def load_ref_physics(variant='contract'):
     lib.ref_phys_run_daq_many.argtypes = _RUN_DAQ_MANY_ARGTYPES
     _ref_libs[variant] = lib
     return lib
+
+
+def load_ref_pdf():
+    """The reference's OWN PDF kernels compiled for the host (oracle/ref_pdf_driver.cc over chroma/cuda/pdf.cu), against
+    the host libm.  Only what oracle/_ref holds is loaded; None when the library is not there."""
+    if 'pdf' in _ref_libs:
+        return _ref_libs['pdf']
+    if not have_ref_pdf():
+        return None
+    lib = ctypes.CDLL(ref_pdf_path())
+    lib.ref_pdf_variant.restype = ctypes.c_char_p
+    assert lib.ref_pdf_variant().decode() == 'libm'
+    lib.ref_pdf_table_size.restype = c_int32
+    lib.ref_pdf_table_size.argtypes = []
+    lib.ref_pdf_bin_hits.restype = c_int32
+    lib.ref_pdf_bin_hits.argtypes = [c_int32, c_int32, c_uint32, c_void_p, c_void_p, c_void_p, c_int32, c_float, c_float,
+                                     c_int32, c_float, c_float, c_void_p]
+    lib.ref_pdf_eval_accumulate.restype = c_int32
+    lib.ref_pdf_eval_accumulate.argtypes = [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float,
+                                            c_float, c_float, c_int32, c_int32, c_void_p, c_void_p, c_void_p]
+    lib.ref_pdf_moments.restype = c_int32
+    lib.ref_pdf_moments.argtypes = [c_int32, c_int32, c_int32, c_uint32] + [c_void_p] * 2 + [c_float] * 4 + [c_void_p] * 5
+    lib.ref_pdf_kernel_eval.restype = c_int32
+    lib.ref_pdf_kernel_eval.argtypes = [c_int32, c_int32, c_int32, c_uint32] + [c_void_p] * 5 + [c_float] * 4 + [c_void_p] * 5
+    _ref_libs['pdf'] = lib
+    return lib
+
+
+REF_PDF_TABLE_SIZE = 1000           # distance_table[1000] of accumulate_nearest_neighbor (pdf.cu:118)
+REF_PDF_GUARD = 0xA5A5A5A5
+
+
+def _channel_copies(a, ndaq, stride, nchannels, dtype=np.float32):
+    """A C-contiguous float32 copy of a GPUChannels-layout array, long enough for ndaq copies of nchannels at stride."""
+    a = np.array(a, dtype=dtype, order='C', copy=True)
+    assert a.ndim == 1 and stride >= nchannels and len(a) >= (ndaq - 1) * stride + nchannels
+    return a
+
+
+def ref_bin_hits(t, q, nchannels, ndaq, stride, tbins, trange, qbins, qrange, hitcount=None, pdf=None):
+    """bin_hits (pdf.cu:9-32), once per copy in copy order, with the argument list of tests/test_pdf_host.bin_hits_*.
+    The histogram carries one guard row behind the last channel, which has to stay as it was: the reference writes the
+    bin a time just below tmax rounds up to, row `tbins`, into the next channel's row.  Returns (hitcount, pdf)."""
+    lib = load_ref_pdf()
+    t, q = _channel_copies(t, ndaq, stride, nchannels), _channel_copies(q, ndaq, stride, nchannels)
+    hitcount = np.zeros(nchannels, np.uint32) if hitcount is None else np.array(hitcount, np.uint32, copy=True)
+    hist = np.full((nchannels + 1, tbins, qbins), REF_PDF_GUARD, np.uint32)
+    hist[:nchannels] = 0 if pdf is None else np.asarray(pdf, np.uint32).reshape(nchannels, tbins, qbins)
+    rc = lib.ref_pdf_bin_hits(nchannels, ndaq, stride, q.ctypes.data, t.ctypes.data, hitcount.ctypes.data, tbins,
+                              float(trange[0]), float(trange[1]), qbins, float(qrange[0]), float(qrange[1]), hist.ctypes.data)
+    if rc != 0:
+        raise RuntimeError('ref_pdf_bin_hits refused its arguments (%d)' % rc)
+    assert (hist[nchannels] == REF_PDF_GUARD).all(), 'the reference binned a hit behind its histogram'
+    return hitcount, np.ascontiguousarray(hist[:nchannels])
+
+
+def ref_eval_accumulate(event_hit, event_time, mc_time, nchannels, ndaq, stride, min_twidth, trange, k, state=None):
+    """accumulate_bincount + accumulate_nearest_neighbor (pdf.cu:34-150) as chroma/gpu/pdf.py launches them, with the
+    argument list of tests/test_pdf_host.eval_accumulate_*: state = (hitcount, bincount, nearest[nchannels, k]).  The
+    copies are packed to stride nchannels for the call (the reference's own indexing).  ValueError, without a call,
+    when k + ndaq exceeds the reference's distance table."""
+    lib = load_ref_pdf()
+    if k + ndaq > REF_PDF_TABLE_SIZE:
+        raise ValueError('k + ndaq = %d exceeds the reference distance table of %d entries' % (k + ndaq, REF_PDF_TABLE_SIZE))
+    assert lib.ref_pdf_table_size() == REF_PDF_TABLE_SIZE
+    hit = np.ascontiguousarray(np.asarray(event_hit).astype(bool))
+    mc = _channel_copies(mc_time, ndaq, stride, nchannels)
+    packed = np.ascontiguousarray(np.stack([mc[i * stride:i * stride + nchannels] for i in range(ndaq)])).reshape(-1)
+    if state is None:
+        state = (np.zeros(nchannels, np.uint32), np.zeros(nchannels, np.uint32), np.full((nchannels, k), 1e9, np.float32))
+    hitcount, bincount, nearest = (np.array(a, copy=True) for a in state)
+    hit_to_channel = np.flatnonzero(hit).astype(np.uint32)
+    channel_to_hit = np.maximum(0, hit.cumsum() - 1).astype(np.uint32)           # chroma/gpu/pdf.py:267
+    nhit = len(hit_to_channel)
+    by_hit = np.ascontiguousarray(nearest[hit_to_channel], dtype=np.float32).reshape(nhit, k)
+    ev_hit = hit.astype(np.uint32)
+    ev_time = np.ascontiguousarray(event_time, dtype=np.float32)
+    rc = lib.ref_pdf_eval_accumulate(nchannels, ndaq, ev_hit.ctypes.data, ev_time.ctypes.data, packed.ctypes.data,
+                                     hitcount.ctypes.data, bincount.ctypes.data, float(min_twidth), float(trange[0]),
+                                     float(trange[1]), k, nhit, channel_to_hit.ctypes.data, hit_to_channel.ctypes.data,
+                                     by_hit.ctypes.data)
+    if rc != 0:
+        raise RuntimeError('ref_pdf_eval_accumulate refused its arguments (%d)' % rc)
+    nearest[hit_to_channel] = by_hit
+    return hitcount, bincount, nearest
+
+
+def ref_moments(t, q, nchannels, ndaq, stride, trange, qrange, time_only=True, state=None):
+    """accumulate_moments (pdf.cu:223-265), once per copy in copy order; arguments of tests/test_pdf_host.moments_*."""
+    lib = load_ref_pdf()
+    t, q = _channel_copies(t, ndaq, stride, nchannels), _channel_copies(q, ndaq, stride, nchannels)
+    if state is None:
+        state = (np.zeros(nchannels, np.uint32),) + tuple(np.zeros(nchannels, np.float32) for _ in range(4))
+    m0, t1, t2, q1, q2 = (np.array(a, copy=True) for a in state)
+    rc = lib.ref_pdf_moments(int(bool(time_only)), nchannels, ndaq, stride, t.ctypes.data, q.ctypes.data, float(trange[0]),
+                             float(trange[1]), float(qrange[0]), float(qrange[1]), m0.ctypes.data, t1.ctypes.data,
+                             t2.ctypes.data, q1.ctypes.data, q2.ctypes.data)
+    if rc != 0:
+        raise RuntimeError('ref_pdf_moments refused its arguments (%d)' % rc)
+    return m0, t1, t2, q1, q2
+
+
+def ref_kernel_eval(event_hit, event_time, event_charge, t, q, nchannels, ndaq, stride, trange, qrange, inv_tbw, inv_qbw,
+                    time_only=True, state=None):
+    """accumulate_kernel_eval (pdf.cu:271-368), once per copy in copy order; arguments of
+    tests/test_pdf_host.kernel_eval_*, but the state and the result are the reference's float32 sums:
+    (hitcount, time_pdf_values, charge_pdf_values)."""
+    lib = load_ref_pdf()
+    t, q = _channel_copies(t, ndaq, stride, nchannels), _channel_copies(q, ndaq, stride, nchannels)
+    if state is None:
+        state = (np.zeros(nchannels, np.uint32), np.zeros(nchannels, np.float32), np.zeros(nchannels, np.float32))
+    count, tv, qv = (np.array(a, dtype=d, copy=True) for a, d in zip(state, (np.uint32, np.float32, np.float32)))
+    ev_hit = np.ascontiguousarray(np.asarray(event_hit).astype(bool).astype(np.uint32))
+    ev_t, ev_q, itb, iqb = (np.ascontiguousarray(a, dtype=np.float32) for a in (event_time, event_charge, inv_tbw, inv_qbw))
+    rc = lib.ref_pdf_kernel_eval(int(bool(time_only)), nchannels, ndaq, stride, ev_hit.ctypes.data, ev_t.ctypes.data,
+                                 ev_q.ctypes.data, t.ctypes.data, q.ctypes.data, float(trange[0]), float(trange[1]),
+                                 float(qrange[0]), float(qrange[1]), itb.ctypes.data, iqb.ctypes.data, count.ctypes.data,
+                                 tv.ctypes.data, qv.ctypes.data)
+    if rc != 0:
+        raise RuntimeError('ref_pdf_kernel_eval refused its arguments (%d)' % rc)
+    return count, tv, qv
 
 
 class HostPhotons(object):

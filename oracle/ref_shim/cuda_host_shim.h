@@ -1,8 +1,8 @@
 /* cuda_host_shim.h -- TEST INFRASTRUCTURE.  The handful of CUDA language and runtime names that the reference's
  * device sources (chroma/cuda/propagate.cu, photon.h, daq.cu and the headers they include) use, given a plain host
  * meaning so that g++ compiles those sources unmodified, from where they lie, into oracle/_ref (oracle/Makefile,
- * oracle/ref_physics_driver.cc).  This text is the project's own: nothing here is taken from the reference or from
- * the CUDA toolkit.
+ * oracle/ref_physics_driver.cc; chroma/cuda/pdf.cu with sorting.h through oracle/ref_pdf_driver.cc).  This text is the
+ * project's own: nothing here is taken from the reference or from the CUDA toolkit.
  *
  * Execution model of the driver: ONE host thread runs the threads of a block one after the other, thread 0 first,
  * and the blocks of a grid one after the other.  Hence

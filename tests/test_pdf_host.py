@@ -1,5 +1,9 @@
 """The PDF layer's semantics on the host (reference: chroma/cuda/pdf.cu, chroma/gpu/pdf.py, chroma/likelihood.py).
 
+A NaN time, and in the (time, charge) paths a NaN charge, is "not hit" in every restatement (the window tests are written
+in the positive form), and a NaN event time gives no nearest-distance candidate: DESIGN.md 3.6.  On every input without
+a NaN the restatements are the reference's (tests/test_ref_pdf_host.py holds them to its own pdf.cu).
+
 Each device kernel is restated twice in NumPy: as the obvious per-channel loop of the reference, and vectorised.  The
 two agree here on small random cases, and tests/test_gpu_pdf.py holds the device to them.  Also: the host arithmetic of
 get_pdf_eval / compute_bandwidth, the NLL of Likelihood against a stub simulation, and the ``chroma`` alias."""
@@ -71,7 +75,7 @@ def eval_accumulate_loop(event_hit, event_time, mc_time, nchannels, ndaq, stride
         cands = []
         for i in range(ndaq):
             mc = F(mc_time[i * stride + c])
-            if mc >= F(1e8) or mc < tmin or mc > tmax:
+            if not (mc < F(1e8) and mc >= tmin and mc <= tmax):          # a NaN time is not a hit
                 continue
             hitcount[c] += 1
             if not event_hit[c]:
@@ -79,7 +83,7 @@ def eval_accumulate_loop(event_hit, event_time, mc_time, nchannels, ndaq, stride
             d = F(abs(mc - F(event_time[c])))
             if d < half:
                 bincount[c] += 1
-            if bincount[c] < k:
+            if bincount[c] < k and d == d:          # a NaN distance (NaN event time) is no candidate
                 cands.append(d)
         if cands:
             nearest[c] = np.sort(np.concatenate([nearest[c], np.array(cands, np.float32)]))[:k]
@@ -94,12 +98,12 @@ def eval_accumulate_vec(event_hit, event_time, mc_time, nchannels, ndaq, stride,
     hitcount, bincount, nearest = (a.copy() for a in state)
     hit = np.asarray(event_hit).astype(bool)
     M = np.stack([_copy(np.asarray(mc_time, np.float32), i, stride, nchannels) for i in range(ndaq)])
-    valid = ~((M >= F(1e8)) | (M < tmin) | (M > tmax))
+    valid = (M < F(1e8)) & (M >= tmin) & (M <= tmax)
     hitcount += valid.sum(axis=0).astype(np.uint32)
     D = np.abs(M - np.asarray(event_time, np.float32)[None, :])
     inbin = valid & (D < half) & hit[None, :]
     running = bincount[None, :].astype(np.int64) + np.cumsum(inbin, axis=0)
-    cand = valid & hit[None, :] & (running < k)
+    cand = valid & hit[None, :] & (running < k) & ~np.isnan(D)
     bincount += inbin.sum(axis=0).astype(np.uint32)
     merged = np.sort(np.concatenate([nearest.T, np.where(cand, D, np.float32(np.inf))], axis=0), axis=0)[:k]
     nearest = np.ascontiguousarray(merged.T)
@@ -115,11 +119,11 @@ def moments_loop(t, q, nchannels, ndaq, stride, trange, qrange, time_only=True, 
     for c in range(nchannels):
         for i in range(ndaq):
             tt = F(t[i * stride + c])
-            if tt < tmin or tt > tmax:
+            if not (tt >= tmin and tt <= tmax):
                 continue
             if not time_only:
                 qq = F(q[i * stride + c])
-                if qq < qmin or qq > qmax:
+                if not (qq >= qmin and qq <= qmax):
                     continue
                 q1[c] = F(q1[c] + qq)
                 q2[c] = F(q2[c] + F(qq * qq))
@@ -137,9 +141,9 @@ def moments_vec(t, q, nchannels, ndaq, stride, trange, qrange, time_only=True, s
     for i in range(ndaq):               # copies in order: float sums round as the device's do
         tt = _copy(np.asarray(t, np.float32), i, stride, nchannels)
         qq = _copy(np.asarray(q, np.float32), i, stride, nchannels)
-        ok = ~((tt < tmin) | (tt > tmax))
+        ok = (tt >= tmin) & (tt <= tmax)
         if not time_only:
-            ok &= ~((qq < qmin) | (qq > qmax))
+            ok &= (qq >= qmin) & (qq <= qmax)
             q1[ok] += qq[ok]
             q2[ok] += qq[ok] * qq[ok]
         m0[ok] += 1
@@ -166,10 +170,10 @@ def kernel_eval_loop(event_hit, event_time, event_charge, t, q, nchannels, ndaq,
     for c in range(nchannels):
         for i in range(ndaq):
             tt = float(t[i * stride + c])
-            if tt < tmin or tt > tmax:
+            if not (tt >= tmin and tt <= tmax):
                 continue
             qq = float(q[i * stride + c])
-            if not time_only and (qq < qmin or qq > qmax):
+            if not time_only and not (qq >= qmin and qq <= qmax):
                 continue
             count[c] += 1
             if not event_hit[c]:
@@ -189,9 +193,9 @@ def kernel_eval_vec(event_hit, event_time, event_charge, t, q, nchannels, ndaq, 
     erf = np.vectorize(math.erf, otypes=[float])
     T = np.stack([_copy(np.asarray(t, np.float32), i, stride, nchannels) for i in range(ndaq)]).astype(float)
     Q = np.stack([_copy(np.asarray(q, np.float32), i, stride, nchannels) for i in range(ndaq)]).astype(float)
-    ok = ~((T < tmin) | (T > tmax))
+    ok = (T >= tmin) & (T <= tmax)
     if not time_only:
-        ok &= ~((Q < qmin) | (Q > qmax))
+        ok &= (Q >= qmin) & (Q <= qmax)
     count += ok.sum(axis=0).astype(np.uint32)
     use = ok & np.asarray(event_hit).astype(bool)[None, :]
 
