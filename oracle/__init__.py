@@ -130,8 +130,95 @@ def load_ref_physics(variant='contract'):
     lib.ref_phys_run_daq.argtypes = _RUN_DAQ_ARGTYPES
     lib.ref_phys_run_daq_many.restype = c_int32
     lib.ref_phys_run_daq_many.argtypes = _RUN_DAQ_MANY_ARGTYPES
+    if hasattr(lib, 'ref_hybrid_lookup'):                    # (a library built before the hybrid render was added has none)
+        lib.ref_hybrid_lookup.restype = c_int32
+        lib.ref_hybrid_lookup.argtypes = [POINTER(_abi.GeometryDesc), c_int32, c_int32, c_int32, POINTER(c_float), _abi.Rng, c_void_p,
+                                          c_float, POINTER(c_float), c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]
+        lib.ref_hybrid_image.restype = c_int32
+        lib.ref_hybrid_image.argtypes = [POINTER(_abi.GeometryDesc), c_int32, _abi.Rng, c_void_p, c_void_p, c_void_p, c_float,
+                                         POINTER(c_float), c_void_p, c_void_p, c_void_p, c_int32, c_int32]
+        lib.ref_hybrid_pixels.restype = c_int32
+        lib.ref_hybrid_pixels.argtypes = [c_int32, c_void_p, c_void_p, c_int32]
     _ref_libs[variant] = lib
     return lib
+
+
+REF_HYBRID_ENTRIES = ('ref_hybrid_lookup', 'ref_hybrid_image', 'ref_hybrid_pixels')
+
+
+def have_ref_hybrid():
+    """True when both physics libraries of oracle/_ref hold the reference's hybrid render (chroma/cuda/hybrid_render.cu
+    behind the three entries of oracle/ref_physics_driver.cc); libraries built before it was added do not."""
+    if not have_ref_physics():
+        return False
+    libs = [load_ref_physics(v) for v in REF_PHYSICS_LIBS]
+    return all(lib is not None and all(hasattr(lib, name) for name in REF_HYBRID_ENTRIES) for lib in libs)
+
+
+def _f3(v):
+    return (c_float * 3)(*[float(x) for x in v])
+
+
+def ref_hybrid_lookup(packed, seed, id_base, counters, nthreads, total_threads, offset, source, wavelength, xyz, lookup1, lookup2,
+                      max_steps=10, variant='contract'):
+    """ONE update_xyz_lookup launch of the reference (hybrid_render.cu:63-131) over ``nthreads`` threads, thread k on the stream
+    ``id_base + k`` at ``counters[k]``, added onto copies of ``lookup1`` / ``lookup2`` ([ntriangles][3] float32).  Returns
+    (lookup1, lookup2, counters, (triangle, side, value)): the tables and the counters after the launch, and thread k's own
+    addition -- the row, the table (side 1: lookup1, side 0: lookup2) and the three values it handed to fAtomicAdd, triangle -1
+    and zeros where it added nothing."""
+    lib = load_ref_physics(variant)
+    ntri = int(packed.desc.ntriangles)
+    l1, l2 = [np.array(a, dtype=np.float32, order='C', copy=True).reshape(ntri, 3) for a in (lookup1, lookup2)]
+    n = max(int(nthreads), 0)
+    ctr = np.array(counters, dtype=np.uint32, order='C', copy=True)
+    assert len(ctr) >= n
+    tri = np.full(n, -1, np.int32)
+    side = np.zeros(n, np.uint32)
+    value = np.zeros((n, 3), np.float32)
+    rc = lib.ref_hybrid_lookup(ctypes.byref(packed.desc), int(nthreads), int(total_threads), int(offset), _f3(source),
+                               _abi.Rng(int(seed), int(id_base)), ctr.ctypes.data, float(wavelength), _f3(xyz), l1.ctypes.data,
+                               l2.ctypes.data, int(max_steps), tri.ctypes.data, side.ctypes.data, value.ctypes.data)
+    if rc != 0:
+        raise RuntimeError('ref_hybrid_lookup failed (%d)' % rc)
+    return l1, l2, ctr, (tri, side, value)
+
+
+def ref_hybrid_image(packed, seed, id_base, counters, origins, directions, wavelength, xyz, lookup1, lookup2, image, nlookup_calls,
+                     max_steps=10, variant='contract'):
+    """ONE update_xyz_image launch of the reference (hybrid_render.cu:133-168) over the rays given, added onto a copy of
+    ``image`` ([nrays][3] float32).  Returns (image, counters) after the launch."""
+    lib = load_ref_physics(variant)
+    ntri = int(packed.desc.ntriangles)
+    o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
+    d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
+    n = len(o)
+    l1, l2 = [np.ascontiguousarray(a, dtype=np.float32).reshape(ntri, 3) for a in (lookup1, lookup2)]
+    img = np.array(image, dtype=np.float32, order='C', copy=True).reshape(-1, 3)
+    ctr = np.array(counters, dtype=np.uint32, order='C', copy=True)
+    assert len(d) == n and len(img) >= n and len(ctr) >= n
+    rc = lib.ref_hybrid_image(ctypes.byref(packed.desc), n, _abi.Rng(int(seed), int(id_base)), ctr.ctypes.data, o.ctypes.data,
+                              d.ctypes.data, float(wavelength), _f3(xyz), l1.ctypes.data, l2.ctypes.data, img.ctypes.data,
+                              int(nlookup_calls), int(max_steps))
+    if rc != 0:
+        raise RuntimeError('ref_hybrid_image failed (%d)' % rc)
+    return img, ctr
+
+
+def ref_hybrid_pixels(image, nimages, variant='contract'):
+    """process_image of the reference (hybrid_render.cu:170-200) on ``image`` ([n][3] float32).  Returns (pixels, left_out):
+    ``left_out`` [n][3] marks the channels that are NaN after the division by ``nimages``.  The reference converts
+    floorf(NaN) to unsigned, which a host build leaves undefined (the device gives 0), so those channels -- and only those --
+    are handed to it as 0.0 and their eight bits of ``pixels`` mean nothing."""
+    lib = load_ref_physics(variant)
+    img = np.array(image, dtype=np.float32, order='C', copy=True).reshape(-1, 3)
+    with np.errstate(invalid='ignore', over='ignore'):
+        left_out = np.isnan(img / np.float32(nimages))
+    img[left_out] = 0.0
+    pixels = np.zeros(len(img), np.uint32)
+    rc = lib.ref_hybrid_pixels(len(img), img.ctypes.data, pixels.ctypes.data, int(nimages))
+    if rc != 0:
+        raise RuntimeError('ref_hybrid_pixels failed (%d)' % rc)
+    return pixels, left_out
 
 
 def load_ref_pdf():

@@ -1,9 +1,11 @@
-// ref_physics_driver.cc -- TEST INFRASTRUCTURE.  A HOST driver around the reference's OWN physics and DAQ sources,
-// compiled by g++ from where they lie (found through -I, see oracle/Makefile; nothing is copied):
+// ref_physics_driver.cc -- TEST INFRASTRUCTURE.  A HOST driver around the reference's OWN physics, DAQ and hybrid-render
+// sources, compiled by g++ from where they lie (found through -I, see oracle/Makefile; nothing is copied):
 // chroma/cuda/propagate.cu (the `propagate` kernel, :217-319) with photon.h (fill_state, Rayleigh scattering, bulk
 // absorption and re-emission, Fresnel, both reflectors, the thin film, WLS, dichroic), random.h, cx.h, mesh.h,
 // intersect.h, geometry.h, rotate.h, interpolate.h, linalg.h; and chroma/cuda/daq.cu (run_daq :35-86, run_daq_many
-// :88-150).  The CUDA names those sources use come from the stand-ins of oracle/ref_shim (the project's own text).
+// :88-150); and chroma/cuda/hybrid_render.cu (fAtomicAdd, to_diffuse :20-58, update_xyz_lookup :63-131, update_xyz_image
+// :133-168, process_image :170-200) with matrix.h.  The CUDA names those sources use come from the stand-ins of
+// oracle/ref_shim (the project's own text).
 //
 // What this pins, and what it cannot: the reference's statements run as written -- every branch, every rescaling,
 // every clamp, which statement draws and in what order.  The random stream is the project's per-photon Philox stream
@@ -39,6 +41,7 @@
 
 #include "propagate.cu"
 #include "daq.cu"
+#include "hybrid_render.cu"
 
 #ifdef REF_PHYS_CONTRACT
 #undef sinf
@@ -358,6 +361,140 @@ int ref_phys_run_daq_many(const chroma_geometry_desc *desc, const chroma_daq_tab
             run_daq_many(states.data(), detection_state, first_photon, nphotons, a->t, a->flags, a->last_hit_triangles,
                          a->weights, (int *)desc->solid_id_map, &det, earliest_time_int, channel_q_int, channel_histories,
                          ndaq, channel_stride, global_weight);
+        }
+    return 0;
+}
+
+}  // extern "C"
+
+// ---- the hybrid render (hybrid_render.cu) ----------------------------------------------------------------------------
+namespace {
+
+// Where and what the running thread of update_xyz_lookup adds: the atomicExch stand-in (ref_shim/cuda_host_shim.h, the
+// project's own text) reports every exchange of a non-zero value, which in fAtomicAdd is `data + what the entry held`.
+// The record pass below runs a thread against tables that hold zeros, so the value noted is 0 + data = data, exactly.
+struct ExchNote {
+    float *table[2];            // [0] xyz_lookup1, [1] xyz_lookup2 of the record pass
+    size_t nfloats;
+    int which, triangle;        // of the running thread: table (-1: none yet), row
+    float value[3];
+    bool confused;              // an exchange outside the tables, or a second row
+} exch_note;
+
+void note_exchange(float *p, float v)
+{
+    for (int w = 0; w < 2; w++) {
+        if (p < exch_note.table[w] || p >= exch_note.table[w] + exch_note.nfloats) continue;
+        size_t at = (size_t)(p - exch_note.table[w]);
+        int tri = (int)(at / 3);
+        if (exch_note.which == -1) { exch_note.which = w; exch_note.triangle = tri; }
+        if (exch_note.which != w || exch_note.triangle != tri) exch_note.confused = true;
+        exch_note.value[at % 3] = v;
+        return;
+    }
+    exch_note.confused = true;
+}
+
+}  // namespace
+
+extern "C" {
+
+// ONE update_xyz_lookup launch (hybrid_render.cu:63-131) over `nthreads` threads, 64 to a block, onto xyz_lookup1 / 2
+// ([ntriangles][3] each).  Thread k holds the stream rng.photon_id_base + k at counters[k]; the counter is written back.
+//
+// rec_triangle / rec_side / rec_value (each may be null, all or none): thread k's OWN addition -- the row, the table
+// (1: xyz_lookup1, the inside_to_outside one; 0: xyz_lookup2) and the three values handed to fAtomicAdd -- or triangle -1
+// where it added nothing.  They come from a record pass BEFORE the launch: every thread once more, from a copy of its
+// state, onto scratch tables of zeros, the exchange stand-in noting what was put there.  (A component whose value is
+// +-0 makes no exchange, hybrid_render.cu:15, and stays 0.0f in the record.)
+int ref_hybrid_lookup(const chroma_geometry_desc *desc, int32_t nthreads, int32_t total_threads, int32_t offset, const float *position,
+                      chroma_rng rng, uint32_t *counters, float wavelength, const float *xyz, float *xyz_lookup1, float *xyz_lookup2,
+                      int32_t max_steps, int32_t *rec_triangle, uint32_t *rec_side, float *rec_value)
+{
+    if (nthreads <= 0) return 0;
+    // the kernel fetches triangle offset + k of every thread below total_threads and checks nothing else (the camera
+    // passes the triangle count, chroma/camera.py:213-217): a launch that would read past the mesh is not made
+    if (offset < 0 || total_threads < 0 || (uint32_t)total_threads > desc->ntriangles) return -3;
+    const unsigned int nthreads_per_block = 64;
+    World w(desc);
+    const float3 pos = make_float3(position[0], position[1], position[2]);
+    const float3 colour = make_float3(xyz[0], xyz[1], xyz[2]);
+    std::vector<curandState> states((size_t)nthreads);
+    unsigned int nblocks = ((unsigned int)nthreads + nthreads_per_block - 1) / nthreads_per_block;
+    set_launch(nblocks, nthreads_per_block);
+
+    if (rec_triangle) {
+        if (!rec_side || !rec_value) return -1;
+        std::vector<float> scratch1((size_t)desc->ntriangles * 3, 0.0f), scratch2((size_t)desc->ntriangles * 3, 0.0f);
+        exch_note.table[0] = scratch1.data(); exch_note.table[1] = scratch2.data();
+        exch_note.nfloats = scratch1.size();
+        exch_note.confused = false;
+        for (int k = 0; k < nthreads; k++) curand_init(rng.seed, rng.photon_id_base + (uint64_t)k, counters[k], &states[k]);
+        ref_shim_exch_note = note_exchange;
+        for (int k = 0; k < nthreads; k++) {
+            exch_note.which = -1; exch_note.triangle = -1;
+            exch_note.value[0] = exch_note.value[1] = exch_note.value[2] = 0.0f;
+            blockIdx.x = (unsigned int)k / nthreads_per_block; threadIdx.x = (unsigned int)k % nthreads_per_block;
+            update_xyz_lookup(nthreads, total_threads, offset, pos, states.data(), wavelength, colour,
+                              (float3 *)scratch1.data(), (float3 *)scratch2.data(), max_steps, &w.g);
+            rec_triangle[k] = exch_note.triangle;
+            rec_side[k] = exch_note.which == 0 ? 1u : 0u;
+            for (int c = 0; c < 3; c++) rec_value[3 * k + c] = exch_note.value[c];
+            if (exch_note.which >= 0) {
+                float *row = exch_note.table[exch_note.which] + 3 * (size_t)exch_note.triangle;
+                row[0] = row[1] = row[2] = 0.0f;
+            }
+        }
+        ref_shim_exch_note = 0;
+        if (exch_note.confused) return -2;
+    }
+
+    for (int k = 0; k < nthreads; k++) curand_init(rng.seed, rng.photon_id_base + (uint64_t)k, counters[k], &states[k]);
+    for (unsigned int b = 0; b < nblocks; b++)
+        for (unsigned int t = 0; t < nthreads_per_block; t++) {
+            blockIdx.x = b; threadIdx.x = t;
+            update_xyz_lookup(nthreads, total_threads, offset, pos, states.data(), wavelength, colour,
+                              (float3 *)xyz_lookup1, (float3 *)xyz_lookup2, max_steps, &w.g);
+        }
+    for (int k = 0; k < nthreads; k++) counters[k] = states[k].counter;
+    return 0;
+}
+
+// ONE update_xyz_image launch (hybrid_render.cu:133-168) over `nthreads` rays, 64 to a block; streams as above.
+int ref_hybrid_image(const chroma_geometry_desc *desc, int32_t nthreads, chroma_rng rng, uint32_t *counters, const float *positions,
+                     const float *directions, float wavelength, const float *xyz, const float *xyz_lookup1, const float *xyz_lookup2,
+                     float *image, int32_t nlookup_calls, int32_t max_steps)
+{
+    if (nthreads <= 0) return 0;
+    const unsigned int nthreads_per_block = 64;
+    World w(desc);
+    std::vector<curandState> states((size_t)nthreads);
+    for (int k = 0; k < nthreads; k++) curand_init(rng.seed, rng.photon_id_base + (uint64_t)k, counters[k], &states[k]);
+    unsigned int nblocks = ((unsigned int)nthreads + nthreads_per_block - 1) / nthreads_per_block;
+    set_launch(nblocks, nthreads_per_block);
+    for (unsigned int b = 0; b < nblocks; b++)
+        for (unsigned int t = 0; t < nthreads_per_block; t++) {
+            blockIdx.x = b; threadIdx.x = t;
+            update_xyz_image(nthreads, states.data(), (float3 *)positions, (float3 *)directions, wavelength,
+                             make_float3(xyz[0], xyz[1], xyz[2]), (float3 *)xyz_lookup1, (float3 *)xyz_lookup2, (float3 *)image,
+                             nlookup_calls, max_steps, &w.g);
+        }
+    for (int k = 0; k < nthreads; k++) counters[k] = states[k].counter;
+    return 0;
+}
+
+// process_image (hybrid_render.cu:170-200) over `nthreads` pixels, 64 to a block.  The caller keeps NaN out of `image`:
+// the kernel converts floorf(NaN) to unsigned, which a host build leaves undefined.
+int ref_hybrid_pixels(int32_t nthreads, const float *image, uint32_t *pixels, int32_t nimages)
+{
+    if (nthreads <= 0) return 0;
+    const unsigned int nthreads_per_block = 64;
+    unsigned int nblocks = ((unsigned int)nthreads + nthreads_per_block - 1) / nthreads_per_block;
+    set_launch(nblocks, nthreads_per_block);
+    for (unsigned int b = 0; b < nblocks; b++)
+        for (unsigned int t = 0; t < nthreads_per_block; t++) {
+            blockIdx.x = b; threadIdx.x = t;
+            process_image(nthreads, (float3 *)image, pixels, nimages);
         }
     return 0;
 }

@@ -63,6 +63,18 @@ static inline unsigned int atomicMin(unsigned int *p, unsigned int v) { unsigned
 static inline int atomicMin(int *p, int v) { int old = *p; if (v < old) *p = v; return old; }
 static inline unsigned int atomicOr(unsigned int *p, unsigned int v) { unsigned int old = *p; *p = old | v; return old; }
 static inline int atomicOr(int *p, int v) { int old = *p; *p = old | v; return old; }
+/* The exchange fAtomicAdd of hybrid_render.cu is made of.  A driver that wants to know WHERE the running thread adds
+ * (the reference has no output for it) sets ref_shim_exch_note: it is told of every exchange of a value other than
+ * 0.0f, which in fAtomicAdd is the one that puts `data + what was there` back. */
+typedef void (*ref_shim_exch_note_fn)(float *p, float v);
+static ref_shim_exch_note_fn ref_shim_exch_note = 0;
+static inline float atomicExch(float *p, float v)
+{
+    float old = *p;
+    *p = v;
+    if (ref_shim_exch_note && !(v == 0.0f)) ref_shim_exch_note(p, v);
+    return old;
+}
 
 /* ---- bit casts ------------------------------------------------------------------------------------------ */
 static inline float __int_as_float(int i) { float f; memcpy(&f, &i, sizeof f); return f; }

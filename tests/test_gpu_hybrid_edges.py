@@ -1,7 +1,9 @@
 """The hybrid render's kernels (k_hybrid_lookup, k_hybrid_reduce, k_hybrid_image, k_hybrid_pixels; chroma/cuda/hybrid_render.cu)
 at their sizes, key runs and edges: launches through the C entry points (chroma_hybrid_lookup / _image / _pixels) on arrays this
 file owns, every sample bit for bit against the oracle restatements of tests/test_gpu_hybrid_render.py, every table, image and
-pixel against the NumPy restatements of chroma_amd.gpu.render.
+pixel against the NumPy restatements of chroma_amd.gpu.render.  Those restatements are the project's own reading of
+hybrid_render.cu: tests/test_ref_hybrid_host.py holds them to the reference's file itself (compiled for the host into oracle/_ref),
+on the scenes, bundles and launches defined here, and tests/test_gpu_ref_hybrid.py the kernels, with this file's call helpers.
 
 Every array a call may write is GUARD rows longer than the call is told and holds a sentinel where the call has no business:
 behind the array, in the sample rows of threads past the last triangle, everywhere when the call returns early or refuses.
@@ -195,24 +197,25 @@ class Want(object):
         return hybrid_accumulate(l1.copy(), l2.copy(), self.tri, self.side, contrib)
 
 
-def want_lookup(oracle_mod, scene, n, offset, counters, max_steps=10, source=None, id_base=0):
+def want_lookup(oracle_mod, scene, n, offset, counters, max_steps=10, source=None, id_base=0, variant='contract'):
     counters = np.asarray(counters, np.uint32)[:n]
-    key = ('lookup', scene, n, offset, counters.tobytes(), max_steps, source, id_base)
+    key = ('lookup', scene, n, offset, counters.tobytes(), max_steps, source, id_base, variant)
     if key not in _memo:
         g, packed, src = SCENES[scene]()
         assert 0 <= offset and offset + n <= len(g.mesh.triangles)
         _memo[key] = Want(oracle_lookup(oracle_mod, packed, g, SEED, id_base, counters, n, offset, src if source is None else source,
-                                        WAVELENGTH, max_steps), n, offset)
+                                        WAVELENGTH, max_steps, variant=variant), n, offset)
     return _memo[key]
 
 
-def want_image(oracle_mod, scene, origins, directions, counters, max_steps=10, id_base=0):
+def want_image(oracle_mod, scene, origins, directions, counters, max_steps=10, id_base=0, variant='contract'):
     n = len(origins)
     counters = np.asarray(counters, np.uint32)[:n]
-    key = ('image', scene, np.asarray(origins, f32).tobytes(), np.asarray(directions, f32).tobytes(), counters.tobytes(), max_steps, id_base)
+    key = ('image', scene, np.asarray(origins, f32).tobytes(), np.asarray(directions, f32).tobytes(), counters.tobytes(), max_steps, id_base,
+           variant)
     if key not in _memo:
         g, packed, _ = SCENES[scene]()
-        _memo[key] = oracle_image(oracle_mod, packed, g, SEED, id_base, counters, origins, directions, WAVELENGTH, max_steps)
+        _memo[key] = oracle_image(oracle_mod, packed, g, SEED, id_base, counters, origins, directions, WAVELENGTH, max_steps, variant=variant)
     return _memo[key]
 
 

@@ -3,7 +3,12 @@
 Every sample of the lookup and image passes is rebuilt on the host: the draws from oracle.uniform_stream, the first hit from
 oracle.distance_to_mesh, the polarisation from oracle.math_fn('sin' / 'cos'), then oracle.propagate stepped one step at a time
 until the first diffuse reflection.  The diffusing triangle, its side, the history and the final draw counter must equal the
-kernel's sample outputs.  Tables, image and pixels must equal their NumPy restatements (chroma_amd.gpu.render) bit for bit."""
+kernel's sample outputs.  Tables, image and pixels must equal their NumPy restatements (chroma_amd.gpu.render) bit for bit.
+
+The comparands here are the project's own restatements of hybrid_render.cu.  What holds THEM to the reference is
+tests/test_ref_hybrid_host.py (oracle_lookup, oracle_image, oracle.to_diffuse, hybrid_accumulate, hybrid_image_update and
+hybrid_pixels against the reference's own file compiled for the host, libm and contract builds; hence the `variant` keyword of
+the helpers below), and tests/test_gpu_ref_hybrid.py compares the kernels with that build directly."""
 import os
 import subprocess
 import sys
@@ -85,12 +90,13 @@ def _normals(geometry):
     return _normalize(_cross(v1 - v0, v2 - v1))
 
 
-def _uniform_sphere(oracle_mod, u_theta, u_z):
+def _uniform_sphere(oracle_mod, u_theta, u_z, variant='contract'):
     """random.h:15-23 with the contract's sin / cos (uniform_sphere of propagate_device.h)."""
     theta = f32(0) + u_theta * (f32(2 * f32(np.pi)) - f32(0))
     u = f32(-1) + u_z * (f32(1) - f32(-1))
     c = np.sqrt(f32(1) - u * u)
-    return np.stack([c * oracle_mod.math_fn('cos', theta), c * oracle_mod.math_fn('sin', theta), u], axis=1).astype(f32)
+    return np.stack([c * oracle_mod.math_fn('cos', theta, variant=variant), c * oracle_mod.math_fn('sin', theta, variant=variant), u],
+                    axis=1).astype(f32)
 
 
 def _draws(oracle_mod, seed, id_base, counters, n):
@@ -131,21 +137,22 @@ def _step_to_diffuse(oracle_mod, packed, normals, photons, active, seed, id_base
     return tri, np.where(diffuse, side, 0).astype(np.uint32), np.where(active, cur[6], 0).astype(np.uint32), ctr
 
 
-def _to_diffuse(oracle_mod, packed, photons, active, seed, id_base, counters, max_steps):
+def _to_diffuse(oracle_mod, packed, photons, active, seed, id_base, counters, max_steps, variant='contract'):
     """oracle.to_diffuse: the reference's own loop (hybrid_render.cu:20-58), which takes direction and polarisation as the
     kernel made them.  _step_to_diffuse goes through oracle.propagate, which divides both by their norms at every step as
     propagate.cu does on load: the same samples, but for a ray that grazes a triangle (where an ulp of the direction decides
     what it meets next).  Returns (triangle or -1, side, history, counters) like _step_to_diffuse."""
     active = np.asarray(active, bool)
     out, ctr, side = oracle_mod.to_diffuse(packed, photons, seed, photon_id_base=id_base, max_steps=max_steps, rng_counters=counters,
-                                           active=active)
+                                           active=active, variant=variant)
     flags = np.asarray(out.flags, np.uint32)
     diffuse = active & ((flags & REFLECT_DIFFUSE) != 0)
     tri = np.where(diffuse, out.last_hit_triangles, -1).astype(np.int32)
     return tri, np.where(diffuse, side, 0).astype(np.uint32), np.where(active, flags, 0).astype(np.uint32), ctr
 
 
-def oracle_lookup(oracle_mod, packed, geometry, seed, id_base, counters, nthreads, offset, source, wavelength, max_steps):
+def oracle_lookup(oracle_mod, packed, geometry, seed, id_base, counters, nthreads, offset, source, wavelength, max_steps,
+                  variant='contract'):
     """One update_xyz_lookup launch restated.  Returns (triangle, side, history, cos_theta, counters) of its samples."""
     from chroma_amd.event import Photons
     ntri = len(geometry.mesh.triangles)
@@ -161,32 +168,35 @@ def oracle_lookup(oracle_mod, packed, geometry, seed, id_base, counters, nthread
     d = d / np.sqrt(_dot(d, d))[:, None]
     # update_xyz_lookup casts the direction it has normalised itself (hybrid_render.cu:84-87); distance_to_mesh would divide
     # it by its norm once more and move a grazing ray by an ulp onto another triangle
-    _, first, _ = oracle_mod.distance_to_mesh(packed, pos, d, normalize=False)
+    _, first, _ = oracle_mod.distance_to_mesh(packed, pos, d, normalize=False, variant=variant)
     mine = first == np.arange(offset, offset + n)
     nrm = _normals(geometry)[offset:offset + n]
     cos = _dot(nrm, -d)
     cos = np.where(cos < f32(0), _dot(-nrm, -d), cos).astype(f32)
     cos[~mine] = 0
-    pol = _uniform_sphere(oracle_mod, u[:, 2], u[:, 3])
+    pol = _uniform_sphere(oracle_mod, u[:, 2], u[:, 3], variant=variant)
     photons = Photons(pos, d, pol, np.full(n, wavelength, f32), np.zeros(n, f32), np.full(n, -1, np.int32),
                       np.zeros(n, np.uint32), np.ones(n, f32), np.zeros(n, np.uint32))
     start = np.where(mine, c0 + 4, c0 + 2).astype(np.uint32)
-    tri, side, hist, ctr = _to_diffuse(oracle_mod, packed, photons, mine, seed, id_base, start, max_steps)
+    # (the keyword only where it says something: a test swaps _to_diffuse for a route of the contract build that takes none)
+    tri, side, hist, ctr = _to_diffuse(oracle_mod, packed, photons, mine, seed, id_base, start, max_steps,
+                                       **({} if variant == 'contract' else {'variant': variant}))
     return tri, side, hist, cos, ctr, mine
 
 
-def oracle_image(oracle_mod, packed, geometry, seed, id_base, counters, origins, directions, wavelength, max_steps):
+def oracle_image(oracle_mod, packed, geometry, seed, id_base, counters, origins, directions, wavelength, max_steps, variant='contract'):
     from chroma_amd.event import Photons
     n = len(origins)
     c0 = np.asarray(counters, np.uint32)[:n]
     u = _draws(oracle_mod, seed, id_base, c0, 2)
-    pol = _uniform_sphere(oracle_mod, u[:, 0], u[:, 1])
+    pol = _uniform_sphere(oracle_mod, u[:, 0], u[:, 1], variant=variant)
     d = np.asarray(directions, f32).reshape(-1, 3)
     with np.errstate(invalid='ignore', divide='ignore'):            # a zero or NaN direction gives NaN, as on the device
         d = d / np.sqrt(_dot(d, d))[:, None]                        # update_xyz_image's direction /= norm(direction), in f32
     photons = Photons(np.asarray(origins, f32), d, pol, np.full(n, wavelength, f32), np.zeros(n, f32),
                       np.full(n, -1, np.int32), np.zeros(n, np.uint32), np.ones(n, f32), np.zeros(n, np.uint32))
-    tri, side, hist, ctr = _to_diffuse(oracle_mod, packed, photons, np.ones(n, bool), seed, id_base, c0 + 2, max_steps)
+    tri, side, hist, ctr = _to_diffuse(oracle_mod, packed, photons, np.ones(n, bool), seed, id_base, c0 + 2, max_steps,
+                                       **({} if variant == 'contract' else {'variant': variant}))
     return tri, side, hist, ctr
 
 
