@@ -92,7 +92,7 @@ DAQ_NOISE_FN Photoelectron photoelectron(const chroma_daq_tables &tab, const chr
     const float time = win.t0 + ((float)pe.bin + f) * win.dt;
     __builtin_memcpy(&pe.time_bits, &time, sizeof(uint32_t));
     const float charge = interp_table(cm_u32_to_uniform(c), tab.charge_cdf_len, tab.d_charge_cdf_y, tab.d_charge_cdf_x);
-    pe.charge_int = (uint32_t)cm_roundf(charge / tab.charge_unit);
+    pe.charge_int = cm_f2u32(cm_roundf(charge / tab.charge_unit));
     return pe;
 }
 

@@ -34,7 +34,7 @@ __global__ void k_run_daq(GeoView g, chroma_daq_tables tab, int first_photon, in
     if (cm_rng_uniform(&rng) < weight) {
         float time = photon_times[photon_id] + interp_table(cm_rng_uniform(&rng), tab.time_cdf_len, tab.d_time_cdf_y, tab.d_time_cdf_x);
         float charge = interp_table(cm_rng_uniform(&rng), tab.charge_cdf_len, tab.d_charge_cdf_y, tab.d_charge_cdf_x);
-        uint32_t charge_int = (uint32_t)cm_roundf(charge / tab.charge_unit);
+        uint32_t charge_int = cm_f2u32(cm_roundf(charge / tab.charge_unit));
         atomicMin(earliest_time_int + channel_index, __float_as_uint(time));
         atomicAdd(channel_q_int + channel_index, charge_int);
         atomicOr(channel_histories + channel_index, history);
@@ -70,7 +70,7 @@ __global__ void k_run_daq_many(GeoView g, chroma_daq_tables tab, int first_photo
         float time = photon_times[photon_id] + jitter +
                      interp_table(cm_rng_uniform(&rng), tab.time_cdf_len, tab.d_time_cdf_y, tab.d_time_cdf_x);
         float charge = interp_table(cm_rng_uniform(&rng), tab.charge_cdf_len, tab.d_charge_cdf_y, tab.d_charge_cdf_x);
-        uint32_t charge_int = (uint32_t)cm_roundf(charge / tab.charge_unit);
+        uint32_t charge_int = cm_f2u32(cm_roundf(charge / tab.charge_unit));
         atomicMin(earliest_time_int + channel_offset, __float_as_uint(time));
         atomicAdd(channel_q_int + channel_offset, charge_int);
         atomicOr(channel_histories + channel_offset, history);
@@ -124,7 +124,7 @@ k_run_daq_events(GeoView g, chroma_daq_tables tab, uint32_t nrows, const uint32_
     if (cm_rng_uniform(&rng) < weight) {
         float time = photon_times[photon_id] + interp_table(cm_rng_uniform(&rng), tab.time_cdf_len, tab.d_time_cdf_y, tab.d_time_cdf_x);
         float charge = interp_table(cm_rng_uniform(&rng), tab.charge_cdf_len, tab.d_charge_cdf_y, tab.d_charge_cdf_x);
-        uint32_t charge_int = (uint32_t)cm_roundf(charge / tab.charge_unit);
+        uint32_t charge_int = cm_f2u32(cm_roundf(charge / tab.charge_unit));
         const uint32_t word = row * channel_stride + (uint32_t)channel_index;
         atomicMin(earliest_time_int + word, __float_as_uint(time));
         atomicAdd(channel_q_int + word, charge_int);

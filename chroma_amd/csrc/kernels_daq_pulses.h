@@ -52,7 +52,7 @@ __device__ inline int daq_pulse_photon(const GeoView &g, const chroma_daq_tables
     const float time = photon_times[photon_id] + interp_table(cm_rng_uniform(&rng), tab.time_cdf_len, tab.d_time_cdf_y, tab.d_time_cdf_x);
     const float charge = interp_table(cm_rng_uniform(&rng), tab.charge_cdf_len, tab.d_charge_cdf_y, tab.d_charge_cdf_x);
     out.channel = (uint32_t)channel_index;
-    out.charge_int = (uint32_t)cm_roundf(charge / tab.charge_unit);
+    out.charge_int = cm_f2u32(cm_roundf(charge / tab.charge_unit));
     out.time_bits = __float_as_uint(time);
     out.history = history;
     const float x = (time - win.t0) / win.dt;

@@ -449,8 +449,10 @@ int chroma_daq_compact_events(chroma_ctx *ctx, uint32_t nrows, uint32_t nchannel
  * triangle, no channel, detection flag not set), the same three draws in the same order from Philox
  * stream 1 + acquisition + r of photon photon_id_base + photon index -- the weight gate, the time smear
  * through the time CDF, the charge through the charge CDF -- time = photon time + smear and charge_int =
- * (uint32)cm_roundf(charge / charge_unit).  A pulse acquisition with the `acquisition` of a
- * chroma_daq_acquire_events call therefore describes the same accepted photons.
+ * cm_f2u32(cm_roundf(charge / charge_unit)): toward zero after rounding; NaN and negatives give 0;
+ * saturating; as cvt.rzi.u32.f32 / v_cvt_u32_f32 (a charge CDF may start below zero).  A pulse
+ * acquisition with the `acquisition` of a chroma_daq_acquire_events call therefore describes the same
+ * accepted photons.
  *
  * The window: dt > 0 and finite, t0 finite, 1 <= nbins <= 65536.  In float32, with IEEE subtract and
  * divide: x = (time - t0) / dt; the photon is in the window iff x >= 0.0f && x < (float)nbins, and its bin
@@ -510,7 +512,8 @@ int chroma_daq_acquire_pulses(chroma_ctx *ctx, chroma_geometry *geom, const chro
  *       operation rounded once.  THE BIN IS THE DRAWN ONE, whatever rounding makes of `time` (a time
  *       that rounds up to the next bin's edge stays in its bin; (time - t0) / dt is not consulted).
  *     Its charge, as a photon's: charge = interp_table(cm_u32_to_uniform(c), the charge CDF) and
- *       charge_int = (uint32)cm_roundf(charge / charge_unit).
+ *       charge_int = cm_f2u32(cm_roundf(charge / charge_unit)): toward zero after rounding; NaN and
+ *       negatives give 0; saturating; as cvt.rzi.u32.f32 / v_cvt_u32_f32.
  *     Its history: `flag`.
  * A kept noise photoelectron enters the pulses exactly like an accepted in-window photon of row r: it
  * counts in npe, adds to the wrapping q_int, competes for t_first and ORs `flag` into flags.  A pulse

@@ -1279,7 +1279,7 @@ int oracle_run_daq(const chroma_geometry_desc *g, const chroma_daq_tables *tab, 
         if (rng_u(&rng) < weight) {
             float time = a->t[photon_id] + interp_table(rng_u(&rng), tab->time_cdf_len, tab->d_time_cdf_y, tab->d_time_cdf_x);
             float charge = interp_table(rng_u(&rng), tab->charge_cdf_len, tab->d_charge_cdf_y, tab->d_charge_cdf_x);
-            uint32_t charge_int = (uint32_t)cm_roundf(charge / tab->charge_unit);
+            uint32_t charge_int = cm_f2u32(cm_roundf(charge / tab->charge_unit));
             uint32_t time_int = cm_f2u(time);
             if (time_int < earliest_time_int[channel_index]) earliest_time_int[channel_index] = time_int;
             channel_q_int[channel_index] += charge_int;
@@ -1314,7 +1314,7 @@ int oracle_run_daq_many(const chroma_geometry_desc *g, const chroma_daq_tables *
                 float jitter = cm_rng_normal(&rng);
                 float time = a->t[photon_id] + jitter + interp_table(rng_u(&rng), tab->time_cdf_len, tab->d_time_cdf_y, tab->d_time_cdf_x);
                 float charge = interp_table(rng_u(&rng), tab->charge_cdf_len, tab->d_charge_cdf_y, tab->d_charge_cdf_x);
-                uint32_t charge_int = (uint32_t)cm_roundf(charge / tab->charge_unit);
+                uint32_t charge_int = cm_f2u32(cm_roundf(charge / tab->charge_unit));
                 uint32_t time_int = cm_f2u(time);
                 if (time_int < earliest_time_int[channel_offset]) earliest_time_int[channel_offset] = time_int;
                 channel_q_int[channel_offset] += charge_int;

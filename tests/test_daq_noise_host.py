@@ -20,7 +20,7 @@ import pytest
 from chroma_amd import event
 from test_gpu_photon_arrays import host_geos, daq_rows, daq_tables, DAQ_BASE, DAQ_FIRST, DAQ_N, DETECT          # noqa: F401
 from test_gpu_daq_events import BASE
-from test_daq_pulses_host import (uniform, interp_table, roundf, restate, place, expected_pulses, time_image, time_bits, W_ALL, W_CUT,
+from test_daq_pulses_host import (uniform, interp_table, roundf, charge_count, restate, place, expected_pulses, time_image, time_bits, W_ALL, W_CUT,
                                   W_FINE, W_ONE, SEED, F)
 
 WINDOWS = {'all': W_ALL, 'cut': W_CUT, 'one': W_ONE, 'fine': W_FINE}
@@ -88,7 +88,7 @@ def restate_noise(oracle_mod, count_cdf, accept, tables, window, nrows, nchannel
                 f = F(F((p & 0xffffffff) >> 8) * F(2.0 ** -24))
                 time = F(t0 + F(F(F(bin_) + f) * dt))
                 charge = interp_table(uniform(d), qy, qx)
-                out.append((r, c, j, bin_, time, int(roundf(F(charge / unit)))))
+                out.append((r, c, j, bin_, time, charge_count(roundf(F(charge / unit)))))
     got = np.array(out, dtype=NOISE_DTYPE)
     got.flags.writeable = False
     return got, drawn, thinned

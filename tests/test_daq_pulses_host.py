@@ -56,9 +56,20 @@ def roundf(x):
     return F(r)
 
 
-def restate(oracle_mod, geo, ph, bounds, base=BASE, weight=WEIGHT, seed=SEED, id_base=DAQ_BASE):
+def charge_count(x):
+    """float -> uint32 as the DAQ counts a charge (cvt.rzi.u32.f32 / v_cvt_u32_f32), in Python integers: toward zero; NaN and
+    negatives give 0; saturating."""
+    x = float(x)
+    if x != x or x < 0.0:
+        return 0
+    if x > float(2 ** 32 - 1):
+        return 2 ** 32 - 1
+    return min(max(int(x), 0), 2 ** 32 - 1)
+
+
+def restate(oracle_mod, geo, ph, bounds, base=BASE, weight=WEIGHT, seed=SEED, id_base=DAQ_BASE, signed=False):
     """The accepted photons of the rows of ``bounds`` in photon order: a structured array of (photon, row, channel, time,
-    charge_int, history)."""
+    charge_int, history).  ``signed``: the detector's charge CDF starts below zero (tests/signed_charge.py)."""
     (tx, ty, qx, qy), unit = daq_tables(geo)
     unit, weight = F(unit), F(weight)
     key = (seed & 0xffffffff, seed >> 32)
@@ -78,9 +89,10 @@ def restate(oracle_mod, geo, ph, bounds, base=BASE, weight=WEIGHT, seed=SEED, id
                 continue
             time = F(ph.t[i] + interp_table(uniform(words[1]), ty, tx))
             charge = interp_table(uniform(words[2]), qy, qx)
-            assert charge >= 0
-            out.append((i, r, channel, time, int(roundf(F(charge / unit))), history))
-    dtype = [('photon', np.int64), ('row', np.int64), ('channel', np.int64), ('time', F), ('charge_int', np.uint32), ('history', np.uint32)]
+            assert charge >= 0 or signed
+            out.append((i, r, channel, time, charge_count(roundf(F(charge / unit))), history, charge))
+    dtype = [('photon', np.int64), ('row', np.int64), ('channel', np.int64), ('time', F), ('charge_int', np.uint32), ('history', np.uint32),
+             ('charge', F)]
     acc = np.array(out, dtype=dtype)
     acc.flags.writeable = False
     return acc

@@ -12,7 +12,9 @@ import pytest
 from conftest import ROOT
 
 
-@pytest.mark.parametrize('flags', [['-O2'], ['-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all']], ids=['plain', 'sanitized'])
+# (float-cast-overflow is named: GCC's -fsanitize=undefined does not include it)
+@pytest.mark.parametrize('flags', [['-O2'], ['-O1', '-g', '-fsanitize=address,undefined,float-cast-overflow', '-fno-sanitize-recover=all']],
+                         ids=['plain', 'sanitized'])
 def test_the_truncating_division_the_dot_product_and_the_renormalisation(tmp_path, flags):
     compiler = shutil.which('c++') or shutil.which('g++')
     command = [compiler] if compiler else ['/opt/rocm/bin/hipcc', '-x', 'c++']          # (what builds the library's host units)

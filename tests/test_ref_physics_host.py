@@ -513,6 +513,7 @@ def daq_input():
     ph = oracle.generate_bomb(60000, seed=31)
     ph.t[:] = 100.0
     end, _, _ = oracle.propagate(packed, ph, seed=9, max_steps=100, nthreads=4)
+    # (non-negative charge tables only: daq.cu's own float -> unsigned conversion, compiled for the host, is undefined below zero)
     tables = _padded_cdf(*geometry.time_cdf) + _padded_cdf(*geometry.charge_cdf)
     unit = float(np.float32(geometry.charge_cdf[0][-1] / 2 ** 16))
     rng = np.random.default_rng(5)
