@@ -5,7 +5,7 @@ from chroma_amd.gpu.tools import (create_cuda_context, get_context, get_rng_stat
 from chroma_amd.gpu.geometry import GPUGeometry, pack_geometry
 from chroma_amd.gpu.detector import GPUDetector
 from chroma_amd.gpu.photon import GPUPhotons, GPUPhotonsSlice, generate_bomb
-from chroma_amd.gpu.daq import GPUDaq, GPUChannels, GPUEventDaq, EventChannels, EventPulses, Pulses, DaqWindow, DaqTrigger, DaqNoise, EventTriggers, Triggers, DaqDigitizer, DaqReducer, FoundPulses
+from chroma_amd.gpu.daq import GPUDaq, GPUChannels, GPUEventDaq, EventChannels, EventPulses, Pulses, DaqWindow, DaqTrigger, DaqNoise, EventTriggers, Triggers, DaqDigitizer, DaqReducer, DaqChain, FoundPulses
 from chroma_amd.gpu.pdf import GPUPDF, GPUKernelPDF
 from chroma_amd.gpu.funcs import get_cu_module, GPUFuncs
 from chroma_amd.gpu.render import GPURays, GPUHybridRender

@@ -22,12 +22,12 @@ as ADC traces (chroma_daq_digitize_gates) and with a ``DaqReducer`` the pulses i
 ``EventTriggers.digitize`` and ``.reduce`` are the same on the host.
 
 The modules, each importing only those before it: ``records`` (the column tables, the chunk stitching, the count-then-fill call),
-``settings`` (the five settings classes), ``results`` (the containers and the host twins that build them), ``device`` (the drivers).
+``settings`` (the five settings classes and the ``DaqChain`` of them), ``results`` (the containers and the host twins that build them), ``device`` (the drivers).
 """
 from chroma_amd.gpu.daq.records import (PULSE_COLUMNS, FIRING_COLUMNS, HIT_COLUMNS, FOUND_COLUMNS, REDUCED_COLUMNS, NO_TRIGGER, Columns,
                                         Ragged, rebase_triggers, count_then_fill)
-from chroma_amd.gpu.daq.settings import (DaqWindow, DaqNoise, DaqTrigger, DaqDigitizer, DaqReducer, CLIPPED_HIGH, CLIPPED_LOW, TIME_AT_EDGE,
-                                         OPEN_AT_START, OPEN_AT_END, BASELINE_BUSY, _padded_cdf)
+from chroma_amd.gpu.daq.settings import (DaqWindow, DaqNoise, DaqTrigger, DaqDigitizer, DaqReducer, DaqChain, DAQ_NEEDS, daq_needs, CLIPPED_HIGH,
+                                         CLIPPED_LOW, TIME_AT_EDGE, OPEN_AT_START, OPEN_AT_END, BASELINE_BUSY, _padded_cdf)
 from chroma_amd.gpu.daq.results import (EventChannels, Pulses, EventPulses, FoundPulses, Triggers, EventTriggers, dense_channels,
                                         trigger_pulses_host, reduce_traces_host, _set_found, _time_image, _time_bits, _follow)
 from chroma_amd.gpu.daq.device import GPUChannels, GPUDaq, GPUEventDaq, _make_tables

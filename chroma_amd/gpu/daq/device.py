@@ -10,7 +10,7 @@ from chroma_amd.gpu.tools import empty, zeros, to_gpu
 from chroma_amd.gpu.photon import _structure
 from chroma_amd.gpu.daq.records import (PULSE_COLUMNS, FIRING_COLUMNS, HIT_COLUMNS, FOUND_COLUMNS, REDUCED_COLUMNS, names, kinds, named,
                                         columns_of, Columns, Ragged, rebase_triggers, count_then_fill)
-from chroma_amd.gpu.daq.settings import DaqWindow, DaqNoise, DaqTrigger, DaqDigitizer, DaqReducer, _padded_cdf
+from chroma_amd.gpu.daq.settings import DaqWindow, DaqChain, daq_needs, _padded_cdf
 from chroma_amd.gpu.daq.results import EventChannels, EventPulses, EventTriggers
 
 
@@ -110,6 +110,9 @@ def _photon_bounds(bounds):
 # what a trigger call leaves on the device for the digitiser: the firings' offsets per row and their bins, the hits' offsets per
 # firing and their channels, and the numbers of firings and hits
 Fired = collections.namedtuple('Fired', 'offsets bin hit_offsets hit_channel nt nh')
+
+# what acquire_pulses says in front of a stage that is given without the one it needs
+_WHY = {'reducer': 'a reducer reads the traces of a digitiser: ', 'digitizer': 'a digitiser reads the gates of a trigger: '}
 
 
 class GPUEventDaq(object):
@@ -275,7 +278,7 @@ class GPUEventDaq(object):
             per_hit.append(columns)
 
     def acquire_pulses(self, gpuphotons, rng_states, bounds, window, acquisition=0, weight=1.0, trigger=None, noise=None, digitizer=None,
-                       reducer=None, keep_traces=True):
+                       reducer=None, keep_traces=True, chain=None):
         """The time-binned view of ``acquire`` with the same arguments: the same accepted photons, per (event, channel, bin of
         ``window``: a DaqWindow or (t0, dt, nbins)).  Counts first (chroma_daq_count_pulses), then acquires into buffers grown to
         the largest count seen, ``rows_per_chunk`` events at a time.  Returns an ``EventPulses``.
@@ -296,21 +299,16 @@ class GPUEventDaq(object):
         ``reducer`` (a DaqReducer or its tuple; needs ``digitizer``): every digitised slice is also reduced where it lies, right behind
         its digitise call (chroma_daq_reduce_traces), and ``.triggers`` carries the found pulses (``found_offsets``, ``found_*``,
         ``trace_base``, ``reduced_flags``, ``reducer``).  With ``keep_traces=False`` the samples are not copied to the host:
-        ``triggers.adc`` is None, ``trace_flags`` still comes back."""
-        window = DaqWindow.of(window)
-        if reducer is not None:
-            if digitizer is None:
-                raise ValueError('a reducer reads the traces of a digitiser: reducer needs digitizer')
-            reducer = DaqReducer.of(reducer)
-        if digitizer is not None:
-            if trigger is None:
-                raise ValueError('a digitiser reads the gates of a trigger: digitizer needs trigger')
-            digitizer = DaqDigitizer.of(digitizer)
-        if noise is not None:
-            noise = DaqNoise.of(noise)
-            noise = None if noise.off else noise
-        if trigger is not None:
-            trigger = DaqTrigger.of(trigger).check(window)
+        ``triggers.adc`` is None, ``trace_flags`` still comes back.
+
+        ``chain`` (a DaqChain): the readout, resolved by the caller; ``window`` and the five keywords above are then not looked at,
+        and nothing is converted or checked again."""
+        if chain is None:
+            window = DaqWindow.of(window)
+            daq_needs(dict(window=window, trigger=trigger, digitizer=digitizer, reducer=reducer), stages=('reducer', 'digitizer'), reasons=_WHY)
+            chain = DaqChain(window, trigger, noise, digitizer, reducer, keep_traces)
+        window, trigger, noise, digitizer, reducer, keep_traces = (chain.window, chain.trigger, chain.noise, chain.digitizer, chain.reducer,
+                                                                   chain.keep_traces)
         bounds = _photon_bounds(bounds)
         nevents = len(bounds) - 1
         rng = gpuphotons._rng(rng_states)
@@ -318,10 +316,7 @@ class GPUEventDaq(object):
         lib, handle = self.ctx._lib, self.ctx.handle
         win = window.struct()
         if digitizer is not None:
-            digitizer.check(trigger)
             G = trigger.pre + trigger.post
-            if reducer is not None:
-                reducer.check(G)
             digitizer_struct, digitizer_arrays = digitizer.struct(self.charge_unit)
             # the electronics noise draws from the pseudo-photons 0xffffffff00000000 | channel, as the dark noise does
             n_ids, base = len(gpuphotons.pos), int(rng.photon_id_base)

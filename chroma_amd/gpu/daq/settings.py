@@ -1,5 +1,6 @@
 """The settings of the time-binned DAQ: ``DaqWindow``, ``DaqNoise``, ``DaqTrigger``, ``DaqDigitizer`` and ``DaqReducer``, each with
-the checks of its values, its ``of`` (itself or the one of a tuple) and the C struct or integer tables the library reads."""
+the checks of its values, its ``of`` (itself or the one of a tuple) and the C struct or integer tables the library reads; and
+``DaqChain``, a readout of them resolved once, over ``DAQ_NEEDS``, the one table of which stage needs which."""
 import ctypes
 
 import numpy as np
@@ -398,3 +399,37 @@ class DaqReducer(_Keyed):
         return ('DaqReducer(threshold=%d, polarity=%d, nbaseline=%d, pedestal=%d, baseline_spread=%d, min_width=%d, lead=%d, lag=%d, cfd=%d/256, '
                 'time_offset_ns=%r, gain=%r)' % (self.threshold, self.polarity, self.nbaseline, self.pedestal, self.baseline_spread, self.min_width,
                                                 self.lead, self.lag, self.cfd, self.time_offset_ns, self.gain))
+
+
+# which stage of a readout reads what another made: (stage, the stage it needs), in the order the stages run
+DAQ_NEEDS = (('trigger', 'window'), ('noise', 'window'), ('digitizer', 'trigger'), ('reducer', 'digitizer'), ('seeder', 'trigger'),
+             ('direction', 'seeder'))
+
+
+def daq_needs(given, names=None, stages=None, reasons=None):
+    """Raises ValueError for the first of ``stages`` (default: all of ``DAQ_NEEDS``, in its order) that is given without the stage it
+    needs.  ``given``: stage -> its value, None or absent for a stage that is not asked for; ``names``: stage -> what the caller
+    calls it (default: the stage itself); ``reasons``: stage -> what the caller puts in front of that stage's message."""
+    needs = dict(DAQ_NEEDS)
+    name = (lambda stage: stage) if names is None else names.__getitem__
+    for stage in (needs if stages is None else stages):
+        if given.get(stage) is not None and given.get(needs[stage]) is None:
+            raise ValueError('%s%s needs %s' % ((reasons or {}).get(stage, ''), name(stage), name(needs[stage])))
+
+
+class DaqChain(object):
+    """A readout, resolved: ``window`` (a DaqWindow), ``trigger``, ``noise`` (None also for noise that is ``off``), ``digitizer``,
+    ``reducer`` -- each None or its settings object, converted (``of``) and checked against the stage it reads exactly once, here --
+    and ``keep_traces``.  ``nchannels``, where it is known: the noise's tables have to fit the window and that many channels."""
+
+    def __init__(self, window, trigger=None, noise=None, digitizer=None, reducer=None, keep_traces=True, nchannels=None):
+        daq_needs(dict(window=window, trigger=trigger, noise=noise, digitizer=digitizer, reducer=reducer))
+        self.window = DaqWindow.of(window)
+        self.trigger = None if trigger is None else DaqTrigger.of(trigger).check(self.window)
+        noise = None if noise is None else DaqNoise.of(noise)
+        if noise is not None and not noise.off and nchannels is not None:
+            noise.tables(self.window, nchannels)          # (raises what does not fit the window or the detector)
+        self.noise = None if noise is None or noise.off else noise
+        self.digitizer = None if digitizer is None else DaqDigitizer.of(digitizer).check(self.trigger)
+        self.reducer = None if reducer is None else DaqReducer.of(reducer).check(self.trigger.pre + self.trigger.post)
+        self.keep_traces = keep_traces

@@ -7,6 +7,7 @@ is accepted; bare Vertex input and Events without photons or steps need a genera
 Events whose vertices carry ``steps`` get their photons made on the device (chroma_amd.gpu.steps).  The PDF entry points take
 Photons (or Events that carry ``photons_beg``) and run their DAQ acquisitions as GPUDaq(ndaq=K) chunks of at most 64.
 """
+import collections
 import os
 import time
 from timeit import default_timer as timer
@@ -14,6 +15,96 @@ from timeit import default_timer as timer
 import numpy as np
 
 from chroma_amd import event, gpu, itertoolset
+from chroma_amd.gpu.daq import DaqChain, daq_needs
+from chroma_amd.tracks import host_tracks
+
+# simulate()'s names for the stages of a readout (daq_needs), and the readout it resolves once per call for _simulate_batch:
+# ``chain`` a DaqChain or None (no daq_window), ``seeder`` a VertexSeeder or None, ``direction`` a DirectionSeeder or None
+_DAQ_NAMES = {stage: 'daq_' + stage for stage in ('window', 'trigger', 'noise', 'digitizer', 'reducer', 'seeder', 'direction')}
+_Readout = collections.namedtuple('_Readout', 'chain seeder direction')
+
+
+def cut_batches(iterable, evid_start, photons_per_batch, admit):
+    """The events of ``iterable`` in batches: ``admit(ev, evid, index)`` -- the event, its id (on from ``evid_start``) and its index
+    in the batch being filled -- refuses the event (raises) or writes on it what its path writes and returns (the event's item in
+    the batch, its weight in photons); a batch is closed when its weights reach ``photons_per_batch``, and what is left over
+    when the iterable ends is the last one.  Lazy: the iterable is read no further than the batch asked for."""
+    total, batch, evid = 0, [], evid_start
+    for ev in iterable:
+        item, weight = admit(ev, evid, len(batch))
+        evid += 1
+        total += weight
+        batch.append(item)
+        if total >= photons_per_batch:
+            yield batch
+            total, batch = 0, []
+    if batch:
+        yield batch
+
+
+def _has_steps(ev):
+    return any(getattr(v, 'steps', None) is not None for v in ev.vertices)
+
+
+# the three ``admit`` of simulate(): events with photons; with steps, weighed by ``expected_photons(segments)``; with neither,
+# weighed by ``stepper.expected_photons_at_most(vertices, media)``
+def _admit_photons(ev, evid, index):
+    ev.id = evid
+    ev.nphotons = len(ev.photons_beg)
+    ev.photons_beg.evidx[:] = index
+    return ev, ev.nphotons
+
+
+def _admit_stepped(expected_photons):
+    def admit(ev, evid, index):
+        if ev.photons_beg is not None or not _has_steps(ev):
+            raise NotImplementedError('events with steps and events with photons (or with neither) in one simulate() call')
+        ev.id = evid
+        segments = gpu.steps.segments_from_vertices(ev.vertices, evidx=index)
+        return (ev, segments), expected_photons(segments)
+    return admit
+
+
+def _admit_tracked(stepper, media):
+    def admit(ev, evid, index):
+        if ev.photons_beg is not None or _has_steps(ev):
+            raise NotImplementedError('events to be tracked and events with photons or steps in one simulate() call')
+        ev.id = evid
+        return ev, stepper.expected_photons_at_most(ev.vertices, media)
+    return admit
+
+
+def hits_by_channel(hits):
+    """{channel: its hits} of one event's ``hits`` in channel order (as the library hands them over): a channel's hits are one slice."""
+    ch = hits.channel
+    first = np.flatnonzero(np.concatenate(([True], ch[1:] != ch[:-1]))) if len(ch) else np.zeros(0, np.intp)
+    last = np.append(first[1:], len(ch))
+    return {c: hits[a:b] for c, a, b in zip(ch[first].tolist(), first.tolist(), last.tolist())}
+
+
+class _SeederTwins(object):
+    """The device twins of simulate()'s seeders and the DirectionSeeder made of what it was given, under one rule: the same
+    seeder object as last time -> the same device object."""
+
+    def __init__(self):
+        self.direction_of = None             # (what simulate() was given, the DirectionSeeder made of it)
+        self._held = {}                      # the class of a seeder -> the device twin made last for one of that class
+
+    def resolve(self, seeder, direction, detector):
+        """(the VertexSeeder of ``seeder``, the DirectionSeeder of ``direction`` about it or None)"""
+        from chroma_amd.seed import DirectionSeeder, VertexSeeder
+        seeder = VertexSeeder.of(seeder, detector)
+        if direction is None:
+            return seeder, None
+        if self.direction_of is None or self.direction_of[0] is not direction or self.direction_of[1].vertex_seeder is not seeder:
+            self.direction_of = (direction, DirectionSeeder.of(direction, seeder))
+        return seeder, self.direction_of[1]
+
+    def twin(self, seeder, make, *args, **kwargs):
+        """``make(*args, seeder, **kwargs)``, made once per seeder object"""
+        if type(seeder) not in self._held or self._held[type(seeder)].seeder is not seeder:
+            self._held[type(seeder)] = make(*args, seeder, **kwargs)
+        return self._held[type(seeder)]
 
 
 def pick_seed():
@@ -35,13 +126,9 @@ class Simulation(object):
                  light_medium=None, stepper=None, daq_seeder=None, daq_direction=None):
         # ``daq_seeder``: what simulate(daq_trigger=...) takes for its ``daq_seeder`` when that is None
         self.daq_seeder = daq_seeder
-        self._gpu_seeder = None              # the GPUVertexSeeder of the seeder simulate() saw last
         # ``daq_direction``: likewise simulate()'s ``daq_direction`` (it needs a ``daq_seeder``, here or there)
-        if daq_direction is not None and daq_seeder is None:
-            raise ValueError('daq_direction needs daq_seeder')
+        daq_needs(dict(seeder=daq_seeder, direction=daq_direction), _DAQ_NAMES, stages=('direction',))
         self.daq_direction = daq_direction
-        self._direction_of = None            # (what simulate() was given, the DirectionSeeder made of it)
-        self._gpu_direction = None           # the GPUDirectionSeeder of the direction seeder simulate() saw last
         # ``light_medium``: the Material whose Cherenkov and scintillation light the steps of Events without photons emit
         # (simulate(); chroma_amd.gpu.steps.LightSource); None: the detector's ``detector_material``; 'located': every segment
         # emits the light of the material it lies in, found on the device in this geometry (chroma_amd.gpu.steps.locate_materials:
@@ -95,6 +182,7 @@ class Simulation(object):
         self.photon_generator = None      # GEANT4 generation is outside the propagate path
 
         self.context = gpu.create_cuda_context(cuda_device)
+        self._seeders = _SeederTwins()
         if getattr(detector, 'bvh', None) is None:
             from chroma_amd.loader import load_bvh
             detector.flatten()
@@ -137,32 +225,25 @@ class Simulation(object):
         bounds = np.cumsum(np.concatenate([[0], [len(ev.photons_beg) for ev in batch_events]]))
         return gpu.GPUPhotons(batch_photons, copy_triangles=False, copy_weights=False, upload=upload), bounds
 
+    @property
+    def _direction_of(self):
+        return self._seeders.direction_of
+
     def _simulate_batch(self, batch_events, keep_photons_beg=False, keep_photons_end=False, keep_hits=True,
                         keep_flat_hits=True, run_daq=False, max_steps=100, verbose=False, uploaded=None, gpu_geometry=None,
-                        daq_window=None, daq_trigger=None, daq_noise=None, daq_digitizer=None, daq_reducer=None, daq_keep_traces=True,
-                        daq_seeder=None, daq_direction=None):
+                        daq=_Readout(None, None, None)):
         """Propagate the photons of all ``batch_events`` in one go and split the results
         back per event (by evidx).  Yields the events.  ``uploaded``: what _upload_batch returned for them;
-        ``gpu_geometry``: the geometry of the lane this batch runs on (default: the simulation's own)."""
+        ``gpu_geometry``: the geometry of the lane this batch runs on (default: the simulation's own); ``daq``: the
+        _Readout simulate() resolved."""
         t_start = timer()
         geometry = gpu_geometry if gpu_geometry is not None else self.gpu_geometry
         if uploaded is None:
             uploaded = self._upload_batch(batch_events, upload=False)
         gpu_photons, bounds = uploaded
         t_copy = timer()
-        is_detector = hasattr(self.detector, 'num_channels')
-        want_hits = is_detector and (keep_hits or keep_flat_hits)
-        batch_hits = tracking = None
-        device_tracks = self.photon_tracking == 'device'
-        if device_tracks:
-            tracking = gpu_photons.propagate_tracks(geometry, self.rng_states, max_steps=max_steps, exact=self.exact)
-        elif want_hits and not self.photon_tracking:
-            # propagate + get_flat_hits as one library call (chroma_propagate_hits): the same set of hits
-            batch_hits = gpu_photons.propagate_hits(geometry, self.rng_states, max_steps=max_steps, exact=self.exact, sort=True)
-        else:
-            tracking = gpu_photons.propagate(geometry, self.rng_states,
-                                             nthreads_per_block=self.nthreads_per_block, max_blocks=self.max_blocks,
-                                             max_steps=max_steps, track=self.photon_tracking, exact=self.exact)
+        want_hits = hasattr(self.detector, 'num_channels') and (keep_hits or keep_flat_hits)
+        batch_hits, tracking = self._propagate(gpu_photons, geometry, want_hits, max_steps)
         t_prop = timer()
         if verbose:
             print('GPU copy took %0.2f s' % (t_copy - t_start))
@@ -171,87 +252,24 @@ class Simulation(object):
         batch_end = gpu_photons.get() if keep_photons_end else None
         if want_hits and batch_hits is None:
             batch_hits = gpu_photons.get_flat_hits(geometry, sort=True)
-
-        # The hits of each event, and within an event of each channel, are SLICES: the library hands the batch's hits over in
-        # (event, channel) order (chroma_hits_sort: a radix sort and a gather on the device), where the reference masks all
-        # hits once per event and once per channel (chroma/sim.py:118-123: hits x events + hits x channels element tests --
-        # 2e11 for one 1e8-photon batch on a 29k-channel detector).
-        per_event_hits = None
-        if batch_hits is not None:
-            if len(batch_events) == 1:
-                per_event_hits = [batch_hits]
-            else:
-                cuts = np.searchsorted(batch_hits.evidx, np.arange(len(batch_events) + 1))
-                per_event_hits = [batch_hits[a:b] for a, b in zip(cuts[:-1], cuts[1:])]
-        event_channels = event_pulses = None
-        if run_daq and hasattr(self, 'gpu_daq') and self.gpu_geometry.nchannels > 0:
-            # the events' acquisitions as ONE (GPUEventDaq: a row of channels per event, read back sparse), numbered as the
-            # reference's one acquisition per event (chroma/sim.py:128-137) numbers them: on from self.gpu_daq's counter
-            if self._gpu_event_daq is None:
-                self._gpu_event_daq = gpu.GPUEventDaq(self.gpu_geometry)
-            event_channels = self._gpu_event_daq.acquire(gpu_photons, self.rng_states, bounds, acquisition=self.gpu_daq.acquisition)
-            if daq_window is not None:
-                # (under the acquisition numbers of the events' channels: both describe the same photoelectrons)
-                event_pulses = self._gpu_event_daq.acquire_pulses(gpu_photons, self.rng_states, bounds, daq_window,
-                                                                  acquisition=self.gpu_daq.acquisition, trigger=daq_trigger,
-                                                                  noise=daq_noise, digitizer=daq_digitizer, reducer=daq_reducer,
-                                                                  keep_traces=daq_keep_traces)
-            self.gpu_daq.acquisition += len(batch_events)
-        vertices = directions = None
-        if daq_seeder is not None and event_pulses is not None and event_pulses.triggers is not None:
-            # every firing of the batch in ONE device call, from what the electronics found where the traces were reduced
-            if self._gpu_seeder is None or self._gpu_seeder.seeder is not daq_seeder:
-                from chroma_amd.gpu.seed import GPUVertexSeeder
-                self._gpu_seeder = GPUVertexSeeder(self.context, daq_seeder)
-            source = 'reco' if daq_reducer is not None else 'gate'
-            if daq_direction is None:
-                vertices = event_pulses.triggers.seed(daq_seeder, source=source, gpu=self._gpu_seeder)
-            else:
-                # the direction about every seed in a second call, on the rows, positions and bins the first left on the device
-                if self._gpu_direction is None or self._gpu_direction.seeder is not daq_direction:
-                    from chroma_amd.gpu.seed import GPUDirectionSeeder
-                    self._gpu_direction = GPUDirectionSeeder(self.context, daq_direction, vertex=self._gpu_seeder)
-                vertices, directions = self._gpu_direction.fit_both(self._gpu_seeder, *event_pulses.triggers.seed_rows(source))
+        per_event_hits = None if batch_hits is None else self._hits_per_event(batch_hits, len(batch_events))
+        acquired = self._read_out(gpu_photons, bounds, daq) if run_daq else None
         for i, (ev, lo, hi) in enumerate(zip(batch_events, bounds[:-1], bounds[1:])):
             if not keep_photons_beg:
                 ev.photons_beg = None
-            if device_tracks:
+            if self.photon_tracking == 'device':
                 ev.photon_tracks = tracking.cut(int(lo), int(hi))
             elif self.photon_tracking:
-                step_ids_list, step_photons_list = tracking
-                tracks = [[] for _ in range(hi - lo)]
-                for step_ids, step_photons in zip(step_ids_list, step_photons_list):
-                    mask = np.logical_and(step_ids >= lo, step_ids < hi)
-                    if np.count_nonzero(mask) == 0:
-                        break
-                    ids = step_ids[mask] - lo
-                    photons = step_photons[mask]
-                    for k, pid in enumerate(ids):
-                        tracks[pid].append(photons[k])
-                ev.photon_tracks = [event.Photons.join(t, concatenate=False) if len(t) > 0 else event.Photons()
-                                    for t in tracks]
+                ev.photon_tracks = host_tracks(tracking[0], tracking[1], lo, hi)
             if keep_photons_end:
                 ev.photons_end = batch_end[lo:hi]
             if batch_hits is not None:
-                ev_hits = per_event_hits[i]
                 if keep_hits:
-                    # (the event's hits are in channel order already: a channel's hits are one slice)
-                    ch = ev_hits.channel
-                    first = np.flatnonzero(np.concatenate(([True], ch[1:] != ch[:-1]))) if len(ch) else np.zeros(0, np.intp)
-                    last = np.append(first[1:], len(ch))
-                    ev.hits = {c: ev_hits[a:b] for c, a, b in zip(ch[first].tolist(), first.tolist(), last.tolist())}
+                    ev.hits = hits_by_channel(per_event_hits[i])
                 if keep_flat_hits:
-                    ev.flat_hits = ev_hits
-            if event_channels is not None:
-                ev.channels = event_channels[i]
-                if event_pulses is not None:
-                    ev.pulses = event_pulses.event(i)
-                    if event_pulses.triggers is not None:
-                        ev.triggers = event_pulses.triggers.event(i)
-                        if vertices is not None:
-                            ev.triggers.vertices = vertices[int(event_pulses.triggers.offsets[i]):int(event_pulses.triggers.offsets[i + 1])]
-                        if directions is not None:
-                            ev.triggers.directions = directions[int(event_pulses.triggers.offsets[i]):int(event_pulses.triggers.offsets[i + 1])]
+                    ev.flat_hits = per_event_hits[i]
+            if acquired is not None:
+                self._attach_readout(ev, i, *acquired)
             elif hasattr(self, 'gpu_daq') and run_daq:
                 # (a detector without channels: one acquisition per event, as the reference, chroma/sim.py:128-137)
                 self.gpu_daq.begin_acquire()
@@ -259,6 +277,71 @@ class Simulation(object):
                                      nthreads_per_block=self.nthreads_per_block, max_blocks=self.max_blocks)
                 ev.channels = self.gpu_daq.end_acquire().get()
             yield ev
+
+    def _propagate(self, gpu_photons, geometry, want_hits, max_steps):
+        """The batch's one propagate call: (its flat hits, where the call makes them itself, else None; what tracking gives, else None)."""
+        if self.photon_tracking == 'device':
+            return None, gpu_photons.propagate_tracks(geometry, self.rng_states, max_steps=max_steps, exact=self.exact)
+        if want_hits and not self.photon_tracking:
+            # propagate + get_flat_hits as one library call (chroma_propagate_hits): the same set of hits
+            return gpu_photons.propagate_hits(geometry, self.rng_states, max_steps=max_steps, exact=self.exact, sort=True), None
+        return None, gpu_photons.propagate(geometry, self.rng_states, nthreads_per_block=self.nthreads_per_block, max_blocks=self.max_blocks,
+                                           max_steps=max_steps, track=self.photon_tracking, exact=self.exact)
+
+    @staticmethod
+    def _hits_per_event(batch_hits, nevents):
+        """The hits of each event, and within an event of each channel (hits_by_channel), are SLICES: the library hands the batch's
+        hits over in (event, channel) order (chroma_hits_sort: a radix sort and a gather on the device), where the reference masks
+        all hits once per event and once per channel (chroma/sim.py:118-123: hits x events + hits x channels element tests --
+        2e11 for one 1e8-photon batch on a 29k-channel detector)."""
+        if nevents == 1:
+            return [batch_hits]
+        cuts = np.searchsorted(batch_hits.evidx, np.arange(nevents + 1))
+        return [batch_hits[a:b] for a, b in zip(cuts[:-1], cuts[1:])]
+
+    def _read_out(self, gpu_photons, bounds, daq):
+        """The DAQ of a batch on a detector with channels (None without them): (the events' channels, their pulses or None, the
+        seeds of their firings or None, the directions about those or None)."""
+        if not hasattr(self, 'gpu_daq') or self.gpu_geometry.nchannels < 1:
+            return None
+        # the events' acquisitions as ONE (GPUEventDaq: a row of channels per event, read back sparse), numbered as the
+        # reference's one acquisition per event (chroma/sim.py:128-137) numbers them: on from self.gpu_daq's counter
+        if self._gpu_event_daq is None:
+            self._gpu_event_daq = gpu.GPUEventDaq(self.gpu_geometry)
+        acquisition = self.gpu_daq.acquisition
+        channels = self._gpu_event_daq.acquire(gpu_photons, self.rng_states, bounds, acquisition=acquisition)
+        pulses = vertices = directions = None
+        if daq.chain is not None:
+            # (under the acquisition numbers of the events' channels: both describe the same photoelectrons)
+            pulses = self._gpu_event_daq.acquire_pulses(gpu_photons, self.rng_states, bounds, daq.chain.window, acquisition=acquisition,
+                                                        chain=daq.chain)
+        self.gpu_daq.acquisition += len(bounds) - 1
+        if daq.seeder is not None and pulses is not None and pulses.triggers is not None:
+            # every firing of the batch in ONE device call, from what the electronics found where the traces were reduced
+            from chroma_amd.gpu.seed import GPUDirectionSeeder, GPUVertexSeeder
+            vertex = self._seeders.twin(daq.seeder, GPUVertexSeeder, self.context)
+            source = 'reco' if daq.chain.reducer is not None else 'gate'
+            if daq.direction is None:
+                vertices = pulses.triggers.seed(daq.seeder, source=source, gpu=vertex)
+            else:
+                # the direction about every seed in a second call, on the rows, positions and bins the first left on the device
+                direction = self._seeders.twin(daq.direction, GPUDirectionSeeder, self.context, vertex=vertex)
+                vertices, directions = direction.fit_both(vertex, *pulses.triggers.seed_rows(source))
+        return channels, pulses, vertices, directions
+
+    @staticmethod
+    def _attach_readout(ev, i, channels, pulses, vertices, directions):
+        """Event ``i``'s share of what _read_out returned."""
+        ev.channels = channels[i]
+        if pulses is not None:
+            ev.pulses = pulses.event(i)
+            if pulses.triggers is not None:
+                ev.triggers = pulses.triggers.event(i)
+                lo, hi = int(pulses.triggers.offsets[i]), int(pulses.triggers.offsets[i + 1])
+                if vertices is not None:
+                    ev.triggers.vertices = vertices[lo:hi]
+                if directions is not None:
+                    ev.triggers.directions = directions[lo:hi]
 
     def simulate(self, iterable, keep_photons_beg=False, keep_photons_end=False, keep_hits=True,
                  keep_flat_hits=True, run_daq=False, max_steps=1000, photons_per_batch=1000000, evid_start=0, daq_window=None,
@@ -293,20 +376,11 @@ class Simulation(object):
         thread while the current one propagates: the iterable is consumed one batch ahead of the events this generator
         yields.  An iterable whose items share buffers, or depend on results already yielded, needs ``prefetch=False``;
         ``keep_photons_beg=True`` turns the read-ahead off by itself (the reference's loop is lazy, chroma/sim.py:141-186)."""
-        if daq_trigger is not None and daq_window is None:
-            raise ValueError('daq_trigger needs daq_window')          # (before anything is looked at)
-        if daq_noise is not None and daq_window is None:
-            raise ValueError('daq_noise needs daq_window')
-        if daq_digitizer is not None and daq_trigger is None:
-            raise ValueError('daq_digitizer needs daq_trigger')
-        if daq_reducer is not None and daq_digitizer is None:
-            raise ValueError('daq_reducer needs daq_digitizer')
-        if daq_seeder is not None and daq_trigger is None:
-            raise ValueError('daq_seeder needs daq_trigger')
+        given = dict(window=daq_window, trigger=daq_trigger, noise=daq_noise, digitizer=daq_digitizer, reducer=daq_reducer, seeder=daq_seeder)
+        daq_needs(given, _DAQ_NAMES, stages=('trigger', 'noise', 'digitizer', 'reducer', 'seeder'))          # (before anything is looked at)
         if daq_seeder is None and daq_trigger is not None:
             daq_seeder = self.daq_seeder
-        if daq_direction is not None and daq_seeder is None:
-            raise ValueError('daq_direction needs daq_seeder')
+        daq_needs(dict(seeder=daq_seeder, direction=daq_direction), _DAQ_NAMES, stages=('direction',))
         if daq_direction is None and daq_seeder is not None:
             daq_direction = self.daq_direction
         tracked = False
@@ -329,90 +403,50 @@ class Simulation(object):
         else:
             raise NotImplementedError('Vertex input needs the GEANT4 generator, which is out of scope')
 
+        daq = _Readout(None, None, None)
         if daq_window is not None:
             if not run_daq:
                 raise ValueError('daq_window needs run_daq=True')
             if not hasattr(self, 'gpu_daq') or self.gpu_geometry.nchannels < 1:
                 raise ValueError('daq_window needs a detector with channels')
-            daq_window = gpu.DaqWindow.of(daq_window)
-            if daq_trigger is not None:
-                daq_trigger = gpu.DaqTrigger.of(daq_trigger).check(daq_window)
-            if daq_noise is not None:
-                daq_noise = gpu.DaqNoise.of(daq_noise)
-                if not daq_noise.off:
-                    daq_noise.tables(daq_window, self.gpu_geometry.nchannels)          # (raises what does not fit the window or the detector)
-            if daq_digitizer is not None:
-                daq_digitizer = gpu.DaqDigitizer.of(daq_digitizer).check(daq_trigger)
-            if daq_reducer is not None:
-                daq_reducer = gpu.DaqReducer.of(daq_reducer).check(daq_trigger.pre + daq_trigger.post)
-            if daq_seeder is not None:
-                from chroma_amd.seed import VertexSeeder
-                daq_seeder = VertexSeeder.of(daq_seeder, self.detector)
-                if daq_direction is not None:
-                    from chroma_amd.seed import DirectionSeeder
-                    given = daq_direction
-                    if self._direction_of is not None and self._direction_of[0] is given and self._direction_of[1].vertex_seeder is daq_seeder:
-                        daq_direction = self._direction_of[1]
-                    else:
-                        daq_direction = DirectionSeeder.of(given, daq_seeder)
-                        self._direction_of = (given, daq_direction)
+            chain = DaqChain(daq_window, daq_trigger, daq_noise, daq_digitizer, daq_reducer, daq_keep_traces, nchannels=self.gpu_geometry.nchannels)
+            seeders = self._seeders.resolve(daq_seeder, daq_direction, self.detector) if daq_seeder is not None else (None, None)
+            daq = _Readout(chain, *seeders)
         kwargs = dict(keep_photons_beg=keep_photons_beg, keep_photons_end=keep_photons_end, keep_hits=keep_hits,
-                      keep_flat_hits=keep_flat_hits, run_daq=run_daq, max_steps=max_steps, daq_window=daq_window, daq_trigger=daq_trigger,
-                      daq_noise=daq_noise, daq_digitizer=daq_digitizer, daq_reducer=daq_reducer, daq_keep_traces=daq_keep_traces, daq_seeder=daq_seeder,
-                      daq_direction=daq_direction)
+                      keep_flat_hits=keep_flat_hits, run_daq=run_daq, max_steps=max_steps, daq=daq)
         if tracked:
             yield from self._simulate_tracked(iterable, photons_per_batch, evid_start, kwargs)
             return
         if isinstance(first, event.Event) and first.photons_beg is None:
             yield from self._simulate_stepped(iterable, photons_per_batch, evid_start, kwargs)
             return
-        def batches():
-            nphotons = 0
-            batch = []
-            evid = evid_start
-            for ev in iterable:
-                ev.id = evid
-                evid += 1
-                ev.nphotons = len(ev.photons_beg)
-                ev.photons_beg.evidx[:] = len(batch)
-                nphotons += ev.nphotons
-                batch.append(ev)
-                if nphotons >= photons_per_batch:
-                    yield batch
-                    nphotons = 0
-                    batch = []
-            if batch:
-                yield batch
-
+        batches = cut_batches(iterable, evid_start, photons_per_batch, _admit_photons)
         # (read-ahead contract: with prefetch the iterable is pulled one batch ahead of the events being yielded, and `evidx` is
         #  written into the photons of that next batch early; a generator that reuses its buffers, or a caller who wants
         #  `photons_beg` back untouched, gets the reference's lazy loop instead)
         if self.nlanes > 1 and not (self.photon_tracking or keep_photons_beg or run_daq):
-            yield from self._simulate_lanes(batches(), kwargs)
+            yield from self._simulate_lanes(batches, kwargs)
             return
         if not self.prefetch or self.photon_tracking or keep_photons_beg:
-            for batch in batches():
+            for batch in batches:
                 yield from self._simulate_batch(batch, **kwargs)
             return
         # one batch ahead: while batch k propagates (the library call releases the GIL), a second thread stages and
         # uploads batch k + 1 on the context's second stream
         from concurrent.futures import ThreadPoolExecutor
-        it = batches()
         with ThreadPoolExecutor(max_workers=1) as pool:
-            cur = next(it, None)
+            cur = next(batches, None)
             fut = pool.submit(self._upload_batch, cur) if cur is not None else None
             while cur is not None:
                 uploaded = fut.result()
-                nxt = next(it, None)
+                nxt = next(batches, None)
                 fut = pool.submit(self._upload_batch, nxt) if nxt is not None else None
                 yield from self._simulate_batch(cur, uploaded=uploaded, **kwargs)
                 uploaded = None
                 cur = nxt
 
     # ---- events that carry steps instead of photons ------------------------------------------------------------------
-    @staticmethod
-    def _has_steps(ev):
-        return any(getattr(v, 'steps', None) is not None for v in ev.vertices)
+    _has_steps = staticmethod(_has_steps)
 
     @property
     def light_source(self):
@@ -452,36 +486,22 @@ class Simulation(object):
         located = isinstance(source, gpu.steps.LightMedia)
         expected_photons = source.expected_at_most if located else source.expected_photons
 
-        def batches():
-            expected, batch, evid = 0.0, [], evid_start
-            for ev in iterable:
-                if ev.photons_beg is not None or not self._has_steps(ev):
-                    raise NotImplementedError('events with steps and events with photons (or with neither) in one simulate() call')
-                ev.id = evid
-                evid += 1
-                segments = gpu.steps.segments_from_vertices(ev.vertices, evidx=len(batch))
-                expected += expected_photons(segments)
-                batch.append((ev, segments))
-                if expected >= photons_per_batch:
-                    yield batch
-                    expected, batch = 0.0, []
-            if batch:
-                yield batch
-
-        for batch in batches():
+        for batch in cut_batches(iterable, evid_start, photons_per_batch, _admit_stepped(expected_photons)):
             segments = gpu.steps.Segments.join([s for _, s in batch], segment_base=self._segment_base)
             self._segment_base += len(segments)
             where = dict(gpu_geometry=self.gpu_geometry, outside=self._outside_row) if located else {}
             gpu_photons, offsets = gpu.steps.generate_photons(segments, source, self.seed, ctx=self.context, return_offsets=True, **where)
             cuts = 2 * np.cumsum([0] + [len(s) for _, s in batch])
-            bounds = offsets[cuts].astype(np.int64)
-            events = [ev for ev, _ in batch]
-            photons_beg = gpu_photons.get() if kwargs['keep_photons_beg'] else None
-            for ev, lo, hi in zip(events, bounds[:-1], bounds[1:]):
-                ev.nphotons = int(hi - lo)
-                if photons_beg is not None:
-                    ev.photons_beg = photons_beg[int(lo):int(hi)]
-            yield from self._simulate_batch(events, uploaded=(gpu_photons, bounds), **kwargs)
+            yield from self._simulate_generated([ev for ev, _ in batch], gpu_photons, offsets[cuts].astype(np.int64), kwargs)
+
+    def _simulate_generated(self, events, gpu_photons, bounds, kwargs):
+        """The tail of a batch whose photons were made on the device: event k's are ``bounds[k]:bounds[k + 1]`` of ``gpu_photons``."""
+        photons_beg = gpu_photons.get() if kwargs['keep_photons_beg'] else None
+        for ev, lo, hi in zip(events, bounds[:-1], bounds[1:]):
+            ev.nphotons = int(hi - lo)
+            if photons_beg is not None:
+                ev.photons_beg = photons_beg[int(lo):int(hi)]
+        yield from self._simulate_batch(events, uploaded=(gpu_photons, bounds), **kwargs)
 
     # ---- vertices that carry nothing: tracked on the device (Simulation(stepper=...)) ---------------------------------
     @staticmethod
@@ -510,22 +530,7 @@ class Simulation(object):
             outside = stepper.media.index(material) if material is not None else -1
         options_stepper = stepper if outside == stepper.outside else _with_outside(stepper, outside)
 
-        def batches():
-            expected, batch, evid = 0.0, [], evid_start
-            for ev in iterable:
-                if ev.photons_beg is not None or self._has_steps(ev):
-                    raise NotImplementedError('events to be tracked and events with photons or steps in one simulate() call')
-                ev.id = evid
-                evid += 1
-                expected += stepper.expected_photons_at_most(ev.vertices, media)
-                batch.append(ev)
-                if expected >= photons_per_batch:
-                    yield batch
-                    expected, batch = 0.0, []
-            if batch:
-                yield batch
-
-        for events in batches():
+        for events in cut_batches(iterable, evid_start, photons_per_batch, _admit_tracked(stepper, media)):
             vertices = [v for ev in events for v in ev.vertices]
             evidx = np.array([i for i, ev in enumerate(events) for _ in ev.vertices], dtype=np.uint32)
             made = gpu.particles.track_segments(vertices, options_stepper, self.seed, gpu_geometry=self.gpu_geometry, ctx=self.context,
@@ -542,13 +547,7 @@ class Simulation(object):
             # (segments, and so photons, are in event order: an event's bounds from its segments' -- their event indices and the
             #  scanned counts are all that is read back, 12 bytes a segment)
             cuts = np.searchsorted(segments.arrays['evidx'].get()[:len(segments)], np.arange(len(events) + 1))
-            bounds = offsets[2 * cuts].astype(np.int64)
-            photons_beg = gpu_photons.get() if kwargs['keep_photons_beg'] else None
-            for ev, lo, hi in zip(events, bounds[:-1], bounds[1:]):
-                ev.nphotons = int(hi - lo)
-                if photons_beg is not None:
-                    ev.photons_beg = photons_beg[int(lo):int(hi)]
-            yield from self._simulate_batch(events, uploaded=(gpu_photons, bounds), **kwargs)
+            yield from self._simulate_generated(events, gpu_photons, offsets[2 * cuts].astype(np.int64), kwargs)
 
     def _simulate_lanes(self, batches, kwargs):
         """``lanes`` batches in flight at once, each on its own context from its own host thread (the library calls

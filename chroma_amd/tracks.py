@@ -10,6 +10,22 @@ import numpy as np
 from chroma_amd.event import Photons
 
 
+def host_tracks(step_photon_ids, step_photons, lo, hi):
+    """The tracks of the photons ``lo:hi`` of a batch as the reference assembles them on the host (chroma/sim.py:102-114): a list of
+    Photons, one per photon, from the per-step lists of ``GPUPhotons.propagate(track=True)``, an append per row.  Like the
+    reference's loop it ENDS at the first step none of these photons took part in."""
+    tracks = [[] for _ in range(hi - lo)]
+    for step_ids, photons in zip(step_photon_ids, step_photons):
+        mask = np.logical_and(step_ids >= lo, step_ids < hi)
+        if np.count_nonzero(mask) == 0:
+            break
+        ids = step_ids[mask] - lo
+        photons = photons[mask]
+        for k, pid in enumerate(ids):
+            tracks[pid].append(photons[k])
+    return [Photons.join(t, concatenate=False) if len(t) > 0 else Photons() for t in tracks]
+
+
 class PhotonTracks(object):
     """A sequence of ``Photons``, one per photon: ``tracks[i]`` is rows ``offsets[i]:offsets[i + 1]`` of ``photons``, in step
     order.  ``len``, indexing (negative indices too), slicing and iteration all slice the flat arrays: no per-photon object

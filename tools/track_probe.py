@@ -19,7 +19,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
 def regroup(step_ids_list, step_photons_list, n):
-    """The loop of Simulation._simulate_batch for one event of ``n`` photons."""
+    """The loop of Simulation._simulate_batch (chroma_amd.tracks.host_tracks) for one event of ``n`` photons."""
     from chroma_amd import event
     tracks = [[] for _ in range(n)]
     for step_ids, step_photons in zip(step_ids_list, step_photons_list):
